@@ -62,7 +62,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before torch / HIP initialise: see zerokit_amd/csrc/common.cpp
 
 # per-proof algorithmic bytes
 BYTES_PER_PROOF = 7468404
@@ -848,6 +847,29 @@ def open_prover(B, factory):
     raise SystemExit("bench: no table size fits this device")
 
 
+DUMP_LIMIT_BYTES = 64 << 20                                 # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, proofs, values, errs):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as float32 .npy files (every byte
+    and error code is exact in float32): proofs.npy (n, 128) the compressed proof bytes, public_values.npy (n, 5, 32) the
+    five public values little-endian, errors.npy (n,) the error codes, rows.npy (n,) float64 the row of each within the
+    step.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of rows is written, in order."""
+    import numpy as np
+    n = len(errs)
+    p = np.frombuffer(proofs, dtype=np.uint8).reshape(n, 128)
+    v = np.frombuffer(values, dtype=np.uint8).reshape(n, 5, 32)
+    e = np.asarray(errs, dtype=np.uint32)
+    row_bytes = (128 + 5 * 32 + 1) * 4 + 8
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0x5EED).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("proofs", p[rows].astype(np.float32)), ("public_values", v[rows].astype(np.float32)),
+                    ("errors", e[rows].astype(np.float32)), ("rows", rows.astype(np.float64))):
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def pool_main(args):
     """plain `python bench.py --gpus N` (no torchrun): one process, N devices, rlnamd_pool"""
     from zerokit_amd import lib, workload
@@ -878,6 +900,8 @@ def pool_main(args):
     for _ in range(args.steps):
         proofs, values, errs = pool.prove_raw(inputs, rsb)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, proofs, values, errs)
     idx = list(range(0, n, 509))
     pub = [[int.from_bytes(values[160 * i + 32 * k:160 * i + 32 * k + 32], "little") for k in range(5)] for i in idx]
     ok = not any(errs) and all(pool.verify_many([proofs[128 * i:128 * i + 128] for i in idx], pub))
@@ -937,7 +961,12 @@ def main():
                     help="after the timed region: this many seconds of back-to-back batches (0: skip)")
     ap.add_argument("--workload", default="proofs", choices=["proofs", "merkle", "msm", "finish", "operating-points"],
                     help="proofs = BASELINE metric (default); merkle / msm / finish / operating-points = side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: the proofs, public values and error codes of the last timed step as "
+                         "DIR/<name>.npy (rank 0's shard under torchrun; see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload not in ("proofs", "finish") or args.steps < 1):
+        raise SystemExit("bench: --dump-outputs needs --workload proofs or finish and --steps >= 1")
     if args.workload == "merkle":
         return merkle_main(args)
     if args.workload == "msm":
@@ -958,7 +987,7 @@ def main():
         return pool_main(args)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    # test hooks for boxes with fewer devices than ranks (tests/test_gpu_stream_pool.py::test_bench_under_torchrun_with_eight_ranks_on_one_device): every rank on one device, gloo
+    # test hooks for boxes with fewer devices than ranks (tests/test_gpu_stream_pool.py::test_bench_under_torchrun_with_four_ranks_on_one_device): every rank on one device, gloo
     # instead of RCCL (which refuses two ranks on one device); the driver never sets them
     backend = os.environ.get("RLNAMD_BENCH_BACKEND", "nccl")
     if "RLNAMD_BENCH_DEVICE" in os.environ:
@@ -967,7 +996,7 @@ def main():
     # A single-GPU run imports no torch at all: librln.so brings in the HIP runtime it was built for (/opt/rocm).  Under
     # torchrun torch is needed for the barrier and the max over ranks, and it goes FIRST: with librln.so (ROCm 7.2's
     # libamdhip64 / librccl) loaded before a torch wheel built for ROCm 7.0 the process aborted at exit ("double free or
-    # corruption", tests/test_gpu_stream_pool.py::test_bench_under_torchrun_with_eight_ranks_on_one_device).  The streamed path no longer depends on which runtime it gets: the inputs
+    # corruption", tests/test_gpu_stream_pool.py::test_bench_under_torchrun_with_four_ranks_on_one_device).  The streamed path no longer depends on which runtime it gets: the inputs
     # are staged by a kernel, not by the copy path that was slow under the wheel's runtime (profiles/r3 section 1).
     use_dist = under_torchrun                              # under torchrun the process group is always created
     torch = dist = None
@@ -1064,6 +1093,10 @@ def main():
     ok = bool(ok and (all(prover.verify_many(vp, vv)) if vp else True))
     # distinct inputs give distinct proofs: the stream really was K different batches
     distinct = len({r[0][:128] for r in results.values()}) == len(results)
+    if args.dump_outputs and rank == 0:   # the last step's batches are the last ones pumped; `results` holds their pass
+        last = [j % nbatches for j in range((args.steps - 1) * per_step, args.steps * per_step)]
+        dump_outputs(args.dump_outputs, b"".join(results[k][0] for k in last), b"".join(results[k][1] for k in last),
+                     [x for k in last for x in results[k][2]])
 
     # ---- what the HOST pays to feed one GPU (eight of them hang off one host): process CPU seconds over the
     #      timed region, and the wall time of the two calls by themselves -- submit with a free slot (copy into pinned

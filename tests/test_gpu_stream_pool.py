@@ -484,26 +484,27 @@ def test_config4_full_65536_over_eight_replicas_on_one_device_boundaries_vs_c_or
         pool.close()
 
 
-def test_bench_under_torchrun_with_eight_ranks_on_one_device():
-    """`bench.py --gpus 8` exactly as the driver launches it (python -m torch.distributed.run, one process per rank), on
-    a box with ONE device: every rank is pinned to device 0 (RLNAMD_BENCH_DEVICE) with gloo in place of RCCL, which
-    refuses two ranks on one device, and small tables so that eight provers fit.  rc 0, exactly one JSON line on stdout,
-    n_gpus 8, config 4 (8 x 8 192 proofs per step), verified"""
+def test_bench_under_torchrun_with_four_ranks_on_one_device():
+    """`bench.py --gpus 4` the way the driver launches a multi-GPU run (python -m torch.distributed.run, one process per
+    rank), on a box with ONE device: every rank is pinned to device 0 (RLNAMD_BENCH_DEVICE) with gloo in place of RCCL,
+    which refuses two ranks on one device, and small tables so that the provers fit.  Four ranks, so that together with
+    this process no more than five processes hold the device.  rc 0, exactly one JSON line on stdout, n_gpus 4,
+    config 4 (4 x 8 192 proofs per step), verified"""
     import json
     port = _free_port()
     env = dict(os.environ, RLNAMD_BENCH_DEVICE="0", RLNAMD_BENCH_BACKEND="gloo", RLNAMD_WINDOW_BITS="8",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0",
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0",
            "--no-side-configs"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["steps"] == 1 and d["unit"] == "proofs/s" and d["scaling"] == "weak"
+    assert d["n_gpus"] == 4 and d["steps"] == 1 and d["unit"] == "proofs/s" and d["scaling"] == "weak"
     assert d["config"]["verified"] is True and d["config"]["batch_per_gpu"] == 8192
-    assert abs(d["value"] - 8 * 8192 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+    assert abs(d["value"] - 4 * 8192 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
     # (under the real backend a line is only printed when RCCL had --gpus ranks; this run says it had none)
     assert d["rccl_ranks"] is None and "test hook" in d["rccl_ranks_source"]
 

@@ -1,6 +1,7 @@
 # fabric / L2 counters of the walks per proof at 1 024 and 8 192 proofs per launch (schedule 114); counters only, no tracing
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$REPO" || exit 1
 O=gpurun_out/r6_ab_pmc
 mkdir -p $O
 for cfg in "1024 5 3" "8192 3 2"; do

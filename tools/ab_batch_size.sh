@@ -1,4 +1,4 @@
-cd $GRAFT_REPO_ROOT
+cd "$(dirname "$0")/.." || exit 1
 for cfg in "1024 5 12" "2048 5 8" "4096 5 6" "8192 3 4"; do
   set -- $cfg
   RLNAMD_WINDOW_BITS=114 RLNAMD_SLOTS=$2 timeout 400 python bench.py --batch $1 --steps $3 --warmup 2 --no-side-configs --no-cpu-baseline --sustained-seconds 6 > gpurun_out/r6_ab_batch_$1.json 2> gpurun_out/r6_ab_batch_$1.err

@@ -8,8 +8,9 @@
 #   stats     rocprofv3 --kernel-trace --stats of the driver's bench command line restricted to FULL proofs (the finish and
 #             sustained legs of the default line launch the same kernels with other durations: their averages would mix)
 #   finish    the same for `bench.py --workload finish`, tools/finish_latency.py and the timeline of one finish per call
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT" || exit 1
+cd "$REPO" || exit 1
 TAG=${1:-prof}; shift
 WHAT=${*:-latency timeline pmc stats}
 O=gpurun_out/$TAG

@@ -3,7 +3,7 @@
 64 / 128 / 256 (c = 8 tables).  Run with RLNAMD_LANECHUNK=<threshold> to compare the small-batch shapes with the lanes =
 proofs pipeline (profiles/r3_rocprof_summary.md section 10).  Prints one JSON line."""
 import json, os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zerokit_amd import workload
 from zerokit_amd.batch import BatchProver
 out = {"RLNAMD_LANECHUNK": os.environ.get("RLNAMD_LANECHUNK")}

@@ -1,6 +1,5 @@
 import json, os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zerokit_amd import workload
 from zerokit_amd.batch import BatchProver
 p = BatchProver(max_batch=64)

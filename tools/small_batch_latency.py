@@ -8,7 +8,6 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from zerokit_amd import workload  # noqa: E402
 from zerokit_amd.batch import BatchProver  # noqa: E402
 

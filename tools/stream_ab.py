@@ -12,7 +12,6 @@ import collections
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 if os.environ.get("RLN_AB_TORCH"):      # what bench.py does under the driver: torch (and its bundled HIP runtime) first
     import torch
     if os.environ["RLN_AB_TORCH"] == "1":

@@ -168,7 +168,7 @@ struct DeviceCount {   // (a member of Impl: a constructor that throws half-way 
 
 struct Prover::Impl {
   hipStream_t sA = nullptr, sAb = nullptr, sA2 = nullptr, sB = nullptr, sB2 = nullptr, sC = nullptr;
-  // EIGHT streams in all: ROCclr maps streams onto GPU_MAX_HW_QUEUES (8, set by common.cpp) hardware queues and two streams
+  // EIGHT streams in all: ROCclr maps streams onto GPU_MAX_HW_QUEUES hardware queues (see common.cpp) and two streams
   // that share a queue serialise -- a ninth stream was measured as a 0.12 ms hole in the single-proof timeline
   hipStream_t sV = nullptr;   // proof values (24 chained Poseidon hashes per proof, latency-bound: ~17 ms of a 46 ms step)
   hipStream_t sW = nullptr;   // wipes: a stream of their own -- on sC a wipe would queue behind the back ends of every later
@@ -1994,7 +1994,11 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // proofs, ~28 ms), A2 = mat-vec + NTTs + quotient (throughput kernels squeezed in beside the MSM, ~25 ms contended).
   // Chained on one stream they were the critical path (54 ms against 49 ms of MSM).
   const uint32_t sq = D.seq++;
-  hipStream_t sA = (sq & 1) ? D.sAb : D.sA;   // two graph interpreters in flight: 16 latency-bound waves each
+  // With nothing of this prover in flight there is no second interpreter to overlap with, and the batch takes sA: on two
+  // hardware queues sAb shares one with sC and sW, and a lone call on it measured 1.31 against 0.89 ms on sA.
+  const bool idle = !D.last || hipEventQuery(D.last->evC) == hipSuccess;
+  (void)hipGetLastError();   // hipErrorNotReady is not an error here
+  hipStream_t sA = (!idle && (sq & 1)) ? D.sAb : D.sA;   // two graph interpreters in flight: 16 latency-bound waves each
   const uint32_t B = (uint32_t)B_, nb = (uint32_t)n;
   // Lone small batches: the G2 chain (recode, walk, sums, inversion, B's bytes -- the longest thing behind the interpreter)
   // stays on the interpreter's own stream, so nothing but kernel boundaries separates its links; the quotient chain
