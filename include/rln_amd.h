@@ -83,7 +83,7 @@ typedef struct {
   uint64_t table_bytes;      /* HBM held by the fixed-base tables */
   int32_t window_bits, windows;       /* G1 comb: narrow window width; table additions per G1 point and proof */
   int32_t window_bits_g2, windows_g2; /* the same for the G2 comb */
-  int32_t glv;                        /* 1: scalars are split k1 + lambda k2 and the combs cover 127 bits */
+  int32_t glv;                        /* always 1: scalars are split k1 + lambda k2 and the combs cover 127 bits */
   int32_t reserved;
   uint64_t g1_rows, g2_rows;          /* finite points of the G1 / G2 walk (table rows) */
 } rlnamd_prover_info;

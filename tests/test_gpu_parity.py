@@ -768,18 +768,17 @@ def test_lane_chunk_walk_and_clock_tap(monkeypatch):
 @pytest.mark.parametrize("env", [
     {"RLNAMD_LONE": "0"},             # as inside a stream of batches: plain small plan, back end on its own stream
     {"RLNAMD_LONE": "1"},
-    {"RLNAMD_VALUES_WITNESS": "0"},   # proof values by the Poseidon chain instead of the circuit's public signals
     {"RLNAMD_WL_REASSOC": "0"},       # the interpreter's schedule with the circuit's sums in source order
     {"RLNAMD_WITROWS": "0"},          # lane-form products
-    {"RLNAMD_EARLY_FIN": "0", "RLNAMD_FUSED_SMUL": "0"},
     {"RLNAMD_LANECHUNK_WALK": "0"},   # the short-chunk plans walked with lanes = proofs (the shape of 49..128 proofs)
     {"RLNAMD_TINY": "0"},             # no one-entry chunks / two-stage sums: the small-batch plan for a single proof too
     {"RLNAMD_TINY": "8"},             # ... and that shape for the batch of five as well
 ], ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
 def test_small_batch_shape_variants_give_the_golden_bytes(monkeypatch, env):
-    """Every latency shape of the single-proof path has a switch that restores the shape it replaced (DESIGN section 4,
-    "Small batches"); each combination must give the golden proof bytes, public inputs and witness digest -- for one
-    proof and for a batch of five, also when the batch is NOT alone on the device (two batches back to back)."""
+    """The switches that pin a shape of the single-proof path ("Small batches") -- a forced lone or
+    stream state, the interpreter's schedule forms, the walk and plan thresholds; each must give the golden proof bytes,
+    public inputs and witness digest -- for one proof and for a batch of five, also when the batch is NOT alone on the
+    device (two batches back to back)."""
     import hashlib
     from zerokit_amd.batch import BatchProver
     for k, v in env.items():
@@ -789,9 +788,7 @@ def test_small_batch_shape_variants_give_the_golden_bytes(monkeypatch, env):
     p = BatchProver(max_batch=64)
     try:
         # the switches are read once, when the prover is built, and rlnamd_prover_describe reports the values in force
-        names = {"RLNAMD_LONE": "lone", "RLNAMD_VALUES_WITNESS": "values_from_witness",
-                 "RLNAMD_EARLY_FIN": "early_fin", "RLNAMD_FUSED_SMUL": "fused_smul", "RLNAMD_LANECHUNK_WALK": "lanechunk_walk",
-                 "RLNAMD_TINY": "tiny"}
+        names = {"RLNAMD_LONE": "lone", "RLNAMD_LANECHUNK_WALK": "lanechunk_walk", "RLNAMD_TINY": "tiny"}
         desc = p.describe().split()
         for k, v in env.items():
             if k in names:
@@ -1216,11 +1213,10 @@ def _golden_batch(p, cases, ws, rs, tag):
         assert p.verify(o["proof"], o["public_inputs"])
 
 
-def test_mixed_window_schedules_give_the_same_proofs(monkeypatch):
+def test_mixed_glv_window_schedules_give_the_same_proofs():
     """The comb tables may use (c + 1)-bit windows for the first few windows and different schedules for G1 and G2
-    (window_bits = g1 + 10000 * g2, spec = c + 100 * wide), over the 127-bit halves of the GLV split or -- RLNAMD_GLV=0
-    -- over the whole 254-bit scalar.  Group elements are canonical, so every schedule must return the golden proof
-    bytes."""
+    (window_bits = g1 + 10000 * g2, spec = c + 100 * wide), over the 127-bit halves of the GLV split.  Group elements
+    are canonical, so every schedule must return the golden proof bytes."""
     from zerokit_amd.batch import BatchProver
     cases = _cases()["cases"]
     ws, rs = [_w(c) for c in cases], [(int(c["r"]), int(c["s"])) for c in cases]
@@ -1229,14 +1225,6 @@ def test_mixed_window_schedules_give_the_same_proofs(monkeypatch):
         p = BatchProver(max_batch=64, window_bits=wb)
         try:
             assert int(p.info.glv) == 1 and int(p.info.windows) == w1 and int(p.info.windows_g2) == w2
-            _golden_batch(p, cases, ws, rs, wb)
-        finally:
-            p.close()
-    monkeypatch.setenv("RLNAMD_GLV", "0")
-    for wb, w1 in ((708, 31), (1010, 25)):   # 7x9+24x8 = 255, 10x11+15x10 = 260 bits
-        p = BatchProver(max_batch=64, window_bits=wb)
-        try:
-            assert int(p.info.glv) == 0 and int(p.info.windows) == w1 and int(p.info.windows_g2) == w1
             _golden_batch(p, cases, ws, rs, wb)
         finally:
             p.close()

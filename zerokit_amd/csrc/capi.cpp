@@ -257,7 +257,7 @@ void fill_prover_info(const Prover& P, rlnamd_prover_info* info) {
   info->windows = P.windows();
   info->window_bits_g2 = P.window_bits_g2();
   info->windows_g2 = P.windows_g2();
-  info->glv = P.glv() ? 1 : 0;
+  info->glv = 1;   // the walks always take the GLV split
   info->reserved = 0;
   info->g1_rows = P.g1_rows();
   info->g2_rows = P.g2_rows();

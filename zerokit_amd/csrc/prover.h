@@ -43,10 +43,12 @@ struct ProverConfig {
 };
 
 // Every switch of the prover, read from the environment ONCE when a Prover is built (ProverTuning::from_env; printed by
-// rlnamd_prover_describe).  Sizes choose an operating point; the shape switches force one of two production shapes --
-// both are what batches of some size / pipeline state take anyway -- so that the parity tests can pin each of them
+// rlnamd_prover_describe).  Sizes choose an operating point; the shape of a batch follows from its size, its mode,
+// whether it is alone on the device, the circuit and the partial-proof cache.  The remaining shape switches reach a
+// fallback (wit29) or override a detected condition (lone), so that the parity tests can pin each shape
 // (tests/test_gpu_parity.py: test_small_batch_shape_variants_give_the_golden_bytes).  Tuning constants whose alternative
-// lost every A/B (NTT through Fr29, the 8 x 32 walk, copy-engine staging, one interpreter stream, ...) are gone.
+// lost every A/B (NTT through Fr29, the 8 x 32 walk, the plain 255-bit walk, copy-engine staging, one interpreter
+// stream, ...) are gone.
 struct ProverTuning {
   // ---- sizes
   int window_bits = 120010;            // RLNAMD_WINDOW_BITS: comb schedule g1 + 10000 * g2, each c + 100 * wide;
@@ -63,14 +65,9 @@ struct ProverTuning {
   uint32_t ntt_lg_max = 96;            // RLNAMD_NTT_LG_MAX: largest small batch whose NTTs run as the three LDS kernels (above, the
                                        // single-wave passes finish earlier beside the walks: 128 proofs 13.2 -> 12.6 ms)
   // ---- shapes (1 = default)
-  bool glv = true;                     // RLNAMD_GLV: walk the 127-bit GLV halves (0: the plain 255-bit walk)
   bool wit29 = true;                   // RLNAMD_WIT29: interpreter in the 9 x 29 form (0: the 8 x 32 fallback k_witness)
   int lone = -1;                       // RLNAMD_LONE: -1 detect whether a batch is alone on the device, 0 / 1 force
   uint32_t lone_small_max = 48;        // RLNAMD_LONE_SMALL: batches of at most this many proofs take the lone (latency) shapes even behind a batch in flight
-  bool early_walk = true;              // RLNAMD_EARLY_WALK: small batches walk the h-independent rows beside the NTTs
-  bool early_fin = true;               // RLNAMD_EARLY_FIN: small batches finish A, B1 before the h rows are walked
-  bool fused_smul = true;              // RLNAMD_FUSED_SMUL: a lone small proof takes s A, r B1 as rows of the C segment
-  bool values_from_witness = true;     // RLNAMD_VALUES_WITNESS: small batches read the proof values off the witness
   uint32_t hint_max = 24;              // RLNAMD_HINTS: largest lone batch interpreted as independent segments behind host-computed hints (cold chains on 8 host threads: 12 / 16 / 24 proofs 3.2 / 3.7 / 4.3 -> 2.5 / 3.0 / 3.9 ms, even at 32)
                                        // (the values between the circuit's chained hashes; 0: never).  A proof's hints are ~0.3 ms of
                                        // hashing on a host core (the proofs of a batch on a thread each) against ~1.3 ms of interpreter
@@ -78,9 +75,6 @@ struct ProverTuning {
   uint32_t hint_max_warm = 64;         // RLNAMD_HINTS_WARM: ... and up to this many when at most 2.5 chains per host thread have to be hashed (the others are remembered: hint_chains)
   uint32_t hint_threads = 8;           // RLNAMD_HINT_THREADS: host threads (the caller's included) that hash the hint chains of a batch's proofs; at most half of the host's hardware threads unless set
   int hint_fault = 0;                  // RLNAMD_HINT_FAULT (test hook): j > 0 corrupts hint j - 1 of the first proof of every hinted batch
-  bool d2h_kernel = true;              // RLNAMD_D2H_KERNEL: big batches copy their results home by a single-wave kernel (0: hipMemcpyAsync)
-  // ---- diagnostics
-  bool marks_small = false;            // RLNAMD_MARKS_SMALL: record stage timing marks for small batches too
   static ProverTuning from_env();
   std::string describe() const;
 };
@@ -114,7 +108,6 @@ class Prover {
   int windows() const { return W_; }          // table additions per G1 point and proof (windows x GLV halves)
   int window_bits_g2() const { return c2_; }
   int windows_g2() const { return W2_; }
-  bool glv() const { return glv_; }
   size_t g1_rows() const;                     // table rows (finite points) of the G1 / G2 walk
   size_t g2_rows() const;
   size_t inputs_per_proof() const { return graph_.inputs_size; }
@@ -240,7 +233,6 @@ class Prover {
   size_t B_ = 0;
   float init_ms_[4] = {0, 0, 0, 0};
   int c_ = 8, W_ = 32, c2_ = 8, W2_ = 32;
-  bool glv_ = true;
 };
 
 }  // namespace rlnamd

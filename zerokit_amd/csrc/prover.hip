@@ -400,7 +400,7 @@ struct Prover::Impl {
   Slot slot[NSLOT];
   int nslot = 5;                // Tuning::slots
   WinSched ws{}, ws2{};         // window schedules of the G1 and G2 comb tables
-  uint32_t nh = 2;              // halves per scalar: 2 = GLV split (k1 + lambda k2), 1 = plain 254-bit walk
+  static constexpr uint32_t nh = 2;   // halves per scalar: the GLV split k1 + lambda k2 (glv.h)
   int cur = 0;
   Slot* last = nullptr;
   uint64_t tickets = 0;         // submit() tickets handed out
@@ -524,19 +524,12 @@ ProverTuning ProverTuning::from_env() {
   t.lanechunk_max = (uint32_t)std::max(0, env_int("RLNAMD_LANECHUNK", (int)t.lanechunk_max));
   t.lanechunk_walk_max = (uint32_t)std::max(0, env_int("RLNAMD_LANECHUNK_WALK", (int)t.lanechunk_walk_max));
   t.witlanes_max = (uint32_t)std::max(0, env_int("RLNAMD_WITLANES_MAX", (int)t.witlanes_max));
-  t.glv = env_int("RLNAMD_GLV", 1) != 0;
   t.wit29 = env_int("RLNAMD_WIT29", 1) != 0;
   t.lone = env_int("RLNAMD_LONE", -1);
   t.lone_small_max = (uint32_t)std::max(0, env_int("RLNAMD_LONE_SMALL", (int)t.lone_small_max));
-  t.early_walk = env_int("RLNAMD_EARLY_WALK", 1) != 0;
-  t.early_fin = env_int("RLNAMD_EARLY_FIN", 1) != 0;
-  t.fused_smul = env_int("RLNAMD_FUSED_SMUL", 1) != 0;
-  t.values_from_witness = env_int("RLNAMD_VALUES_WITNESS", 1) != 0;
   t.tiny_max = (uint32_t)std::max(0, env_int("RLNAMD_TINY", (int)t.tiny_max));
   t.ntt_lg_max = (uint32_t)std::max(0, env_int("RLNAMD_NTT_LG_MAX", (int)t.ntt_lg_max));
   t.partial_cache = (uint32_t)std::max(0, env_int("RLNAMD_PARTIAL_CACHE", (int)t.partial_cache));
-  t.marks_small = env_int("RLNAMD_MARKS_SMALL", 0) != 0;
-  t.d2h_kernel = env_int("RLNAMD_D2H_KERNEL", 1) != 0;
   t.hint_max = (uint32_t)std::min<int>(std::max(0, env_int("RLNAMD_HINTS", (int)t.hint_max)), (int)HINT_PROOFS);
   t.hint_fault = env_int("RLNAMD_HINT_FAULT", 0);
   {   // (at most half of the host's hardware threads unless the switch says otherwise)
@@ -551,12 +544,10 @@ ProverTuning ProverTuning::from_env() {
 std::string ProverTuning::describe() const {
   char b[768];
   snprintf(b, sizeof b,
-           "window_bits=%d slots=%d lanechunk=%u lanechunk_walk=%u witlanes_max=%u tiny=%u ntt_lg_max=%u partial_cache=%u glv=%d wit29=%d lone=%d "
-           "lone_small=%u early_walk=%d early_fin=%d fused_smul=%d values_from_witness=%d marks_small=%d d2h_kernel=%d hints=%u hints_warm=%u "
-           "hint_threads=%u hint_chains=%u",
-           window_bits, slots, lanechunk_max, lanechunk_walk_max, witlanes_max, tiny_max, ntt_lg_max, partial_cache, (int)glv, (int)wit29, lone,
-           lone_small_max, (int)early_walk, (int)early_fin, (int)fused_smul, (int)values_from_witness, (int)marks_small, (int)d2h_kernel,
-           hint_max, hint_max_warm, hint_threads, hint_chains);
+           "window_bits=%d slots=%d lanechunk=%u lanechunk_walk=%u witlanes_max=%u tiny=%u ntt_lg_max=%u partial_cache=%u wit29=%d lone=%d "
+           "lone_small=%u hints=%u hints_warm=%u hint_threads=%u hint_chains=%u",
+           window_bits, slots, lanechunk_max, lanechunk_walk_max, witlanes_max, tiny_max, ntt_lg_max, partial_cache, (int)wit29, lone,
+           lone_small_max, hint_max, hint_max_warm, hint_threads, hint_chains);
   return b;
 }
 const ProverTuning& Prover::tuning() const { return d_->tune; }
@@ -618,12 +609,12 @@ static void build_table29(const std::vector<Affine<F>>& pts, const WinSched& ws,
   g_init_ms[2] += ms_since(t_build);
 }
 
-// c-bit windows, the first `wide` of them one bit wider; W = the fewest windows that cover `total` bits: 255 for the
-// plain walk (254-bit scalars plus the carry of the signed recoding), 127 for the halves of a GLV split (< 2^126)
-static WinSched make_sched(int c, int wide, int total) {
+// c-bit windows, the first `wide` of them one bit wider; W = the fewest windows that cover the 127 bits of a GLV half
+// (< 2^126, plus the carry of the signed recoding)
+static WinSched make_sched(int c, int wide) {
   if (c < 2 || c > 16 || wide < 0 || c + (wide > 0 ? 1 : 0) > 16) throw Error("window bits must be in [2, 16]");
   WinSched ws{};
-  int W = (total - wide + c - 1) / c;
+  int W = (GlvParams::HALF_BITS - wide + c - 1) / c;
   if (wide > W) throw Error("more wide windows than windows");
   if (W > 32) throw Error("window bits too small: more than 32 windows");
   ws.W = W;
@@ -652,23 +643,20 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
   g_init_ms[0] = ms_since(t_ctor);
   Impl& D = *d_;
   // window_bits = g1 + 10000 * g2, each spec = c + 100 * wide: c-bit windows, the first `wide` of them (c + 1)-bit
-  // (see WinSched); g2 = 0: the G2 table takes the G1 schedule.  With the GLV split (default; RLNAMD_GLV=0 keeps the
-  // plain 254-bit walk) the windows cover the 127-bit halves: spec 114 = 15 + 8 x 14 bits, 9 windows, 18 additions
-  // per G1 point; spec 715 = 7 x 16 + 15 bits, 8 windows, 16 additions per G2 point.
+  // (see WinSched); g2 = 0: the G2 table takes the G1 schedule.  The windows cover the 127-bit halves of the GLV split:
+  // spec 114 = 15 + 8 x 14 bits, 9 windows, 18 additions per G1 point; spec 715 = 7 x 16 + 15 bits, 8 windows, 16
+  // additions per G2 point.
   D.tune = ProverTuning::from_env();
   const int wb = cfg.window_bits > 0 ? cfg.window_bits : D.tune.window_bits;
   D.tune.window_bits = wb;
   const int spec1 = wb % 10000, spec2 = wb / 10000 ? wb / 10000 : spec1;
-  D.nh = D.tune.glv ? 2 : 1;
-  const int total = D.nh == 2 ? GlvParams::HALF_BITS : 255;
   c_ = spec1 % 100;
   const int wide = spec1 / 100;
-  D.ws = make_sched(c_, wide, total);
-  D.ws2 = make_sched(spec2 % 100, spec2 >= 100 ? spec2 / 100 : (wb / 10000 ? 0 : wide), total);
+  D.ws = make_sched(c_, wide);
+  D.ws2 = make_sched(spec2 % 100, spec2 >= 100 ? spec2 / 100 : (wb / 10000 ? 0 : wide));
   W_ = D.ws.W * D.nh;
   c2_ = spec2 % 100;
   W2_ = D.ws2.W * D.nh;
-  glv_ = D.nh == 2;
   B_ = ((cfg.max_batch ? cfg.max_batch : 1) + 63) / 64 * 64;
   D.batch_cap = B_;
 
@@ -1348,9 +1336,8 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     std::vector<VRow> vrows;
     for (uint32_t k = 0; k < sids.size(); k++)
       vrows.push_back({k, sids[k], sids[k], row_seg[k], sids[k] >= D.NS && sids[k] < D.NS + D.n});
-    // rows (x halves) per single-wave workgroup: ~150 additions each, as before the split (8 rows x 19 windows)
-    make_plans(vrows, 3, (uint32_t)(D.nh == 2 ? 16 : 8), D.plan1, &D.max_chunks1,
-               &D.max_groups1, -1, npaired, true);
+    // rows (x halves) per single-wave workgroup
+    make_plans(vrows, 3, 16u, D.plan1, &D.max_chunks1, &D.max_groups1, -1, npaired, true);
     {
       uint32_t unused = 0;
       make_plans(vrows, 3, 4u, D.plan1s, &D.max_chunks1s, &unused, -1, npaired);
@@ -1410,8 +1397,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     D.sid2.upload(dsid.data(), dsid.size(), s);
     std::vector<VRow> vrows;
     for (uint32_t k = 0; k < sids.size(); k++) vrows.push_back({k, sids[k], dsid[k], 0u, false});
-    make_plans(vrows, 1, (uint32_t)(D.nh == 2 ? 8 : 4), D.plan2, &D.max_chunks2,
-               &D.max_groups2, -1);
+    make_plans(vrows, 1, 8u, D.plan2, &D.max_chunks2, &D.max_groups2, -1);
     {
       uint32_t unused = 0;
       make_plans(vrows, 1, 2u, D.plan2s, &D.max_chunks2s, &unused, -1);
@@ -1878,12 +1864,14 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   const bool lone = lone_force >= 0 ? lone_force != 0
                                     : (n <= T.lone_small_max || !D.last || hipEventQuery(D.last->evC) == hipSuccess);
   (void)hipGetLastError();   // hipErrorNotReady is not an error here
-  const bool small = n <= D.lanechunk_max && n <= D.small_stride;   // lanes = chunks
+  // small batches (ProverTuning::lanechunk_max) take the latency shapes: walks with lanes = chunks (walk29.h), kernels with
+  // the lanes on one proof's elements, the copy engine for the results.  (n <= B_, so such a batch fits in small_stride.)
+  const bool small = n <= D.lanechunk_max;
   // The lanes = nodes interpreter (a wave and 157 KB of LDS per proof, ~25 x the instructions per proof of k_witness29,
   // 1.5 ms per 256 proofs against 11 ms): always below the small-batch threshold; up to witlanes_max only for a LONE batch -- in a stream
   // of such batches it costs throughput (profiles/r3_rocprof_summary.md, section 10), and there the previous batch is still in flight.
   const uint32_t wl_lone_max = D.device.shared() ? std::min(D.witlanes_max, 256u) : D.witlanes_max;
-  const bool wl_used = D.wit29 && D.witlanes.ok && (n <= D.lanechunk_max || (n <= wl_lone_max && lone));
+  const bool wl_used = D.wit29 && D.witlanes.ok && (small || (n <= wl_lone_max && lone));
   // Finish with the partial run's values at hand (prover.h: submit_finish): every proof of the batch has a live cache
   // entry and the batch is one the wave-per-proof interpreter takes -> the known rows come back from the cache and only
   // the cone evaluate_partial leaves unknown is interpreted (depth-20 circuit: 1 947 of 23 414 nodes, a twelfth of the
@@ -1944,18 +1932,17 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // 0.1 - 0.15 ms), the digits of the witness scalars are recoded right behind the interpreter, and both walks start on
   // everything that does not depend on the quotient h while mat-vec / NTTs still run; only the h rows of the G1 walk
   // wait for them.
-  const bool early = n <= D.lanechunk_max && mode != PROVE_PARTIAL && T.early_walk;
-  // small full proofs: s A and r B1 are rows of the C segment (plan1f), no k_fin_smul
+  const bool early = small && mode != PROVE_PARTIAL;
+  // small full proofs: s A and r B1 are rows of the C segment (plan1f), no ladder; the back end is the split one below
   // (up to 96 proofs: above, the walks are issue-bound even for a lone batch and the extra rows cost more than the ladder
   // they replace -- 128 proofs 16.6 -> 15.3 ms without them, 64 proofs 10.1 -> 10.3 ms)
   // (round 6: a streamed finish takes it too -- the variable-base part that is left, s pi_a + r rho,
   // comes from powers of the two points: k_pp_smul -- cached with the partial run's values, or made beside the interpreter)
-  const bool fused = lone && n <= 96 && early && small && (mode == PROVE_FULL || (mode == PROVE_FINISH && h_inputs && h_pp320)) &&
-                     D.nh == 2 && T.fused_smul && T.early_fin;   // (its back end is the split one below)
+  const bool fused = lone && n <= 96 && early && (mode == PROVE_FULL || (mode == PROVE_FINISH && h_inputs && h_pp320));
   // tiny: a lane per (row, half) and a two-stage sum (plan1tf / plan2t) -- only the fused full proof of a lone batch, and
   // only when it walks with lanes = chunks (the lanes = proofs form of the mid-size batches needs 64 proofs of stride)
   // (round 6: a lone tiny PARTIAL proof as well -- its plan is the plain rows of the known signals, one per lane)
-  const bool tiny_partial = lone && small && mode == PROVE_PARTIAL && D.nh == 2 && n <= T.tiny_max && n <= Impl::tiny_stride &&
+  const bool tiny_partial = lone && small && mode == PROVE_PARTIAL && n <= T.tiny_max && n <= Impl::tiny_stride &&
                             n <= D.lanechunk_walk_max;
   const bool tiny = (fused && n <= T.tiny_max && n <= Impl::tiny_stride && n <= D.lanechunk_walk_max) || tiny_partial;
   const Impl::Plan& P1 = tiny ? D.plan1tf[mode] : fused ? D.plan1f[mode] : small ? D.plan1s[mode] : D.plan1[mode];
@@ -1965,7 +1952,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // (64: 11.3 -> 9.9 ms, 128: 18.1 -> 16.3 ms; 32: 6.9 ms against 8.4).  In a stream of batches the lanes = chunks form
   // pays its scattered gathers in throughput much earlier (streams of 64 / 128-proof batches: 9.5 -> 10.8 k, 10.7 -> 11.9 k
   // proofs/s), so there it stops at 16 proofs.
-  const bool walk_lp = small && early && (n > D.lanechunk_walk_max || (!lone && n >= 16));
+  const bool walk_lp = early && (n > D.lanechunk_walk_max || (!lone && n >= 16));
   // proof stride of the digit arrays: compact where the walks run with lanes = chunks (k_recode); the batch capacity
   // otherwise (the lanes = proofs walks have padding lanes that read beside the batch: those must stay digits of the
   // same window)
@@ -2013,9 +2000,8 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // runtime's copy kernel behind hipMemcpyAsync is a multi-wave workgroup that waits for wave slots beside the walks
   // (profiles/r6_kernel_stats.csv: __amd_rocclr_copyBuffer 0.45 ms on average, 17 ms at worst, for 0.3 MB).  Small batches
   // keep the copy engine path (5 us each, nothing beside them).
-  const bool d2h_kernel = n > D.lanechunk_max && T.d2h_kernel;
   auto d2h = [&](void* host, const void* dev, size_t bytes, hipStream_t st) {
-    if (d2h_kernel && bytes % 16 == 0)
+    if (!small && bytes % 16 == 0)
       hipLaunchKernelGGL(k_stage_in, dim3(div_up(bytes / 16, 64)), dim3(64), 0, st, (const uint4*)dev, (uint4*)host, (uint32_t)(bytes / 16));
     else
       RLN_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
@@ -2037,8 +2023,8 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   }
   // Timing marks (stage_ms): a timed event record is a barrier packet and a timestamp write on its stream -- three of
   // them sit between the interpreter and the mat-vec of a single proof (~0.1 ms of its 5 ms).  Small batches record
-  // them only when asked to (RLNAMD_MARKS_SMALL=1; tools/single_latency.py); their stage_ms reads 0 otherwise.
-  const bool marks = nb > D.lanechunk_max || T.marks_small;
+  // none: their stage_ms reads 0.
+  const bool marks = !small;
   S.marked = marks;
 #define MARK(i, stream)                                   \
   do {                                                    \
@@ -2091,7 +2077,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     } else
     hipLaunchKernelGGL(k_witness29<false>, dim3(pg), dim3(64), WIT29_LDS_BYTES, sA, D.nodes29.p, D.nprog29,
                        D.consts29.p, (uint32_t)graph_.constants.size(), in_p, D.NI, S.V29.p, S.err.p, B, nbp, nullptr);
-    if (nb <= D.lanechunk_max)
+    if (small)
       hipLaunchKernelGGL(k_v29_to_fr, dim3(div_up(D.nstore29, 64), nb), dim3(64, 1), 0, sA, S.V29.p, D.slot2node.p,
                          D.nstore29, S.V.p, B, nb, 1u);
     else
@@ -2114,7 +2100,6 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // Small batches (latency): the digits of the witness scalars and of r, s are recoded right behind the interpreter,
   // so the G2 walk -- the longer of the two, and independent of the quotient h -- starts beside mat-vec / NTT instead
   // of behind them; only h's digits wait for the NTTs.
-  const bool early_g2 = early;
   RLN_HIP(hipEventRecord(S.evX, sA));   // mat-vec / NTT (sA2) need the witness, not the recodes below
   if (early) {
     // The witness digits right behind the interpreter, on its stream.  A lone batch keeps its whole G2 chain there
@@ -2123,14 +2108,14 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     // and both walks wait for them on their own streams.
     hipStream_t sR1 = sA, sR3 = lone ? D.sB : sA;
     hipLaunchKernelGGL(k_recode, dim3(div_up(D.NS + 3, 64), nb), dim3(64, 1), 0, sR1, S.V.p, D.sig2node.p, D.NS,
-                       S.abc.p, D.n, rs_p, D.ws, D.ws2, D.nh, S.digits.p, S.digits2.p, B, nb, 1u, 1u, dB);
+                       S.abc.p, D.n, rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nb, 1u, 1u, dB);
     if (lone) {
       RLN_HIP(hipEventRecord(S.evW, sA));
       RLN_HIP(hipStreamWaitEvent(D.sB, S.evW, 0));
     }
     if (fused)
       hipLaunchKernelGGL(k_recode, dim3(div_up(2 * D.NS + 1, 64), nb), dim3(64, 1), 0, sR3, S.V.p, D.sig2node.p, D.NS,
-                         S.abc.p, D.n, rs_p, D.ws, D.ws2, D.nh, S.digits.p, S.digits2.p, B, nb, 3u, 1u, dB);
+                         S.abc.p, D.n, rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nb, 3u, 1u, dB);
     if (!lone) {
       RLN_HIP(hipEventRecord(S.evW, sA));
       RLN_HIP(hipStreamWaitEvent(D.sB, S.evW, 0));
@@ -2152,7 +2137,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   MARK(12, sA2);
   if (mode != PROVE_PARTIAL) {  // the quotient h depends on the whole witness: not part of a partial proof
     CsrView A{D.a_ptr.p, D.a_col.p, D.a_coef.p}, Bm{D.b_ptr.p, D.b_col.p, D.b_coef.p};
-    if (nb <= D.lanechunk_max)
+    if (small)
       hipLaunchKernelGGL(k_matvec<true>, dim3(div_up(D.n, 64) + D.n_mv_long, nb), dim3(64, 1), 0, sA2, A, Bm, S.V.p,
                          D.sig2node.p, D.nc, D.ni, D.n, S.abc.p, B, nb, D.mv_long.p, div_up(D.n, 64));
     else
@@ -2161,11 +2146,11 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   }
   MARK(3, sA2);
   if (mode != PROVE_PARTIAL) {
-    const bool lg = nb <= D.lanechunk_max;   // below a wave of proofs: lanes = groups
+    // small batches: lanes = groups
     // (above ~100 proofs the walks beside the quotient chain leave the 4-wave workgroups of the LDS kernels waiting for
     // four free wave slots on one CU: the single-wave passes then finish earlier -- 128 proofs 13.3 -> 12.6 ms, 96 and
     // below no better or worse; RLNAMD_NTT_LG_MAX)
-    if (lg && nb <= D.tune.ntt_lg_max && D.logn >= 9 && D.logn <= 18) {
+    if (small && nb <= D.tune.ntt_lg_max && D.logn >= 9 && D.logn <= 18) {
       // iNTT, coset scaling and NTT as edge / mid / edge: one butterfly per lane per level (prover_front.hip: k_ntt_mid)
       const dim3 grid(nb, D.n >> 9, 3);
       if (D.logn > 9) hipLaunchKernelGGL(k_ntt_edge<true>, grid, dim3(256), 0, sA2, S.abc.p, D.tw_i.p, D.logn, B, nb);
@@ -2176,32 +2161,26 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
       launch_ntt<true>(S.abc.p, D.tw_i.p, D.logn, D.coset.p, B, nbp, sA2);   // iNTT (DIF) + g^i / n
       launch_ntt<false>(S.abc.p, D.tw_f.p, D.logn, nullptr, B, nbp, sA2);    // NTT (DIT)
     }
-    if (early_g2) {
-      // (the recode below forms h = a o b - c itself)
-    } else if (nb <= D.lanechunk_max)
-      hipLaunchKernelGGL(k_hquot, dim3(div_up(D.n, 64), nb), dim3(64, 1), 0, sA2, S.abc.p, D.n, B, nb, 1u);
-    else
+    if (!early)   // (early: the recode below forms h = a o b - c itself)
       hipLaunchKernelGGL(k_hquot, dim3(pg, D.n), dim3(64, 1), 0, sA2, S.abc.p, D.n, B, nbp, 0u);
   }
   MARK(4, sA2);
   // digit recoding closes the front end: the MSM streams carry nothing but the two table walks
   hipStream_t sR = sA2;
   MARK(5, sR);
-  if (early_g2)
+  if (early)
     hipLaunchKernelGGL(k_recode, dim3(div_up(D.n, 64), nb), dim3(64, 1), 0, sR, S.V.p, D.sig2node.p, D.NS, S.abc.p, D.n,
-                       rs_p, D.ws, D.ws2, D.nh, S.digits.p, S.digits2.p, B, nb, 2u, 2u, dB);
+                       rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nb, 2u, 2u, dB);
   else
     hipLaunchKernelGGL(k_recode, dim3(pg, D.NS + D.n + 3), dim3(64, 1), 0, sR, S.V.p, D.sig2node.p, D.NS,
-                       S.abc.p, D.n, rs_p, D.ws, D.ws2, D.nh, S.digits.p, S.digits2.p, B, nbp, 0u, 0u, dB);
+                       S.abc.p, D.n, rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nbp, 0u, 0u, dB);
   MARK(6, sR);
   // ---------------- stage B
   if (!early) {
     RLN_HIP(hipEventRecord(S.evA, sA2));
     RLN_HIP(hipStreamWaitEvent(D.sB, S.evA, 0));
+    MARK(14, D.sB);
   }
-  if (!early) MARK(14, D.sB);
-  // small batches walk with lanes = chunks (walk29.h); ProverTuning::lanechunk_max is the threshold
-  const bool lanechunk = nb <= D.lanechunk_max;
   hipStream_t s2 = g2_on_front ? sA : D.sB2;   // the G2 walk on its own stream: its workgroups fill the G1 kernel's tail
   if (!early) {   // (early: the G2 walk's stream already has the witness + part-1 digits, all it reads)
     RLN_HIP(hipEventRecord(S.evR, D.sB));
@@ -2220,7 +2199,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     RLN_HIP(hipStreamWaitEvent(D.sB, S.evR, 0));   // evB below then covers both launches
   } else if (P1.nchunks) {
     uint32_t blocks = div_up(P1.nchunks, 8) * 8 * pg;
-    if (lanechunk)
+    if (small)
       hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 2, true>), dim3(div_up(P1.nchunks, 64), nb), dim3(64), 0, D.sB,
                          D.t1_29.p, P1.rsid.p, P1.rows.p, P1.chunks.p, P1.nchunks, S.digits.p, S.part1.p, D.ws, dB, PB, D.nh,
                          nullptr);
@@ -2244,7 +2223,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
       hipLaunchKernelGGL((k_msm29<G2AccPair29, G2Affine29, G2XYZZ, 1, true>), dim3(div_up(2 * P2.nchunks, 64), nb), dim3(64), 0, s2,
                          D.t2_29.p, P2.rsid.p, P2.rows.p, P2.chunks.p, P2.nchunks, S.digits2.p, S.part2.p, D.ws2, dB, PB, D.nh,
                          nullptr);
-    else if (lanechunk)
+    else if (small)
       hipLaunchKernelGGL((k_msm29<G2Acc29, G2Affine29, G2XYZZ, 1, true>), dim3(div_up(P2.nchunks, 64), nb), dim3(64), 0, s2,
                          D.t2_29.p, P2.rsid.p, P2.rows.p, P2.chunks.p, P2.nchunks, S.digits2.p, S.part2.p, D.ws2, dB, PB, D.nh,
                          nullptr);
@@ -2266,7 +2245,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   if (streamed) RLN_HIP(hipStreamWaitEvent(sV, S.evU, 0));
   MARK(0, sV);
   // (whenever the batch is small enough for the lanes = nodes interpreter: the Poseidon chain alone is 5.3 ms)
-  const bool values_w = (early || wl_used) && D.have_values_kernel && D.ni == 6 && T.values_from_witness;
+  const bool values_w = (early || wl_used) && D.have_values_kernel && D.ni == 6;
   if (values_w) {   // small batches: the circuit's own outputs (see k_values_from_witness)
     RLN_HIP(hipStreamWaitEvent(sV, S.evX, 0));   // sA: witness stored
     hipLaunchKernelGGL(k_values_from_witness, dim3(pg, 5), dim3(64), 0, sV, S.V.p, D.sig2node.p, B, nbp, S.values.p);
@@ -2279,11 +2258,8 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // walk is done -- beside the NTTs and the walk of the h rows, not behind them.  sums1 segments: h * 3 + {A, B1, C}.
   // (round 6: PROVE_FINISH as well -- the partial points join their sums where each sum is complete, k_add_partial per
   // task; until then a lone finish took the serial back end of the big batches and was SLOWER than a lone full proof)
-  const bool early_fin = early && (mode == PROVE_FULL || mode == PROVE_FINISH) && D.nh == 2 && T.early_fin;
   const bool fin_pp = mode == PROVE_FINISH;
   const TaskSel all6 = task_sel({0, 1, 2, 3, 4, 5}), all4 = task_sel({0, 1, 2, 3}), all3 = task_sel({0, 1, 2});
-  // below a wave of proofs s A / r B1 are a lone lane's chain: NAF ladder in the 9 x 29 form (fin29.hip)
-  const bool fin29 = nb <= D.lanechunk_max;
   hipStream_t sF = D.sC;   // the stream of k_fin_out and of the copies to the host
   // segment sums of a small batch: one 512-lane tree per (proof, segment); tiny batches (four times the partial sums) in
   // two stages -- every 512-chunk block of a segment to one point, then the blocks of the segment -- so that the depth
@@ -2309,7 +2285,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
       hipLaunchKernelGGL((k_sum_tree<Fq2, G2Acc29>), dim3(nb, P2.nseg), dim3(SUM_TREE_LANES), SUM_TREE_LDS_G2, st, S.part2.p, P2.segchunks.p, S.sums2.p, B, PB, sel);
     }
   };
-  if (early_fin) {
+  if (early) {
     RLN_HIP(hipStreamWaitEvent(D.sA2, S.evE, 0));   // sB: the early G1 walk
     if (fused) {
       // fused plan: only A's segment sums are formed early; its fold and inversion ride in k_fin_out_ac_fused, and s A,
@@ -2322,10 +2298,8 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
       hipLaunchKernelGGL(k_glv_fold, dim3(pg, 2), dim3(64), 0, D.sA2, S.sums1.p, S.sums2.p, 3u, B, nbp, task_sel({0, 1}));
       hipLaunchKernelGGL(k_fin_affine, dim3(pg, 2), dim3(64), 0, D.sA2, S.sums1.p, S.sums2.p, S.affA.p, S.affB1.p,
                          S.affB2.p, B, nbp, task_sel({0, 1}));
-      if (fin29)
-        launch_fin_smul29(D.sA2, S.affA.p, S.affB1.p, rs_p, S.prod.p, B, nb);
-      else
-        hipLaunchKernelGGL(k_fin_smul, dim3(pg, 2), dim3(64), 0, D.sA2, S.affA.p, S.affB1.p, rs_p, S.tbl.p, S.prod.p, B, nbp);
+      // small batches: s A / r B1 are a lone lane's chain, the NAF ladder in the 9 x 29 form (fin29.hip)
+      launch_fin_smul29(D.sA2, S.affA.p, S.affB1.p, rs_p, S.prod.p, B, nb);
     }
     RLN_HIP(hipGetLastError());
     RLN_HIP(hipEventRecord(S.evA, D.sA2));
@@ -2384,8 +2358,8 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     RLN_HIP(hipStreamWaitEvent(D.sC, S.evB2, 0));
     MARK(9, D.sC);
   }
-  if (early_fin || tiny_partial) {
-  } else if (lanechunk) {   // small batch: lanes = partial sums (k_sum_tree)
+  if (early || tiny_partial) {
+  } else if (small) {   // (here: a small partial batch) lanes = partial sums (k_sum_tree)
     hipLaunchKernelGGL((k_sum_tree<Fq, G1Acc29>), dim3(nb, P1.nseg), dim3(SUM_TREE_LANES), SUM_TREE_LDS_G1, D.sC, S.part1.p, P1.segchunks.p, S.sums1.p, B, PB, all6);
     hipLaunchKernelGGL((k_sum_tree<Fq2, G2Acc29>), dim3(nb, P2.nseg), dim3(SUM_TREE_LANES), SUM_TREE_LDS_G2, D.sC, S.part2.p, P2.segchunks.p, S.sums2.p, B, PB, all6);
   } else {
@@ -2398,28 +2372,23 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     hipLaunchKernelGGL(k_sum_ranges<Fq>, dim3(pg, P1.nseg), dim3(64), 0, D.sC, S.grp1.p, P1.segs.p, P1.nseg, S.sums1.p, B, nbp);
     hipLaunchKernelGGL(k_sum_ranges<Fq2>, dim3(pg, P2.nseg), dim3(64), 0, D.sC, S.grp2.p, P2.segs.p, P2.nseg, S.sums2.p, B, nbp);
   }
-  if (early_fin) {
-  } else if (D.nh == 2)  // sums of the second halves through phi, onto the first: afterwards sums1[0..3) / sums2[0] as without GLV
+  if (!early)   // sums of the second halves through phi, onto the first: afterwards sums1[0..3) / sums2[0]
     hipLaunchKernelGGL(k_glv_fold, dim3(pg, 4), dim3(64), 0, D.sC, S.sums1.p, S.sums2.p, 3u, B, nbp, all4);
   if (mode == PROVE_PARTIAL) {
     hipLaunchKernelGGL(k_partial_out, dim3(pg, 4), dim3(64), 0, D.sC, S.sums1.p, S.sums2.p, S.pp_out.p, B, nbp);
     RLN_HIP(hipGetLastError());
     d2h(S.h_pp, S.pp_out.p, n * 320, D.sC);
   } else {
-    if (mode == PROVE_FINISH && !early_fin)
-      hipLaunchKernelGGL(k_add_partial, dim3(pg, 4), dim3(64), 0, D.sC, S.sums1.p, S.sums2.p, pp_p, B, nbp, all4, (const G1XYZZ*)nullptr);
-    if (!early_fin) {
+    if (!early) {   // (here: a big batch)
+      if (mode == PROVE_FINISH)
+        hipLaunchKernelGGL(k_add_partial, dim3(pg, 4), dim3(64), 0, D.sC, S.sums1.p, S.sums2.p, pp_p, B, nbp, all4, (const G1XYZZ*)nullptr);
       hipLaunchKernelGGL(k_fin_affine, dim3(pg, 3), dim3(64), 0, D.sC, S.sums1.p, S.sums2.p, S.affA.p, S.affB1.p,
                          S.affB2.p, B, nbp, all3);
-      if (fin29)
-        launch_fin_smul29(D.sC, S.affA.p, S.affB1.p, rs_p, S.prod.p, B, nb);
-      else
-        hipLaunchKernelGGL(k_fin_smul, dim3(pg, 2), dim3(64), 0, D.sC, S.affA.p, S.affB1.p, rs_p, S.tbl.p, S.prod.p, B,
-                           nbp);
-    }
-    if (!early_fin)
+      hipLaunchKernelGGL(k_fin_smul, dim3(pg, 2), dim3(64), 0, D.sC, S.affA.p, S.affB1.p, rs_p, S.tbl.p, S.prod.p, B,
+                         nbp);
       hipLaunchKernelGGL(k_fin_out, dim3(pg), dim3(64), 0, sF, S.sums1.p, S.prod.p, S.affA.p, S.affB2.p, S.coords.p,
                          S.comp.p, B, nbp);
+    }
     RLN_HIP(hipGetLastError());
     d2h(S.h_comp, S.comp.p, n * 128, sF);
     d2h(S.h_values, S.values.p, n * 160, sF);

@@ -619,10 +619,10 @@ __device__ __forceinline__ void emit_digits(uint32_t* l, bool neg, const WinSche
 }
 // Scalar ids: [0, ns) witness signals, [ns, ns + n) quotient coefficients h, then r, s, -(r s).  dig1 holds the G1
 // schedule for all of them; dig2 the G2 schedule for the ones the G2 walk uses (witness, r, s, -(r s): id - n).
-// nh = 2: every scalar is split as k1 + lambda k2 (glv.h) and both halves are recoded; nh = 1: the plain 254-bit walk.
+// Every scalar is split as k1 + lambda k2 (glv.h) and both halves are recoded.
 __global__ void __launch_bounds__(256) k_recode(const Fr* __restrict__ V, const uint32_t* __restrict__ sig2node,
                                                 uint32_t ns, const Fr* H, uint32_t n,
-                                                const uint32_t* __restrict__ rs, WinSched ws1, WinSched ws2, uint32_t nh,
+                                                const uint32_t* __restrict__ rs, WinSched ws1, WinSched ws2,
                                                 int16_t* __restrict__ dig1, int16_t* __restrict__ dig2, uint32_t B,
                                                 uint32_t nb, uint32_t part, uint32_t lg, uint32_t dB) {
   // dB: the proof stride of the digit arrays ([scalar][half][window][dB]).  The batch capacity B in the throughput
@@ -673,27 +673,17 @@ __global__ void __launch_bounds__(256) k_recode(const Fr* __restrict__ V, const 
   x.to_canonical(l);
   const bool g2 = sid < ns || (sid >= ns + n && sid < ns + n + 3);
   const uint32_t sid2 = sid < ns ? sid : sid - n;
-  if (nh == 2) {
-    uint32_t k[2][4], neg[2];
-    glv_split(l, k[0], &neg[0], k[1], &neg[1]);
+  uint32_t k[2][4], neg[2];
+  glv_split(l, k[0], &neg[0], k[1], &neg[1]);
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
-      uint32_t t[4];
-      if (g2) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) t[i] = k[h][i];
-        emit_digits<4>(t, neg[h] != 0, ws2, dig2 + ((size_t)sid2 * 2 + h) * ws2.W * dB + p, dB);
-      }
-      emit_digits<4>(k[h], neg[h] != 0, ws1, dig1 + ((size_t)sid * 2 + h) * ws1.W * dB + p, dB);
-    }
-  } else {
+  for (int h = 0; h < 2; h++) {
+    uint32_t t[4];
     if (g2) {
-      uint32_t t[8];
 #pragma unroll
-      for (int i = 0; i < 8; i++) t[i] = l[i];
-      emit_digits<8>(t, false, ws2, dig2 + (size_t)sid2 * ws2.W * dB + p, dB);
+      for (int i = 0; i < 4; i++) t[i] = k[h][i];
+      emit_digits<4>(t, neg[h] != 0, ws2, dig2 + ((size_t)sid2 * 2 + h) * ws2.W * dB + p, dB);
     }
-    emit_digits<8>(l, false, ws1, dig1 + (size_t)sid * ws1.W * dB + p, dB);
+    emit_digits<4>(k[h], neg[h] != 0, ws1, dig1 + ((size_t)sid * 2 + h) * ws1.W * dB + p, dB);
   }
 }
 
