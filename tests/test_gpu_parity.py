@@ -701,16 +701,20 @@ def test_other_circuits_throughput_shape_vs_oracle(depth, multi):
 
 
 def test_both_graph_interpreters_give_the_golden_witness(monkeypatch):
-    """The graph interpreter runs in the 9 x 29-bit limb form by default (k_witness29: static value bounds and G_RED
-    reductions chosen on the host, stored signals converted by k_v29_to_fr); RLNAMD_WIT29=0 keeps the 8 x 32 one.  Both
-    must reproduce the oracle's witness digests -- the depth-20 goldens, and the multi message-id circuit whose graph
-    carries the slow operations (Shr / Band / Neq / Div on canonical integers), TernCond and Neg."""
+    """These small batches take the lanes = nodes interpreter by default (k_witness_lanes, a wave per proof);
+    RLNAMD_WITLANES=0 turns it and the segment interpreter off, so the same batches run k_witness29 (lanes = proofs,
+    static value bounds and W29_RED reductions chosen on the host).  Both must reproduce the oracle's proofs and witness
+    digests -- the depth-20 goldens, and the multi message-id circuit whose graph carries the slow operations
+    (Shr / Band / Neq / Div on canonical integers), TernCond and Neg."""
     from zerokit_amd.batch import BatchProver
     cases = _cases()["cases"]
     other = [c for c in json.load(open(os.path.join(ROOT, "tests", "golden", "rln_other_circuits.json")))["cases"]
              if c["multi"]]
-    for flag in ("1", "0"):
-        monkeypatch.setenv("RLNAMD_WIT29", flag)
+    for flag in ("default", "0"):
+        if flag == "0":
+            monkeypatch.setenv("RLNAMD_WITLANES", "0")
+        else:
+            monkeypatch.delenv("RLNAMD_WITLANES", raising=False)
         p = BatchProver(max_batch=64)
         try:
             out = p.prove([_w(c) for c in cases], [(int(c["r"]), int(c["s"])) for c in cases])

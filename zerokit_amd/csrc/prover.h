@@ -2,7 +2,7 @@
 //
 // Device-side replacement for the path below generate_zk_proof_with_rs
 // (/root/reference/rln/src/protocol/proof.rs:753-777):
-//   calc_witness            (circuit/iden3calc.rs:20-60, iden3calc/graph.rs:246-272)  -> k_witness
+//   calc_witness            (circuit/iden3calc.rs:20-60, iden3calc/graph.rs:246-272)  -> k_witness29, k_witness_lanes
 //   CircomReduction         (circuit/qap.rs:30-98)                                     -> k_matvec, k_ntt_pass, k_hquot
 //   create_proof_with_...   (ark-groth16 0.5.0; restated in partial_proof.rs:182-274)  -> k_recode, k_msm_*, k_finalize
 //   proof_values_from_witness (protocol/witness.rs:759-828)                            -> k_proof_values
@@ -44,8 +44,8 @@ struct ProverConfig {
 
 // Every switch of the prover, read from the environment ONCE when a Prover is built (ProverTuning::from_env; printed by
 // rlnamd_prover_describe).  Sizes choose an operating point; the shape of a batch follows from its size, its mode,
-// whether it is alone on the device, the circuit and the partial-proof cache.  The remaining shape switches reach a
-// fallback (wit29) or override a detected condition (lone), so that the parity tests can pin each shape
+// whether it is alone on the device, the circuit and the partial-proof cache.  The one remaining shape switch that is
+// not a size overrides a detected condition (lone), so that the parity tests can pin each shape
 // (tests/test_gpu_parity.py: test_small_batch_shape_variants_give_the_golden_bytes).  Tuning constants whose alternative
 // lost every A/B (NTT through Fr29, the 8 x 32 walk, the plain 255-bit walk, copy-engine staging, one interpreter
 // stream, ...) are gone.
@@ -64,8 +64,7 @@ struct ProverTuning {
                                        // partial run, ~0.26 MB each on the depth-20 circuit); 0: finish always re-walks the whole graph
   uint32_t ntt_lg_max = 96;            // RLNAMD_NTT_LG_MAX: largest small batch whose NTTs run as the three LDS kernels (above, the
                                        // single-wave passes finish earlier beside the walks: 128 proofs 13.2 -> 12.6 ms)
-  // ---- shapes (1 = default)
-  bool wit29 = true;                   // RLNAMD_WIT29: interpreter in the 9 x 29 form (0: the 8 x 32 fallback k_witness)
+  // ---- shapes
   int lone = -1;                       // RLNAMD_LONE: -1 detect whether a batch is alone on the device, 0 / 1 force
   uint32_t lone_small_max = 48;        // RLNAMD_LONE_SMALL: batches of at most this many proofs take the lone (latency) shapes even behind a batch in flight
   uint32_t hint_max = 24;              // RLNAMD_HINTS: largest lone batch interpreted as independent segments behind host-computed hints (cold chains on 8 host threads: 12 / 16 / 24 proofs 3.2 / 3.7 / 4.3 -> 2.5 / 3.0 / 3.9 ms, even at 32)

@@ -177,7 +177,6 @@ struct Prover::Impl {
   float ms[PROVER_STAGES] = {0};
   DevBuf<unsigned long long> walk_clk;  // clock tap of the two walks: G1 cycles, G1 ticks, G2 cycles, G2 ticks
   ProverTuning tune;             // every switch, read once (prover.h)
-  bool wit29 = true;             // = tune.wit29
   uint32_t lanechunk_max = 128, lanechunk_walk_max = 48, witlanes_max = 1024;   // = tune.*
   DeviceCount device;            // counted in g_provers_on_device while the object lives
   DevBuf<GNode29> nodes29;
@@ -187,8 +186,6 @@ struct Prover::Impl {
 
   uint32_t N = 0, NS = 0, NI = 0, nc = 0, ni = 0, n = 0;
   int logn = 0;
-  DevBuf<GNode> nodes;
-  DevBuf<Fr> consts;
   DevBuf<uint32_t> sig2node;
   DevBuf<uint32_t> a_ptr, a_col, b_ptr, b_col;
   DevBuf<uint32_t> mv_long;       // rows with more than MV_LONG entries in A or B
@@ -445,15 +442,11 @@ struct Prover::Impl {
       zero(S.rs.p, n * 64);
     }
     const uint32_t pg = div_up(n, 64);
-    if (wit29 && S.V29.p) {
-      hipLaunchKernelGGL(k_wipe_cols, dim3(pg, nstore29), dim3(64), 0, sW, S.V.p, slot2node.p, nstore29, (uint32_t)B, (uint32_t)n);
-      hipLaunchKernelGGL(k_wipe_v29, dim3(div_up(3 * n, 64), nstore29 + 1), dim3(64), 0, sW, S.V29.p, nstore29 + 1, (uint32_t)B,
-                         (uint32_t)n);
-      // an externally supplied witness (upload_witness) was stored at the signal rows
-      hipLaunchKernelGGL(k_wipe_cols, dim3(pg, NS), dim3(64), 0, sW, S.V.p, sig2node.p, NS, (uint32_t)B, (uint32_t)n);
-    } else {
-      hipLaunchKernelGGL(k_wipe_cols, dim3(pg, N), dim3(64), 0, sW, S.V.p, (const uint32_t*)nullptr, N, (uint32_t)B, (uint32_t)n);
-    }
+    hipLaunchKernelGGL(k_wipe_cols, dim3(pg, nstore29), dim3(64), 0, sW, S.V.p, slot2node.p, nstore29, (uint32_t)B, (uint32_t)n);
+    hipLaunchKernelGGL(k_wipe_v29, dim3(div_up(3 * n, 64), nstore29 + 1), dim3(64), 0, sW, S.V29.p, nstore29 + 1, (uint32_t)B,
+                       (uint32_t)n);
+    // an externally supplied witness (upload_witness) was stored at the signal rows
+    hipLaunchKernelGGL(k_wipe_cols, dim3(pg, NS), dim3(64), 0, sW, S.V.p, sig2node.p, NS, (uint32_t)B, (uint32_t)n);
     // The signed window digits are a lossless re-encoding of every witness scalar (the identity secret among them) and
     // of r, s; A w, B w and the quotient are linear images of the witness; a walk's partial sum over a handful of rows is
     // w_i P_i for guessable w_i.  Columns [0, n) of all of them, by the strides the batch used.
@@ -524,7 +517,6 @@ ProverTuning ProverTuning::from_env() {
   t.lanechunk_max = (uint32_t)std::max(0, env_int("RLNAMD_LANECHUNK", (int)t.lanechunk_max));
   t.lanechunk_walk_max = (uint32_t)std::max(0, env_int("RLNAMD_LANECHUNK_WALK", (int)t.lanechunk_walk_max));
   t.witlanes_max = (uint32_t)std::max(0, env_int("RLNAMD_WITLANES_MAX", (int)t.witlanes_max));
-  t.wit29 = env_int("RLNAMD_WIT29", 1) != 0;
   t.lone = env_int("RLNAMD_LONE", -1);
   t.lone_small_max = (uint32_t)std::max(0, env_int("RLNAMD_LONE_SMALL", (int)t.lone_small_max));
   t.tiny_max = (uint32_t)std::max(0, env_int("RLNAMD_TINY", (int)t.tiny_max));
@@ -544,9 +536,9 @@ ProverTuning ProverTuning::from_env() {
 std::string ProverTuning::describe() const {
   char b[768];
   snprintf(b, sizeof b,
-           "window_bits=%d slots=%d lanechunk=%u lanechunk_walk=%u witlanes_max=%u tiny=%u ntt_lg_max=%u partial_cache=%u wit29=%d lone=%d "
+           "window_bits=%d slots=%d lanechunk=%u lanechunk_walk=%u witlanes_max=%u tiny=%u ntt_lg_max=%u partial_cache=%u lone=%d "
            "lone_small=%u hints=%u hints_warm=%u hint_threads=%u hint_chains=%u",
-           window_bits, slots, lanechunk_max, lanechunk_walk_max, witlanes_max, tiny_max, ntt_lg_max, partial_cache, (int)wit29, lone,
+           window_bits, slots, lanechunk_max, lanechunk_walk_max, witlanes_max, tiny_max, ntt_lg_max, partial_cache, lone,
            lone_small_max, hint_max, hint_max_warm, hint_threads, hint_chains);
   return b;
 }
@@ -704,46 +696,10 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
   }
   hipStream_t s = D.sB;
 
-  // ---- graph program
-  D.nodes.alloc(D.N);
-  {
-    // device program: operands tagged with where the interpreter finds them (k_witness)
-    std::vector<GNode> prog(graph_.nodes);
-    auto enc = [&](uint32_t n, uint32_t o) -> uint32_t {
-      if (o >= n) throw Error("Graph error: node operand refers forward");
-      if (graph_.nodes[o].op == G_CONST) return OPK_CONST | graph_.nodes[o].a;
-      if (n - o < WIT_RING) return OPK_RING | o;
-      return OPK_FAR | o;
-    };
-    std::vector<uint8_t> store(D.N, 0);
-    for (uint32_t sgn : graph_.signals) store[sgn] = 1;
-    for (uint32_t n = 0; n < D.N; n++) {
-      GNode& g = prog[n];
-      if (g.op == G_INPUT) store[n] = 1;
-      if (g.op == G_INPUT || g.op == G_CONST) continue;
-      const uint32_t oa = g.a, ob = g.b, oc = g.c;
-      g.a = enc(n, oa);
-      if ((g.a & OPK_MASK) == OPK_FAR) store[oa] = 1;
-      if (g.op != G_NEG && g.op != G_ID) {
-        g.b = enc(n, ob);
-        if ((g.b & OPK_MASK) == OPK_FAR) store[ob] = 1;
-      }
-      if (g.op == G_TERN) {
-        g.c = enc(n, oc);
-        if ((g.c & OPK_MASK) == OPK_FAR) store[oc] = 1;
-      }
-    }
-    for (uint32_t n = 0; n < D.N; n++)
-      if (store[n]) prog[n].op |= G_STORE;
-    D.nodes.upload(prog.data(), D.N, s);
-    RLN_HIP(hipStreamSynchronize(s));
-  }
   RLN_HIP(hipFuncSetAttribute((const void*)(k_sum_tree<Fq2, G2Acc29>), hipFuncAttributeMaxDynamicSharedMemorySize, SUM_TREE_LDS_G2));
   RLN_HIP(hipFuncSetAttribute((const void*)(k_sum_blocks<Fq2, G2Acc29>), hipFuncAttributeMaxDynamicSharedMemorySize, SUM_TREE_LDS_G2));
-  RLN_HIP(hipFuncSetAttribute((const void*)k_witness, hipFuncAttributeMaxDynamicSharedMemorySize, WIT_RING * 8 * 64 * 4 + WIT_LDS_CONSTS * 32));
-  D.consts.alloc(std::max<size_t>(graph_.constants.size(), 1));
-  if (!graph_.constants.empty()) D.consts.upload(graph_.constants.data(), graph_.constants.size(), s);
-  D.wit29 = D.tune.wit29;
+  // k_witness29 takes 152 KiB of dynamic LDS; gfx950, the only target, gives a workgroup 160 KiB
+  RLN_HIP(hipFuncSetAttribute((const void*)k_witness29<false>, hipFuncAttributeMaxDynamicSharedMemorySize, WIT29_LDS_BYTES));
   // Largest batch that takes the small-batch shapes (lanes = chunks walks, a wave per proof in the interpreter, early walks
   // and back end).  tools/lanechunk_sweep.py / tools/midstream.py: one batch alone is faster that way up to ~450 proofs
   // (64: 12.4 vs 23.2 ms, 128: 17.8 vs 27.4, 256: 28.4 vs 36.8), a STREAM of such batches up to ~150 (chunks of 64: 9.4 k
@@ -842,9 +798,8 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
       D.n_hints = 0;
     }
   }
-  std::vector<GNode29> wit29_prog;
-  std::vector<uint32_t> wit29_slot2node;
-  if (D.wit29) {
+  std::vector<uint32_t> slot2node;   // stored values: slot -> graph node
+  {
     // The program of k_witness29.  (1) Fusion: an Add one of whose operands is a product used nowhere else (and is no
     // witness signal) becomes ONE node, a * b + c (W29_FMA: the addend enters the product's final carry chain,
     // Fr29::mul_add) -- in the shipped circuits every addition of a Poseidon round is of that kind, 23 414 nodes become
@@ -906,17 +861,19 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
         if (!is_const(o) && i - pidx[o] >= WIT29_RING) store[o] = 1;
       }
     std::vector<uint32_t> slot_of(D.N, 0);
-    std::vector<uint32_t>& slot2node = wit29_slot2node;
     for (uint32_t n = 0; n < D.N; n++)
       if (store[n] && !removed[n]) {
         slot_of[n] = (uint32_t)slot2node.size();
         slot2node.push_back(n);
       }
-    if (slot2node.size() >= 65536) D.wit29 = false;   // the descriptor has 16 bits for the slot: larger graphs keep k_witness
-    std::vector<GNode29>& prog = wit29_prog;
-    prog.resize(P.size());
+    // The descriptor holds the slot in 16 bits.  The shipped circuits have at most 29 254 graph nodes, stored values
+    // being a subset of them, so only a much larger circuit can fail here.
+    if (slot2node.size() >= 65536)
+      throw Error("graph too large for the witness interpreter: " + std::to_string(slot2node.size()) +
+                  " stored values, the descriptor holds 16 bits");
+    std::vector<GNode29> prog(P.size());
     std::vector<double> bnd(D.N, 1.01);
-    for (uint32_t i = 0; D.wit29 && i < P.size(); i++) {
+    for (uint32_t i = 0; i < P.size(); i++) {
       const PNode& q = P[i];
       GNode29 d{};
       uint32_t flags = store[q.node] ? W29_STORE : 0;
@@ -962,10 +919,6 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
       d.w0 = q.op | flags | (slot_of[q.node] << 16);
       prog[i] = d;
     }
-  }
-  if (D.wit29) {
-    std::vector<GNode29>& prog = wit29_prog;
-    std::vector<uint32_t>& slot2node = wit29_slot2node;
     D.nprog29 = (uint32_t)prog.size();
     D.nstore29 = (uint32_t)slot2node.size();
     prog.resize(((size_t)D.nprog29 / WIT29_CH + 4) * WIT29_CH, GNode29{});   // the kernel prefetches two chunks past the end
@@ -974,9 +927,12 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     D.slot2node.alloc(std::max<size_t>(slot2node.size(), 1));
     if (!slot2node.empty()) D.slot2node.upload(slot2node.data(), slot2node.size(), s);
     D.consts29.alloc(std::max<size_t>(graph_.constants.size(), 1) * 9);
-    if (!graph_.constants.empty())
-      hipLaunchKernelGGL(k_consts_to29, dim3(div_up(graph_.constants.size(), 256)), dim3(256), 0, s, D.consts.p,
+    DevBuf<Fr> consts(graph_.constants.size());   // the constants in Fr form, for the conversion only
+    if (!graph_.constants.empty()) {
+      consts.upload(graph_.constants.data(), graph_.constants.size(), s);
+      hipLaunchKernelGGL(k_consts_to29, dim3(div_up(graph_.constants.size(), 256)), dim3(256), 0, s, consts.p,
                          D.consts29.p, (uint32_t)graph_.constants.size());
+    }
     RLN_HIP(hipGetLastError());
     RLN_HIP(hipStreamSynchronize(s));
     {   // the same stored values, produced by a wave per proof (witness_lanes.h) when a batch is below a wave of proofs
@@ -997,14 +953,6 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
           RLN_HIP(hipStreamSynchronize(s));
         }
       }
-    }
-    // 152 KiB of dynamic LDS: a device / partition with a smaller limit keeps the 8 x 32 interpreter (k_witness), the
-    // same fallback as for graphs with 65 536 or more stored values -- a resource limit must not fail the constructor
-    if (hipFuncSetAttribute((const void*)k_witness29<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            WIT29_LDS_BYTES) != hipSuccess) {
-      (void)hipGetLastError();
-      D.wit29 = false;
-      D.witlanes.ok = false;
     }
   }
   D.sig2node.alloc(D.NS);
@@ -1107,15 +1055,15 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     // ---- the cone program and the cache of known stored values (prover.h: collect_partial_cached / submit_finish)
     const long want = cfg.partial_cache >= 0 ? cfg.partial_cache : (long)D.tune.partial_cache;
     D.tune.partial_cache = (uint32_t)std::max(0l, want);
-    if (D.wit29 && D.witlanes.ok && want > 0) {
+    if (D.witlanes.ok && want > 0) {
       WlCone C = wl_cone(graph_);
       if (C.node_known != node_known) throw Error("internal: the cone's known mask differs from the prover's");
       std::vector<uint32_t> store_slot(D.N, 0xFFFFFFFFu), rows;
-      for (uint32_t i = 0; i < wit29_slot2node.size(); i++) {
-        store_slot[wit29_slot2node[i]] = i;
-        if (node_known[wit29_slot2node[i]]) rows.push_back(i);
+      for (uint32_t i = 0; i < slot2node.size(); i++) {
+        store_slot[slot2node[i]] = i;
+        if (node_known[slot2node[i]]) rows.push_back(i);
       }
-      D.cone.build(C.graph, wl_cone_store_slots(C, store_slot), (uint32_t)wit29_slot2node.size(), s);
+      D.cone.build(C.graph, wl_cone_store_slots(C, store_slot), (uint32_t)slot2node.size(), s);
       D.cone_nodes = (uint32_t)C.node_of.size();
       if (D.cone.ok && !rows.empty()) {
         D.cone_nk = (uint32_t)rows.size();
@@ -1426,7 +1374,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     S.values.alloc(B * 40);
     S.comp.alloc(B * 128);
     S.V.alloc((size_t)D.N * B);
-    if (D.wit29) S.V29.alloc(((size_t)D.nstore29 + 1) * 3 * B);   // + the trash row of k_witness_lanes
+    S.V29.alloc(((size_t)D.nstore29 + 1) * 3 * B);   // + the trash row of k_witness_lanes
     S.abc.alloc(3 * (size_t)D.n * B);
     S.digits.alloc((size_t)(3 * D.NS + D.n + 4) * D.nh * D.ws.W * B);   // + s w_i, r w_i, r s of the fused small-batch plan
     S.digits2.alloc((size_t)(D.NS + 3) * D.nh * D.ws2.W * B);
@@ -1871,7 +1819,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // 1.5 ms per 256 proofs against 11 ms): always below the small-batch threshold; up to witlanes_max only for a LONE batch -- in a stream
   // of such batches it costs throughput (profiles/r3_rocprof_summary.md, section 10), and there the previous batch is still in flight.
   const uint32_t wl_lone_max = D.device.shared() ? std::min(D.witlanes_max, 256u) : D.witlanes_max;
-  const bool wl_used = D.wit29 && D.witlanes.ok && (small || (n <= wl_lone_max && lone));
+  const bool wl_used = D.witlanes.ok && (small || (n <= wl_lone_max && lone));
   // Finish with the partial run's values at hand (prover.h: submit_finish): every proof of the batch has a live cache
   // entry and the batch is one the wave-per-proof interpreter takes -> the known rows come back from the cache and only
   // the cone evaluate_partial leaves unknown is interpreted (depth-20 circuit: 1 947 of 23 414 nodes, a twelfth of the
@@ -2061,36 +2009,31 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     RLN_HIP(hipEventRecord(S.evP, D.sC));
   }
   MARK(1, sA);
-  if (D.wit29) {
-    if (cone) {
-      RLN_HIP(hipStreamWaitEvent(sA, D.evConeSaved, 0));   // sW: the entries are written by the partial batch's collect
-      hipLaunchKernelGGL(k_cone_restore, dim3(div_up(D.cone_nk * 3, 256), nb), dim3(256), 0, sA, D.cone_cache.p, D.cone_rows.p,
-                         D.cone_nk, B, S.h_cone, S.V29.p, D.cone_stride);
-      RLN_HIP(hipEventRecord(D.evConeRead, sA));
-      D.cone.launch(sA, in_p, D.NI, S.V29.p, S.err.p, B, nb);
-      D.cone_batches++;
-    } else if (hinted) {
-      hipLaunchKernelGGL(k_wipe_bytes, dim3(1), dim3(64), 0, sA, (uint4*)S.err.p, (uint32_t)div_up(nb * 4, 16));   // the segments OR into it
-      D.segs.launch(sA, in_p, D.NI, S.h_hints, S.V29.p, S.err.p, B, nb);
-    } else if (wl_used) {
-      D.witlanes.launch(sA, in_p, D.NI, S.V29.p, S.err.p, B, nb);
-    } else
+  if (cone) {
+    RLN_HIP(hipStreamWaitEvent(sA, D.evConeSaved, 0));   // sW: the entries are written by the partial batch's collect
+    hipLaunchKernelGGL(k_cone_restore, dim3(div_up(D.cone_nk * 3, 256), nb), dim3(256), 0, sA, D.cone_cache.p, D.cone_rows.p,
+                       D.cone_nk, B, S.h_cone, S.V29.p, D.cone_stride);
+    RLN_HIP(hipEventRecord(D.evConeRead, sA));
+    D.cone.launch(sA, in_p, D.NI, S.V29.p, S.err.p, B, nb);
+    D.cone_batches++;
+  } else if (hinted) {
+    hipLaunchKernelGGL(k_wipe_bytes, dim3(1), dim3(64), 0, sA, (uint4*)S.err.p, (uint32_t)div_up(nb * 4, 16));   // the segments OR into it
+    D.segs.launch(sA, in_p, D.NI, S.h_hints, S.V29.p, S.err.p, B, nb);
+  } else if (wl_used) {
+    D.witlanes.launch(sA, in_p, D.NI, S.V29.p, S.err.p, B, nb);
+  } else {
     hipLaunchKernelGGL(k_witness29<false>, dim3(pg), dim3(64), WIT29_LDS_BYTES, sA, D.nodes29.p, D.nprog29,
                        D.consts29.p, (uint32_t)graph_.constants.size(), in_p, D.NI, S.V29.p, S.err.p, B, nbp, nullptr);
-    if (small)
-      hipLaunchKernelGGL(k_v29_to_fr, dim3(div_up(D.nstore29, 64), nb), dim3(64, 1), 0, sA, S.V29.p, D.slot2node.p,
-                         D.nstore29, S.V.p, B, nb, 1u);
-    else
-      hipLaunchKernelGGL(k_v29_to_fr, dim3(pg, D.nstore29), dim3(64, 1), 0, sA, S.V29.p, D.slot2node.p, D.nstore29, S.V.p,
-                         B, nbp);
-    if (hinted)
-      hipLaunchKernelGGL(k_hint_check, dim3(div_up(D.n_cut, 64), nb), dim3(64), 0, sA, S.V.p, D.cut_node.p, D.cut_hint.p, D.n_cut,
-                         S.h_hints, D.n_hints, B, S.err.p);
-  } else {
-    hipLaunchKernelGGL(k_witness, dim3(pg), dim3(64), WIT_RING * 8 * 64 * 4 + WIT_LDS_CONSTS * 32, sA, D.nodes.p, D.N, D.consts.p,
-                       (uint32_t)graph_.constants.size(), in_p, D.NI, S.V.p,
-                       S.err.p, B, nbp);
   }
+  if (small)
+    hipLaunchKernelGGL(k_v29_to_fr, dim3(div_up(D.nstore29, 64), nb), dim3(64, 1), 0, sA, S.V29.p, D.slot2node.p,
+                       D.nstore29, S.V.p, B, nb, 1u);
+  else
+    hipLaunchKernelGGL(k_v29_to_fr, dim3(pg, D.nstore29), dim3(64, 1), 0, sA, S.V29.p, D.slot2node.p, D.nstore29, S.V.p,
+                       B, nbp);
+  if (hinted)
+    hipLaunchKernelGGL(k_hint_check, dim3(div_up(D.n_cut, 64), nb), dim3(64), 0, sA, S.V.p, D.cut_node.p, D.cut_hint.p, D.n_cut,
+                       S.h_hints, D.n_hints, B, S.err.p);
   if (D.wgiven_n) {
     if (D.wgiven_n != n || mode != PROVE_FULL) throw Error("upload_witness: the next run must be a full proof of the same batch");
     hipLaunchKernelGGL(k_scatter_witness, dim3(pg, div_up(D.NS, 4)), dim3(64, 4), 0, sA, D.wgiven.p, D.sig2node.p,

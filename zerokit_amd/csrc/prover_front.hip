@@ -11,113 +11,16 @@
 namespace rlnamd {
 
 // =====================================================================================================
-// 256-bit integer helpers on canonical limbs (witness-graph ops that are not field ops)
-// =====================================================================================================
-// =====================================================================================================
 // 1. witness: one lane per proof interprets the straight-line graph (graph.rs:246-272)
 // =====================================================================================================
-// Operand encoding of the device program (built once on the host, Prover::Prover): the top two bits of a / b / c say
-// where the value lives -- RING: produced at most 63 nodes earlier, read from the LDS ring; CONST: index into the
-// constant table, a wave-uniform scalar load; FAR: anything else, read from the value array in HBM.  In the shipped
-// circuits every operand is a constant (23 %), the previous node (33 %, forwarded in registers) or within the last 16
-// nodes; only the 124 reads of input nodes go to HBM.  The ring is 64 slots x 64 lanes x 32 B = 128 KiB of LDS -- one
-// wave per CU is all this kernel ever has (16 waves per 1024 proofs).
-__device__ __forceinline__ Fr ring_load(const uint32_t* ring, uint32_t node, uint32_t lane) {
-  Fr r;
-  const uint32_t* s = ring + (node % WIT_RING) * 8 * 64 + lane;
-#pragma unroll
-  for (int k = 0; k < 8; k++) r.v[k] = s[k * 64];
-  return r;
-}
-__device__ __forceinline__ Fr operand_load(uint32_t enc, const uint32_t* ring, const Fr* __restrict__ consts,
-                                           const Fr* __restrict__ V, uint32_t B, uint32_t p, uint32_t lane) {
-  uint32_t kind = enc & OPK_MASK, id = enc & ~OPK_MASK;
-  if (kind == OPK_RING) return ring_load(ring, id, lane);
-  if (kind == OPK_CONST) {
-    if (id >= WIT_LDS_CONSTS) return consts[id];
-    Fr r;
-    const uint32_t* c = ring + WIT_RING * 8 * 64 + id * 8;  // broadcast read: every lane the same address
-#pragma unroll
-    for (int k = 0; k < 8; k++) r.v[k] = c[k];
-    return r;
-  }
-  return V[(size_t)id * B + p];
-}
-__global__ void __launch_bounds__(64) k_witness(const GNode* __restrict__ nodes, uint32_t n_nodes,
-                                                const Fr* __restrict__ consts, uint32_t n_consts,
-                                                const uint32_t* __restrict__ inputs, uint32_t n_inputs,
-                                                Fr* __restrict__ V, uint32_t* __restrict__ err, uint32_t B, uint32_t nb) {
-  extern __shared__ uint32_t ring[];  // [WIT_RING][8][64] node values, then [WIT_LDS_CONSTS][8] constants
-  __builtin_amdgcn_s_setprio(3);  // few, latency-bound waves: issue ahead of the MSM waves sharing the SIMD
-  const uint32_t lane = threadIdx.x;
-  uint32_t p = blockIdx.x * 64 + lane;
-  if (p >= nb) return;
-  uint32_t e = WERR_NONE;
-  Fr last = Fr::zero();
-  {
-    uint32_t* lc = ring + WIT_RING * 8 * 64;
-    const uint32_t* gc = (const uint32_t*)consts;
-    const uint32_t words = (n_consts < WIT_LDS_CONSTS ? n_consts : WIT_LDS_CONSTS) * 8;
-    for (uint32_t i = lane; i < words; i += 64) lc[i] = gc[i];
-    __syncthreads();
-  }
-  GNode ahead = nodes[0];
-#pragma unroll 1
-  for (uint32_t n = 0; n < n_nodes; n++) {
-    // the descriptor of the next node is fetched while this one executes (scalar load)
-    GNode nd = ahead;
-    if (n + 1 < n_nodes) ahead = nodes[n + 1];
-    const bool store = (nd.op & G_STORE) != 0;
-    nd.op &= ~G_STORE;
-    Fr v;
-    if (nd.op == G_INPUT) {
-      const uint32_t* src = inputs + ((size_t)p * n_inputs + nd.a) * 8;
-      if (limbs_geq(src, FrParams::MOD)) e = e ? e : WERR_INPUT_RANGE;  // u256_to_fr fails (graph.rs:42-45)
-      v = Fr::from_canonical(src);
-    } else if (nd.op == G_CONST) {
-      v = consts[nd.a];
-    } else {
-      // operand forwarding: chains (x^5 s-boxes, MDS sums) read the value produced one node earlier
-      // (reading the NEXT node's LDS operands ahead of time was tried: 33 ms instead of 19.5 -- register pressure)
-      Fr va = (nd.a == (OPK_RING | (n - 1))) ? last : operand_load(nd.a, ring, consts, V, B, p, lane);
-      if (nd.op == G_NEG) {
-        v = va.neg();
-      } else if (nd.op == G_ID) {
-        v = witness_slow_op(G_ID, va, va, &e);
-      } else {
-        Fr vb = (nd.b == (OPK_RING | (n - 1))) ? last : operand_load(nd.b, ring, consts, V, B, p, lane);
-        if (nd.op == G_MUL)
-          v = va * vb;
-        else if (nd.op == G_ADD)
-          v = va + vb;
-        else if (nd.op == G_SUB)
-          v = va - vb;
-        else if (nd.op == G_TERN) {
-          Fr vc = operand_load(nd.c, ring, consts, V, B, p, lane);
-          v = va.is_zero() ? vc : vb;  // graph.rs:214-224
-        } else {
-          uint32_t e2 = 0;
-          v = witness_slow_op(nd.op, va, vb, &e2);
-          if (e2 && !e) e = e2;
-        }
-      }
-    }
-    // only ~6 000 of the 23 414 node values are read outside this kernel (190 MB instead of 767 MB per batch)
-    if (store) V[(size_t)n * B + p] = v;
-    uint32_t* slot = ring + (n % WIT_RING) * 8 * 64 + lane;
-#pragma unroll
-    for (int k = 0; k < 8; k++) slot[k * 64] = v.v[k];
-    last = v;
-  }
-  err[p] = e;
-}
-
-// ---- The same interpreter with node values in the 9 x 29-bit form of fq29.h (default; RLNAMD_WIT29=0 keeps the one
-// above).  One wave per SIMD is all this kernel ever has, so its time is latency, and tools/microbench_lonewave.hip
-// shows what a lone wave pays on gfx950: ~12 cycles per LDS instruction issued (a 9 x ds_read_b32 operand is a 118-cycle
-// round trip, two of them 225), 25 - 70 cycles per uniform branch hop, ~5.7 cycles per dependent multiply-add.  The 8 x 32
-// interpreter spends two thirds of its 1 950 cycles per node on exactly that (profiled: an ADD node of 30 instructions
-// takes 1 250 - 1 750 cycles).  Hence:
+// Node values are in the 9 x 29-bit form of fq29.h.  The device program is built once on the host (Prover::Prover); the
+// top two bits of an operand say where its value lives -- RING: produced fewer than WIT29_RING program nodes earlier,
+// read from the LDS ring; CONST: index into the constant table; FAR: anything else, read from the compact array of
+// stored values in HBM.  One wave per SIMD is all this kernel ever has, so its time is latency, and
+// tools/microbench_lonewave.hip shows what a lone wave pays on gfx950: ~12 cycles per LDS instruction issued (a
+// 9 x ds_read_b32 operand is a 118-cycle round trip, two of them 225), 25 - 70 cycles per uniform branch hop, ~5.7 cycles
+// per dependent multiply-add.  An earlier interpreter with values as 8 x 32 bits spent two thirds of its 1 950 cycles per
+// node on exactly that (profiled: an ADD node of 30 instructions took 1 250 - 1 750 cycles).  Hence:
 //   * values live in LDS as [slot][lane][12 words]: an operand is ds_read_b128 x 2 + ds_read_b32, conflict-free at
 //     the 48-byte lane stride; constants as [id][12 words] are the SAME address form with lane multiplier 0, so both
 //     operands of a node are read without a branch and share one round trip;

@@ -19,9 +19,6 @@ namespace rlnamd {
 
 // ---- witness interpreters (prover_front.hip)
 constexpr uint32_t OPK_RING = 0u << 30, OPK_CONST = 1u << 30, OPK_FAR = 2u << 30, OPK_MASK = 3u << 30;
-constexpr uint32_t G_STORE = 1u << 31;  // flag on GNode.op: this node's value must reach HBM (witness signal, input, far operand)
-constexpr uint32_t WIT_RING = 32;        // node values kept in LDS (64 KiB)
-constexpr uint32_t WIT_LDS_CONSTS = 2048;  // constants kept in LDS (64 KiB)
 constexpr uint32_t W29_STORE = 1u << 8, W29_RED = 1u << 9, W29_RARE = 1u << 10;  // flags in descriptor word 0
 constexpr uint32_t W29_FMA = 25;             // program-only operation: a * b + c (an Add fused with its single-use product)
 constexpr uint32_t WIT29_RING = 32;          // node values kept in LDS: 32 x 64 x 48 B = 96 KiB
@@ -64,10 +61,6 @@ struct InputSlots {
 #endif
 
 // ---- kernels of prover_front.hip
-__global__ void __launch_bounds__(64) k_witness(const GNode* __restrict__ nodes, uint32_t n_nodes,
-                                                const Fr* __restrict__ consts, uint32_t n_consts,
-                                                const uint32_t* __restrict__ inputs, uint32_t n_inputs,
-                                                Fr* __restrict__ V, uint32_t* __restrict__ err, uint32_t B, uint32_t nb);
 template <bool PROF>
 __global__ void __launch_bounds__(64) k_witness29(const GNode29* __restrict__ nodes, uint32_t n_nodes,
                                                   const uint32_t* __restrict__ consts29, uint32_t n_consts,

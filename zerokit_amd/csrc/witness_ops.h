@@ -1,4 +1,4 @@
-// Device-side graph operations shared by the witness interpreters (prover.hip: k_witness, k_witness29;
+// Device-side graph operations shared by the witness interpreters (prover_front.hip: k_witness29;
 // witness_lanes.hip: k_witness_lanes): 256-bit integer helpers and every operation of
 // /root/reference/rln/src/circuit/iden3calc/graph.rs:72-143, 314-466 that is not Mul / Add / Sub / Neg / TernCond.
 #pragma once
