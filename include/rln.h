@@ -96,6 +96,13 @@ CResult_FFI_RLNProof_ptr_Vec_uint8_t ffi_generate_rln_proof_with_rs(FFI_RLN_t* c
  * blinding) or 2n CFr (r_0, s_0, r_1, ...); out: array of n proof pointers filled on success. */
 CBoolResult_t ffi_generate_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNWitnessInput_t* const* witnesses, size_t n,
                                             const CFr_t* rs, FFI_RLNProof_t** out);
+/* EXT: n proofs checked in one call.  roots: NULL = this object's current root (ffi_verify_rln_proof),
+ * otherwise ffi_verify_with_roots' rule (an empty vector accepts any root).  ok[i] = 1 when proof i passes the
+ * three checks of public.rs:725-771 (pairing, root, xs[i] == the proof's x), else 0.  The call itself fails only
+ * for a call-level error (null pointers, a proof of the other circuit kind).  The pairing checks run on the device
+ * when n is at least the object's "verify_gpu_min" (config JSON), on host threads below it. */
+CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
+                                          const CFr_t* xs, const Vec_CFr_t* roots, bool* ok);
 
 /* EXT: n finishes in one call (single message-id): partials[i] is the partial proof witnesses[i] is finished from -- the
  * same pointer may repeat, one member's partial proof finished for n messages being what partial proofs are for

@@ -257,6 +257,15 @@ int rlnamd_verify(rlnamd_prover* p, const uint8_t proof[128], const uint8_t valu
  * (protocol/proof.rs:856-894); a relay node verifies every message it forwards. */
 int rlnamd_verify_many(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t n_values,
                        int threads, uint8_t* ok);
+/* EXT: n independent verifications on the device (a lane per proof; verify.hip).  Same inputs and the same verdicts as
+ * rlnamd_verify_many.  The verifier has its own stream and buffers and never waits for a proving batch; calls from
+ * several threads serialise.  n = 0 succeeds and writes nothing. */
+int rlnamd_verify_many_gpu(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t n_values,
+                           uint8_t* ok);
+/* test / diagnosis: the final-exponentiated pairing product of each proof, 12 x 32 bytes canonical LE in
+ * pairing.h's coefficient order (1 = accept); rows of proofs rejected before the pairing are all zero. */
+int rlnamd_verify_many_gpu_gt(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                              size_t n_values, uint8_t* gt384);
 int rlnamd_verify_many_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n, const uint8_t* proofs,
                                  const uint8_t* values_le, size_t n_values, int threads, uint8_t* ok);
 /* same check straight from arkzkey bytes; needs no GPU (host parser + host pairing only) */

@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""Verification throughput: the device verifier (rlnamd_verify_many_gpu) against 16 host threads
+(rlnamd_verify_many), compressed proof bytes in, verdicts out, copies to and from the device inside the timed region.
+
+    python tools/verify_throughput.py [--calls 9] [--out FILE]
+
+prints ONE JSON line.  Torch-free (ctypes through zerokit_amd).  Each of the two steps runs in a child process of its
+own under a time limit; a step that fails or runs out of time ends the run there.
+
+  sweep       host at n = 64, 1 024, 8 192 (and at the smaller device sizes, for the crossover); device at
+              n = 1 ... 65 536 (512 added to the sizes the host is measured at, to place the crossover); median and spread of `calls` calls after a warm-up call per size; the crossover (smallest
+              measured n where the device's median beats the host's at that n)
+  concurrent  device verification at n = 8 192 while a proving stream runs, and the proving rate alone and meanwhile
+"""
+import argparse
+import collections
+import ctypes as C
+import json
+import os
+import statistics
+import subprocess
+import sys
+import threading
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HOST_THREADS = 16
+DEVICE_N = (1, 8, 64, 256, 512, 1024, 8192, 65536)
+HOST_N = (1, 8, 64, 256, 512, 1024, 8192)
+STEP_LIMIT_S = {"sweep": 420, "concurrent": 240}
+
+
+def setup():
+    from zerokit_amd import lib, workload
+    from zerokit_amd.batch import BatchProver
+    if lib().rlnamd_device_count() < 1:
+        raise SystemExit("verify_throughput: no HIP device (there is no CPU fallback for the device side)")
+    p = BatchProver(max_batch=1024)
+    ws, rs = workload.config2_range(0, 1024)
+    inp, rsb = p.pack_inputs(ws), p.pack_rs(rs)
+    t, n = p.submit(inp, rsb)
+    proofs, values, errs = p.collect_raw(t, n)
+    assert not any(errs)
+    return p, inp, rsb, proofs, values
+
+
+def tiled(proofs, values, n):
+    reps = (n + 1023) // 1024
+    return (proofs * reps)[:128 * n], (values * reps)[:160 * n]
+
+
+def timed(fn, calls):
+    fn()   # warm-up: code objects, buffers at their size
+    ts = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return ts
+
+
+def row(n, ts):
+    med = statistics.median(ts)
+    return {"n": n, "calls": len(ts), "median_ms": round(med * 1e3, 3), "min_ms": round(min(ts) * 1e3, 3),
+            "max_ms": round(max(ts) * 1e3, 3), "per_s": round(n / med, 1)}
+
+
+def step_sweep(calls):
+    from zerokit_amd import lib
+    from zerokit_amd._native import check
+    p, _inp, _rsb, proofs, values = setup()
+    host, dev = [], []
+    for n in DEVICE_N:
+        pr, va = tiled(proofs, values, n)
+        ok = C.create_string_buffer(n)
+
+        def gpu():
+            check(lib().rlnamd_verify_many_gpu(p._h, n, pr, va, 5, ok))
+        dev.append(row(n, timed(gpu, calls)))
+        assert ok.raw == b"\x01" * n
+    for n in HOST_N:
+        pr, va = tiled(proofs, values, n)
+        ok = C.create_string_buffer(n)
+
+        def cpu():
+            check(lib().rlnamd_verify_many(p._h, n, pr, va, 5, HOST_THREADS, ok))
+        host.append(row(n, timed(cpu, calls if n < 8192 else max(3, calls // 3))))
+        assert ok.raw == b"\x01" * n
+    hmed = {r["n"]: r["median_ms"] for r in host}
+    wins = [r["n"] for r in dev if r["n"] in hmed and r["median_ms"] < hmed[r["n"]]]
+    p.close()
+    return {"host_threads": HOST_THREADS, "host": host, "device": dev, "crossover_n": min(wins) if wins else None}
+
+
+def step_concurrent(calls):
+    from zerokit_amd import lib
+    from zerokit_amd._native import check
+    p, inp, rsb, proofs, values = setup()
+    pr, va = tiled(proofs, values, 8192)
+    ok = C.create_string_buffer(8192)
+
+    def gpu():
+        check(lib().rlnamd_verify_many_gpu(p._h, 8192, pr, va, 5, ok))
+
+    def prove_stream(batches):
+        nslots, inflight = p.n_slots(), collections.deque()
+        p.sync()
+        t0 = time.perf_counter()
+        for _ in range(batches):
+            if len(inflight) == nslots:
+                p.collect_raw(inflight.popleft(), 1024)
+            inflight.append(p.submit(inp, rsb)[0])
+        while inflight:
+            p.collect_raw(inflight.popleft(), 1024)
+        p.sync()
+        return batches * 1024 / (time.perf_counter() - t0)
+    prove_stream(4)
+    alone_prove = prove_stream(24)
+    alone_verify = row(8192, timed(gpu, calls))
+    res = {}
+    th = threading.Thread(target=lambda: res.update(rate=prove_stream(48)))
+    th.start()
+    time.sleep(0.2)   # the stream's first batches are in flight
+    ts, t_end = [], None
+    while th.is_alive():
+        t0 = time.perf_counter()
+        gpu()
+        ts.append(time.perf_counter() - t0)
+    th.join()
+    assert ok.raw == b"\x01" * 8192
+    p.close()
+    return {"prove_alone_per_s": round(alone_prove, 1), "verify_alone": alone_verify,
+            "prove_meanwhile_per_s": round(res["rate"], 1), "verify_meanwhile": row(8192, ts) if ts else None}
+
+
+STEPS = {"sweep": step_sweep, "concurrent": step_concurrent}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=9)
+    ap.add_argument("--out")
+    ap.add_argument("--step", choices=sorted(STEPS))
+    a = ap.parse_args()
+    if a.calls < 9:
+        ap.error("--calls: at least 9")
+    if a.step:
+        print(json.dumps(STEPS[a.step](a.calls)))
+        return 0
+    out = {"tool": "verify_throughput", "calls": a.calls}
+    for name in ("sweep", "concurrent"):
+        try:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--calls", str(a.calls)],
+                               stdout=subprocess.PIPE, timeout=STEP_LIMIT_S[name])
+        except subprocess.TimeoutExpired:
+            out[name] = {"error": "time limit of %d s" % STEP_LIMIT_S[name]}
+            break
+        if r.returncode != 0:
+            out[name] = {"error": "exit status %d" % r.returncode}
+            break   # nothing more is started on the device after a failed step
+        out[name] = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if all("error" not in out.get(k, {"error": 1}) for k in ("sweep", "concurrent")) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

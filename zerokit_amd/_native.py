@@ -140,6 +140,8 @@ SIGNATURES = {
     "rlnamd_verify_public": (C.c_int, [P, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]),
     "rlnamd_verify_with_zkey": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]),
     "rlnamd_verify_many": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_char_p]),
+    "rlnamd_verify_many_gpu": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p]),
+    "rlnamd_verify_many_gpu_gt": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p]),
     "rlnamd_verify_many_with_zkey": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t,
                                                C.c_int, C.c_char_p]),
     "rlnamd_parse_resources": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)]),
@@ -209,6 +211,7 @@ SIGNATURES = {
     "ffi_generate_rln_proofs_batch": (CBoolResult, [PP, PP, C.c_size_t, CFRP, PP]),
     "ffi_finish_rln_proofs_batch": (CBoolResult, [PP, PP, PP, C.c_size_t, CFRP, PP]),
     "ffi_verify_rln_proof": (CBoolResult, [PP, PP, CFRP]),
+    "ffi_verify_rln_proofs_batch": (CBoolResult, [PP, PP, C.c_size_t, CFRP, C.POINTER(VecCFr), C.POINTER(C.c_bool)]),
     "ffi_verify_with_roots": (CBoolResult, [PP, PP, C.POINTER(VecCFr), CFRP]),
     "ffi_rln_proof_get_values": (P, [PP]),
     "ffi_rln_proof_get_version_byte": (C.c_uint8, [PP]),

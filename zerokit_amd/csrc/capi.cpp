@@ -18,6 +18,7 @@
 #include "pairing.h"
 #include "poseidon.h"
 #include "prover.h"
+#include "verify.h"
 #include "capi_util.h"
 
 using namespace rlnamd;
@@ -620,6 +621,20 @@ int rlnamd_verify_many(rlnamd_prover* p, size_t n, const uint8_t* proofs, const 
   RLN_TRY
   if (n_values + 1 != p->p->zkey().gamma_abc_g1.size()) throw Error("MalformedVerifyingKey");
   verify_many_common(p->p->zkey(), n, proofs, values_le, n_values, threads, ok);
+  RLN_CATCH
+}
+int rlnamd_verify_many_gpu(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t n_values,
+                           uint8_t* ok) {
+  RLN_TRY
+  if (n_values + 1 != p->p->zkey().gamma_abc_g1.size()) throw Error("MalformedVerifyingKey");
+  if (n) p->p->gpu_verifier().verify(n, proofs, values_le, n_values, ok, nullptr);
+  RLN_CATCH
+}
+int rlnamd_verify_many_gpu_gt(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                              size_t n_values, uint8_t* gt384) {
+  RLN_TRY
+  if (n_values + 1 != p->p->zkey().gamma_abc_g1.size()) throw Error("MalformedVerifyingKey");
+  if (n) p->p->gpu_verifier().verify(n, proofs, values_le, n_values, nullptr, gt384);
   RLN_CATCH
 }
 int rlnamd_verify_many_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n, const uint8_t* proofs,

@@ -37,6 +37,7 @@
 #include "pairing.h"
 #include "poseidon.h"
 #include "prover.h"
+#include "verify.h"
 #include "gather.h"
 #include "ffi_wire.h"   // CFr, the FFI object structs, Cursor / V3Reader, every (de)serialiser and validation
 
@@ -267,6 +268,12 @@ std::string json_str_array(const std::vector<std::string>& v) {
 
 // -------------------------------------------------------------------------------------- object model
 
+// Smallest batch that ffi_verify_rln_proofs_batch sends to the device unless the config says otherwise
+// ("verify_gpu_min").  Measured crossover against 16 host threads (tools/verify_throughput.py, profiles/verify_gpu.md):
+// a device pass is 29.9 ms whatever n is up to 8 192; the host takes 25.3 ms for 256 proofs and 50.3 ms for 512, so
+// 512 is the smallest measured n where the device wins (and a power of two already).
+static constexpr size_t VERIFY_GPU_MIN_DEFAULT = 512;
+
 struct FFI_RLN {
   // generate / verify take &self in the reference and may be called from several threads (SURVEY section 8b,
   // "Threading"); the prover owns one set of device workspaces, so proving calls on one object take turns
@@ -286,6 +293,8 @@ struct FFI_RLN {
   // What it costs is a policy decision, hence opt-in: the member's witness values stay on the device, and the key
   // (secret included) in host memory, until the entry is evicted (LRU), the tree moves on, or the object is freed.
   size_t auto_partial = 0;
+  // ffi_verify_rln_proofs_batch: calls of at least this many proofs are verified on the device ("verify_gpu_min")
+  size_t verify_gpu_min = VERIFY_GPU_MIN_DEFAULT;
   // single calls from several threads gathered into batches: gather.h
   struct GatherReq {
     FFI_RLNWitnessInput* w = nullptr;
@@ -368,6 +377,7 @@ struct FFI_RLN {
   void make_prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_t graph_len, const TreeConfig& tcfg) {
     const ProverConfig cfg = tcfg.prover_config();
     auto_partial = tcfg.auto_partial > 0 ? (size_t)tcfg.auto_partial : 0;
+    verify_gpu_min = tcfg.verify_gpu_min >= 0 ? (size_t)tcfg.verify_gpu_min : VERIFY_GPU_MIN_DEFAULT;
     gather_wanted = tcfg.gather_calls;
     if (const char* e = getenv("RLNAMD_GATHER_CALLS"))
       if (*e) gather_wanted = atol(e);
@@ -1506,6 +1516,60 @@ CBoolResult_t ffi_verify_with_roots(FFI_RLN_t* const* rln, FFI_RLNProof_t* const
       if (!found) throw Error("Verification error: Expected one of the provided roots");
     }
     if (cfr_cmp(R(x), pr.values.x) != 0) throw Error("Verification error: Signal value does not match");
+    return true;
+  });
+}
+// EXT: n proofs in one call; the public-input rows are verify_zk's (proof.rs:863-885), the pairing checks run on the
+// device from verify_gpu_min proofs on and on host threads below
+CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
+                                          const CFr_t* xs, const Vec_CFr_t* roots, bool* ok) {
+  return guard_bool([&]() {
+    if (!rln || !*rln) throw Error("Verification error: null RLN object");
+    if (n == 0) return true;
+    if (!proofs || !xs || !ok) throw Error("Verification error: null argument");
+    FFI_RLN& r = *(FFI_RLN*)*rln;
+    const size_t nv = r.prover->zkey().gamma_abc_g1.size() - 1;
+    std::vector<uint8_t> bytes(128 * n), rows;
+    rows.reserve(32 * nv * n);
+    auto put = [&](const CFr& v) { rows.insert(rows.end(), v.le, v.le + 32); };
+    for (size_t i = 0; i < n; i++) {
+      if (!proofs[i]) throw Error("Verification error: null proof");
+      const FFI_RLNProof& pr = *(const FFI_RLNProof*)proofs[i];
+      const FFI_RLNProofValues& v = pr.values;
+      const size_t before = rows.size();
+      if (!v.multi) {
+        put(v.y); put(v.root); put(v.nullifier); put(v.x); put(v.external_nullifier);
+      } else {
+        for (auto& y : v.ys) put(y);
+        put(v.root);
+        for (auto& nl : v.nullifiers) put(nl);
+        put(v.x);
+        put(v.external_nullifier);
+        for (uint8_t b : v.selector_used) put(cfr_from_u64(b ? 1 : 0));
+      }
+      if (rows.size() - before != 32 * nv)
+        throw Error("Error producing proof: malformed verifying key (public input count does not match the circuit)");
+      memcpy(&bytes[128 * i], pr.proof, 128);
+    }
+    std::vector<uint8_t> pass(n);
+    if (n >= r.verify_gpu_min)
+      r.prover->gpu_verifier().verify(n, bytes.data(), rows.data(), nv, pass.data(), nullptr);
+    else
+      verify_many_common(r.prover->zkey(), n, bytes.data(), rows.data(), nv, 0, pass.data());
+    CFr own;
+    if (!roots) r.tree.get_node_host(0, own.le);
+    for (size_t i = 0; i < n; i++) {
+      const FFI_RLNProofValues& v = ((const FFI_RLNProof*)proofs[i])->values;
+      bool good = pass[i] != 0;
+      if (!roots) {
+        good = good && cfr_cmp(own, v.root) == 0;
+      } else if (roots->len) {
+        bool found = false;
+        for (size_t k = 0; k < roots->len; k++) found |= cfr_cmp(((const CFr*)roots->ptr)[k], v.root) == 0;
+        good = good && found;
+      }
+      ok[i] = good && cfr_cmp(((const CFr*)xs)[i], v.x) == 0;
+    }
     return true;
   });
 }

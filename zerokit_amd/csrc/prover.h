@@ -21,6 +21,7 @@
 #pragma once
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -86,6 +87,8 @@ struct ProofOut {            // one proof, host side
   uint8_t values[5][32];     // y, root, nullifier, x, external_nullifier (verifier order, proof.rs:863-869)
   uint32_t error;            // 0 ok; otherwise witness-graph evaluation failed for this proof
 };
+
+class GpuVerifier;
 
 class Prover {
  public:
@@ -219,6 +222,8 @@ class Prover {
   // [G1 digits, G2 digits, a|b|c (h), G1 partial sums, G2 partial sums, staged inputs + (r, s)]
   static constexpr int RESIDUE_FIELDS = 6;
   void residue(uint64_t out[RESIDUE_FIELDS]);
+  // the device Groth16 verifier of this prover's key (verify.h), made on first use; independent of the proving pipeline
+  GpuVerifier& gpu_verifier();
 
  private:
   uint64_t settle_hints(uint64_t ticket);
@@ -232,6 +237,8 @@ class Prover {
   size_t B_ = 0;
   float init_ms_[4] = {0, 0, 0, 0};
   int c_ = 8, W_ = 32, c2_ = 8, W2_ = 32;
+  std::mutex verifier_mu_;
+  std::shared_ptr<GpuVerifier> verifier_;
 };
 
 }  // namespace rlnamd

@@ -62,6 +62,10 @@ struct TreeConfig {
   // "auto_partial": N -- ffi_generate_rln_proof remembers the partial proofs of up to N members and finishes instead of
   // proving from scratch when a member proves again at the same root (ffi.cpp: FFI_RLN::auto_partial).  0 (default): off
   long auto_partial = 0;
+  // "verify_gpu_min": N -- ffi_verify_rln_proofs_batch verifies on the device when a call brings at least N proofs, on host
+  // threads below (a lane verifies one proof, so a device pass takes as long as one serial verification on a lane
+  // whatever n is).  -1 (default): VERIFY_GPU_MIN_DEFAULT; 0: always the device
+  long verify_gpu_min = -1;
   // "gather_calls": N -- single-proof calls that arrive from other threads while a proof is on the device go out together,
   // as one batch of up to N, when it returns (ffi.cpp: prove_one).  -1 (default): on, up to the workspace's capacity;
   // 0 or 1: every call is its own batch, one after the other
@@ -193,6 +197,10 @@ inline TreeConfig parse_tree_config(const std::string& js) {
       if (key == "auto_partial") {
         if (num < 0 || num > 65536) throw Error("Configuration error: auto_partial: expected 0 .. 65536 members");
         c.auto_partial = num;
+      }
+      if (key == "verify_gpu_min") {
+        if (num < 0 || num > 1000000000) throw Error("Configuration error: verify_gpu_min: expected 0 .. 1000000000 proofs");
+        c.verify_gpu_min = num;
       }
       if (key == "gather_calls") {
         if (num < 0 || num > 65536) throw Error("Configuration error: gather_calls: expected 0 .. 65536 calls");

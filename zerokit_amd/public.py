@@ -509,6 +509,25 @@ class RLN:
         return _ok_bool(lib().ffi_verify_with_roots(C.byref(self._h), C.byref(proof._h), C.byref(v),
                                                     C.byref(_cfr(x))))
 
+    def verify_rln_proofs_batch(self, proofs, xs, roots=None):
+        """EXT: n proofs checked in one call (ffi_verify_rln_proofs_batch).  roots=None checks against this object's
+        current root, a list is verify_with_roots' rule (an empty list accepts any root).  Returns a list of bools;
+        the pairing checks run on the device when n is at least the object's "verify_gpu_min"."""
+        n = len(proofs)
+        if len(xs) != n:
+            raise RLNError("verify_rln_proofs_batch: %d proofs but %d signals" % (n, len(xs)))
+        if n == 0:
+            return []
+        hs = (C.c_void_p * n)(*[p._h.value for p in proofs])
+        flat, _k = _vec_cfr(list(xs))
+        rp = None
+        if roots is not None:
+            v, _k2 = _vec_cfr(list(roots))
+            rp = C.byref(v)
+        ok = (C.c_bool * n)()
+        _ok_bool(lib().ffi_verify_rln_proofs_batch(C.byref(self._h), hs, n, flat.ptr, rp, ok))
+        return [bool(b) for b in ok]
+
 
 def compute_id_secret(share1, share2) -> int:
     """protocol/slashing.rs:12-36: shares are (x, y) pairs"""
