@@ -100,7 +100,9 @@ CBoolResult_t ffi_generate_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNWitnes
  * otherwise ffi_verify_with_roots' rule (an empty vector accepts any root).  ok[i] = 1 when proof i passes the
  * three checks of public.rs:725-771 (pairing, root, xs[i] == the proof's x), else 0.  The call itself fails only
  * for a call-level error (null pointers, a proof of the other circuit kind).  The pairing checks run on the device
- * when n is at least the object's "verify_gpu_min" (config JSON), on host threads below it. */
+ * when n is at least the object's "verify_gpu_min" (config JSON), on host threads below it; "verify_lanes" (1 | 8 | 0)
+ * names the shape of those device passes (rln_amd.h: rlnamd_verify_many_gpu_ex; 0, the default: by the size of the
+ * call). */
 CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
                                           const CFr_t* xs, const Vec_CFr_t* roots, bool* ok);
 

@@ -257,15 +257,26 @@ int rlnamd_verify(rlnamd_prover* p, const uint8_t proof[128], const uint8_t valu
  * (protocol/proof.rs:856-894); a relay node verifies every message it forwards. */
 int rlnamd_verify_many(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t n_values,
                        int threads, uint8_t* ok);
-/* EXT: n independent verifications on the device (a lane per proof; verify.hip).  Same inputs and the same verdicts as
- * rlnamd_verify_many.  The verifier has its own stream and buffers and never waits for a proving batch; calls from
- * several threads serialise.  n = 0 succeeds and writes nothing. */
+/* EXT: n independent verifications on the device.  Same inputs and the same verdicts as rlnamd_verify_many.  The
+ * verifier has its own stream and buffers and never waits for a proving batch; calls from several threads serialise.
+ * n = 0 succeeds and writes nothing.  The verifier chooses the shape by n: a team of 8 lanes per proof (verify_team.hip)
+ * for calls that a lane per proof (verify.hip) cannot spread over the chip -- see rlnamd_verify_many_gpu_ex. */
 int rlnamd_verify_many_gpu(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t n_values,
                            uint8_t* ok);
 /* test / diagnosis: the final-exponentiated pairing product of each proof, 12 x 32 bytes canonical LE in
  * pairing.h's coefficient order (1 = accept); rows of proofs rejected before the pairing are all zero. */
 int rlnamd_verify_many_gpu_gt(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
                               size_t n_values, uint8_t* gt384);
+/* The same with the shape named: lanes = 1 a lane per proof (chunks of 65 536), 8 a team of 8 lanes per proof (chunks
+ * of 8 192; a verification's serial chain is about a third as long), 0 the verifier chooses -- teams for calls of at
+ * most verify_team_max proofs (1 024), unless RLNAMD_VERIFY_LANES = 1 | 8 was set when the prover was built.  Any
+ * other value of lanes is an error.  Both shapes give the same bytes.  ok (n bytes) and gt384 (n x 384 bytes) may
+ * each be null. */
+int rlnamd_verify_many_gpu_ex(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                              size_t n_values, int lanes, uint8_t* ok, uint8_t* gt384);
+/* test / diagnosis: chunks the device verifier has run so far with a lane per proof (passes[0]) and in team form
+ * (passes[1]) */
+int rlnamd_verify_gpu_passes(rlnamd_prover* p, size_t passes[2]);
 int rlnamd_verify_many_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n, const uint8_t* proofs,
                                  const uint8_t* values_le, size_t n_values, int threads, uint8_t* ok);
 /* same check straight from arkzkey bytes; needs no GPU (host parser + host pairing only) */

@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""Verification throughput: the device verifier (rlnamd_verify_many_gpu) against 16 host threads
-(rlnamd_verify_many), compressed proof bytes in, verdicts out, copies to and from the device inside the timed region.
+"""Verification throughput: the device verifier (rlnamd_verify_many_gpu_ex), a lane per proof and a team of 8 lanes
+per proof, against 16 host threads (rlnamd_verify_many), compressed proof bytes in, verdicts out, copies to and from the
+device inside the timed region.
 
-    python tools/verify_throughput.py [--calls 9] [--out FILE]
+    python tools/verify_throughput.py [--calls 9] [--lanes 1,8] [--out FILE]
 
 prints ONE JSON line.  Torch-free (ctypes through zerokit_amd).  Each of the two steps runs in a child process of its
 own under a time limit; a step that fails or runs out of time ends the run there.
 
-  sweep       host at n = 64, 1 024, 8 192 (and at the smaller device sizes, for the crossover); device at
-              n = 1 ... 65 536 (512 added to the sizes the host is measured at, to place the crossover); median and spread of `calls` calls after a warm-up call per size; the crossover (smallest
-              measured n where the device's median beats the host's at that n)
+  sweep       host at n = 1 ... 8 192; device at n = 1 ... 65 536, one column per shape of --lanes (1: a lane per
+              proof, 8: teams, 0: the verifier's choice), the shapes alternated call by call at each size; median and
+              spread of `calls` calls after a warm-up call per size and shape; per shape the crossover (smallest measured
+              n where the device's median beats the host's at that n); with both shapes measured, team_max: the largest
+              measured n at which the teams' median is below the minimum of a lane per proof
   concurrent  device verification at n = 8 192 while a proving stream runs, and the proving rate alone and meanwhile
 """
 import argparse
@@ -27,9 +30,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HOST_THREADS = 16
-DEVICE_N = (1, 8, 64, 256, 512, 1024, 8192, 65536)
-HOST_N = (1, 8, 64, 256, 512, 1024, 8192)
-STEP_LIMIT_S = {"sweep": 420, "concurrent": 240}
+DEVICE_N = (1, 8, 64, 96, 128, 192, 256, 384, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536)
+HOST_N = (1, 8, 64, 96, 128, 192, 256, 384, 512, 1024, 8192)
+STEP_LIMIT_S = {"sweep": 540, "concurrent": 240}
 
 
 def setup():
@@ -67,19 +70,28 @@ def row(n, ts):
             "max_ms": round(max(ts) * 1e3, 3), "per_s": round(n / med, 1)}
 
 
-def step_sweep(calls):
+def step_sweep(calls, shapes=(1, 8)):
     from zerokit_amd import lib
     from zerokit_amd._native import check
     p, _inp, _rsb, proofs, values = setup()
-    host, dev = [], []
+    host, dev = [], {k: [] for k in shapes}
     for n in DEVICE_N:
         pr, va = tiled(proofs, values, n)
         ok = C.create_string_buffer(n)
 
-        def gpu():
-            check(lib().rlnamd_verify_many_gpu(p._h, n, pr, va, 5, ok))
-        dev.append(row(n, timed(gpu, calls)))
-        assert ok.raw == b"\x01" * n
+        def gpu(lanes):
+            check(lib().rlnamd_verify_many_gpu_ex(p._h, n, pr, va, 5, lanes, ok, None))
+        ts = {k: [] for k in shapes}
+        for k in shapes:   # warm-up: code objects, buffers at their size
+            gpu(k)
+            assert ok.raw == b"\x01" * n
+        for _ in range(calls):
+            for k in shapes:
+                t0 = time.perf_counter()
+                gpu(k)
+                ts[k].append(time.perf_counter() - t0)
+        for k in shapes:
+            dev[k].append(row(n, ts[k]))
     for n in HOST_N:
         pr, va = tiled(proofs, values, n)
         ok = C.create_string_buffer(n)
@@ -89,12 +101,21 @@ def step_sweep(calls):
         host.append(row(n, timed(cpu, calls if n < 8192 else max(3, calls // 3))))
         assert ok.raw == b"\x01" * n
     hmed = {r["n"]: r["median_ms"] for r in host}
-    wins = [r["n"] for r in dev if r["n"] in hmed and r["median_ms"] < hmed[r["n"]]]
+    out = {"host_threads": HOST_THREADS, "host": host}
+    for k in shapes:
+        wins = [r["n"] for r in dev[k] if r["n"] in hmed and r["median_ms"] < hmed[r["n"]]]
+        out["device_lanes%d" % k] = dev[k]
+        out["crossover_n_lanes%d" % k] = min(wins) if wins else None
+    if 1 in dev and 8 in dev:
+        lane_min = {r["n"]: r["min_ms"] for r in dev[1]}
+        faster = [r["n"] for r in dev[8] if r["median_ms"] < lane_min[r["n"]]]
+        out["team_max"] = max(faster) if faster else 0
     p.close()
-    return {"host_threads": HOST_THREADS, "host": host, "device": dev, "crossover_n": min(wins) if wins else None}
+    return out
 
 
-def step_concurrent(calls):
+def step_concurrent(calls, shapes=(0,)):
+    lanes = shapes[0] if len(shapes) == 1 else 0
     from zerokit_amd import lib
     from zerokit_amd._native import check
     p, inp, rsb, proofs, values = setup()
@@ -102,7 +123,7 @@ def step_concurrent(calls):
     ok = C.create_string_buffer(8192)
 
     def gpu():
-        check(lib().rlnamd_verify_many_gpu(p._h, 8192, pr, va, 5, ok))
+        check(lib().rlnamd_verify_many_gpu_ex(p._h, 8192, pr, va, 5, lanes, ok, None))
 
     def prove_stream(batches):
         nslots, inflight = p.n_slots(), collections.deque()
@@ -131,7 +152,7 @@ def step_concurrent(calls):
     th.join()
     assert ok.raw == b"\x01" * 8192
     p.close()
-    return {"prove_alone_per_s": round(alone_prove, 1), "verify_alone": alone_verify,
+    return {"lanes": lanes, "prove_alone_per_s": round(alone_prove, 1), "verify_alone": alone_verify,
             "prove_meanwhile_per_s": round(res["rate"], 1), "verify_meanwhile": row(8192, ts) if ts else None}
 
 
@@ -141,18 +162,24 @@ STEPS = {"sweep": step_sweep, "concurrent": step_concurrent}
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=9)
+    ap.add_argument("--lanes", default="1,8", help="shapes to measure, of 1 (a lane per proof), 8 (teams), 0 (the "
+                    "verifier's choice): a column each in the sweep; the concurrent step takes a single one, else 0")
     ap.add_argument("--out")
     ap.add_argument("--step", choices=sorted(STEPS))
     a = ap.parse_args()
     if a.calls < 9:
         ap.error("--calls: at least 9")
+    shapes = tuple(int(k) for k in a.lanes.split(","))
+    if not shapes or any(k not in (0, 1, 8) for k in shapes) or len(set(shapes)) != len(shapes):
+        ap.error("--lanes: a list of distinct values of 0, 1, 8")
     if a.step:
-        print(json.dumps(STEPS[a.step](a.calls)))
+        print(json.dumps(STEPS[a.step](a.calls, shapes)))
         return 0
-    out = {"tool": "verify_throughput", "calls": a.calls}
+    out = {"tool": "verify_throughput", "calls": a.calls, "lanes": list(shapes)}
     for name in ("sweep", "concurrent"):
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--calls", str(a.calls)],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--calls", str(a.calls), "--lanes",
+                                a.lanes],
                                stdout=subprocess.PIPE, timeout=STEP_LIMIT_S[name])
         except subprocess.TimeoutExpired:
             out[name] = {"error": "time limit of %d s" % STEP_LIMIT_S[name]}

@@ -142,6 +142,9 @@ SIGNATURES = {
     "rlnamd_verify_many": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_char_p]),
     "rlnamd_verify_many_gpu": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p]),
     "rlnamd_verify_many_gpu_gt": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p]),
+    "rlnamd_verify_many_gpu_ex": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_char_p,
+                                            C.c_char_p]),
+    "rlnamd_verify_gpu_passes": (C.c_int, [P, C.POINTER(C.c_size_t)]),
     "rlnamd_verify_many_with_zkey": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t,
                                                C.c_int, C.c_char_p]),
     "rlnamd_parse_resources": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)]),

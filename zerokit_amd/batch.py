@@ -396,30 +396,36 @@ class BatchProver:
                                        nv, threads, ok))
         return [bool(x) for x in ok.raw]
 
-    def verify_many_gpu(self, proofs, public_inputs):
-        """n independent verifications on the device (rlnamd_verify_many_gpu): the verdicts of verify_many; returns a
-        list of bools"""
+    def verify_many_gpu(self, proofs, public_inputs, lanes=0):
+        """n independent verifications on the device (rlnamd_verify_many_gpu_ex): the verdicts of verify_many; returns
+        a list of bools.  lanes: 1 a lane per proof, 8 a team of 8 lanes per proof, 0 the verifier chooses by n"""
         n = len(proofs)
         if n == 0:
             return []
         nv = _check_verify_shapes(proofs, public_inputs)
         ok = C.create_string_buffer(n)
-        check(lib().rlnamd_verify_many_gpu(self._h, n, b"".join(proofs),
-                                           b"".join(_b(v) for pi in public_inputs for v in pi), nv, ok))
+        check(lib().rlnamd_verify_many_gpu_ex(self._h, n, b"".join(proofs),
+                                              b"".join(_b(v) for pi in public_inputs for v in pi), nv, lanes, ok, None))
         return [bool(x) for x in ok.raw]
 
-    def verify_many_gpu_gt(self, proofs, public_inputs):
+    def verify_many_gpu_gt(self, proofs, public_inputs, lanes=0):
         """the final-exponentiated pairing product of each proof as computed on the device
-        (rlnamd_verify_many_gpu_gt): a list of 384-byte strings, 12 canonical LE field elements in pairing.h's
+        (rlnamd_verify_many_gpu_ex): a list of 384-byte strings, 12 canonical LE field elements in pairing.h's
         coefficient order; the encoding of 1 for an accepted proof, all zero for one rejected before the pairing"""
         n = len(proofs)
         if n == 0:
             return []
         nv = _check_verify_shapes(proofs, public_inputs)
         gt = C.create_string_buffer(384 * n)
-        check(lib().rlnamd_verify_many_gpu_gt(self._h, n, b"".join(proofs),
-                                              b"".join(_b(v) for pi in public_inputs for v in pi), nv, gt))
+        check(lib().rlnamd_verify_many_gpu_ex(self._h, n, b"".join(proofs),
+                                              b"".join(_b(v) for pi in public_inputs for v in pi), nv, lanes, None, gt))
         return [gt.raw[384 * i:384 * (i + 1)] for i in range(n)]
+
+    def verify_gpu_passes(self):
+        """(chunks the device verifier has run with a lane per proof, chunks in team form) so far"""
+        out = (C.c_size_t * 2)()
+        check(lib().rlnamd_verify_gpu_passes(self._h, out))
+        return int(out[0]), int(out[1])
 
     def verify(self, proof: bytes, public_inputs):
         """verify_zk_proof (protocol/proof.rs:856-894); public_inputs = [y, root, nullifier, x, ext]."""

@@ -637,6 +637,19 @@ int rlnamd_verify_many_gpu_gt(rlnamd_prover* p, size_t n, const uint8_t* proofs,
   if (n) p->p->gpu_verifier().verify(n, proofs, values_le, n_values, nullptr, gt384);
   RLN_CATCH
 }
+int rlnamd_verify_many_gpu_ex(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                              size_t n_values, int lanes, uint8_t* ok, uint8_t* gt384) {
+  RLN_TRY
+  if (lanes != 0 && lanes != 1 && lanes != 8) throw Error("rlnamd_verify_many_gpu_ex: lanes must be 0, 1 or 8");
+  if (n_values + 1 != p->p->zkey().gamma_abc_g1.size()) throw Error("MalformedVerifyingKey");
+  if (n && (ok || gt384)) p->p->gpu_verifier().verify(n, proofs, values_le, n_values, ok, gt384, lanes);
+  RLN_CATCH
+}
+int rlnamd_verify_gpu_passes(rlnamd_prover* p, size_t passes[2]) {
+  RLN_TRY
+  p->p->gpu_verifier().passes(passes);
+  RLN_CATCH
+}
 int rlnamd_verify_many_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n, const uint8_t* proofs,
                                  const uint8_t* values_le, size_t n_values, int threads, uint8_t* ok) {
   RLN_TRY

@@ -295,6 +295,7 @@ struct FFI_RLN {
   size_t auto_partial = 0;
   // ffi_verify_rln_proofs_batch: calls of at least this many proofs are verified on the device ("verify_gpu_min")
   size_t verify_gpu_min = VERIFY_GPU_MIN_DEFAULT;
+  int verify_lanes = 0;   // "verify_lanes": lanes per proof of those passes (0: the verifier chooses)
   // single calls from several threads gathered into batches: gather.h
   struct GatherReq {
     FFI_RLNWitnessInput* w = nullptr;
@@ -378,6 +379,7 @@ struct FFI_RLN {
     const ProverConfig cfg = tcfg.prover_config();
     auto_partial = tcfg.auto_partial > 0 ? (size_t)tcfg.auto_partial : 0;
     verify_gpu_min = tcfg.verify_gpu_min >= 0 ? (size_t)tcfg.verify_gpu_min : VERIFY_GPU_MIN_DEFAULT;
+    verify_lanes = (int)tcfg.verify_lanes;
     gather_wanted = tcfg.gather_calls;
     if (const char* e = getenv("RLNAMD_GATHER_CALLS"))
       if (*e) gather_wanted = atol(e);
@@ -1553,7 +1555,7 @@ CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t*
     }
     std::vector<uint8_t> pass(n);
     if (n >= r.verify_gpu_min)
-      r.prover->gpu_verifier().verify(n, bytes.data(), rows.data(), nv, pass.data(), nullptr);
+      r.prover->gpu_verifier().verify(n, bytes.data(), rows.data(), nv, pass.data(), nullptr, r.verify_lanes);
     else
       verify_many_common(r.prover->zkey(), n, bytes.data(), rows.data(), nv, 0, pass.data());
     CFr own;

@@ -74,6 +74,7 @@ struct ProverTuning {
   uint32_t hint_chains = 64;           // RLNAMD_HINT_CHAINS: members whose public chain of hints (rate commitment, the hash after every level) is remembered on the host; 0: none
   uint32_t hint_max_warm = 64;         // RLNAMD_HINTS_WARM: ... and up to this many when at most 2.5 chains per host thread have to be hashed (the others are remembered: hint_chains)
   uint32_t hint_threads = 8;           // RLNAMD_HINT_THREADS: host threads (the caller's included) that hash the hint chains of a batch's proofs; at most half of the host's hardware threads unless set
+  int verify_lanes = 0;                // RLNAMD_VERIFY_LANES: lanes per proof of the device verifier (verify.h): 1 a lane, 8 a team, 0 by the size of the call (at most GpuVerifier::TEAM_MAX proofs: teams); any other value counts as 0
   int hint_fault = 0;                  // RLNAMD_HINT_FAULT (test hook): j > 0 corrupts hint j - 1 of the first proof of every hinted batch
   static ProverTuning from_env();
   std::string describe() const;

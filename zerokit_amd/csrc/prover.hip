@@ -524,6 +524,8 @@ ProverTuning ProverTuning::from_env() {
   t.partial_cache = (uint32_t)std::max(0, env_int("RLNAMD_PARTIAL_CACHE", (int)t.partial_cache));
   t.hint_max = (uint32_t)std::min<int>(std::max(0, env_int("RLNAMD_HINTS", (int)t.hint_max)), (int)HINT_PROOFS);
   t.hint_fault = env_int("RLNAMD_HINT_FAULT", 0);
+  t.verify_lanes = env_int("RLNAMD_VERIFY_LANES", 0);
+  if (t.verify_lanes != 1 && t.verify_lanes != 8) t.verify_lanes = 0;
   {   // (at most half of the host's hardware threads unless the switch says otherwise)
     const unsigned hw = std::thread::hardware_concurrency();
     const int dflt = hw ? (int)std::min<unsigned>(t.hint_threads, std::max(1u, hw / 2)) : (int)t.hint_threads;
@@ -537,9 +539,9 @@ std::string ProverTuning::describe() const {
   char b[768];
   snprintf(b, sizeof b,
            "window_bits=%d slots=%d lanechunk=%u lanechunk_walk=%u witlanes_max=%u tiny=%u ntt_lg_max=%u partial_cache=%u lone=%d "
-           "lone_small=%u hints=%u hints_warm=%u hint_threads=%u hint_chains=%u",
+           "lone_small=%u hints=%u hints_warm=%u hint_threads=%u hint_chains=%u verify_lanes=%d",
            window_bits, slots, lanechunk_max, lanechunk_walk_max, witlanes_max, tiny_max, ntt_lg_max, partial_cache, lone,
-           lone_small_max, hint_max, hint_max_warm, hint_threads, hint_chains);
+           lone_small_max, hint_max, hint_max_warm, hint_threads, hint_chains, verify_lanes);
   return b;
 }
 const ProverTuning& Prover::tuning() const { return d_->tune; }

@@ -66,6 +66,9 @@ struct TreeConfig {
   // threads below (a lane verifies one proof, so a device pass takes as long as one serial verification on a lane
   // whatever n is).  -1 (default): VERIFY_GPU_MIN_DEFAULT; 0: always the device
   long verify_gpu_min = -1;
+  // "verify_lanes": 1 | 8 | 0 -- lanes per proof of those device passes: a lane, a team of 8 (verify_team.hip), or by the
+  // size of the call (0, the default: RLNAMD_VERIFY_LANES if set, else teams up to GpuVerifier::TEAM_MAX proofs)
+  long verify_lanes = 0;
   // "gather_calls": N -- single-proof calls that arrive from other threads while a proof is on the device go out together,
   // as one batch of up to N, when it returns (ffi.cpp: prove_one).  -1 (default): on, up to the workspace's capacity;
   // 0 or 1: every call is its own batch, one after the other
@@ -201,6 +204,10 @@ inline TreeConfig parse_tree_config(const std::string& js) {
       if (key == "verify_gpu_min") {
         if (num < 0 || num > 1000000000) throw Error("Configuration error: verify_gpu_min: expected 0 .. 1000000000 proofs");
         c.verify_gpu_min = num;
+      }
+      if (key == "verify_lanes") {
+        if (num != 0 && num != 1 && num != 8) throw Error("Configuration error: verify_lanes: expected 0, 1 or 8");
+        c.verify_lanes = num;
       }
       if (key == "gather_calls") {
         if (num < 0 || num > 65536) throw Error("Configuration error: gather_calls: expected 0 .. 65536 calls");

@@ -12,23 +12,46 @@
 
 namespace rlnamd {
 
+namespace vm {
+struct PreparedKey;
+struct Prep;
+struct F12;
+}  // namespace vm
+
 class GpuVerifier {
  public:
   // Proofs per pass over the three kernels.  A lane verifies one proof, a workgroup is one wave, so a full chunk is
   // 1 024 waves: one for each SIMD of an MI355X (256 CUs x 4).  Staging for a chunk is 65 536 x (128 + 32 n_values)
   // bytes of pinned memory in and 65 536 bytes out; any n runs as ceil(n / CHUNK) passes.
   static constexpr size_t CHUNK = 65536;
-  explicit GpuVerifier(const Zkey& zk);   // uploads the prepared key to the current device
+  // The same pass with a team of 8 lanes per proof (verify_team.hip): 8 proofs per wave, so a full chunk is again one
+  // wave per SIMD.  A verification's serial chain is about a third as long, which is what a call that cannot fill the
+  // chip with a lane per proof waits for.
+  static constexpr size_t TEAM_CHUNK = 8192;
+  // verify_team_max: a call of at most this many proofs takes teams when the shape is left to the verifier: the
+  // largest measured n at which the teams' median is below the lane-per-proof minimum (profiles/verify_gpu_lanes.md)
+  static constexpr size_t TEAM_MAX = 1024;
+  // forced_lanes: 0 the verifier chooses by n, 1 / 8 every call that leaves the choice open takes that shape
+  // (ProverTuning::verify_lanes)
+  explicit GpuVerifier(const Zkey& zk, int forced_lanes = 0);   // uploads the prepared key to the current device
   ~GpuVerifier();
   GpuVerifier(const GpuVerifier&) = delete;
   GpuVerifier& operator=(const GpuVerifier&) = delete;
   // ok (n bytes) and gt384 (n x 384 bytes, the final-exponentiated pairing products) may each be null.  Throws
   // MalformedVerifyingKey when nv + 1 is not the key's gamma_abc_g1.size().  Calls from several threads serialise.
-  void verify(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv, uint8_t* ok, uint8_t* gt384);
+  // lanes: 1 a lane per proof, 8 a team per proof, 0 the verifier's choice; anything else throws.
+  void verify(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv, uint8_t* ok, uint8_t* gt384,
+              int lanes = 0);
+  // chunks run so far with a lane per proof ([0]) and in team form ([1]); for tests
+  void passes(size_t out[2]);
 
  private:
   struct Impl;
   std::unique_ptr<Impl> d_;
 };
+
+// verify_team.hip: the three team kernels over n <= TEAM_CHUNK proofs, enqueued on `stream` (a hipStream_t)
+void verify_team_enqueue(void* stream, const vm::PreparedKey* vk, const uint32_t* proofs, const uint32_t* vals,
+                         vm::Prep* prep, vm::F12* f, uint8_t* ok, uint32_t* gt, uint32_t n);
 
 }  // namespace rlnamd

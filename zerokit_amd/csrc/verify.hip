@@ -1,4 +1,5 @@
-// Groth16 verification on the device: a lane per proof, three kernels per chunk (decompress + subgroup test + public
+// Groth16 verification on the device: a lane per proof (the kernels below) or a team of 8 lanes per proof
+// (verify_team.hip; GpuVerifier::verify chooses by the size of the call), three kernels per chunk (decompress + subgroup test + public
 // input combination -> Miller loop -> final exponentiation) with a small per-proof record in HBM between them.  The
 // mathematics is verify_math.h; the prepared verifying key (line coefficients of gamma and delta, the Miller value of
 // (-alpha, beta), the d * IC_i rows, Frobenius constants: a few tens of KiB) is uploaded once and read at
@@ -72,6 +73,8 @@ struct GpuVerifier::Impl {
   uint8_t* h_ok = nullptr;
   uint8_t* h_gt = nullptr;
   size_t cap = 0;           // proofs the buffers hold: grows to the largest chunk seen, at most CHUNK
+  int forced_lanes = 0;     // 0: the shape follows the size of the call
+  size_t n_passes[2] = {0, 0};   // chunks run with a lane per proof, in team form (under mu)
 
   void reserve(size_t n, bool want_gt) {
     if (n > cap) {
@@ -97,19 +100,25 @@ struct GpuVerifier::Impl {
     h_in = h_ok = h_gt = nullptr;
     cap = 0;
   }
-  void chunk(size_t n, const uint8_t* proofs, const uint8_t* values, uint8_t* ok, uint8_t* gt384) {
+  void chunk(size_t n, const uint8_t* proofs, const uint8_t* values, uint8_t* ok, uint8_t* gt384, bool team) {
     reserve(n, gt384 != nullptr);
     memcpy(h_in, proofs, 128 * n);
     memcpy(h_in + 128 * n, values, 32 * nv * n);
     RLN_HIP(hipMemcpyAsync(d_in.p, h_in, n * (128 + 32 * nv), hipMemcpyHostToDevice, st));
     const uint32_t* d_proofs = d_in.p;
     const uint32_t* d_vals = d_in.p + 32 * n;
-    const dim3 grid(div_up(n, 64)), block(64);
-    hipLaunchKernelGGL(k_verify_prepare, grid, block, 0, st, key.p, d_proofs, d_vals, d_prep.p, (uint32_t)n);
-    hipLaunchKernelGGL(k_verify_miller, grid, block, 0, st, key.p, d_prep.p, d_f.p, (uint32_t)n);
-    hipLaunchKernelGGL(k_verify_final_exp, grid, block, 0, st, key.p, d_prep.p, d_f.p, ok ? d_ok.p : nullptr,
-                       gt384 ? d_gt.p : nullptr, (uint32_t)n);
+    if (team) {
+      verify_team_enqueue(st, key.p, d_proofs, d_vals, d_prep.p, d_f.p, ok ? d_ok.p : nullptr, gt384 ? d_gt.p : nullptr,
+                          (uint32_t)n);
+    } else {
+      const dim3 grid(div_up(n, 64)), block(64);
+      hipLaunchKernelGGL(k_verify_prepare, grid, block, 0, st, key.p, d_proofs, d_vals, d_prep.p, (uint32_t)n);
+      hipLaunchKernelGGL(k_verify_miller, grid, block, 0, st, key.p, d_prep.p, d_f.p, (uint32_t)n);
+      hipLaunchKernelGGL(k_verify_final_exp, grid, block, 0, st, key.p, d_prep.p, d_f.p, ok ? d_ok.p : nullptr,
+                         gt384 ? d_gt.p : nullptr, (uint32_t)n);
+    }
     RLN_HIP(hipGetLastError());
+    n_passes[team ? 1 : 0]++;
     if (ok) RLN_HIP(hipMemcpyAsync(h_ok, d_ok.p, n, hipMemcpyDeviceToHost, st));
     if (gt384) RLN_HIP(hipMemcpyAsync(h_gt, d_gt.p, n * 384, hipMemcpyDeviceToHost, st));
     RLN_HIP(hipStreamSynchronize(st));
@@ -118,9 +127,10 @@ struct GpuVerifier::Impl {
   }
 };
 
-GpuVerifier::GpuVerifier(const Zkey& zk) : d_(new Impl) {
+GpuVerifier::GpuVerifier(const Zkey& zk, int forced_lanes) : d_(new Impl) {
   require_gpu();
   Impl& D = *d_;
+  D.forced_lanes = (forced_lanes == 1 || forced_lanes == 8) ? forced_lanes : 0;
   RLN_HIP(hipGetDevice(&D.dev));
   PreparedKey K;
   std::vector<G1Affine> rows;
@@ -145,19 +155,24 @@ GpuVerifier::~GpuVerifier() {
 }
 
 void GpuVerifier::verify(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv, uint8_t* ok,
-                         uint8_t* gt384) {
+                         uint8_t* gt384, int lanes) {
   Impl& D = *d_;
+  if (lanes != 0 && lanes != 1 && lanes != 8) throw Error("verify: lanes must be 0 (choose), 1 or 8");
   if (nv != D.nv) throw Error("MalformedVerifyingKey");
   if (n == 0) return;
   std::lock_guard<std::mutex> lk(D.mu);
+  // One threshold: a call that a lane per proof cannot spread over the chip takes teams
+  if (lanes == 0) lanes = D.forced_lanes ? D.forced_lanes : (n <= TEAM_MAX ? 8 : 1);
+  const bool team = lanes == 8;
+  const size_t step = team ? TEAM_CHUNK : CHUNK;
   int cur = 0;
   RLN_HIP(hipGetDevice(&cur));
   if (cur != D.dev) RLN_HIP(hipSetDevice(D.dev));
   try {
-    for (size_t off = 0; off < n; off += CHUNK) {
-      const size_t m = n - off < CHUNK ? n - off : CHUNK;
+    for (size_t off = 0; off < n; off += step) {
+      const size_t m = n - off < step ? n - off : step;
       D.chunk(m, proofs + 128 * off, values_le + 32 * nv * off, ok ? ok + off : nullptr,
-              gt384 ? gt384 + 384 * off : nullptr);
+              gt384 ? gt384 + 384 * off : nullptr, team);
     }
   } catch (...) {
     if (cur != D.dev) (void)hipSetDevice(cur);
@@ -166,9 +181,15 @@ void GpuVerifier::verify(size_t n, const uint8_t* proofs, const uint8_t* values_
   if (cur != D.dev) RLN_HIP(hipSetDevice(cur));
 }
 
+void GpuVerifier::passes(size_t out[2]) {
+  std::lock_guard<std::mutex> lk(d_->mu);
+  out[0] = d_->n_passes[0];
+  out[1] = d_->n_passes[1];
+}
+
 GpuVerifier& Prover::gpu_verifier() {
   std::lock_guard<std::mutex> lk(verifier_mu_);
-  if (!verifier_) verifier_ = std::make_shared<GpuVerifier>(zk_);
+  if (!verifier_) verifier_ = std::make_shared<GpuVerifier>(zk_, tuning().verify_lanes);
   return *verifier_;
 }
 
