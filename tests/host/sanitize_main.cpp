@@ -1,6 +1,7 @@
 // Sanitizer harness ("ASan/UBSan in CPU tests").  The product's HOST code that reads bytes it does not
 // control -- the arkzkey and graph parsers (zkey.cpp), the config_path JSON parser (tree_config.h), proof decompression
-// and the pairing verifier (pairing.h) -- plus the interpreter's scheduler (witness_sched.cpp), compiled by g++ with
+// and the pairing verifier (pairing.h) -- plus the interpreter's scheduler (witness_sched.cpp) and the prover's host
+// planning (prover_plan.cpp, through tests/host/proverplan.cpp), compiled by g++ with
 // -fsanitize=address,undefined and run on the shipped resources, on a golden proof and on a few thousand truncated /
 // bit-flipped inputs.  Malformed input must end in rlnamd::Error, never in a sanitizer report.  CPU only: the GPU pool
 // refuses sanitizer runs, and no HIP call is reached here.
@@ -23,6 +24,16 @@
 #include "witness_sched.h"
 #include "zkey.h"
 using namespace rlnamd;
+
+// tests/host/proverplan.cpp: the prover's host planning (prover_plan.cpp) on the shipped files
+extern "C" {
+const char* proverplan_error();
+int proverplan_run_program(const uint8_t* graph, size_t len, uint32_t ni, const uint8_t* inputs_le, size_t inputs_size,
+                           uint8_t* witness_out_le, uint32_t* stats);
+int proverplan_check_plans(const uint8_t* zkey, size_t zlen, const uint8_t* graph, size_t glen, char* log, size_t log_len,
+                           uint32_t* stats);
+int proverplan_check_hints(const uint8_t* graph, size_t len, uint32_t ni, const uint8_t* inputs_le, size_t inputs_size, uint32_t* stats);
+}
 
 static std::vector<uint8_t> slurp(const char* path) {
   std::vector<uint8_t> v;
@@ -322,6 +333,27 @@ int main(int argc, char** argv) {
     st[0] = 0;
     st[h.nodes.size() - 1] = 1;
     try { (void)wl_schedule(h, st, 2, true); parsed++; } catch (const std::exception&) { threw++; }
+  }
+  // 3c. the prover's planning on the shipped files: the k_witness29 program compiled and run over an all-zero member, every
+  //     walk plan built and checked, the hints hashed twice (chain cache)
+  {
+    std::vector<uint8_t> in((size_t)g.inputs_size * 32, 0), wit(g.signals.size() * 32);
+    in[0] = 1;
+    uint32_t stats[8] = {0};
+    char log[2048] = {0};
+    const uint32_t ni = (uint32_t)zk.num_instance_variables;
+    if (proverplan_run_program(gb.data(), gb.size(), ni, in.data(), g.inputs_size, wit.data(), stats) != 0 || stats[0] == 0) {
+      fprintf(stderr, "witness29 program: %s\n", proverplan_error());
+      failures++;
+    }
+    if (proverplan_check_plans(zb.data(), zb.size(), gb.data(), gb.size(), log, sizeof log, stats) != 0) {
+      fprintf(stderr, "walk plans: %s%s\n", log, proverplan_error());
+      failures++;
+    }
+    if (proverplan_check_hints(gb.data(), gb.size(), ni, in.data(), g.inputs_size, stats) != 0 || stats[2] || stats[3] || stats[5] != 1) {
+      fprintf(stderr, "hints: %s\n", proverplan_error());
+      failures++;
+    }
   }
   // 4. config_path JSON: well-formed, malformed, hostile
   const char* cfgs[] = {"{}", "{\"temporary\": true}", "{\"devices\": [0, 1, 2]}", "{\"devices\": [0, ]}", "{\"devices\": [",

@@ -1,7 +1,8 @@
 """AddressSanitizer + UBSan build of the product's host code that parses bytes it does not control (SURVEY section 5:
 sanitizers belong to the CPU suite; the GPU pool refuses them).  tests/host/sanitize_main.cpp compiles zkey.cpp (arkzkey
 and graph parsers, point decompression), pairing.h (the verifier), tree_config.h (the config_path JSON) and
-witness_sched.cpp (the interpreter's scheduler) with g++ -fsanitize=address,undefined and runs them on the shipped
+witness_sched.cpp (the interpreter's scheduler) and prover_plan.cpp (the prover's host planning: the k_witness29 program,
+the walk plans, the hints) with g++ -fsanitize=address,undefined and runs them on the shipped
 resources, on a golden proof and on ~2 500 truncated / mutated inputs: every malformed input must end in an error,
 and the sanitizers must stay silent.  Round 6: ffi_wire.h -- the (de)serialisers of the C ABI (rln proofs, proof values,
 witnesses, partial witnesses, partial proofs; V1 LE / BE and the V3 forms) -- on golden records and > 10 000 truncations,
@@ -17,7 +18,8 @@ CSRC = os.path.join(ROOT, "zerokit_amd", "csrc")
 def test_host_parsers_verifier_and_scheduler_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "sanitize_main")
     srcs = [os.path.join(ROOT, "tests", "host", "sanitize_main.cpp"), os.path.join(CSRC, "zkey.cpp"),
-            os.path.join(CSRC, "witness_sched.cpp")]
+            os.path.join(CSRC, "witness_sched.cpp"), os.path.join(ROOT, "tests", "host", "proverplan.cpp"),
+            os.path.join(CSRC, "prover_plan.cpp"), os.path.join(CSRC, "poseidon_host.cpp")]
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__",
                            "-I", "/opt/rocm/include", "-I", CSRC] + srcs + ["-o", exe])

@@ -53,6 +53,12 @@ struct DevBuf {
   void upload(const T* src, size_t count, hipStream_t s = 0) {
     RLN_HIP(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s));
   }
+  // a buffer for a host vector and its copy; an empty vector still gets one element, so that a kernel always has a pointer
+  // (the caller keeps `v` alive until the stream has passed the copy)
+  void assign(const std::vector<T>& v, hipStream_t s) {
+    alloc(v.empty() ? 1 : v.size());
+    if (!v.empty()) upload(v.data(), v.size(), s);
+  }
   void download(T* dst, size_t count, hipStream_t s = 0) const {
     RLN_HIP(hipMemcpyAsync(dst, p, count * sizeof(T), hipMemcpyDeviceToHost, s));
   }

@@ -139,7 +139,7 @@ class Prover {
   // submits later.  This is the path of SURVEY 8(d)'s timed region: H2D of witness inputs -> D2H of proofs.
   uint64_t submit(size_t n, const uint8_t* inputs, const uint8_t* rs, int mode = PROVE_FULL,
                   const uint8_t* partial320 = nullptr);
-  // The hints of a lone small batch (the values between the circuit's chained hashes: prover.hip, Impl::rln_hints) may be
+  // The hints of a lone small batch (the values between the circuit's chained hashes: prover_plan.h, HintChains) may be
   // computed ahead of the call, by any thread, one proof at a time: hint_words() 32-bit words per proof (0: this circuit
   // has no such form), hints_for() fills them from one proof's packed inputs.  submit_hinted() is submit() for a full
   // proof batch of at most 64 proofs whose hints are at hand (n x hint_words() words): nothing is hashed inside the call,

@@ -1,6 +1,8 @@
-// prover.hip -- host side of the batched prover: tables and walk plans, workspace slots, the stream pipeline
-// (Prover::enqueue), streamed submit / collect, wipes and the parity taps.  The kernels live in prover_front.hip,
-// prover_walks.hip and prover_back.hip (declarations: prover_kernels.h).
+// prover.hip -- host side of the batched prover: uploads of the tables and plans, workspace slots, the stream pipeline
+// (Prover::enqueue), streamed submit / collect, wipes and the parity taps.  What is uploaded and which shape a batch takes
+// is decided in prover_plan.cpp (host only, no HIP call: the k_witness29 program, hint cuts and hint hashing, point lists,
+// walk plans, batch_shape); the kernels live in prover_front.hip, prover_walks.hip and prover_back.hip (declarations:
+// prover_kernels.h).
 #include "prover.h"
 
 #include <fcntl.h>
@@ -18,6 +20,7 @@
 #include <thread>
 
 #include "prover_kernels.h"
+#include "prover_plan.h"
 #include "fq29.h"
 #include "glv.h"
 #include "pairing.h"
@@ -38,7 +41,6 @@ const char* const kProverStageNames[PROVER_STAGES] = {"witness", "matvec", "ntt"
 // Everything one in-flight batch owns.  Two slots let batch k+1 run its latency-bound front end (witness
 // interpreter, NTT) and batch k-1 its back end (reduction, finalize) on their own streams while batch k
 // keeps the chip busy with the MSM.
-constexpr uint32_t HINT_PROOFS = 64;   // most proofs of a batch that is interpreted as segments (ProverTuning::hint_max <= this)
 struct Slot {
   DevBuf<uint32_t> err, coords, values;
   DevBuf<uint8_t> comp;
@@ -177,7 +179,6 @@ struct Prover::Impl {
   float ms[PROVER_STAGES] = {0};
   DevBuf<unsigned long long> walk_clk;  // clock tap of the two walks: G1 cycles, G1 ticks, G2 cycles, G2 ticks
   ProverTuning tune;             // every switch, read once (prover.h)
-  uint32_t lanechunk_max = 128, lanechunk_walk_max = 48, witlanes_max = 1024;   // = tune.*
   DeviceCount device;            // counted in g_provers_on_device while the object lives
   DevBuf<GNode29> nodes29;
   DevBuf<uint32_t> consts29, slot2node;
@@ -197,38 +198,51 @@ struct Prover::Impl {
   DevBuf<G2Affine29> t2_29;
   DevBuf<uint32_t> sid1, sid2;
   // a walk = a list of table rows cut into chunks, plus the two-level reduction ranges; one per mode
-  struct Plan {
-    DevBuf<uint32_t> rows;
-    DevBuf<ChunkDesc> chunks, groups, segs, segchunks;   // segchunks: the chunk range of every segment (k_sum_tree)
-    DevBuf<uint32_t> rsid;                  // scalar id of every entry of `rows`
-    DevBuf<uint32_t> early_ids, late_ids;   // chunk indices without / with rows that depend on the quotient h
-    uint32_t nchunks = 0, ngroups = 0, nseg = 0, n_early = 0, n_late = 0;
-    // pair chunks (throughput plan of the full proof only; walk29.h PairPlan): rows of the even members, their scalar ids,
-    // the chunk ranges over them and the two output chunk slots of every pair chunk
-    DevBuf<uint32_t> prows, prsid, pout;
-    DevBuf<ChunkDesc> pchunks;
-    uint32_t npchunks = 0;
-    // two-stage sum of the tiny plans: segblocks[seg] = the range of 512-chunk blocks of a segment (block b covers
-    // chunks [segfirst + 512 b, ...)), maxblk = the most blocks any segment has
-    DevBuf<ChunkDesc> segblocks;
-    uint32_t nblocks = 0, maxblk = 0;
+  struct Plan {   // a WalkPlan (prover_plan.h) on the device, field by field
+    DevBuf<uint32_t> rows, rsid, early_ids, late_ids, prows, prsid, pout;
+    DevBuf<ChunkDesc> chunks, groups, segs, segchunks, segblocks, pchunks;
+    uint32_t nchunks = 0, ngroups = 0, nseg = 0, n_early = 0, n_late = 0, npchunks = 0, nblocks = 0, maxblk = 0;
+    void upload(const WalkPlan& W, hipStream_t s) {   // (waits for the copies: W may be a temporary)
+      nchunks = (uint32_t)W.chunks.size();
+      ngroups = (uint32_t)W.groups.size();
+      nseg = W.nseg;
+      n_early = (uint32_t)W.early_ids.size();
+      n_late = (uint32_t)W.late_ids.size();
+      npchunks = (uint32_t)W.pchunks.size();
+      nblocks = W.nblocks;
+      maxblk = W.maxblk;
+      rows.assign(W.rows, s);
+      rsid.assign(W.rsid, s);
+      chunks.assign(W.chunks, s);
+      groups.assign(W.groups, s);
+      segs.assign(W.segs, s);
+      segchunks.assign(W.segchunks, s);
+      segblocks.assign(W.segblocks, s);
+      early_ids.assign(W.early_ids, s);
+      late_ids.assign(W.late_ids, s);
+      if (npchunks) {
+        prows.assign(W.prows, s);
+        prsid.assign(W.prsid, s);
+        pout.assign(W.pout, s);
+        pchunks.assign(W.pchunks, s);
+      }
+      RLN_HIP(hipStreamSynchronize(s));
+    }
   };
-  Plan plan1[3], plan2[3];  // [PROVE_FULL, PROVE_PARTIAL, PROVE_FINISH]
+  // [WalkPlanKind][PROVE_FULL, PROVE_PARTIAL, PROVE_FINISH] (prover_plan.h).  PLAN_BIG: the throughput plans.  PLAN_SMALL:
   // the same walks cut into shorter chunks for batches walked with lanes = chunks: a walk lasts as long as its longest
-  // chunk (a lane's serial chain of additions), and a handful of proofs cannot fill the chip anyway
-  Plan plan1s[3], plan2s[3];
-  Plan plan1f[3];               // [PROVE_FULL] only: the fused small-batch plan (s A and r B1 as rows of the C segment)
-  // tiny batches (<= tune.tiny_max proofs, alone on the device): ONE (row, half) per lane -- a lane's chain is 9 (G1) or
-  // 8 (G2) additions instead of 36 / 16 -- and the partial sums, four times as many, meet in a two-stage tree
-  Plan plan1tf[3], plan2t[3];   // [PROVE_FULL] only: the fused plan and the G2 plan with chunks of one entry
+  // chunk (a lane's serial chain of additions), and a handful of proofs cannot fill the chip anyway.  PLAN_FUSED (G1,
+  // full and finish): s A and r B1 as rows of the C segment.  PLAN_TINY (<= tune.tiny_max proofs, alone on the device):
+  // ONE (row, half) per lane -- a lane's chain is 9 (G1) or 8 (G2) additions instead of 36 / 16 -- and the partial sums,
+  // four times as many, meet in a two-stage tree; its G1 plan is the fused one except for a partial proof.
+  Plan plan1[4][3], plan2[4][3];
   uint32_t max_chunks1t = 0, max_chunks2t = 0, max_blocks1t = 0, max_blocks2t = 0;
-  static constexpr uint32_t tiny_stride = 8;   // partial sums of a tiny batch: [chunk][8]
   uint32_t max_chunks1s = 0, max_chunks2s = 0, small_stride = 64;   // partial sums of a small batch: [chunk][64]
   uint32_t max_chunks1 = 0, max_chunks2 = 0, max_groups1 = 0, max_groups2 = 0;
   uint32_t npts1 = 0, npts2 = 0, npaired1 = 0;   // npaired1: G1 points [0, npaired1) are pair members
   std::vector<uint8_t> known;  // per witness signal: computable from the partial witness (evaluate_partial)
   // ---- the graph as independent segments behind hints (witness_sched.h: wl_segments; Prover::enqueue): the values between
-  //      the circuit's chained hashes are computed on a host core (rln_hints: depth + 2 Poseidon hashes, ~0.3 ms), every
+  //      the circuit's chained hashes are computed on a host core (HintChains: depth + 2 Poseidon hashes, ~0.3 ms), every
   //      segment of the graph is interpreted at once on the device with them as extra inputs, and every cut node's own value
   //      is compared with its hint afterwards (k_hint_check -> WERR_HINT -> the batch is run again over the whole graph)
   WitSegs segs;
@@ -236,132 +250,7 @@ struct Prover::Impl {
   uint32_t n_cut = 0, n_hints = 0;
   uint64_t hinted_batches = 0, hint_fallbacks = 0;
   bool no_hints_now = false;     // set around the re-run of a batch whose hints did not check
-  // The chain part of a member's hints -- rate commitment and the running hash after every level -- is a function of PUBLIC
-  // values only: the identity commitment (hint 0, hashed from the secret on every call) and the tree's nodes along the
-  // member's path.  A node that proves message after message with one identity while the root stands asks for the same
-  // chain again and again: the last few are remembered under a fingerprint of (identity commitment, limit, path
-  // elements, path bits) -- no secret in it, none in what is stored -- and a call that finds its chain hashes twice
-  // (identity commitment, a1) instead of depth + 2 times.  Nothing is trusted for it: k_hint_check compares every hint
-  // with the device's own value, a fingerprint collision or a stale entry costs one run over the whole graph.
-  struct ChainEntry {
-    uint64_t fp[2] = {0, 0};
-    uint64_t stamp = 0;
-    std::vector<Fr> chain;   // hints 1 .. depth
-  };
-  mutable std::mutex chain_mu;
-  mutable std::vector<ChainEntry> chain_cache;
-  mutable uint64_t chain_clock = 0, chain_hits = 0;
-  // the first step of a proof's hints by itself: identity commitment, the chain's fingerprint, and whether that chain is
-  // remembered -- what a batch above hint_max needs to know before it decides for the segments (enqueue)
-  struct HintProbe {
-    Fr idc;
-    uint64_t fp[2];
-    bool found;
-  };
-  void rln_hint_probe(const uint8_t* in_le, HintProbe* pr) const {
-    auto rd = [&](uint32_t slot) {
-      uint32_t c[8];
-      memcpy(c, in_le + 32 * (size_t)slot, 32);
-      return Fr::from_canonical(c);
-    };
-    const Fr secret = rd(slots.secret);
-    pr->idc = poseidon_hash_host(poseidon_host_params(2), &secret);
-    // fingerprint of the public values the chain depends on (two multiply-xorshift lanes over the 32-bit words)
-    uint64_t fp[2] = {0x9E3779B97F4A7C15ull, 0xC2B2AE3D27D4EB4Full};
-    auto mix = [&](const uint32_t* w, int n) {
-      for (int k = 0; k < n; k++) {
-        fp[0] = (fp[0] ^ w[k]) * 0xFF51AFD7ED558CCDull;
-        fp[0] ^= fp[0] >> 29;
-        fp[1] = (fp[1] + w[k]) * 0xC4CEB9FE1A85EC53ull;
-        fp[1] ^= fp[1] >> 31;
-      }
-    };
-    auto mix_slots = [&](uint32_t first, uint32_t count) {
-      for (uint32_t k = 0; k < count; k++) {
-        uint32_t w[8];
-        memcpy(w, in_le + 32 * (size_t)(first + k), 32);
-        mix(w, 8);
-      }
-    };
-    mix(pr->idc.v, 8);
-    mix_slots(slots.limit, 1);
-    mix_slots(slots.path, slots.depth);
-    mix_slots(slots.path_idx, slots.depth);
-    pr->fp[0] = fp[0];
-    pr->fp[1] = fp[1];
-    pr->found = false;
-    if (tune.hint_chains) {
-      std::lock_guard<std::mutex> lk(chain_mu);
-      for (const ChainEntry& e : chain_cache)
-        if (e.fp[0] == fp[0] && e.fp[1] == fp[1] && e.chain.size() == slots.depth) pr->found = true;
-    }
-  }
-  // idc, rate commitment, the running hash after levels 1 .. depth - 1, a1 (probe: rln_hint_probe's result for these inputs, or null)
-  void rln_hints(const uint8_t* in_le, Fr* out, const HintProbe* probe = nullptr) const {
-    auto rd = [&](uint32_t slot) {
-      uint32_t c[8];
-      memcpy(c, in_le + 32 * (size_t)slot, 32);
-      return Fr::from_canonical(c);
-    };
-    const PoseidonParams &P3 = poseidon_host_params(3), &P4 = poseidon_host_params(4);
-    HintProbe mine;
-    if (!probe) {
-      rln_hint_probe(in_le, &mine);
-      probe = &mine;
-    }
-    const Fr secret = rd(slots.secret), limit = rd(slots.limit);
-    const Fr idc = probe->idc;
-    out[0] = idc;
-    const uint64_t fp[2] = {probe->fp[0], probe->fp[1]};
-    bool found = false;
-    const size_t CHAIN_ENTRIES = tune.hint_chains;
-    if (CHAIN_ENTRIES) {
-      std::lock_guard<std::mutex> lk(chain_mu);
-      for (ChainEntry& e : chain_cache)
-        if (e.fp[0] == fp[0] && e.fp[1] == fp[1] && e.chain.size() == slots.depth) {
-          for (uint32_t l = 0; l < slots.depth; l++) out[1 + l] = e.chain[l];
-          e.stamp = ++chain_clock;
-          chain_hits++;
-          found = true;
-          break;
-        }
-    }
-    if (!found) {
-      Fr in2[2] = {idc, limit};
-      Fr node = poseidon_hash_host(P3, in2);
-      out[1] = node;
-      for (uint32_t l = 0; l < slots.depth; l++) {
-        const Fr e = rd(slots.path + l);
-        const bool right = !rd(slots.path_idx + l).is_zero();   // the node is the right child: hash(sibling, node)
-        in2[0] = right ? e : node;
-        in2[1] = right ? node : e;
-        node = poseidon_hash_host(P3, in2);
-        if (l + 1 < slots.depth) out[2 + l] = node;
-      }
-      if (CHAIN_ENTRIES) {
-        std::lock_guard<std::mutex> lk(chain_mu);
-        ChainEntry* slot = nullptr;
-        if (chain_cache.size() < CHAIN_ENTRIES) {
-          chain_cache.emplace_back();
-          slot = &chain_cache.back();
-        } else {
-          slot = &chain_cache[0];
-          for (ChainEntry& e : chain_cache)
-            if (e.stamp < slot->stamp) slot = &e;
-        }
-        slot->fp[0] = fp[0];
-        slot->fp[1] = fp[1];
-        slot->stamp = ++chain_clock;
-        slot->chain.assign(out + 1, out + 1 + slots.depth);
-      }
-    }
-    for (uint32_t k = 0; k < hint_msgs; k++) {   // a1 of every message slot (one on the single-message circuits)
-      const Fr in3[3] = {secret, rd(slots.ext), rd(hint_msg_off + k)};
-      out[slots.depth + 1 + k] = poseidon_hash_host(P4, in3);
-    }
-  }
-  bool have_hint_slots = false;          // the named inputs rln_hints reads exist (single- and multi-message-id circuits)
-  uint32_t hint_msg_off = 0, hint_msgs = 1;
+  HintChains hints;              // their hashing on the host, with the cache of remembered chains (prover_plan.h)
   // ---- the partial-proof cache and the cone program (prover.h: collect_partial_cached / submit_finish)
   WitLanes cone;                 // the unknown cone of evaluate_partial, scheduled like the full graph (witness_sched.h: wl_cone)
   uint32_t cone_nodes = 0;
@@ -397,7 +286,7 @@ struct Prover::Impl {
   Slot slot[NSLOT];
   int nslot = 5;                // Tuning::slots
   WinSched ws{}, ws2{};         // window schedules of the G1 and G2 comb tables
-  static constexpr uint32_t nh = 2;   // halves per scalar: the GLV split k1 + lambda k2 (glv.h)
+  static constexpr uint32_t nh = GLV_HALVES;  // halves per scalar: the GLV split k1 + lambda k2 (glv.h)
   int cur = 0;
   Slot* last = nullptr;
   uint64_t tickets = 0;         // submit() tickets handed out
@@ -553,18 +442,6 @@ static uint32_t bitrev(uint32_t x, int bits) {
   return r;
 }
 
-// chunks of one segment -> groups of <= 16 chunks -> the segment
-static void make_reduce_ranges(const std::vector<uint32_t>& segfirst, std::vector<ChunkDesc>& groups,
-                               std::vector<ChunkDesc>& segs) {
-  const uint32_t G = 16;
-  for (size_t sgi = 0; sgi + 1 < segfirst.size(); sgi++) {
-    uint32_t g0 = (uint32_t)groups.size();
-    for (uint32_t c = segfirst[sgi]; c < segfirst[sgi + 1]; c += G)
-      groups.push_back({c, std::min(c + G, segfirst[sgi + 1])});
-    segs.push_back({g0, (uint32_t)groups.size()});
-  }
-}
-
 // G1 table in the 9 x 29 form: slabs are built in the 8 x 32 form (k_table_build reads its own rows back) and
 // converted into place
 // where the constructor's time goes (Prover::init_ms): [0] parsing the arkzkey / graph + the verifier's precomputation,
@@ -601,28 +478,6 @@ static void build_table29(const std::vector<Affine<F>>& pts, const WinSched& ws,
   }
   RLN_HIP(hipStreamSynchronize(s));
   g_init_ms[2] += ms_since(t_build);
-}
-
-// c-bit windows, the first `wide` of them one bit wider; W = the fewest windows that cover the 127 bits of a GLV half
-// (< 2^126, plus the carry of the signed recoding)
-static WinSched make_sched(int c, int wide) {
-  if (c < 2 || c > 16 || wide < 0 || c + (wide > 0 ? 1 : 0) > 16) throw Error("window bits must be in [2, 16]");
-  WinSched ws{};
-  int W = (GlvParams::HALF_BITS - wide + c - 1) / c;
-  if (wide > W) throw Error("more wide windows than windows");
-  if (W > 32) throw Error("window bits too small: more than 32 windows");
-  ws.W = W;
-  uint32_t bit = 0, off = 0;
-  for (int j = 0; j < W; j++) {
-    int cw = c + (j < wide ? 1 : 0);
-    ws.cw[j] = (uint8_t)cw;
-    ws.bo[j] = (uint16_t)bit;
-    ws.ro[j] = off;
-    bit += cw;
-    off += 1u << (cw - 1);
-  }
-  ws.stride = off;
-  return ws;
 }
 
 Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_t graph_len, ProverConfig cfg)
@@ -706,259 +561,55 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
   // and back end).  tools/lanechunk_sweep.py / tools/midstream.py: one batch alone is faster that way up to ~450 proofs
   // (64: 12.4 vs 23.2 ms, 128: 17.8 vs 27.4, 256: 28.4 vs 36.8), a STREAM of such batches up to ~150 (chunks of 64: 9.4 k
   // vs 8.1 k proofs/s, 128: equal, 256: 10.1 k vs 12.1 k) -- 128 wins or ties on both.
-  D.lanechunk_max = D.tune.lanechunk_max;
-  D.witlanes_max = D.tune.witlanes_max;
-  D.lanechunk_walk_max = D.tune.lanechunk_walk_max;
   // partial sums of a small batch: [chunk][stride]
-  D.small_stride = std::max<uint32_t>(64, (std::min<uint32_t>(D.lanechunk_max, (uint32_t)B_) + 63) / 64 * 64);
-  // ---- named input slots (single message-id circuits; witness.rs:832-881): the proof-values kernel and the hints need them
-  D.have_values_kernel = false;
-  {
-    auto find = [&](const char* name, uint32_t want_len, uint32_t* off) {
-      auto it = graph_.input_mapping.find(name);
-      if (it == graph_.input_mapping.end() || it->second.second != want_len) return false;
-      *off = it->second.first;
-      return true;
-    };
-    D.slots.depth = graph_.tree_depth;
-    bool ok = graph_.max_out == 1 && D.ni == 6;
-    ok = ok && find("identitySecret", 1, &D.slots.secret) && find("userMessageLimit", 1, &D.slots.limit) &&
-         find("messageId", 1, &D.slots.msg_id) && find("pathElements", graph_.tree_depth, &D.slots.path) &&
-         find("identityPathIndex", graph_.tree_depth, &D.slots.path_idx) && find("x", 1, &D.slots.x) &&
-         find("externalNullifier", 1, &D.slots.ext);
-    D.have_values_kernel = ok;
-    // the hints need the same names, with one message id per message slot (the multi-message-id circuit: max_out of them)
-    uint32_t unused = 0;
-    D.hint_msgs = graph_.max_out;
-    D.have_hint_slots = find("identitySecret", 1, &D.slots.secret) && find("userMessageLimit", 1, &D.slots.limit) &&
-                        find("messageId", graph_.max_out, &D.hint_msg_off) && find("pathElements", graph_.tree_depth, &D.slots.path) &&
-                        find("identityPathIndex", graph_.tree_depth, &D.slots.path_idx) && find("x", 1, &D.slots.x) &&
-                        find("externalNullifier", 1, &D.slots.ext) &&
-                        (graph_.max_out == 1 || find("selectorUsed", graph_.max_out, &unused));
-  }
-  // ---- where the graph can be cut (segments behind hints): the nodes that hold the values between the chained hashes,
-  //      found on a probe witness -- every computed node whose value equals one of rln_hints' -- so that nothing about the
-  //      circuit's node numbering is assumed; a circuit on which a hint matches no node keeps the whole-graph interpreter
+  D.small_stride = std::max<uint32_t>(64, (std::min<uint32_t>(D.tune.lanechunk_max, (uint32_t)B_) + 63) / 64 * 64);
+  // ---- named input slots: the proof-values kernel and the hints need them
+  const NamedInputs named = find_named_inputs(graph_, D.ni);
+  D.slots = named.slots;
+  D.have_values_kernel = named.have_values_kernel;
+  D.hints.configure(named, D.tune.hint_chains);
+  // ---- where the graph can be cut (segments behind hints; find_hint_cuts): a circuit on which a hint matches no node
+  //      keeps the whole-graph interpreter
   std::vector<std::vector<uint32_t>> hint_cuts;
   std::vector<uint8_t> is_cut(D.N, 0);
-  if (D.have_hint_slots && D.tune.hint_max > 0 && graph_.tree_depth + 1 + graph_.max_out <= 64) {
-    // two probes with complementary path bits and unrelated values: a node that merely carries the running hash on one
-    // side of a level's left / right selection equals the hint under one of them only
-    D.n_hints = graph_.tree_depth + 1 + graph_.max_out;
-    hint_cuts.assign(D.n_hints, {});
-    std::vector<uint8_t> match(D.N, 1);
-    std::vector<uint32_t> match_hint(D.N, 0xFFFFFFFFu);
-    bool all = true;
-    uint64_t st = 0x9E3779B97F4A7C15ull;
-    for (int round = 0; round < 2 && all; round++) {
-      std::vector<uint8_t> probe((size_t)D.NI * 32, 0);
-      probe[0] = 1;
-      auto put = [&](uint32_t slot) {
-        for (int k = 0; k < 31; k++) {   // 248 pseudo-random bits: below r
-          st = st * 6364136223846793005ull + 1442695040888963407ull;
-          probe[32 * (size_t)slot + k] = (uint8_t)(st >> 56);
-        }
-      };
-      put(D.slots.secret); put(D.slots.x); put(D.slots.ext);
-      probe[32 * (size_t)D.slots.limit] = (uint8_t)(100 + round);
-      for (uint32_t k = 0; k < D.hint_msgs; k++) probe[32 * (size_t)(D.hint_msg_off + k)] = (uint8_t)(7 + round + 3 * k);
-      {
-        auto it = graph_.input_mapping.find("selectorUsed");   // every message slot in use
-        if (it != graph_.input_mapping.end())
-          for (uint32_t k = 0; k < it->second.second; k++) probe[32 * (size_t)(it->second.first + k)] = 1;
-      }
-      for (uint32_t l = 0; l < D.slots.depth; l++) {
-        put(D.slots.path + l);
-        probe[32 * (size_t)(D.slots.path_idx + l)] = (uint8_t)((l + round) & 1);
-      }
-      uint32_t perr = 0;
-      const std::vector<Fr> val = wl_eval_host(graph_, probe.data(), &perr);
-      std::vector<Fr> hv(D.n_hints);
-      D.rln_hints(probe.data(), hv.data());
-      all = perr == 0;
-      for (uint32_t n = 0; n < D.N && all; n++) {
-        if (!match[n]) continue;
-        if (graph_.nodes[n].op == G_INPUT || graph_.nodes[n].op == G_CONST) { match[n] = 0; continue; }
-        uint32_t j = round == 0 ? 0xFFFFFFFFu : match_hint[n];
-        if (round == 0) {
-          for (uint32_t q = 0; q < D.n_hints; q++)
-            if (val[n] == hv[q]) j = q;
-          match_hint[n] = j;
-        }
-        if (j == 0xFFFFFFFFu || !(val[n] == hv[j])) match[n] = 0;
-      }
-    }
-    for (uint32_t n = 0; n < D.N && all; n++)
-      if (match[n]) {
-        hint_cuts[match_hint[n]].push_back(n);
-        is_cut[n] = 1;
-      }
-    for (uint32_t j = 0; j < D.n_hints && all; j++) all = !hint_cuts[j].empty();
-    if (!all) {
-      hint_cuts.clear();
-      std::fill(is_cut.begin(), is_cut.end(), 0);
-      D.n_hints = 0;
-    }
+  if (named.have_hint_slots && D.tune.hint_max > 0 && D.hints.count() <= 64) {
+    hint_cuts = find_hint_cuts(graph_, named, D.hints);
+    if (!hint_cuts.empty()) D.n_hints = D.hints.count();
+    for (const auto& nodes : hint_cuts)
+      for (uint32_t n : nodes) is_cut[n] = 1;
   }
-  std::vector<uint32_t> slot2node;   // stored values: slot -> graph node
+  // ---- the program of k_witness29 and the compact array of stored values (compile_witness29)
+  const Wit29Program W29 = compile_witness29(graph_, is_cut);
+  D.nprog29 = W29.nprog;
+  D.nstore29 = (uint32_t)W29.slot2node.size();
+  D.nodes29.assign(W29.prog, s);
+  D.slot2node.assign(W29.slot2node, s);
+  D.consts29.alloc(std::max<size_t>(graph_.constants.size(), 1) * 9);
   {
-    // The program of k_witness29.  (1) Fusion: an Add one of whose operands is a product used nowhere else (and is no
-    // witness signal) becomes ONE node, a * b + c (W29_FMA: the addend enters the product's final carry chain,
-    // Fr29::mul_add) -- in the shipped circuits every addition of a Poseidon round is of that kind, 23 414 nodes become
-    // ~15 000.  (2) Program order = node order without the fused products; the LDS ring is addressed by program
-    // index.  (3) Stored values (witness signals, inputs, operands further back than the ring) live in a compact array
-    // indexed by `slot`.  (4) W29_RED where the static bound of a value (in units of r) would pass WIT29_BMAX.
-    const uint32_t NONE = 0xFFFFFFFFu;
-    const std::vector<GNode>& G = graph_.nodes;
-    auto is_const = [&](uint32_t o) { return G[o].op == G_CONST; };
-    auto nops = [&](const GNode& g) {
-      return (g.op == G_INPUT || g.op == G_CONST) ? 0 : (g.op == G_NEG || g.op == G_ID) ? 1 : g.op == G_TERN ? 3 : 2;
-    };
-    std::vector<uint32_t> uses(D.N, 0);
-    for (uint32_t n = 0; n < D.N; n++) {
-      const uint32_t o[3] = {G[n].a, G[n].b, G[n].c};
-      for (int k = 0; k < nops(G[n]); k++) {
-        if (o[k] >= n) throw Error("Graph error: node operand refers forward");
-        uses[o[k]]++;
-      }
-    }
-    std::vector<uint8_t> is_signal(D.N, 0);
-    for (uint32_t sgn : graph_.signals) is_signal[sgn] = 1;
-    std::vector<uint32_t> fused_mul(D.N, NONE);   // for an Add: the product folded into it
-    std::vector<uint8_t> removed(D.N, 0);
-    const bool fuse = true;
-    for (uint32_t n = 0; fuse && n < D.N; n++) {
-      if (G[n].op != G_ADD) continue;
-      for (uint32_t m : {G[n].b, G[n].a}) {
-        if (G[m].op == G_MUL && uses[m] == 1 && !is_signal[m] && !is_cut[m] && !removed[m] && G[n].a != G[n].b) {
-          fused_mul[n] = m;
-          removed[m] = 1;
-          break;
-        }
-      }
-    }
-    // program nodes: operands as ORIGINAL node ids
-    struct PNode { uint32_t op, node, src[3]; };
-    std::vector<PNode> P;
-    std::vector<uint32_t> pidx(D.N, NONE);
-    for (uint32_t n = 0; n < D.N; n++) {
-      if (removed[n]) continue;
-      PNode q{G[n].op, n, {G[n].a, G[n].b, G[n].c}};
-      if (fused_mul[n] != NONE) {
-        const uint32_t m = fused_mul[n];
-        q.op = W29_FMA;
-        q.src[0] = G[m].a;
-        q.src[1] = G[m].b;
-        q.src[2] = G[n].a == m ? G[n].b : G[n].a;
-      }
-      pidx[n] = (uint32_t)P.size();
-      P.push_back(q);
-    }
-    auto pn_ops = [&](const PNode& q) { return q.op == W29_FMA ? 3 : nops(GNode{q.op, 0, 0, 0}); };
-    std::vector<uint8_t> store(D.N, 0);
-    for (uint32_t n = 0; n < D.N; n++) store[n] = is_signal[n] || G[n].op == G_INPUT || is_cut[n];   // (a cut node is compared with its hint)
-    for (uint32_t i = 0; i < P.size(); i++)
-      for (int k = 0; k < pn_ops(P[i]); k++) {
-        const uint32_t o = P[i].src[k];
-        if (!is_const(o) && i - pidx[o] >= WIT29_RING) store[o] = 1;
-      }
-    std::vector<uint32_t> slot_of(D.N, 0);
-    for (uint32_t n = 0; n < D.N; n++)
-      if (store[n] && !removed[n]) {
-        slot_of[n] = (uint32_t)slot2node.size();
-        slot2node.push_back(n);
-      }
-    // The descriptor holds the slot in 16 bits.  The shipped circuits have at most 29 254 graph nodes, stored values
-    // being a subset of them, so only a much larger circuit can fail here.
-    if (slot2node.size() >= 65536)
-      throw Error("graph too large for the witness interpreter: " + std::to_string(slot2node.size()) +
-                  " stored values, the descriptor holds 16 bits");
-    std::vector<GNode29> prog(P.size());
-    std::vector<double> bnd(D.N, 1.01);
-    for (uint32_t i = 0; i < P.size(); i++) {
-      const PNode& q = P[i];
-      GNode29 d{};
-      uint32_t flags = store[q.node] ? W29_STORE : 0;
-      d.a = q.src[0];   // G_INPUT: input index, G_CONST: constant index
-      double b = 1.01;  // inputs, constants, slow operations: a fresh product with a constant
-      // the fast path of the kernel: Mul / Add / a * b + c with every operand in LDS (ring or constant table)
-      bool rare = q.op != G_MUL && q.op != G_ADD && q.op != W29_FMA;
-      if (q.op != G_INPUT && q.op != G_CONST) {
-        auto enc = [&](uint32_t o) -> uint32_t {
-          if (is_const(o)) {
-            if (G[o].a >= WIT29_LDS_CONSTS) rare = true;
-            return OPK_CONST | G[o].a;
-          }
-          if (i - pidx[o] < WIT29_RING) return OPK_RING | pidx[o];
-          rare = true;
-          return OPK_FAR | slot_of[o];
-        };
-        auto bo = [&](uint32_t o) { return is_const(o) ? 1.01 : bnd[o]; };
-        const int k = pn_ops(q);
-        double bs[3] = {0, 0, 0};
-        uint32_t e[3] = {0, 0, 0};
-        for (int j = 0; j < k; j++) {
-          e[j] = enc(q.src[j]);
-          bs[j] = bo(q.src[j]);
-        }
-        d.a = e[0];
-        d.b = e[1];
-        d.c = e[2];
-        if (q.op == G_MUL) b = 1.0 + 0.006 * bs[0] * bs[1];
-        else if (q.op == W29_FMA) b = 1.0 + 0.006 * bs[0] * bs[1] + bs[2];
-        else if (q.op == G_ADD) b = bs[0] + bs[1];
-        else if (q.op == G_SUB) b = bs[0] + 8.0;
-        else if (q.op == G_NEG) b = 8.0;
-        else if (q.op == G_TERN) b = std::max(bs[1], bs[2]);
-      }
-      if (b > WIT29_BMAX) {
-        flags |= W29_RED;
-        rare = true;
-        b = 1.0 + 0.006 * b;
-      }
-      if (rare) flags |= W29_RARE;
-      bnd[q.node] = b;
-      d.w0 = q.op | flags | (slot_of[q.node] << 16);
-      prog[i] = d;
-    }
-    D.nprog29 = (uint32_t)prog.size();
-    D.nstore29 = (uint32_t)slot2node.size();
-    prog.resize(((size_t)D.nprog29 / WIT29_CH + 4) * WIT29_CH, GNode29{});   // the kernel prefetches two chunks past the end
-    D.nodes29.alloc(prog.size());
-    D.nodes29.upload(prog.data(), prog.size(), s);
-    D.slot2node.alloc(std::max<size_t>(slot2node.size(), 1));
-    if (!slot2node.empty()) D.slot2node.upload(slot2node.data(), slot2node.size(), s);
-    D.consts29.alloc(std::max<size_t>(graph_.constants.size(), 1) * 9);
-    DevBuf<Fr> consts(graph_.constants.size());   // the constants in Fr form, for the conversion only
+    DevBuf<Fr> consts;   // the constants in Fr form, for the conversion only
     if (!graph_.constants.empty()) {
-      consts.upload(graph_.constants.data(), graph_.constants.size(), s);
+      consts.assign(graph_.constants, s);
       hipLaunchKernelGGL(k_consts_to29, dim3(div_up(graph_.constants.size(), 256)), dim3(256), 0, s, consts.p,
                          D.consts29.p, (uint32_t)graph_.constants.size());
     }
     RLN_HIP(hipGetLastError());
     RLN_HIP(hipStreamSynchronize(s));
-    {   // the same stored values, produced by a wave per proof (witness_lanes.h) when a batch is below a wave of proofs
-      std::vector<uint32_t> store_slot(D.N, 0xFFFFFFFFu);
-      for (uint32_t i = 0; i < slot2node.size(); i++) store_slot[slot2node[i]] = i;
-      D.witlanes.build(graph_, store_slot, (uint32_t)slot2node.size(), s);   // V29 has one row more than stored values
-      if (D.witlanes.ok && !hint_cuts.empty()) {
-        const WlSegments SG = wl_segments(graph_, hint_cuts);
-        D.segs.build(SG, store_slot, (uint32_t)slot2node.size(), s);
-        // worth it only where the cuts really shorten the program (the shipped circuits: 381 of 4 813 steps)
-        if (D.segs.ok && (D.segs.max_steps * 4 > D.witlanes.nsteps || D.segs.nseg > 256)) D.segs.ok = false;
-        if (D.segs.ok) {
-          D.n_cut = (uint32_t)SG.cut_nodes.size();
-          D.cut_node.alloc(D.n_cut);
-          D.cut_hint.alloc(D.n_cut);
-          D.cut_node.upload(SG.cut_nodes.data(), D.n_cut, s);
-          D.cut_hint.upload(SG.cut_hint.data(), D.n_cut, s);
-          RLN_HIP(hipStreamSynchronize(s));
-        }
-      }
+  }
+  // the same stored values, produced by a wave per proof (witness_lanes.h) when a batch is below a wave of proofs
+  D.witlanes.build(graph_, W29.store_slot, D.nstore29, s);   // V29 has one row more than stored values
+  if (D.witlanes.ok && !hint_cuts.empty()) {
+    const WlSegments SG = wl_segments(graph_, hint_cuts);
+    D.segs.build(SG, W29.store_slot, D.nstore29, s);
+    // worth it only where the cuts really shorten the program (the shipped circuits: 381 of 4 813 steps)
+    if (D.segs.ok && (D.segs.max_steps * 4 > D.witlanes.nsteps || D.segs.nseg > 256)) D.segs.ok = false;
+    if (D.segs.ok) {
+      D.n_cut = (uint32_t)SG.cut_nodes.size();
+      D.cut_node.assign(SG.cut_nodes, s);
+      D.cut_hint.assign(SG.cut_hint, s);
+      RLN_HIP(hipStreamSynchronize(s));
     }
   }
-  D.sig2node.alloc(D.NS);
-  D.sig2node.upload(graph_.signals.data(), D.NS, s);
+  D.sig2node.assign(graph_.signals, s);
 
   // ---- matrices as CSR over graph node ids
   auto csr = [&](const std::vector<SparseRow>& m, DevBuf<uint32_t>& ptr, DevBuf<uint32_t>& col, DevBuf<Fr>& coef) {
@@ -971,14 +622,9 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
       }
       hp[r + 1] = (uint32_t)hc.size();
     }
-    ptr.alloc(hp.size());
-    ptr.upload(hp.data(), hp.size(), s);
-    col.alloc(std::max<size_t>(hc.size(), 1));
-    coef.alloc(std::max<size_t>(hv.size(), 1));
-    if (!hc.empty()) {
-      col.upload(hc.data(), hc.size(), s);
-      coef.upload(hv.data(), hv.size(), s);
-    }
+    ptr.assign(hp, s);
+    col.assign(hc, s);
+    coef.assign(hv, s);
     RLN_HIP(hipStreamSynchronize(s));
   };
   csr(zk_.a, D.a_ptr, D.a_col, D.a_coef);
@@ -988,8 +634,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     for (uint32_t r = 0; r < D.nc; r++)
       if (zk_.a[r].col.size() > MV_LONG || zk_.b[r].col.size() > MV_LONG) lr.push_back(r);
     D.n_mv_long = (uint32_t)lr.size();
-    D.mv_long.alloc(std::max<size_t>(lr.size(), 1));
-    if (!lr.empty()) D.mv_long.upload(lr.data(), lr.size(), s);
+    D.mv_long.assign(lr, s);
     RLN_HIP(hipStreamSynchronize(s));
   }
 
@@ -1016,61 +661,36 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
       acc = acc * g;
     }
     for (uint32_t pos = 0; pos < D.n; pos++) cs[pos] = gp[bitrev(pos, D.logn)];
-    D.tw_f.alloc(tf.size());
-    D.tw_i.alloc(ti.size());
-    D.coset.alloc(cs.size());
-    D.tw_f.upload(tf.data(), tf.size(), s);
-    D.tw_i.upload(ti.data(), ti.size(), s);
-    D.coset.upload(cs.data(), cs.size(), s);
+    D.tw_f.assign(tf, s);
+    D.tw_i.assign(ti, s);
+    D.coset.assign(cs, s);
     RLN_HIP(hipStreamSynchronize(s));
   }
 
-  // ---- which witness signals are fixed by the partial witness (evaluate_partial, graph.rs:274-312): a node
-  //      is known iff all its operands are; the unknown inputs are the per-message ones
-  //      (inputs_for_partial_witness_calculation, witness.rs:887-937)
+  // ---- which witness signals are fixed by the partial witness (evaluate_partial, graph.rs:274-312; wl_known_nodes)
   {
-    std::vector<uint8_t> in_known(D.NI, 1), node_known(D.N, 0);
-    for (const char* name : {"messageId", "selectorUsed", "x", "externalNullifier"}) {
-      auto it = graph_.input_mapping.find(name);
-      if (it == graph_.input_mapping.end()) continue;
-      for (uint32_t k = 0; k < it->second.second; k++) in_known[it->second.first + k] = 0;
-    }
-    for (uint32_t i = 0; i < D.N; i++) {
-      const GNode& nd = graph_.nodes[i];
-      bool k;
-      if (nd.op == G_INPUT) k = in_known[nd.a];
-      else if (nd.op == G_CONST) k = true;
-      else if (nd.op == G_NEG || nd.op == G_ID) k = node_known[nd.a];
-      else if (nd.op == G_TERN) k = node_known[nd.a] && node_known[nd.b] && node_known[nd.c];
-      else k = node_known[nd.a] && node_known[nd.b];
-      node_known[i] = k;
-    }
+    std::vector<uint8_t> node_known = wl_known_nodes(graph_);
     D.known.resize(D.NS);
     for (uint32_t i = 0; i < D.NS; i++) D.known[i] = node_known[graph_.signals[i]];
     {
       std::vector<uint32_t> io(96);
       for (uint32_t i = 0; i < 96; i++) io[i] = i;
-      D.iota96.alloc(96);
-      D.iota96.upload(io.data(), 96, s);
+      D.iota96.assign(io, s);
       RLN_HIP(hipStreamSynchronize(s));
     }
     // ---- the cone program and the cache of known stored values (prover.h: collect_partial_cached / submit_finish)
     const long want = cfg.partial_cache >= 0 ? cfg.partial_cache : (long)D.tune.partial_cache;
     D.tune.partial_cache = (uint32_t)std::max(0l, want);
     if (D.witlanes.ok && want > 0) {
-      WlCone C = wl_cone(graph_);
-      if (C.node_known != node_known) throw Error("internal: the cone's known mask differs from the prover's");
-      std::vector<uint32_t> store_slot(D.N, 0xFFFFFFFFu), rows;
-      for (uint32_t i = 0; i < slot2node.size(); i++) {
-        store_slot[slot2node[i]] = i;
-        if (node_known[slot2node[i]]) rows.push_back(i);
-      }
-      D.cone.build(C.graph, wl_cone_store_slots(C, store_slot), (uint32_t)slot2node.size(), s);
+      const WlCone C = wl_cone(graph_, std::move(node_known));
+      std::vector<uint32_t> rows;   // stored slots of the known nodes
+      for (uint32_t i = 0; i < W29.slot2node.size(); i++)
+        if (C.node_known[W29.slot2node[i]]) rows.push_back(i);
+      D.cone.build(C.graph, wl_cone_store_slots(C, W29.store_slot), D.nstore29, s);
       D.cone_nodes = (uint32_t)C.node_of.size();
       if (D.cone.ok && !rows.empty()) {
         D.cone_nk = (uint32_t)rows.size();
-        D.cone_rows.alloc(rows.size());
-        D.cone_rows.upload(rows.data(), rows.size(), s);
+        D.cone_rows.assign(rows, s);
         RLN_HIP(hipStreamSynchronize(s));
         D.cone_cap = (uint32_t)std::min<long>(want, (1l << 24) - 2);
         static std::atomic<uint32_t> next_tag{1};
@@ -1090,273 +710,49 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     }
   }
 
-  // ---- MSM segments.  Scalar ids: [0, NS) witness, [NS, NS+n) h, then r, s, -(r s).
-  //      Every table row belongs to one output segment; the three walks are subsets of the rows:
-  //      full = all, partial = rows whose scalar is a known witness signal (incl. w_0 = 1, which carries
-  //      alpha / beta / query[0]), finish = the rest (unknown signals, h, blinding terms).
-  const uint32_t SID_R = D.NS + D.n, SID_S = SID_R + 1, SID_NRS = SID_R + 2;
-  // A walk = a list of (table row, scalar id, output segment) entries cut into chunks.  `dig_sid` = the id the digits
-  // of an entry live under (G2: the ids above the h block move down), `is_h` = the scalar is a coefficient of h.
-  struct VRow { uint32_t k, sid, dig_sid, seg; bool is_h; };
-  // npaired: points [0, npaired) are pair members (walk29.h ROW_PAIRED; their row words carry the flag in every plan).
-  // pair_chunks: the throughput plans (lanes = proofs, every mode) walk them as pair chunks (lane pairs, one 128-byte
-  // line per two additions) instead of as single rows; every pair chunk owns a chunk slot in each of its two members' segments.
-  auto make_plans = [&](const std::vector<VRow>& vrows, uint32_t nseg, uint32_t chunk_pts, Impl::Plan* plans,
-                        uint32_t* max_chunks, uint32_t* max_groups, int only_mode, uint32_t npaired = 0,
-                        bool pair_chunks = false, uint32_t block_pts = SUM_TREE_LANES) {
-    auto roww = [&](uint32_t k, uint32_t h) { return k | (k < npaired ? ROW_PAIRED : 0u) | (h << 31); };
-    for (int mode = 0; mode < 3; mode++) {
-      if (only_mode >= 0 && mode != only_mode) continue;
-      std::vector<uint32_t> rows, rsid, segfirst, early_ids, late_ids;
-      std::vector<ChunkDesc> chunks;
-      const bool pairs_here = pair_chunks && npaired > 0;
-      // rows a mode walks: everything (full), the signals the partial witness fixes (partial), the others (finish)
-      auto walked = [&](const VRow& v) {
-        const bool is_known = v.sid < D.NS && D.known[v.sid];
-        return mode == PROVE_FULL || (mode == PROVE_PARTIAL) == is_known;
-      };
-      // pair chunks first: entries grouped by (half, segment of member 0, segment of member 1)
-      struct PairChunk { uint32_t h, sg0, sg1, begin, end; };
-      std::vector<PairChunk> pcs;
-      std::vector<uint32_t> prows, prsid, pout;
-      if (pairs_here) {
-        std::vector<const VRow*> byk(npaired, nullptr);
-        for (const VRow& v : vrows)
-          if (v.k < npaired) byk[v.k] = &v;
-        for (uint32_t h = 0; h < D.nh; h++)
-          for (uint32_t sg0 = 0; sg0 < nseg; sg0++)
-            for (uint32_t sg1 = 0; sg1 < nseg; sg1++) {
-              const uint32_t first = (uint32_t)prows.size();
-              for (uint32_t q = 0; q + 1 < npaired; q += 2) {
-                const VRow *a = byk[q], *b = byk[q + 1];
-                if (!a || !b || a->seg != sg0 || b->seg != sg1) continue;
-                if (a->dig_sid != b->dig_sid || a->is_h || b->is_h) throw Error("internal: pair members must share a witness scalar");
-                if (!walked(*a)) continue;   // (the members share the scalar, so the mode takes both or neither)
-                prows.push_back(roww(q, h));
-                prsid.push_back(a->dig_sid);
-              }
-              for (uint32_t k = first; k < prows.size(); k += chunk_pts)
-                pcs.push_back({h, sg0, sg1, k, (uint32_t)std::min<size_t>(k + chunk_pts, prows.size())});
-            }
-        pout.assign(2 * pcs.size(), 0);
-      }
-      // reduction segment h * nseg + sg: the rows of output sg walked with GLV half h (bit 31 of the row entry)
-      for (uint32_t h = 0; h < D.nh; h++)
-        for (uint32_t sg = 0; sg < nseg; sg++) {
-          segfirst.push_back((uint32_t)chunks.size());
-          // rows whose scalar is a coefficient of h come last and start a chunk of their own, so that a small batch can
-          // walk everything else while the NTTs still run (early_ids / late_ids)
-          for (int late = 0; late < 2; late++) {
-            uint32_t first = (uint32_t)rows.size();
-            for (const VRow& v : vrows) {
-              if (v.seg != sg || (int)v.is_h != late) continue;
-              if (pairs_here && v.k < npaired) continue;   // walked by a pair chunk
-              if (walked(v)) {
-                rows.push_back(roww(v.k, h));
-                rsid.push_back(v.dig_sid);
-              }
-            }
-            for (uint32_t k = first; k < rows.size(); k += chunk_pts) {
-              (late ? late_ids : early_ids).push_back((uint32_t)chunks.size());
-              chunks.push_back({k, (uint32_t)std::min<size_t>(k + chunk_pts, rows.size())});
-            }
-          }
-          // chunk slots of this segment that pair chunks fill: empty ranges in `chunks` (the single-chunk path skips them)
-          for (size_t c = 0; c < pcs.size(); c++)
-            for (uint32_t m = 0; m < 2; m++)
-              if (pcs[c].h == h && (m ? pcs[c].sg1 : pcs[c].sg0) == sg) {
-                pout[2 * c + m] = (uint32_t)chunks.size();
-                chunks.push_back({0, 0});
-              }
-        }
-      segfirst.push_back((uint32_t)chunks.size());
-      std::vector<ChunkDesc> groups, segs;
-      make_reduce_ranges(segfirst, groups, segs);
-      Impl::Plan& P = plans[mode];
-      P.nchunks = (uint32_t)chunks.size();
-      P.ngroups = (uint32_t)groups.size();
-      P.nseg = nseg * D.nh;
-      P.rows.alloc(std::max<size_t>(rows.size(), 1));
-      P.rsid.alloc(std::max<size_t>(rsid.size(), 1));
-      if (!rsid.empty()) P.rsid.upload(rsid.data(), rsid.size(), s);
-      P.chunks.alloc(std::max<size_t>(chunks.size(), 1));
-      P.groups.alloc(std::max<size_t>(groups.size(), 1));
-      P.segs.alloc(segs.size());
-      if (!rows.empty()) P.rows.upload(rows.data(), rows.size(), s);
-      if (!chunks.empty()) P.chunks.upload(chunks.data(), chunks.size(), s);
-      if (!groups.empty()) P.groups.upload(groups.data(), groups.size(), s);
-      P.segs.upload(segs.data(), segs.size(), s);
-      std::vector<ChunkDesc> segchunks;
-      for (size_t sgi = 0; sgi + 1 < segfirst.size(); sgi++) segchunks.push_back({segfirst[sgi], segfirst[sgi + 1]});
-      P.segchunks.alloc(segchunks.size());
-      P.segchunks.upload(segchunks.data(), segchunks.size(), s);
-      {
-        std::vector<ChunkDesc> segblocks;
-        uint32_t nb = 0;
-        P.maxblk = 0;
-        for (size_t sgi = 0; sgi + 1 < segfirst.size(); sgi++) {
-          const uint32_t k = div_up(segfirst[sgi + 1] - segfirst[sgi], block_pts);
-          segblocks.push_back({nb, nb + k});
-          nb += k;
-          P.maxblk = std::max(P.maxblk, k);
-        }
-        P.nblocks = nb;
-        P.segblocks.alloc(segblocks.size());
-        P.segblocks.upload(segblocks.data(), segblocks.size(), s);
-      }
-      P.npchunks = (uint32_t)pcs.size();
-      if (P.npchunks) {
-        std::vector<ChunkDesc> pcd;
-        for (const PairChunk& c : pcs) pcd.push_back({c.begin, c.end});
-        P.prows.alloc(prows.size());
-        P.prsid.alloc(prsid.size());
-        P.pout.alloc(pout.size());
-        P.pchunks.alloc(pcd.size());
-        P.prows.upload(prows.data(), prows.size(), s);
-        P.prsid.upload(prsid.data(), prsid.size(), s);
-        P.pout.upload(pout.data(), pout.size(), s);
-        P.pchunks.upload(pcd.data(), pcd.size(), s);
-      }
-      P.n_early = (uint32_t)early_ids.size();
-      P.n_late = (uint32_t)late_ids.size();
-      P.early_ids.alloc(std::max<size_t>(early_ids.size(), 1));
-      P.late_ids.alloc(std::max<size_t>(late_ids.size(), 1));
-      if (!early_ids.empty()) P.early_ids.upload(early_ids.data(), early_ids.size(), s);
-      if (!late_ids.empty()) P.late_ids.upload(late_ids.data(), late_ids.size(), s);
-      RLN_HIP(hipStreamSynchronize(s));
-      *max_chunks = std::max(*max_chunks, P.nchunks);
-      *max_groups = std::max(*max_groups, P.ngroups);
-    }
+  // ---- MSM segments (prover_plan.h: g1_walk_rows / g2_walk_rows / make_walk_plan).  Every table row belongs to one output
+  //      segment; the three walks are subsets of the rows: full = all, partial = rows whose scalar is a known witness
+  //      signal, finish = the rest (unknown signals, h, blinding terms).
+  auto plan = [&](Impl::Plan& P, const std::vector<VRow>& rows, uint32_t nseg, uint32_t chunk_pts, int mode, uint32_t* max_chunks,
+                  uint32_t npaired = 0, bool pair_chunks = false, uint32_t block_pts = SUM_TREE_LANES) {
+    P.upload(make_walk_plan(rows, nseg, chunk_pts, mode, D.known, npaired, pair_chunks, block_pts), s);
+    *max_chunks = std::max(*max_chunks, P.nchunks);
   };
+  const int modes[3] = {PROVE_FULL, PROVE_PARTIAL, PROVE_FINISH};
   {
-    std::vector<G1Affine> pts;
-    std::vector<uint32_t> sids, row_seg;
-    auto push = [&](const G1Affine& P, uint32_t sid, uint32_t seg) {
-      if (P.is_inf()) return;
-      pts.push_back(P);
-      sids.push_back(sid);
-      row_seg.push_back(seg);
-    };
-    // seg 0: A = alpha + sum_i w_i A_i + r delta      (w_0 = 1 carries a_query[0] and alpha)
-    for (uint32_t i = 0; i < D.NS; i++) push(zk_.a_query[i], i, 0);
-    push(zk_.alpha_g1, 0, 0);
-    push(zk_.delta_g1, SID_R, 0);
-    // seg 1: B1 = beta + sum_i w_i B_i + s delta
-    for (uint32_t i = 0; i < D.NS; i++) push(zk_.b_g1_query[i], i, 1);
-    push(zk_.beta_g1, 0, 1);
-    push(zk_.delta_g1, SID_S, 1);
-    // seg 2: Cpart = sum_j w_(ni+j) L_j + sum_k h_k H_k - (r s) delta
-    for (uint32_t j = 0; j < zk_.l_query.size(); j++) push(zk_.l_query[j], D.ni + j, 2);
-    for (uint32_t k = 0; k < D.n; k++) push(zk_.h_query[k], D.NS + k, 2);
-    push(zk_.delta_g1, SID_NRS, 2);
-    // PAIRS: points walked under the same witness scalar (A_i, B1_i, L_i share w_i; a_query[0], alpha, b_g1_query[0],
-    // beta share w_0 = 1) are put side by side, two by two, at the front of the point list; their tables are interleaved
-    // (walk29.h ROW_PAIRED) and the throughput plan walks them with lane pairs.  A third row of a scalar stays single.
-    uint32_t npaired = 0;
-    {
-      std::vector<std::vector<uint32_t>> by_sid(D.NS);
-      for (uint32_t k = 0; k < sids.size(); k++)
-        if (sids[k] < D.NS) by_sid[sids[k]].push_back(k);
-      std::vector<uint32_t> order;
-      std::vector<uint8_t> taken(sids.size(), 0);
-      for (const auto& v : by_sid)
-        for (size_t t = 0; t + 1 < v.size(); t += 2) {
-          order.push_back(v[t]);
-          order.push_back(v[t + 1]);
-          taken[v[t]] = taken[v[t + 1]] = 1;
-        }
-      npaired = (uint32_t)order.size();
-      for (uint32_t k = 0; k < sids.size(); k++)
-        if (!taken[k]) order.push_back(k);
-      std::vector<G1Affine> p2(pts.size());
-      std::vector<uint32_t> s2(sids.size()), g2(sids.size());
-      for (size_t i = 0; i < order.size(); i++) {
-        p2[i] = pts[order[i]];
-        s2[i] = sids[order[i]];
-        g2[i] = row_seg[order[i]];
-      }
-      pts.swap(p2);
-      sids.swap(s2);
-      row_seg.swap(g2);
+    const G1Rows R = g1_walk_rows(zk_, D.NS, D.n, D.ni);
+    D.npaired1 = R.npaired;
+    D.npts1 = (uint32_t)R.pts.size();
+    D.sid1.assign(R.sids, s);
+    for (int m : modes) {
+      plan(D.plan1[PLAN_BIG][m], R.rows, 3, 16u, m, &D.max_chunks1, R.npaired, true);   // rows (x halves) per single-wave workgroup
+      D.max_groups1 = std::max(D.max_groups1, D.plan1[PLAN_BIG][m].ngroups);
     }
-    D.npaired1 = npaired;
-    D.npts1 = (uint32_t)pts.size();
-    D.sid1.alloc(sids.size());
-    D.sid1.upload(sids.data(), sids.size(), s);
-    std::vector<VRow> vrows;
-    for (uint32_t k = 0; k < sids.size(); k++)
-      vrows.push_back({k, sids[k], sids[k], row_seg[k], sids[k] >= D.NS && sids[k] < D.NS + D.n});
-    // rows (x halves) per single-wave workgroup
-    make_plans(vrows, 3, 16u, D.plan1, &D.max_chunks1, &D.max_groups1, -1, npaired, true);
-    {
-      uint32_t unused = 0;
-      make_plans(vrows, 3, 4u, D.plan1s, &D.max_chunks1s, &unused, -1, npaired);
+    for (int m : modes) plan(D.plan1[PLAN_SMALL][m], R.rows, 3, 4u, m, &D.max_chunks1s, R.npaired);
+    // a lone tiny partial proof: the plain rows; full and finish: the fused rows (finish: the rows of the unknown signals
+    // only -- alpha, beta, the known w_i are in pi_a, rho).  The tiny plans are summed by lane pairs.
+    plan(D.plan1[PLAN_TINY][PROVE_PARTIAL], R.rows, 3, 1u, PROVE_PARTIAL, &D.max_chunks1t, R.npaired, false, SUM_TREE_LANES / 2);
+    for (int m : {(int)PROVE_FULL, (int)PROVE_FINISH}) {
+      plan(D.plan1[PLAN_FUSED][m], R.fused, 3, 4u, m, &D.max_chunks1s, R.npaired);
+      plan(D.plan1[PLAN_TINY][m], R.fused, 3, 1u, m, &D.max_chunks1t, R.npaired, false, SUM_TREE_LANES / 2);
     }
-    {
-      // Small full proofs, fused plan: s A + r B1 - r s delta = s alpha + r beta + r s delta + sum (s w_i) A_i + sum (r w_i) B1_i,
-      // so the two variable-base products of the back end (k_fin_smul: a lone lane's ladder of 127 doublings, the longest
-      // kernel behind the interpreter) become extra rows of the C segment -- the A and B1 rows walked a second time under
-      // the scalar ids of s w_i and r w_i (k_recode part 3) -- and the B1 segment is not walked at all.  More additions
-      // in total (+ 25 % G1 rows), which is why only batches below the small-batch threshold take this plan.
-      std::vector<VRow> f;
-      const uint32_t NX = D.NS + D.n + 3;   // first extra scalar id: s w_i at NX + i, r w_i at NX + NS + i, r s at NX + 2 NS
-      for (uint32_t k = 0; k < sids.size(); k++) {
-        const uint32_t sd = sids[k], sg = row_seg[k];
-        const bool is_h = sd >= D.NS && sd < D.NS + D.n;
-        if (sg == 0) {
-          f.push_back({k, sd, sd, 0, false});                                   // A itself is an output
-          if (sd < D.NS) f.push_back({k, sd, NX + sd, 2, false});               // (s w_i) A_i   (alpha carries sid 0: s alpha)
-          // delta with r (part of A) contributes s r delta to s A: counted once below
-        } else if (sg == 1) {
-          if (sd < D.NS) f.push_back({k, sd, NX + D.NS + sd, 2, false});        // (r w_i) B1_i  (beta carries sid 0: r beta)
-        } else if (sd == SID_NRS) {
-          f.push_back({k, sd, NX + 2 * D.NS, 2, false});                        // + r s delta instead of - r s delta
-        } else {
-          f.push_back({k, sd, sd, 2, is_h});                                    // L and H rows
-        }
-      }
-      uint32_t unused = 0;
-      make_plans(vrows, 3, 1u, D.plan1tf, &D.max_chunks1t, &unused, PROVE_PARTIAL, npaired, false, SUM_TREE_LANES / 2);   // a lone tiny partial proof: the plain rows
-      D.max_blocks1t = std::max(D.max_blocks1t, D.plan1tf[PROVE_PARTIAL].nblocks);
-      for (int m : {(int)PROVE_FULL, (int)PROVE_FINISH}) {   // finish: the rows of the unknown signals only (alpha, beta, the known w_i: in pi_a, rho)
-        make_plans(f, 3, 4u, D.plan1f, &D.max_chunks1s, &unused, m, npaired);
-        make_plans(f, 3, 1u, D.plan1tf, &D.max_chunks1t, &unused, m, npaired, false, SUM_TREE_LANES / 2);   // summed by lane pairs
-        D.max_blocks1t = std::max(D.max_blocks1t, D.plan1tf[m].nblocks);
-      }
-    }
-    build_table29<Fq, G1Affine29>(pts, D.ws, D.t1_29, s, npaired);
+    for (int m : modes) D.max_blocks1t = std::max(D.max_blocks1t, D.plan1[PLAN_TINY][m].nblocks);
+    build_table29<Fq, G1Affine29>(R.pts, D.ws, D.t1_29, s, R.npaired);
   }
   {
-    std::vector<G2Affine> pts;
-    std::vector<uint32_t> sids, row_seg;
-    auto push = [&](const G2Affine& P, uint32_t sid) {
-      if (P.is_inf()) return;
-      pts.push_back(P);
-      sids.push_back(sid);
-      row_seg.push_back(0);
-    };
-    for (uint32_t i = 0; i < D.NS; i++) push(zk_.b_g2_query[i], i);
-    push(zk_.beta_g2, 0);
-    push(zk_.delta_g2, SID_S);
-    D.npts2 = (uint32_t)pts.size();
-    // the G2 digit array holds the witness scalars and r, s, -(r s) only (k_recode): ids above the h block move down
-    std::vector<uint32_t> dsid(sids);
-    for (uint32_t& v : dsid)
-      if (v >= D.NS) v -= D.n;
-    D.sid2.alloc(dsid.size());
-    D.sid2.upload(dsid.data(), dsid.size(), s);
-    std::vector<VRow> vrows;
-    for (uint32_t k = 0; k < sids.size(); k++) vrows.push_back({k, sids[k], dsid[k], 0u, false});
-    make_plans(vrows, 1, 8u, D.plan2, &D.max_chunks2, &D.max_groups2, -1);
-    {
-      uint32_t unused = 0;
-      make_plans(vrows, 1, 2u, D.plan2s, &D.max_chunks2s, &unused, -1);
-      for (int m : {(int)PROVE_FULL, (int)PROVE_PARTIAL, (int)PROVE_FINISH}) {
-        make_plans(vrows, 1, 1u, D.plan2t, &D.max_chunks2t, &unused, m, 0, false, SUM_TREE_LANES / 2);   // walked and summed by lane pairs
-        D.max_blocks2t = std::max(D.max_blocks2t, D.plan2t[m].nblocks);
-      }
+    const G2Rows R = g2_walk_rows(zk_, D.NS, D.n);
+    D.npts2 = (uint32_t)R.pts.size();
+    D.sid2.assign(R.dsid, s);
+    for (int m : modes) {
+      plan(D.plan2[PLAN_BIG][m], R.rows, 1, 8u, m, &D.max_chunks2);
+      D.max_groups2 = std::max(D.max_groups2, D.plan2[PLAN_BIG][m].ngroups);
     }
-    build_table29<Fq2, G2Affine29>(pts, D.ws2, D.t2_29, s);
+    for (int m : modes) plan(D.plan2[PLAN_SMALL][m], R.rows, 1, 2u, m, &D.max_chunks2s);
+    for (int m : modes) {   // walked and summed by lane pairs
+      plan(D.plan2[PLAN_TINY][m], R.rows, 1, 1u, m, &D.max_chunks2t, 0, false, SUM_TREE_LANES / 2);
+      D.max_blocks2t = std::max(D.max_blocks2t, D.plan2[PLAN_TINY][m].nblocks);
+    }
+    build_table29<Fq2, G2Affine29>(R.pts, D.ws2, D.t2_29, s);
   }
 
   poseidon_dev();
@@ -1381,12 +777,12 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     S.digits.alloc((size_t)(3 * D.NS + D.n + 4) * D.nh * D.ws.W * B);   // + s w_i, r w_i, r s of the fused small-batch plan
     S.digits2.alloc((size_t)(D.NS + 3) * D.nh * D.ws2.W * B);
     S.part1.alloc(std::max({(size_t)D.max_chunks1 * B, (size_t)D.max_chunks1s * D.small_stride,
-                            (size_t)D.max_chunks1t * Impl::tiny_stride}));
-    S.grp1.alloc(std::max((size_t)D.max_groups1 * B, (size_t)D.max_blocks1t * Impl::tiny_stride));
+                            (size_t)D.max_chunks1t * TINY_STRIDE}));
+    S.grp1.alloc(std::max((size_t)D.max_groups1 * B, (size_t)D.max_blocks1t * TINY_STRIDE));
     S.sums1.alloc(3 * D.nh * B);
     S.part2.alloc(std::max({(size_t)D.max_chunks2 * B, (size_t)D.max_chunks2s * D.small_stride,
-                            (size_t)D.max_chunks2t * Impl::tiny_stride}));
-    S.grp2.alloc(std::max((size_t)D.max_groups2 * B, (size_t)D.max_blocks2t * Impl::tiny_stride));
+                            (size_t)D.max_chunks2t * TINY_STRIDE}));
+    S.grp2.alloc(std::max((size_t)D.max_groups2 * B, (size_t)D.max_blocks2t * TINY_STRIDE));
     S.sums2.alloc(D.nh * B);
     S.prod.alloc(2 * B);
     S.tbl.alloc(2 * 16 * B);
@@ -1544,7 +940,7 @@ void Prover::hints_for(const uint8_t* inputs, uint32_t* hints) const {
   const Impl& D = *d_;
   if (!D.segs.ok) throw Error("hints_for: this prover interprets no segments (hint_words() is 0)");
   Fr hv[64];
-  D.rln_hints(inputs, hv);
+  D.hints.hints(inputs, hv);
   for (uint32_t j = 0; j < D.n_hints; j++) hv[j].to_canonical(hints + (size_t)j * 8);
 }
 
@@ -1624,7 +1020,7 @@ void Prover::hint_stats(uint64_t out[HINT_STATS_FIELDS]) const {
   out[3] = D.witlanes.ok ? D.witlanes.nsteps : 0;
   out[4] = D.hinted_batches;
   out[5] = D.hint_fallbacks;
-  out[6] = D.chain_hits;
+  out[6] = D.hints.hits();
 }
 
 void Prover::partial_cache_info(uint64_t out[PARTIAL_CACHE_FIELDS]) {
@@ -1697,7 +1093,7 @@ void Prover::collect(uint64_t ticket, size_t n, uint8_t* proofs, uint8_t* values
   // a big batch is tens of milliseconds away: poll and sleep instead of hipEventSynchronize, whose wait spins in the runtime
   // (a host core per GPU as measured, hipEventBlockingSync or not) -- eight replicas must not need eight cores to wait.
   // Small batches keep the spinning wait: their latency is the product.
-  if (S.n > D.lanechunk_max) wait_yielding(S.evC); else RLN_HIP(hipEventSynchronize(S.evC));
+  if (S.n > D.tune.lanechunk_max) wait_yielding(S.evC); else RLN_HIP(hipEventSynchronize(S.evC));
   if (S.mode == PROVE_PARTIAL) {
     if (partial320) memcpy(partial320, S.h_pp, n * 320);
   } else {
@@ -1798,115 +1194,95 @@ void Prover::prove_stream_from(const ChunkSource& next, const uint8_t* inputs, c
   }
 }
 
+// per_proof(i) for the n proofs of a batch: proofs i = k, k + nth, ... on thread k; the caller is thread 0
+template <class F>
+static void on_hint_threads(size_t n, size_t nth, F&& per_proof) {
+  std::vector<std::thread> helpers;
+  std::atomic<bool> failed{false};     // (an exception must not leave a helper thread: it would end the process)
+  auto strand = [&](size_t k) {
+    try {
+      for (size_t i = k; i < n; i += nth) per_proof(i);
+    } catch (...) {
+      failed = true;
+    }
+  };
+  try {
+    for (size_t k = 1; k < nth; k++) helpers.emplace_back(strand, k);
+  } catch (...) {   // no more threads to be had: the caller's thread takes what the missing ones would have
+    const size_t started = helpers.size() + 1;
+    for (size_t k = started; k < nth; k++) strand(k);
+  }
+  strand(0);
+  for (std::thread& th : helpers) th.join();
+  if (failed) throw Error("out of memory while hashing the hints of a batch");
+}
+
 uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint8_t* h_rs, const uint8_t* h_pp320,
                          const uint64_t* cone_handles, const uint32_t* pre_hints) {
   if (n == 0) return 0;
   if (n > B_) throw Error("batch larger than the prover workspace (max_batch)");
   if (mode < PROVE_FULL || mode > PROVE_FINISH) throw Error("unknown prover mode");
   Impl& D = *d_;
-  // lone: nothing else in flight -- the batch may trade throughput for latency (the fused plan's + 25 % G1 rows, the
-  // single-stream chains, the wave-per-proof interpreter above the small-batch threshold)
   const ProverTuning& T = D.tune;
-  const int lone_force = T.lone;   // -1: detect; 0 / 1: force (measurements, tests)
-  // (round 6: up to lone_small_max proofs the lone shapes are taken behind a batch that is still in flight as well -- a
-  // stream of such batches was measured 1.2 - 2 x slower in the throughput shapes: three batches of 16 in flight 11.9 ms,
-  // 5.7 ms in the lone shapes; above 48 the two are the same)
-  const bool lone = lone_force >= 0 ? lone_force != 0
-                                    : (n <= T.lone_small_max || !D.last || hipEventQuery(D.last->evC) == hipSuccess);
+  // ---- the shape of the batch (prover_plan.h: batch_shape), decided before anything is launched
+  BatchQuery q;
+  q.n = n;
+  q.mode = mode;
+  q.inputs = h_inputs != nullptr;
+  q.partial_points = h_pp320 != nullptr;
+  q.handles = cone_handles != nullptr;
+  q.pre_hints = pre_hints != nullptr;
+  // nothing of this prover in flight?  (asked only where the answer decides `lone`)
+  q.idle = T.lone >= 0 || n <= T.lone_small_max || !D.last || hipEventQuery(D.last->evC) == hipSuccess;
   (void)hipGetLastError();   // hipErrorNotReady is not an error here
-  // small batches (ProverTuning::lanechunk_max) take the latency shapes: walks with lanes = chunks (walk29.h), kernels with
-  // the lanes on one proof's elements, the copy engine for the results.  (n <= B_, so such a batch fits in small_stride.)
-  const bool small = n <= D.lanechunk_max;
-  // The lanes = nodes interpreter (a wave and 157 KB of LDS per proof, ~25 x the instructions per proof of k_witness29,
-  // 1.5 ms per 256 proofs against 11 ms): always below the small-batch threshold; up to witlanes_max only for a LONE batch -- in a stream
-  // of such batches it costs throughput (profiles/r3_rocprof_summary.md, section 10), and there the previous batch is still in flight.
-  const uint32_t wl_lone_max = D.device.shared() ? std::min(D.witlanes_max, 256u) : D.witlanes_max;
-  const bool wl_used = D.witlanes.ok && (small || (n <= wl_lone_max && lone));
-  // Finish with the partial run's values at hand (prover.h: submit_finish): every proof of the batch has a live cache
-  // entry and the batch is one the wave-per-proof interpreter takes -> the known rows come back from the cache and only
-  // the cone evaluate_partial leaves unknown is interpreted (depth-20 circuit: 1 947 of 23 414 nodes, a twelfth of the
-  // multiplication depth).  Anything else -- a dead handle, a big batch -- walks the whole graph: same bytes.
+  q.shared = D.device.shared();
+  q.no_hints_now = D.no_hints_now;
+  q.witlanes_ok = D.witlanes.ok;
+  q.segs_ok = D.segs.ok;
+  q.cone_ok = D.cone.ok;
+  q.have_values_kernel = D.have_values_kernel;
+  q.ni = D.ni;
+  q.logn = D.logn;
+  q.capacity = B_;
+  q.small_stride = D.small_stride;
+  BatchShape sh = batch_shape(q, T);
+  // the cone needs a live cache entry for every proof: a dead handle walks the whole graph
   std::vector<uint32_t> cone_entries;
-  bool cone = mode == PROVE_FINISH && cone_handles && h_inputs && wl_used && D.cone.ok;
-  for (size_t i = 0; i < n && cone; i++) {
+  for (size_t i = 0; i < n && sh.cone; i++) {
     const uint32_t e = D.cone_entry(cone_handles[i]);
-    if (e == 0xFFFFFFFFu) cone = false; else cone_entries.push_back(e);
-  }
-  // A lone batch of one or two proofs: the graph as independent segments behind hints computed on this thread (Impl::rln_hints)
-  // (up to hint_max proofs whatever their chains cost; above it, up to HINT_PROOFS, when few enough of the proofs' chains
-  // have to be hashed -- the others are remembered, Impl::rln_hints -- that the host threads are done in ~0.5 ms)
-  // (or whatever the batch's size up to HINT_PROOFS when the caller brings the hints: submit_hinted)
-  bool hinted = D.segs.ok && h_inputs && wl_used && !cone && lone && !D.no_hints_now &&
-                n <= (pre_hints ? HINT_PROOFS : std::max(T.hint_max, T.hint_max_warm));
-  std::vector<Impl::HintProbe> probes;
-  const size_t hint_nth = std::min<size_t>(std::max<size_t>(n, 1), std::max<uint32_t>(1u, T.hint_threads));
-  auto on_hint_threads = [&](auto&& per_proof) {   // proofs i = k, k + nth, ... on thread k; the caller is thread 0
-    std::vector<std::thread> helpers;
-    std::atomic<bool> failed{false};     // (an exception must not leave a helper thread: it would end the process)
-    auto strand = [&](size_t k) {
-      try {
-        for (size_t i = k; i < n; i += hint_nth) per_proof(i);
-      } catch (...) {
-        failed = true;
-      }
-    };
-    try {
-      for (size_t k = 1; k < hint_nth; k++) helpers.emplace_back(strand, k);
-    } catch (...) {   // no more threads to be had: the caller's thread takes what the missing ones would have
-      const size_t started = helpers.size() + 1;
-      for (size_t k = started; k < hint_nth; k++) strand(k);
+    if (e != 0xFFFFFFFFu) {
+      cone_entries.push_back(e);
+    } else {
+      q.handles = false;
+      sh = batch_shape(q, T);
     }
-    strand(0);
-    for (std::thread& th : helpers) th.join();
-    if (failed) throw Error("out of memory while hashing the hints of a batch");
-  };
-  if (hinted && !pre_hints && n > T.hint_max) {
+  }
+  // above hint_max proofs the segments pay only when few enough of the proofs' chains have to be hashed (the others are
+  // remembered: HintChains) that the host threads are done in ~0.5 ms
+  std::vector<HintChains::Probe> probes;
+  const size_t hint_nth = std::min<size_t>(std::max<size_t>(n, 1), std::max<uint32_t>(1u, T.hint_threads));
+  if (sh.probe_chains) {
     probes.resize(n);
     // the first two proofs on this thread (15 us): a batch of members never seen ends here, before a helper thread is started
-    for (size_t i = 0; i < 2 && hinted; i++) {
-      D.rln_hint_probe(h_inputs + i * (size_t)D.NI * 32, &probes[i]);
-      hinted = probes[i].found;
+    for (size_t i = 0; i < 2 && sh.hinted; i++) {
+      D.hints.probe(h_inputs + i * (size_t)D.NI * 32, &probes[i]);
+      sh.hinted = probes[i].found;
     }
   }
-  if (hinted && !pre_hints && n > T.hint_max) {
-    on_hint_threads([&](size_t i) {
-      if (i >= 2) D.rln_hint_probe(h_inputs + i * (size_t)D.NI * 32, &probes[i]);
+  if (sh.probe_chains && sh.hinted) {
+    on_hint_threads(n, hint_nth, [&](size_t i) {
+      if (i >= 2) D.hints.probe(h_inputs + i * (size_t)D.NI * 32, &probes[i]);
     });
     size_t to_hash = 0;
-    for (const Impl::HintProbe& pr : probes) to_hash += pr.found ? 0 : 1;
+    for (const HintChains::Probe& pr : probes) to_hash += pr.found ? 0 : 1;
     // a chain is ~0.2 ms on a host core against ~1.3 ms the segments save: at most 2.5 chains per thread
-    hinted = 2 * to_hash <= 5 * hint_nth;
+    sh.hinted = 2 * to_hash <= 5 * hint_nth;
   }
-  if (!hinted) probes.clear();
-  // Small batches (latency, not throughput): the whole front end stays on ONE stream (every cross-stream event hop costs
-  // 0.1 - 0.15 ms), the digits of the witness scalars are recoded right behind the interpreter, and both walks start on
-  // everything that does not depend on the quotient h while mat-vec / NTTs still run; only the h rows of the G1 walk
-  // wait for them.
-  const bool early = small && mode != PROVE_PARTIAL;
-  // small full proofs: s A and r B1 are rows of the C segment (plan1f), no ladder; the back end is the split one below
-  // (up to 96 proofs: above, the walks are issue-bound even for a lone batch and the extra rows cost more than the ladder
-  // they replace -- 128 proofs 16.6 -> 15.3 ms without them, 64 proofs 10.1 -> 10.3 ms)
-  // (round 6: a streamed finish takes it too -- the variable-base part that is left, s pi_a + r rho,
-  // comes from powers of the two points: k_pp_smul -- cached with the partial run's values, or made beside the interpreter)
-  const bool fused = lone && n <= 96 && early && (mode == PROVE_FULL || (mode == PROVE_FINISH && h_inputs && h_pp320));
-  // tiny: a lane per (row, half) and a two-stage sum (plan1tf / plan2t) -- only the fused full proof of a lone batch, and
-  // only when it walks with lanes = chunks (the lanes = proofs form of the mid-size batches needs 64 proofs of stride)
-  // (round 6: a lone tiny PARTIAL proof as well -- its plan is the plain rows of the known signals, one per lane)
-  const bool tiny_partial = lone && small && mode == PROVE_PARTIAL && n <= T.tiny_max && n <= Impl::tiny_stride &&
-                            n <= D.lanechunk_walk_max;
-  const bool tiny = (fused && n <= T.tiny_max && n <= Impl::tiny_stride && n <= D.lanechunk_walk_max) || tiny_partial;
-  const Impl::Plan& P1 = tiny ? D.plan1tf[mode] : fused ? D.plan1f[mode] : small ? D.plan1s[mode] : D.plan1[mode];
-  const Impl::Plan& P2 = tiny ? D.plan2t[mode] : small ? D.plan2s[mode] : D.plan2[mode];
-  const uint32_t PB = tiny ? Impl::tiny_stride : small ? D.small_stride : (uint32_t)B_;   // stride of the partial-sum arrays
-  // mid-size small batches: the short-chunk plans walked with lanes = proofs (walk29.h).  A lone batch: above 48 proofs
-  // (64: 11.3 -> 9.9 ms, 128: 18.1 -> 16.3 ms; 32: 6.9 ms against 8.4).  In a stream of batches the lanes = chunks form
-  // pays its scattered gathers in throughput much earlier (streams of 64 / 128-proof batches: 9.5 -> 10.8 k, 10.7 -> 11.9 k
-  // proofs/s), so there it stops at 16 proofs.
-  const bool walk_lp = early && (n > D.lanechunk_walk_max || (!lone && n >= 16));
-  // proof stride of the digit arrays: compact where the walks run with lanes = chunks (k_recode); the batch capacity
-  // otherwise (the lanes = proofs walks have padding lanes that read beside the batch: those must stay digits of the
-  // same window)
-  const uint32_t dB = (early && !walk_lp) ? (uint32_t)n : (uint32_t)B_;
+  if (!sh.hinted) probes.clear();
+  const bool lone = sh.lone, small = sh.small, wl_used = sh.wl_used, cone = sh.cone, hinted = sh.hinted, early = sh.early,
+             fused = sh.fused, tiny = sh.tiny, tiny_partial = sh.tiny_partial, walk_lp = sh.walk_lp;
+  const Impl::Plan &P1 = D.plan1[sh.plan1][mode], &P2 = D.plan2[sh.plan2][mode];
+  const uint32_t PB = sh.PB, dB = sh.dB;
   Slot& S = D.slot[D.cur];
   S.dB = dB;
   S.PB = PB;
@@ -1942,8 +1318,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // (mat-vec, NTTs, h rows, C sums, A's and C's bytes), which has ~0.2 ms of slack since the NTTs run in LDS, takes the
   // cross-stream hop (50 - 100 us each) instead.  In a stream of batches the front-end stream must be free for the
   // batch after next: there the walks keep their own streams.
-  const bool g2_on_front = lone && early;
-  hipStream_t sA2 = !early ? D.sA2 : g2_on_front ? D.sB2 : sA;
+  hipStream_t sA2 = !early ? D.sA2 : sh.g2_on_front ? D.sB2 : sA;
   const uint32_t pg = div_up(nb, 64);
   const uint32_t nbp = pg * 64;  // padded lanes compute on stale / zero inputs; results ignored
   // Results home.  Big batches: by a single-wave kernel writing the pinned pages (as the inputs come in: k_stage_in) -- the
@@ -1955,6 +1330,27 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
       hipLaunchKernelGGL(k_stage_in, dim3(div_up(bytes / 16, 64)), dim3(64), 0, st, (const uint4*)dev, (uint4*)host, (uint32_t)(bytes / 16));
     else
       RLN_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+  };
+  // The G1 walk of `cnt` chunks of the plan on stream `st` (ids: their chunk indices; null: the whole plan, chunks [0, cnt)).
+  // Small batches: lanes = proofs over the short chunks (walk_lp) or lanes = chunks.  Big batches: the throughput form --
+  // single chunks first, pair chunks (32 proofs x 2 members per wave: twice the proof groups) behind them.
+  auto walk1 = [&](hipStream_t st, const uint32_t* ids, uint32_t cnt) {
+    if (!cnt) return;
+    const uint32_t blocks = div_up(cnt, 8) * 8 * pg;
+    if (!small) {
+      const PairPlan pp{P1.prows.p, P1.prsid.p, P1.pchunks.p, P1.pout.p, P1.npchunks};
+      const uint32_t pblocks = div_up(P1.npchunks, 8) * 8 * (2 * pg);
+      hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 4>), dim3(blocks + pblocks), dim3(64), 0, st, D.t1_29.p,
+                         P1.rsid.p, P1.rows.p, P1.chunks.p, cnt, S.digits.p, S.part1.p, D.ws, dB, pg, D.nh, D.walk_clk.p, ids,
+                         0u, pp);
+    } else if (walk_lp) {
+      hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 4>), dim3(blocks), dim3(64), 0, st, D.t1_29.p, P1.rsid.p,
+                         P1.rows.p, P1.chunks.p, cnt, S.digits.p, S.part1.p, D.ws, dB, pg, D.nh, nullptr, ids, PB);
+    } else {
+      hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 2, true>), dim3(div_up(cnt, 64), nb), dim3(64), 0, st,
+                         D.t1_29.p, P1.rsid.p, P1.rows.p, P1.chunks.p, cnt, S.digits.p, S.part1.p, D.ws, dB, PB, D.nh,
+                         nullptr, ids);
+    }
   };
   // ---------------- stage A
   if (S.used) RLN_HIP(hipStreamWaitEvent(sA, S.free_event(), 0));  // slot free again
@@ -1988,9 +1384,9 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     if (pre_hints)
       memcpy(S.h_hints, pre_hints, n * (size_t)D.n_hints * 32);
     else
-      on_hint_threads([&](size_t i) {
+      on_hint_threads(n, hint_nth, [&](size_t i) {
         Fr hv[64];
-        D.rln_hints(h_inputs + i * (size_t)D.NI * 32, hv, probes.empty() ? nullptr : &probes[i]);
+        D.hints.hints(h_inputs + i * (size_t)D.NI * 32, hv, probes.empty() ? nullptr : &probes[i]);
         for (uint32_t j = 0; j < D.n_hints; j++) hv[j].to_canonical(S.h_hints + (i * D.n_hints + j) * 8);
       });
     if (T.hint_fault > 0 && (uint32_t)T.hint_fault <= D.n_hints) S.h_hints[(size_t)(T.hint_fault - 1) * 8] ^= 1u;   // test hook
@@ -2067,14 +1463,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
       RLN_HIP(hipStreamWaitEvent(D.sB2, S.evW, 0));
     }
     MARK(14, D.sB);
-    if (P1.n_early && walk_lp)
-      hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 4>), dim3(div_up(P1.n_early, 8) * 8 * pg), dim3(64), 0,
-                         D.sB, D.t1_29.p, P1.rsid.p, P1.rows.p, P1.chunks.p, P1.n_early, S.digits.p, S.part1.p, D.ws, dB, pg,
-                         D.nh, nullptr, P1.early_ids.p, PB);
-    else if (P1.n_early)
-      hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 2, true>), dim3(div_up(P1.n_early, 64), nb), dim3(64), 0,
-                         D.sB, D.t1_29.p, P1.rsid.p, P1.rows.p, P1.chunks.p, P1.n_early, S.digits.p, S.part1.p, D.ws, dB, PB,
-                         D.nh, nullptr, P1.early_ids.p);
+    walk1(D.sB, P1.early_ids.p, P1.n_early);
     RLN_HIP(hipEventRecord(S.evE, D.sB));
   }
   MARK(2, sA);
@@ -2095,7 +1484,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     // (above ~100 proofs the walks beside the quotient chain leave the 4-wave workgroups of the LDS kernels waiting for
     // four free wave slots on one CU: the single-wave passes then finish earlier -- 128 proofs 13.3 -> 12.6 ms, 96 and
     // below no better or worse; RLNAMD_NTT_LG_MAX)
-    if (small && nb <= D.tune.ntt_lg_max && D.logn >= 9 && D.logn <= 18) {
+    if (sh.ntt_lds) {
       // iNTT, coset scaling and NTT as edge / mid / edge: one butterfly per lane per level (prover_front.hip: k_ntt_mid)
       const dim3 grid(nb, D.n >> 9, 3);
       if (D.logn > 9) hipLaunchKernelGGL(k_ntt_edge<true>, grid, dim3(256), 0, sA2, S.abc.p, D.tw_i.p, D.logn, B, nb);
@@ -2126,36 +1515,17 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     RLN_HIP(hipStreamWaitEvent(D.sB, S.evA, 0));
     MARK(14, D.sB);
   }
-  hipStream_t s2 = g2_on_front ? sA : D.sB2;   // the G2 walk on its own stream: its workgroups fill the G1 kernel's tail
+  hipStream_t s2 = sh.g2_on_front ? sA : D.sB2;   // the G2 walk on its own stream: its workgroups fill the G1 kernel's tail
   if (!early) {   // (early: the G2 walk's stream already has the witness + part-1 digits, all it reads)
     RLN_HIP(hipEventRecord(S.evR, D.sB));
     RLN_HIP(hipStreamWaitEvent(D.sB2, S.evR, 0));
   }
   if (early) {   // the h rows, on the front-end stream itself (no event hop); everything else is already walking
-    if (P1.n_late && walk_lp)
-      hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 4>), dim3(div_up(P1.n_late, 8) * 8 * pg), dim3(64), 0,
-                         sA2, D.t1_29.p, P1.rsid.p, P1.rows.p, P1.chunks.p, P1.n_late, S.digits.p, S.part1.p, D.ws, dB, pg,
-                         D.nh, nullptr, P1.late_ids.p, PB);
-    else if (P1.n_late)
-      hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 2, true>), dim3(div_up(P1.n_late, 64), nb), dim3(64), 0, sA2,
-                         D.t1_29.p, P1.rsid.p, P1.rows.p, P1.chunks.p, P1.n_late, S.digits.p, S.part1.p, D.ws, dB, PB, D.nh,
-                         nullptr, P1.late_ids.p);
+    walk1(sA2, P1.late_ids.p, P1.n_late);
     RLN_HIP(hipEventRecord(S.evR, sA2));
     RLN_HIP(hipStreamWaitEvent(D.sB, S.evR, 0));   // evB below then covers both launches
-  } else if (P1.nchunks) {
-    uint32_t blocks = div_up(P1.nchunks, 8) * 8 * pg;
-    if (small)
-      hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 2, true>), dim3(div_up(P1.nchunks, 64), nb), dim3(64), 0, D.sB,
-                         D.t1_29.p, P1.rsid.p, P1.rows.p, P1.chunks.p, P1.nchunks, S.digits.p, S.part1.p, D.ws, dB, PB, D.nh,
-                         nullptr);
-    else {
-      // single chunks first, pair chunks (32 proofs x 2 members per wave: twice the proof groups) behind them
-      const PairPlan pp{P1.prows.p, P1.prsid.p, P1.pchunks.p, P1.pout.p, P1.npchunks};
-      const uint32_t pblocks = div_up(P1.npchunks, 8) * 8 * (2 * pg);
-      hipLaunchKernelGGL((k_msm29<G1Acc29, G1Affine29, G1XYZZ, 4>), dim3(blocks + pblocks), dim3(64), 0, D.sB, D.t1_29.p,
-                         P1.rsid.p, P1.rows.p, P1.chunks.p, P1.nchunks, S.digits.p, S.part1.p, D.ws, dB, pg, D.nh,
-                         D.walk_clk.p, (const uint32_t*)nullptr, 0u, pp);
-    }
+  } else {
+    walk1(D.sB, nullptr, P1.nchunks);
   }
   MARK(7, D.sB);
   MARK(11, s2);
@@ -2190,8 +1560,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   if (streamed) RLN_HIP(hipStreamWaitEvent(sV, S.evU, 0));
   MARK(0, sV);
   // (whenever the batch is small enough for the lanes = nodes interpreter: the Poseidon chain alone is 5.3 ms)
-  const bool values_w = (early || wl_used) && D.have_values_kernel && D.ni == 6;
-  if (values_w) {   // small batches: the circuit's own outputs (see k_values_from_witness)
+  if (sh.values_w) {   // small batches: the circuit's own outputs (see k_values_from_witness)
     RLN_HIP(hipStreamWaitEvent(sV, S.evX, 0));   // sA: witness stored
     hipLaunchKernelGGL(k_values_from_witness, dim3(pg, 5), dim3(64), 0, sV, S.V.p, D.sig2node.p, B, nbp, S.values.p);
   } else if (D.have_values_kernel)
@@ -2204,7 +1573,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // (round 6: PROVE_FINISH as well -- the partial points join their sums where each sum is complete, k_add_partial per
   // task; until then a lone finish took the serial back end of the big batches and was SLOWER than a lone full proof)
   const bool fin_pp = mode == PROVE_FINISH;
-  const TaskSel all6 = task_sel({0, 1, 2, 3, 4, 5}), all4 = task_sel({0, 1, 2, 3}), all3 = task_sel({0, 1, 2});
+  const TaskSel all4 = task_sel({0, 1, 2, 3}), all3 = task_sel({0, 1, 2});
   hipStream_t sF = D.sC;   // the stream of k_fin_out and of the copies to the host
   // segment sums of a small batch: one 512-lane tree per (proof, segment); tiny batches (four times the partial sums) in
   // two stages -- every 512-chunk block of a segment to one point, then the blocks of the segment -- so that the depth
@@ -2305,8 +1674,8 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   }
   if (early || tiny_partial) {
   } else if (small) {   // (here: a small partial batch) lanes = partial sums (k_sum_tree)
-    hipLaunchKernelGGL((k_sum_tree<Fq, G1Acc29>), dim3(nb, P1.nseg), dim3(SUM_TREE_LANES), SUM_TREE_LDS_G1, D.sC, S.part1.p, P1.segchunks.p, S.sums1.p, B, PB, all6);
-    hipLaunchKernelGGL((k_sum_tree<Fq2, G2Acc29>), dim3(nb, P2.nseg), dim3(SUM_TREE_LANES), SUM_TREE_LDS_G2, D.sC, S.part2.p, P2.segchunks.p, S.sums2.p, B, PB, all6);
+    sum1(D.sC, {0, 1, 2, 3, 4, 5});
+    sum2(D.sC);
   } else {
     if (P1.ngroups)
       hipLaunchKernelGGL(k_sum_ranges<Fq>, dim3(pg, P1.ngroups), dim3(64), 0, D.sC, S.part1.p, P1.groups.p, P1.ngroups,

@@ -1,5 +1,5 @@
 // prover_front.hip -- front end of the prover pipeline: the witness-graph interpreters, the QAP mat-vec, the NTT passes
-// and the quotient, the digit recoding.  Declarations and shared descriptors: prover_kernels.h; host side: prover.hip.
+// and the quotient, the digit recoding.  Declarations: prover_kernels.h; shared descriptors: prover_desc.h; host side: prover.hip, prover_plan.cpp.
 //
 // The 256-bit multiply is inlined (measured on MI355X: G1 MSM 44.5 -> 41.7 ms, G2 MSM 30.7 -> 22.5 ms per 1024
 // proofs against the out-of-line form, which costs call overhead and a VGPR-hungry calling convention);

@@ -1,7 +1,8 @@
 // prover_kernels.h -- internal to the prover: what the host pipeline (prover.hip) and the kernel translation units
 // (prover_front.hip: witness interpreters, mat-vec, NTT, recoding; prover_walks.hip: table build, table walks, partial-sum
-// reductions; prover_back.hip: finalize, proof values, taps, staging, wipes) share -- descriptor structs, constants and the
-// kernel DECLARATIONS.  The kernels are defined (and their templates explicitly instantiated) in exactly one unit each, so
+// reductions; prover_back.hip: finalize, proof values, taps, staging, wipes) share -- the kernel DECLARATIONS and the
+// descriptors only kernels and launches need.  The descriptors the host planning builds (GNode29, the W29_* / WIT29_*
+// constants, InputSlots, ...) are in prover_desc.h, which has no HIP in it.  The kernels are defined (and their templates explicitly instantiated) in exactly one unit each, so
 // a change to one kernel recompiles one unit, and the units compile in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,24 +13,11 @@
 #include "fq29.h"
 #include "poseidon.h"
 #include "prover.h"
+#include "prover_desc.h"
 #include "walk29.h"
 #include "witness_ops.h"
 
 namespace rlnamd {
-
-// ---- witness interpreters (prover_front.hip)
-constexpr uint32_t OPK_RING = 0u << 30, OPK_CONST = 1u << 30, OPK_FAR = 2u << 30, OPK_MASK = 3u << 30;
-constexpr uint32_t W29_STORE = 1u << 8, W29_RED = 1u << 9, W29_RARE = 1u << 10;  // flags in descriptor word 0
-constexpr uint32_t W29_FMA = 25;             // program-only operation: a * b + c (an Add fused with its single-use product)
-constexpr uint32_t WIT29_RING = 32;          // node values kept in LDS: 32 x 64 x 48 B = 96 KiB
-constexpr uint32_t WIT29_LDS_CONSTS = 1024;  // constants kept in LDS: 48 KiB
-constexpr uint32_t WIT29_CH = 256;           // descriptors per program chunk: 64 lanes x 64 B; two chunks in LDS (8 KiB)
-constexpr uint32_t WIT29_LDS_BYTES = WIT29_RING * 64 * 48 + WIT29_LDS_CONSTS * 48 + 2 * WIT29_CH * 16;
-constexpr double WIT29_BMAX = 7.5;
-struct GNode29 {
-  uint32_t w0;       // op | flags | slot << 16 (slot: index into the compact array of stored values)
-  uint32_t a, b, c;  // operands as in GNode: OPK_RING | node, OPK_CONST | index, OPK_FAR | slot
-};
 
 // ---- mat-vec
 struct CsrView {
@@ -37,7 +25,6 @@ struct CsrView {
   const uint32_t* col;  // already mapped to graph node ids
   const Fr* coef;
 };
-constexpr uint32_t MV_LONG = 8;
 
 // ---- partial-sum reductions and the back end
 struct TaskSel {
@@ -49,12 +36,8 @@ inline TaskSel task_sel(std::initializer_list<uint32_t> ids) {
   for (uint32_t v : ids) t.id[k++] = (uint8_t)v;
   return t;
 }
-constexpr uint32_t SUM_TREE_LANES = 512;
 // dynamic LDS of k_sum_tree / k_sum_blocks: the upper half of a level, one point in the 9 x 29 form per lane
 constexpr uint32_t SUM_TREE_LDS_G1 = SUM_TREE_LANES / 2 * 4 * 9 * 4, SUM_TREE_LDS_G2 = 2 * SUM_TREE_LDS_G1;
-struct InputSlots {
-  uint32_t secret, limit, msg_id, path, path_idx, x, ext, depth;
-};
 
 #ifndef RLN_NTT_WAVES
 #define RLN_NTT_WAVES 1

@@ -1,39 +1,16 @@
-// walk29.h -- the fixed-base table walk of the prover in the 9 x 29-bit limb form (fq29.h): window schedule, chunk
-// descriptor and the DECLARATION of the kernel.  The body lives in walk29_impl.h and is compiled once, by prover_walks.hip
-// (explicit instantiations there); tools/asm_walk.hip includes the body to look at the ISA of one instantiation.
+// walk29.h -- the fixed-base table walk of the prover in the 9 x 29-bit limb form (fq29.h): the DECLARATION of the
+// kernel (window schedule, chunk descriptor and row words: prover_desc.h).  The body lives in walk29_impl.h and is
+// compiled once, by prover_walks.hip (explicit instantiations there); tools/asm_walk.hip includes the body to look at
+// the ISA of one instantiation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "fq29.h"
+#include "prover_desc.h"
 
 namespace rlnamd {
 
-// Window schedule of the comb tables.  Window j covers cw[j] scalar bits starting at bit bo[j]; its table row holds
-// the 2^(cw[j]-1) multiples d 2^bo[j] P (signed digits) at entry offset ro[j] inside the point's block of `stride`
-// entries.  Uniform widths (c, c, ...) are the classical comb; with 288 GB of HBM the first `wide` windows take one
-// more bit so that W drops from 20 to 19 at c = 13 (8 x 14 + 11 x 13 = 255 bits, table x 1.35).  Passed by value:
-// the kernels index it with wave-uniform j (scalar loads from the kernarg segment).
-struct WinSched {
-  int W;
-  uint32_t stride;
-  uint8_t cw[32];
-  uint16_t bo[32];
-  uint32_t ro[32];
-};
-
-struct ChunkDesc {
-  uint32_t pt_begin, pt_end;  // compact point range
-};
-
-// A row word (the `rows` lists of the walk plans) = table point index | flags.
-//   ROW_HALF2   bit 31: the second GLV half of the scalar (k2; the sum goes through phi afterwards)
-//   ROW_PAIRED  bit 30: the point is a member of a PAIR (two points whose rows are walked under the SAME scalar: A_i and
-//               B1_i, or one of them and L_i).  The two members sit at consecutive point indices 2 q, 2 q + 1 and their
-//               tables are interleaved entry by entry: entry x of member m at ((2 q) stride + 2 x + m) -- the two entries a
-//               digit selects share one 128-byte line.  Any walk may read a paired point by itself (a strided row); the
-//               pair chunks of the throughput plan read both with a lane pair and halve the HBM requests of those rows.
-constexpr uint32_t ROW_HALF2 = 1u << 31, ROW_PAIRED = 1u << 30, ROW_INDEX = ROW_PAIRED - 1;
 // first entry of point k's table and the entry stride inside it (in entries)
 template <class Entry>
 __device__ __forceinline__ const Entry* row_base(const Entry* __restrict__ table, uint32_t roww, uint32_t stride, uint32_t* shift) {

@@ -828,33 +828,42 @@ static WlProgram wl_schedule_graph(const Graph& graph, const std::vector<uint32_
 
 
 // ------------------------------------------------------------------------------------------------- the unknown cone
-WlCone wl_cone(const Graph& g) {
+std::vector<uint8_t> wl_known_nodes(const Graph& g) {
   const std::vector<GNode>& G = g.nodes;
   const uint32_t N = (uint32_t)G.size();
-  auto nops = [&](const GNode& q) {
-    return (q.op == G_INPUT || q.op == G_CONST) ? 0 : (q.op == G_NEG || q.op == G_ID) ? 1 : q.op == G_TERN ? 3 : 2;
-  };
-  WlCone C;
-  std::vector<uint8_t> in_known(g.inputs_size, 1);
+  std::vector<uint8_t> in_known(g.inputs_size, 1), node_known(N, 0);
   for (const char* name : {"messageId", "selectorUsed", "x", "externalNullifier"}) {
     auto it = g.input_mapping.find(name);
     if (it == g.input_mapping.end()) continue;
     for (uint32_t k = 0; k < it->second.second; k++)
       if (it->second.first + k < in_known.size()) in_known[it->second.first + k] = 0;
   }
-  C.node_known.assign(N, 0);
   for (uint32_t i = 0; i < N; i++) {
     const GNode& q = G[i];
     const uint32_t o[3] = {q.a, q.b, q.c};
+    const int nops = (q.op == G_INPUT || q.op == G_CONST) ? 0 : (q.op == G_NEG || q.op == G_ID) ? 1 : q.op == G_TERN ? 3 : 2;
     bool k = true;
     if (q.op == G_INPUT) k = q.a < in_known.size() && in_known[q.a];
     else
-      for (int j = 0; j < nops(q); j++) {
+      for (int j = 0; j < nops; j++) {
         if (o[j] >= i) throw std::runtime_error("Graph error: node operand refers forward");
-        k = k && C.node_known[o[j]];
+        k = k && node_known[o[j]];
       }
-    C.node_known[i] = k;
+    node_known[i] = k;
   }
+  return node_known;
+}
+
+WlCone wl_cone(const Graph& g) { return wl_cone(g, wl_known_nodes(g)); }
+
+WlCone wl_cone(const Graph& g, std::vector<uint8_t> node_known) {
+  const std::vector<GNode>& G = g.nodes;
+  const uint32_t N = (uint32_t)G.size();
+  auto nops = [&](const GNode& q) {
+    return (q.op == G_INPUT || q.op == G_CONST) ? 0 : (q.op == G_NEG || q.op == G_ID) ? 1 : q.op == G_TERN ? 3 : 2;
+  };
+  WlCone C;
+  C.node_known = std::move(node_known);
   // members: every unknown node; from there down, every operand (known ones included) until inputs and constants
   std::vector<uint8_t> member(N, 0);
   for (uint32_t i = N; i-- > 0;) {

@@ -53,6 +53,10 @@ struct WlCone {
   std::vector<uint8_t> recomputed;    // per cone node: a known non-input node that is computed again (never stored)
 };
 WlCone wl_cone(const Graph& graph);
+// evaluate_partial's Some / None per node of the graph: the prover computes it once, for its known-signal mask and,
+// through the second form of wl_cone, for the cone
+std::vector<uint8_t> wl_known_nodes(const Graph& graph);
+WlCone wl_cone(const Graph& graph, std::vector<uint8_t> node_known);
 // store slots of the cone's nodes from the full graph's: an unknown node keeps its slot (the same row of the stored
 // values), everything else is not stored -- the known rows come from the partial run
 std::vector<uint32_t> wl_cone_store_slots(const WlCone& cone, const std::vector<uint32_t>& store_slot_full);
