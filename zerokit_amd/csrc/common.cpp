@@ -2,10 +2,11 @@
 
 #include <stdlib.h>
 
-// The prover keeps seven HIP streams busy (two graph interpreters, mat-vec/NTT, MSM, back end, two proof-value
-// streams).  ROCclr multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues and streams that share a queue
-// serialise.  The library leaves that variable to the host program and its environment: the hardware queues of a card
-// are shared by every process on it.
+// The prover creates eight HIP streams (two graph interpreters, mat-vec/NTT, the two table walks, back end, proof values,
+// wipes).  ROCclr multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues and streams that share a queue serialise,
+// so a big batch keeps all eight busy only where the process has eight queues and four at four to seven (prover_plan.h:
+// stream_plan).  The library reads that variable and leaves setting it to the host program and its environment: the
+// hardware queues of a card are shared by every process on it.
 namespace rlnamd {
 void require_gpu() {
   static int checked = 0;

@@ -41,6 +41,7 @@ struct ProverConfig {
   int window_bits = 0;      // 0 = take RLNAMD_WINDOW_BITS or the default (120010: G1 c = 10, G2 c = 12); g1 + 10000 * g2, spec = c + 100 * wide
   size_t max_batch = 1024;  // workspace capacity in proofs (rounded up to a multiple of 64)
   long partial_cache = -1;  // entries of the partial-proof cache (collect_partial_cached); -1 = RLNAMD_PARTIAL_CACHE or 64
+  int stream_shape = -1;    // streams of a big batch: -1 = RLNAMD_STREAM_SHAPE or auto; 0 auto, 1 wide, 2 compact (ProverTuning::stream_shape)
 };
 
 // Every switch of the prover, read from the environment ONCE when a Prover is built (ProverTuning::from_env; printed by
@@ -75,6 +76,11 @@ struct ProverTuning {
   uint32_t hint_max_warm = 64;         // RLNAMD_HINTS_WARM: ... and up to this many when at most 2.5 chains per host thread have to be hashed (the others are remembered: hint_chains)
   uint32_t hint_threads = 8;           // RLNAMD_HINT_THREADS: host threads (the caller's included) that hash the hint chains of a batch's proofs; at most half of the host's hardware threads unless set
   int verify_lanes = 0;                // RLNAMD_VERIFY_LANES: lanes per proof of the device verifier (verify.h): 1 a lane, 8 a team, 0 by the size of the call (at most GpuVerifier::TEAM_MAX proofs: teams); any other value counts as 0
+  int stream_shape = 0;                // RLNAMD_STREAM_SHAPE (config key "stream_shape"): auto (0), wide (1) or compact (2) -- the streams a BIG batch
+                                       // keeps busy (prover_plan.h: stream_plan).  wide: eight streams, for a process with 8 hardware queues or
+                                       // more; compact: four, with the public values read off the witness.  auto: compact at 4 .. 7 hw_queues, else wide.  Small batches
+                                       // take the same streams either way.  A Prover holds the resolved shape (never auto)
+  int hw_queues = 4;                   // GPU_MAX_HW_QUEUES as the process got it (read, never set); 4, HIP's default, when absent or unparsable
   int hint_fault = 0;                  // RLNAMD_HINT_FAULT (test hook): j > 0 corrupts hint j - 1 of the first proof of every hinted batch
   static ProverTuning from_env();
   std::string describe() const;

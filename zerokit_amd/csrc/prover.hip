@@ -80,6 +80,8 @@ struct Slot {
   size_t n = 0;
   // what the batch's walks used (wipe_slot): proof stride of the digit rows, stride and row counts of the partial sums
   uint32_t dB = 0, PB = 0, nch1 = 0, nch2 = 0;
+  uint32_t seq = 0;             // the batch's sequence number (Impl::seq) and whether it took the big-batch streams
+  bool big = false;             // (prover_plan.h: stream_plan): which stream its wipe goes to
 };
 
 // Provers alive per device, in this process.  `lone` (nothing of THIS prover in flight) lets a batch trade instructions for
@@ -171,11 +173,16 @@ struct DeviceCount {   // (a member of Impl: a constructor that throws half-way 
 struct Prover::Impl {
   hipStream_t sA = nullptr, sAb = nullptr, sA2 = nullptr, sB = nullptr, sB2 = nullptr, sC = nullptr;
   // EIGHT streams in all: ROCclr maps streams onto GPU_MAX_HW_QUEUES hardware queues (see common.cpp) and two streams
-  // that share a queue serialise -- a ninth stream was measured as a 0.12 ms hole in the single-proof timeline
+  // that share a queue serialise -- a ninth stream was measured as a 0.12 ms hole in the single-proof timeline.  A big
+  // batch keeps all eight busy only where the process has eight queues; at four to seven, four (st / splan further down)
   hipStream_t sV = nullptr;   // proof values (24 chained Poseidon hashes per proof, latency-bound: ~17 ms of a 46 ms step)
   hipStream_t sW = nullptr;   // wipes: a stream of their own -- on sC a wipe would queue behind the back ends of every later
                               // batch, and the slot's next user would wait for all of them (measured: the pipeline drained)
-  uint32_t seq = 0;  // batches enqueued: consecutive front ends alternate between sA and sA2
+  uint32_t seq = 0;  // batches enqueued: consecutive front ends alternate between sA and sAb
+  // Big batches take their streams from the plan (prover_plan.h: stream_plan, by StreamId): eight of them busy with 8
+  // hardware queues or more (wide), four at 4 .. 7 queues (compact).  Small batches take the streams named in enqueue either way.
+  hipStream_t st[ST_COUNT] = {};
+  StreamPlan splan;
   float ms[PROVER_STAGES] = {0};
   DevBuf<unsigned long long> walk_clk;  // clock tap of the two walks: G1 cycles, G1 ticks, G2 cycles, G2 ticks
   ProverTuning tune;             // every switch, read once (prover.h)
@@ -299,7 +306,13 @@ struct Prover::Impl {
     const size_t n = S.n ? S.n : batch_cap;
     const size_t B = batch_cap;
     if (!n) return;
+    // compact: the wipe of a big batch's slot goes to the front-end stream of the slot's next batch -- wipe and reuse in
+    // stream order (the slot's evZ is recorded all the same: a small batch, or a caller that collects out of order, may
+    // be the next user)
+    hipStream_t sW = (S.big && splan.shape == SHAPE_COMPACT) ? st[splan.at[S.seq & 1][ROLE_WIPE]] : this->sW;
     RLN_HIP(hipStreamWaitEvent(sW, S.evC, 0));
+    // (away from the wipes' own stream: behind the save of the batch's cache entries, which reads the witness there)
+    if (sW != this->sW && evConeSaved) RLN_HIP(hipStreamWaitEvent(sW, evConeSaved, 0));
     // contiguous ranges are gathered and go out sixteen to a launch (k_wipe_ranges): a lone proof's collect used to make a
     // dozen launches for as many tiny buffers before it returned
     WipeRanges WR{};
@@ -413,6 +426,11 @@ ProverTuning ProverTuning::from_env() {
   t.partial_cache = (uint32_t)std::max(0, env_int("RLNAMD_PARTIAL_CACHE", (int)t.partial_cache));
   t.hint_max = (uint32_t)std::min<int>(std::max(0, env_int("RLNAMD_HINTS", (int)t.hint_max)), (int)HINT_PROOFS);
   t.hint_fault = env_int("RLNAMD_HINT_FAULT", 0);
+  {
+    const int shape = stream_shape_from_name(getenv("RLNAMD_STREAM_SHAPE"));
+    t.stream_shape = shape >= 0 ? shape : SHAPE_AUTO;
+    t.hw_queues = hw_queues_from_env(getenv("GPU_MAX_HW_QUEUES"));   // read, never set: the host program's to choose
+  }
   t.verify_lanes = env_int("RLNAMD_VERIFY_LANES", 0);
   if (t.verify_lanes != 1 && t.verify_lanes != 8) t.verify_lanes = 0;
   {   // (at most half of the host's hardware threads unless the switch says otherwise)
@@ -428,9 +446,9 @@ std::string ProverTuning::describe() const {
   char b[768];
   snprintf(b, sizeof b,
            "window_bits=%d slots=%d lanechunk=%u lanechunk_walk=%u witlanes_max=%u tiny=%u ntt_lg_max=%u partial_cache=%u lone=%d "
-           "lone_small=%u hints=%u hints_warm=%u hint_threads=%u hint_chains=%u verify_lanes=%d",
+           "lone_small=%u hints=%u hints_warm=%u hint_threads=%u hint_chains=%u verify_lanes=%d stream_shape=%s hw_queues=%d",
            window_bits, slots, lanechunk_max, lanechunk_walk_max, witlanes_max, tiny_max, ntt_lg_max, partial_cache, lone,
-           lone_small_max, hint_max, hint_max_warm, hint_threads, hint_chains, verify_lanes);
+           lone_small_max, hint_max, hint_max_warm, hint_threads, hint_chains, verify_lanes, stream_shape_name(stream_shape), hw_queues);
   return b;
 }
 const ProverTuning& Prover::tuning() const { return d_->tune; }
@@ -496,6 +514,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
   // spec 114 = 15 + 8 x 14 bits, 9 windows, 18 additions per G1 point; spec 715 = 7 x 16 + 15 bits, 8 windows, 16
   // additions per G2 point.
   D.tune = ProverTuning::from_env();
+  if (cfg.stream_shape >= SHAPE_AUTO && cfg.stream_shape <= SHAPE_COMPACT) D.tune.stream_shape = cfg.stream_shape;
   const int wb = cfg.window_bits > 0 ? cfg.window_bits : D.tune.window_bits;
   D.tune.window_bits = wb;
   const int spec1 = wb % 10000, spec2 = wb / 10000 ? wb / 10000 : spec1;
@@ -545,11 +564,15 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     RLN_HIP(hipStreamCreateWithPriority(&D.sB, hipStreamNonBlocking, lo));
     RLN_HIP(hipStreamCreateWithPriority(&D.sC, hipStreamNonBlocking, hi));
     D.nslot = std::min(std::max(D.tune.slots, 2), (int)Impl::NSLOT);
+    D.splan = stream_plan(D.tune.hw_queues, D.nslot, D.tune.stream_shape);
+    D.tune.stream_shape = D.splan.shape;
     D.walk_clk.alloc(4);
     RLN_HIP(hipMemset(D.walk_clk.p, 0, 4 * sizeof(unsigned long long)));
     // the G1 walk is ~12 rounds of 2.8 ms workgroups: on one stream its last round leaves SIMDs idle until the G2
     // walk may start; on two streams the walks of neighbouring batches fill each other's tails (+3.3 - 3.7 % measured)
     RLN_HIP(hipStreamCreateWithPriority(&D.sB2, hipStreamNonBlocking, lo));
+    D.st[ST_W] = D.sW; D.st[ST_A] = D.sA; D.st[ST_A2] = D.sA2; D.st[ST_AB] = D.sAb;
+    D.st[ST_V] = D.sV; D.st[ST_B] = D.sB; D.st[ST_C] = D.sC; D.st[ST_B2] = D.sB2;
   }
   hipStream_t s = D.sB;
 
@@ -838,7 +861,8 @@ Prover::~Prover() {
       if (D.cone_cache.p)   // entries a caller never released hold witness values too
         hipLaunchKernelGGL(k_wipe_bytes, dim3(div_up(D.cone_cache.bytes() / 16, 256)), dim3(64), 0, D.sW, D.cone_cache.p,
                            (uint32_t)(D.cone_cache.bytes() / 16));
-      (void)hipStreamSynchronize(D.sW);
+      for (hipStream_t st : D.st)   // (compact: a big batch's wipe went to a front-end stream)
+        if (st) (void)hipStreamSynchronize(st);
     }
   } catch (...) {
   }
@@ -1120,7 +1144,7 @@ void Prover::wipe(uint64_t ticket) {
   if (ticket == 0) {
     D.sync_all();
     if (D.last) D.wipe_slot(*D.last, true);
-    RLN_HIP(hipStreamSynchronize(D.sW));
+    D.sync_all();   // (the wipe's stream is the plan's: sW, or a front-end stream)
     return;
   }
   for (int k = 0; k < D.nslot; k++)
@@ -1245,6 +1269,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   q.logn = D.logn;
   q.capacity = B_;
   q.small_stride = D.small_stride;
+  q.compact = D.splan.shape == SHAPE_COMPACT;
   BatchShape sh = batch_shape(q, T);
   // the cone needs a live cache entry for every proof: a dead handle walks the whole graph
   std::vector<uint32_t> cone_entries;
@@ -1311,14 +1336,21 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // hardware queues sAb shares one with sC and sW, and a lone call on it measured 1.31 against 0.89 ms on sA.
   const bool idle = !D.last || hipEventQuery(D.last->evC) == hipSuccess;
   (void)hipGetLastError();   // hipErrorNotReady is not an error here
-  hipStream_t sA = (!idle && (sq & 1)) ? D.sAb : D.sA;   // two graph interpreters in flight: 16 latency-bound waves each
+  // Big batches take their streams from the plan (prover_plan.h: stream_plan).  compact: the interpreter's stream by the
+  // parity of the sequence number alone, so that a slot's wipe knows the stream of the slot's next batch.
+  const bool big = !small, compact = big && D.splan.shape == SHAPE_COMPACT;
+  const uint8_t* role = D.splan.at[(compact || !idle) ? (sq & 1) : 0];
+  hipStream_t sA = big ? D.st[role[ROLE_INTERP]] : (!idle && (sq & 1)) ? D.sAb : D.sA;   // two graph interpreters in flight: 16 latency-bound waves each
+  hipStream_t sB1 = big ? D.st[role[ROLE_WALK1]] : D.sB;   // the G1 walk's stream
+  S.seq = sq;
+  S.big = big;
   const uint32_t B = (uint32_t)B_, nb = (uint32_t)n;
   // Lone small batches: the G2 chain (recode, walk, sums, inversion, B's bytes -- the longest thing behind the interpreter)
   // stays on the interpreter's own stream, so nothing but kernel boundaries separates its links; the quotient chain
   // (mat-vec, NTTs, h rows, C sums, A's and C's bytes), which has ~0.2 ms of slack since the NTTs run in LDS, takes the
   // cross-stream hop (50 - 100 us each) instead.  In a stream of batches the front-end stream must be free for the
   // batch after next: there the walks keep their own streams.
-  hipStream_t sA2 = !early ? D.sA2 : sh.g2_on_front ? D.sB2 : sA;
+  hipStream_t sA2 = big ? D.st[role[ROLE_QUOTIENT]] : !early ? D.sA2 : sh.g2_on_front ? D.sB2 : sA;
   const uint32_t pg = div_up(nb, 64);
   const uint32_t nbp = pg * 64;  // padded lanes compute on stale / zero inputs; results ignored
   // Results home.  Big batches: by a single-wave kernel writing the pinned pages (as the inputs come in: k_stage_in) -- the
@@ -1467,6 +1499,16 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     RLN_HIP(hipEventRecord(S.evE, D.sB));
   }
   MARK(2, sA);
+  // compact: the public values are the circuit's own outputs w[1..5], read right here behind the interpreter -- no stream
+  // and no queue for the 24 chained hashes of k_proof_values (17 ms of a step's span for 0.04 G of its 22.6 G
+  // instructions).  A partial run returns no values and keeps k_proof_values, behind its G2 walk.
+  const bool values_front = sh.values_front;   // (prover_plan.cpp: batch_shape)
+  if (values_front) {
+    MARK(0, sA);
+    hipLaunchKernelGGL(k_values_from_witness, dim3(pg, 5), dim3(64), 0, sA, S.V.p, D.sig2node.p, B, nbp, S.values.p);
+    MARK(13, sA);
+    RLN_HIP(hipEventRecord(S.evV, sA));
+  }
   if (sA2 != sA) RLN_HIP(hipStreamWaitEvent(sA2, S.evX, 0));
   MARK(12, sA2);
   if (mode != PROVE_PARTIAL) {  // the quotient h depends on the whole witness: not part of a partial proof
@@ -1512,22 +1554,24 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // ---------------- stage B
   if (!early) {
     RLN_HIP(hipEventRecord(S.evA, sA2));
-    RLN_HIP(hipStreamWaitEvent(D.sB, S.evA, 0));
-    MARK(14, D.sB);
+    RLN_HIP(hipStreamWaitEvent(sB1, S.evA, 0));
+    MARK(14, sB1);
   }
-  hipStream_t s2 = sh.g2_on_front ? sA : D.sB2;   // the G2 walk on its own stream: its workgroups fill the G1 kernel's tail
-  if (!early) {   // (early: the G2 walk's stream already has the witness + part-1 digits, all it reads)
-    RLN_HIP(hipEventRecord(S.evR, D.sB));
-    RLN_HIP(hipStreamWaitEvent(D.sB2, S.evR, 0));
+  hipStream_t s2 = big ? D.st[role[ROLE_WALK2]] : sh.g2_on_front ? sA : D.sB2;   // the G2 walk on its own stream: its workgroups fill the G1 kernel's tail
+  if (compact) {   // the G1 stream carries the previous batch's sums: the G2 walk waits for the digits, not for them
+    RLN_HIP(hipStreamWaitEvent(s2, S.evA, 0));
+  } else if (!early) {   // (early: the G2 walk's stream already has the witness + part-1 digits, all it reads)
+    RLN_HIP(hipEventRecord(S.evR, sB1));
+    RLN_HIP(hipStreamWaitEvent(s2, S.evR, 0));
   }
   if (early) {   // the h rows, on the front-end stream itself (no event hop); everything else is already walking
     walk1(sA2, P1.late_ids.p, P1.n_late);
     RLN_HIP(hipEventRecord(S.evR, sA2));
     RLN_HIP(hipStreamWaitEvent(D.sB, S.evR, 0));   // evB below then covers both launches
   } else {
-    walk1(D.sB, nullptr, P1.nchunks);
+    walk1(sB1, nullptr, P1.nchunks);
   }
-  MARK(7, D.sB);
+  MARK(7, sB1);
   MARK(11, s2);
   if (P2.nchunks) {
     uint32_t blocks = div_up(P2.nchunks, 8) * 8 * pg;
@@ -1548,25 +1592,29 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
                          D.walk_clk.p ? D.walk_clk.p + 2 : nullptr);
   }
   MARK(8, s2);
-  RLN_HIP(hipEventRecord(S.evB, D.sB));
+  if (!compact) RLN_HIP(hipEventRecord(S.evB, sB1));   // (compact: behind the G1 sums, below)
   RLN_HIP(hipEventRecord(S.evB2, s2));
   // ---------------- stage C
   // proof values (Poseidon chain, latency-bound, depends on the inputs only): the back-end stream has slack
-  hipStream_t sV = D.sV;
-  if (S.used) {
-    RLN_HIP(hipStreamWaitEvent(D.sC, S.free_event(), 0));
+  // (compact: the whole back end behind the G2 walk, on its stream -- in stream order behind the front end's events)
+  hipStream_t sV = compact ? s2 : D.sV;
+  hipStream_t sC = big ? D.st[role[ROLE_SUMS2]] : D.sC;
+  if (S.used && !compact) {
+    RLN_HIP(hipStreamWaitEvent(sC, S.free_event(), 0));
     RLN_HIP(hipStreamWaitEvent(sV, S.free_event(), 0));
   }
-  if (streamed) RLN_HIP(hipStreamWaitEvent(sV, S.evU, 0));
-  MARK(0, sV);
-  // (whenever the batch is small enough for the lanes = nodes interpreter: the Poseidon chain alone is 5.3 ms)
-  if (sh.values_w) {   // small batches: the circuit's own outputs (see k_values_from_witness)
-    RLN_HIP(hipStreamWaitEvent(sV, S.evX, 0));   // sA: witness stored
-    hipLaunchKernelGGL(k_values_from_witness, dim3(pg, 5), dim3(64), 0, sV, S.V.p, D.sig2node.p, B, nbp, S.values.p);
-  } else if (D.have_values_kernel)
-    hipLaunchKernelGGL(k_proof_values, dim3(pg), dim3(64), 0, sV, in_p, D.NI, D.slots, poseidon_view(2),
-                       poseidon_view(3), poseidon_view(4), S.values.p, nbp);
-  MARK(13, sV);
+  if (!values_front) {
+    if (streamed && !compact) RLN_HIP(hipStreamWaitEvent(sV, S.evU, 0));
+    MARK(0, sV);
+    // (whenever the batch is small enough for the lanes = nodes interpreter: the Poseidon chain alone is 5.3 ms)
+    if (sh.values_w) {   // small batches: the circuit's own outputs (see k_values_from_witness)
+      RLN_HIP(hipStreamWaitEvent(sV, S.evX, 0));   // sA: witness stored
+      hipLaunchKernelGGL(k_values_from_witness, dim3(pg, 5), dim3(64), 0, sV, S.V.p, D.sig2node.p, B, nbp, S.values.p);
+    } else if (D.have_values_kernel)
+      hipLaunchKernelGGL(k_proof_values, dim3(pg), dim3(64), 0, sV, in_p, D.NI, D.slots, poseidon_view(2),
+                         poseidon_view(3), poseidon_view(4), S.values.p, nbp);
+    MARK(13, sV);
+  }
   // Small full proofs: A and B1 are sums over h-independent rows only, so their reduction, the two inversions and the two
   // variable-base products s A, r B1 (the longest kernel of the back end) run on the idle D.sA2 as soon as the early G1
   // walk is done -- beside the NTTs and the walk of the h rows, not behind them.  sums1 segments: h * 3 + {A, B1, C}.
@@ -1574,7 +1622,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   // task; until then a lone finish took the serial back end of the big batches and was SLOWER than a lone full proof)
   const bool fin_pp = mode == PROVE_FINISH;
   const TaskSel all4 = task_sel({0, 1, 2, 3}), all3 = task_sel({0, 1, 2});
-  hipStream_t sF = D.sC;   // the stream of k_fin_out and of the copies to the host
+  hipStream_t sF = sC;   // the stream of k_fin_out and of the copies to the host
   // segment sums of a small batch: one 512-lane tree per (proof, segment); tiny batches (four times the partial sums) in
   // two stages -- every 512-chunk block of a segment to one point, then the blocks of the segment -- so that the depth
   // stays log2(partial sums) + 1 instead of growing with the serial share of a lane
@@ -1665,40 +1713,58 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
       sum2(s2);
       RLN_HIP(hipEventRecord(S.evB2, s2));
     }
-    RLN_HIP(hipEventRecord(S.evV, sV));
-    RLN_HIP(hipStreamWaitEvent(D.sC, S.evV, 0));
-    RLN_HIP(hipStreamWaitEvent(D.sC, S.evB, 0));
-    if (tiny_partial) sum1(D.sC, {0, 1, 2, 3, 4, 5});
-    RLN_HIP(hipStreamWaitEvent(D.sC, S.evB2, 0));
-    MARK(9, D.sC);
+    if (!values_front) RLN_HIP(hipEventRecord(S.evV, sV));
+    if (compact) {
+      // every walk's sums behind it on its own stream: the G1 sums run in the G1 stream's gap, with no G1 walk beside
+      // them; fold, finalize and the results home follow the G2 sums and wait for the G1 sums and the values
+      hipStream_t sS1 = D.st[role[ROLE_SUMS1]];
+      if (P1.ngroups)
+        hipLaunchKernelGGL(k_sum_ranges<Fq>, dim3(pg, P1.ngroups), dim3(64), 0, sS1, S.part1.p, P1.groups.p, P1.ngroups,
+                           S.grp1.p, B, nbp);
+      hipLaunchKernelGGL(k_sum_ranges<Fq>, dim3(pg, P1.nseg), dim3(64), 0, sS1, S.grp1.p, P1.segs.p, P1.nseg, S.sums1.p, B, nbp);
+      RLN_HIP(hipEventRecord(S.evB, sS1));
+      MARK(9, sC);   // (`finalize` here: from the end of the G2 walk; the G1 sums above are on the G1 stream, in no span)
+      if (P2.ngroups)
+        hipLaunchKernelGGL(k_sum_ranges<Fq2>, dim3(pg, P2.ngroups), dim3(64), 0, sC, S.part2.p, P2.groups.p, P2.ngroups,
+                           S.grp2.p, B, nbp);
+      hipLaunchKernelGGL(k_sum_ranges<Fq2>, dim3(pg, P2.nseg), dim3(64), 0, sC, S.grp2.p, P2.segs.p, P2.nseg, S.sums2.p, B, nbp);
+      RLN_HIP(hipStreamWaitEvent(sC, S.evB, 0));
+      RLN_HIP(hipStreamWaitEvent(sC, S.evV, 0));
+    } else {
+      RLN_HIP(hipStreamWaitEvent(sC, S.evV, 0));
+      RLN_HIP(hipStreamWaitEvent(sC, S.evB, 0));
+      if (tiny_partial) sum1(sC, {0, 1, 2, 3, 4, 5});
+      RLN_HIP(hipStreamWaitEvent(sC, S.evB2, 0));
+      MARK(9, sC);
+    }
   }
-  if (early || tiny_partial) {
+  if (early || tiny_partial || compact) {
   } else if (small) {   // (here: a small partial batch) lanes = partial sums (k_sum_tree)
-    sum1(D.sC, {0, 1, 2, 3, 4, 5});
-    sum2(D.sC);
+    sum1(sC, {0, 1, 2, 3, 4, 5});
+    sum2(sC);
   } else {
     if (P1.ngroups)
-      hipLaunchKernelGGL(k_sum_ranges<Fq>, dim3(pg, P1.ngroups), dim3(64), 0, D.sC, S.part1.p, P1.groups.p, P1.ngroups,
+      hipLaunchKernelGGL(k_sum_ranges<Fq>, dim3(pg, P1.ngroups), dim3(64), 0, sC, S.part1.p, P1.groups.p, P1.ngroups,
                          S.grp1.p, B, nbp);
     if (P2.ngroups)
-      hipLaunchKernelGGL(k_sum_ranges<Fq2>, dim3(pg, P2.ngroups), dim3(64), 0, D.sC, S.part2.p, P2.groups.p, P2.ngroups,
+      hipLaunchKernelGGL(k_sum_ranges<Fq2>, dim3(pg, P2.ngroups), dim3(64), 0, sC, S.part2.p, P2.groups.p, P2.ngroups,
                          S.grp2.p, B, nbp);
-    hipLaunchKernelGGL(k_sum_ranges<Fq>, dim3(pg, P1.nseg), dim3(64), 0, D.sC, S.grp1.p, P1.segs.p, P1.nseg, S.sums1.p, B, nbp);
-    hipLaunchKernelGGL(k_sum_ranges<Fq2>, dim3(pg, P2.nseg), dim3(64), 0, D.sC, S.grp2.p, P2.segs.p, P2.nseg, S.sums2.p, B, nbp);
+    hipLaunchKernelGGL(k_sum_ranges<Fq>, dim3(pg, P1.nseg), dim3(64), 0, sC, S.grp1.p, P1.segs.p, P1.nseg, S.sums1.p, B, nbp);
+    hipLaunchKernelGGL(k_sum_ranges<Fq2>, dim3(pg, P2.nseg), dim3(64), 0, sC, S.grp2.p, P2.segs.p, P2.nseg, S.sums2.p, B, nbp);
   }
   if (!early)   // sums of the second halves through phi, onto the first: afterwards sums1[0..3) / sums2[0]
-    hipLaunchKernelGGL(k_glv_fold, dim3(pg, 4), dim3(64), 0, D.sC, S.sums1.p, S.sums2.p, 3u, B, nbp, all4);
+    hipLaunchKernelGGL(k_glv_fold, dim3(pg, 4), dim3(64), 0, sC, S.sums1.p, S.sums2.p, 3u, B, nbp, all4);
   if (mode == PROVE_PARTIAL) {
-    hipLaunchKernelGGL(k_partial_out, dim3(pg, 4), dim3(64), 0, D.sC, S.sums1.p, S.sums2.p, S.pp_out.p, B, nbp);
+    hipLaunchKernelGGL(k_partial_out, dim3(pg, 4), dim3(64), 0, sC, S.sums1.p, S.sums2.p, S.pp_out.p, B, nbp);
     RLN_HIP(hipGetLastError());
-    d2h(S.h_pp, S.pp_out.p, n * 320, D.sC);
+    d2h(S.h_pp, S.pp_out.p, n * 320, sC);
   } else {
     if (!early) {   // (here: a big batch)
       if (mode == PROVE_FINISH)
-        hipLaunchKernelGGL(k_add_partial, dim3(pg, 4), dim3(64), 0, D.sC, S.sums1.p, S.sums2.p, pp_p, B, nbp, all4, (const G1XYZZ*)nullptr);
-      hipLaunchKernelGGL(k_fin_affine, dim3(pg, 3), dim3(64), 0, D.sC, S.sums1.p, S.sums2.p, S.affA.p, S.affB1.p,
+        hipLaunchKernelGGL(k_add_partial, dim3(pg, 4), dim3(64), 0, sC, S.sums1.p, S.sums2.p, pp_p, B, nbp, all4, (const G1XYZZ*)nullptr);
+      hipLaunchKernelGGL(k_fin_affine, dim3(pg, 3), dim3(64), 0, sC, S.sums1.p, S.sums2.p, S.affA.p, S.affB1.p,
                          S.affB2.p, B, nbp, all3);
-      hipLaunchKernelGGL(k_fin_smul, dim3(pg, 2), dim3(64), 0, D.sC, S.affA.p, S.affB1.p, rs_p, S.tbl.p, S.prod.p, B,
+      hipLaunchKernelGGL(k_fin_smul, dim3(pg, 2), dim3(64), 0, sC, S.affA.p, S.affB1.p, rs_p, S.tbl.p, S.prod.p, B,
                          nbp);
       hipLaunchKernelGGL(k_fin_out, dim3(pg), dim3(64), 0, sF, S.sums1.p, S.prod.p, S.affA.p, S.affB2.p, S.coords.p,
                          S.comp.p, B, nbp);

@@ -1,6 +1,7 @@
 // prover_plan.cpp -- the host planning of the batched prover (prover_plan.h).  No device code and no HIP call.
 #include "prover_plan.h"
 
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -601,7 +602,85 @@ BatchShape batch_shape(const BatchQuery& q, const ProverTuning& T) {
   // NTTs as the three LDS kernels (above ~100 proofs the walks beside the quotient chain leave their 4-wave workgroups
   // waiting for four free wave slots on one CU: the single-wave passes then finish earlier)
   S.ntt_lds = S.small && n <= T.ntt_lg_max && q.logn >= 9 && q.logn <= 18;
+  // compact stream shape, big batches: the same outputs behind the interpreter on its own stream -- every mode for a batch
+  // that takes them anyway (values_w), otherwise full and finish
+  S.values_front = q.compact && !S.small && q.have_values_kernel && q.ni == 6 && (S.values_w || mode != PROVE_PARTIAL);
   return S;
+}
+
+// ------------------------------------------------------------------------------------------------- the streams of a big batch
+const StreamEdge StreamPlan::edges[StreamPlan::NEDGE] = {
+    {ROLE_INTERP, ROLE_VALUES}, {ROLE_INTERP, ROLE_QUOTIENT}, {ROLE_QUOTIENT, ROLE_WALK1}, {ROLE_QUOTIENT, ROLE_WALK2},
+    {ROLE_WALK1, ROLE_SUMS1},   {ROLE_WALK2, ROLE_SUMS2},     {ROLE_SUMS1, ROLE_SUMS2},    {ROLE_VALUES, ROLE_SUMS2},
+    {ROLE_SUMS2, ROLE_WIPE}};
+
+int StreamPlan::busy_streams() const {
+  uint32_t seen = 0;
+  int n = 0;
+  for (int p = 0; p < 2; p++)
+    for (int r = 0; r < ROLE_COUNT; r++)
+      if (r != ROLE_WIPE && !(seen >> at[p][r] & 1u)) {
+        seen |= 1u << at[p][r];
+        n++;
+      }
+  return n;
+}
+
+int hw_queues_from_env(const char* value) {
+  if (!value || !*value) return 4;
+  char* end = nullptr;
+  const long v = strtol(value, &end, 10);
+  if (end == value || *end != 0 || v < 1 || v > 1024) return 4;
+  return (int)v;
+}
+
+int stream_shape_from_name(const char* name) {
+  if (!name) return -1;
+  if (!strcmp(name, "auto")) return SHAPE_AUTO;
+  if (!strcmp(name, "wide")) return SHAPE_WIDE;
+  if (!strcmp(name, "compact")) return SHAPE_COMPACT;
+  return -1;
+}
+const char* stream_shape_name(int shape) { return shape == SHAPE_WIDE ? "wide" : shape == SHAPE_COMPACT ? "compact" : "auto"; }
+
+StreamPlan stream_plan(int queues, int nslot, int shape) {
+  StreamPlan P;
+  P.shape = shape == SHAPE_WIDE || shape == SHAPE_COMPACT ? shape
+            : (queues >= 8 || queues < COMPACT_MIN_QUEUES)        ? SHAPE_WIDE
+                                                                  : SHAPE_COMPACT;
+  if (P.shape == SHAPE_WIDE) {
+    // Eight streams: two interpreters in flight (consecutive batches alternate), the quotient chain beside them, a stream
+    // per walk, one back end, the Poseidon chain of the values and the wipes on streams of their own.
+    const uint8_t order[ROLE_COUNT] = {ROLE_INTERP, ROLE_QUOTIENT, ROLE_WALK1, ROLE_WALK2, ROLE_VALUES, ROLE_SUMS1, ROLE_SUMS2, ROLE_WIPE};
+    for (int r = 0; r < ROLE_COUNT; r++) P.order[r] = order[r];
+    for (int p = 0; p < 2; p++) {
+      P.at[p][ROLE_INTERP] = p ? ST_AB : ST_A;
+      P.at[p][ROLE_VALUES] = ST_V;
+      P.at[p][ROLE_QUOTIENT] = ST_A2;
+      P.at[p][ROLE_WALK1] = ST_B;
+      P.at[p][ROLE_WALK2] = ST_B2;
+      P.at[p][ROLE_SUMS1] = ST_C;
+      P.at[p][ROLE_SUMS2] = ST_C;
+      P.at[p][ROLE_WIPE] = ST_W;
+    }
+    return P;
+  }
+  // Four streams (auto takes this map only where the process has at least four queues).  The whole front end of a batch in stream
+  // order on one of two alternating high-priority streams -- each has two steps for it and runs up to two batches ahead
+  // of its walks -- with the values read off the witness behind the interpreter; every walk with its own sums behind it
+  // on a low-priority stream, the rest of the back end behind the G2 sums.  A slot's wipe goes to the stream its next
+  // batch's front end takes (nslot batches later), so wipe and reuse are in stream order.
+  const uint8_t order[ROLE_COUNT] = {ROLE_INTERP, ROLE_VALUES, ROLE_QUOTIENT, ROLE_WALK1, ROLE_WALK2, ROLE_SUMS1, ROLE_SUMS2, ROLE_WIPE};
+  for (int r = 0; r < ROLE_COUNT; r++) P.order[r] = order[r];
+  P.values_front = true;
+  const uint8_t front[2] = {ST_A, ST_AB};
+  for (int p = 0; p < 2; p++) {
+    P.at[p][ROLE_INTERP] = P.at[p][ROLE_VALUES] = P.at[p][ROLE_QUOTIENT] = front[p];
+    P.at[p][ROLE_WALK1] = P.at[p][ROLE_SUMS1] = ST_B;
+    P.at[p][ROLE_WALK2] = P.at[p][ROLE_SUMS2] = ST_B2;
+    P.at[p][ROLE_WIPE] = front[(p + nslot) & 1];
+  }
+  return P;
 }
 
 }  // namespace rlnamd

@@ -146,13 +146,66 @@ struct BatchQuery {
   int logn = 0;
   size_t capacity = 0;         // Prover::capacity()
   uint32_t small_stride = 64;
+  bool compact = false;        // the prover's big batches take the compact stream shape (stream_plan below)
 };
 struct BatchShape {
   bool lone, small, wl_used, cone, hinted, early, fused, tiny_partial, tiny, walk_lp, g2_on_front, values_w, ntt_lds;
   bool probe_chains;           // hinted holds only if few enough of the proofs' chains have to be hashed (enqueue asks)
+  // big batches in the compact stream shape: the public values are the circuit's outputs, read behind k_v29_to_fr on the
+  // interpreter's own stream (values_w says the same for the small shapes and the lanes = nodes interpreter, on the
+  // values' stream).  Full and finish; a partial batch returns no values and keeps k_proof_values.
+  bool values_front;
   WalkPlanKind plan1, plan2;
   uint32_t PB, dB;             // strides of the partial-sum arrays and of the digit rows
 };
 BatchShape batch_shape(const BatchQuery& q, const ProverTuning& T);
+
+// ---- which stream every role of a BIG batch (!BatchShape::small) takes: Prover::enqueue, wipe_slot.  ROCclr maps streams
+// onto GPU_MAX_HW_QUEUES hardware queues; streams that share a queue run their kernels in submission order, and a wait at
+// the head of one holds up what the other submitted behind it.  So a big batch keeps no more streams busy than the process
+// has queues: `wide` (8 queues and more) is the map of eight streams, `compact` the same launches on four.
+// The prover's streams by index, in the order they are created (the first stream of a process runs every kernel ~70 us
+// slower: the wipes' own stream, which only the small shapes and the wide map use).
+enum StreamId : uint8_t { ST_W = 0, ST_A, ST_A2, ST_AB, ST_V, ST_B, ST_C, ST_B2, ST_COUNT };
+enum StreamRole : uint8_t {
+  ROLE_INTERP = 0,   // stage-in, graph interpreter, k_v29_to_fr
+  ROLE_VALUES,       // public values
+  ROLE_QUOTIENT,     // mat-vec, NTTs, quotient, recode
+  ROLE_WALK1,        // G1 table walk
+  ROLE_WALK2,        // G2 table walk
+  ROLE_SUMS1,        // G1 group / segment sums
+  ROLE_SUMS2,        // G2 sums, fold, finalize, output kernels, results home, evC
+  ROLE_WIPE,         // the wipe of the slot the batch used (collect)
+  ROLE_COUNT
+};
+enum StreamShape { SHAPE_AUTO = 0, SHAPE_WIDE = 1, SHAPE_COMPACT = 2 };
+struct StreamEdge {   // `to` reads what `from` wrote: in stream order behind it where they share a stream, else behind an event
+  uint8_t from, to;
+};
+// What Prover::enqueue takes from the plan is the stream table `at`, `shape` and `values_front`; its event records and
+// waits are written out in enqueue.  `order`, `edges`, `needs_event` and `busy_streams` DESCRIBE those launches for the
+// host test (tests/host/streamplan.cpp), which therefore covers the table -- who shares a stream with whom, whether the
+// table admits an acyclic submission -- and not the presence of each hipStreamWaitEvent (the GPU tests cover those).
+struct StreamPlan {
+  int shape = SHAPE_WIDE;                 // resolved: SHAPE_WIDE or SHAPE_COMPACT
+  uint8_t at[2][ROLE_COUNT] = {};         // [parity of the batch's sequence number][role] -> StreamId
+  uint8_t order[ROLE_COUNT] = {};         // the roles in the order enqueue submits them (ROLE_WIPE last: at collect)
+  bool values_front = false;              // ROLE_VALUES is k_values_from_witness behind the interpreter (BatchShape::values_front)
+  static constexpr int NEDGE = 9;
+  static const StreamEdge edges[NEDGE];   // producer -> consumer inside one batch
+  // the next batch on the slot (nslot batches later) waits for the wipe: always through the slot's event (evZ), and in
+  // stream order as well where the wipe went to that batch's interpreter stream
+  bool needs_event(int parity, const StreamEdge& e) const { return at[parity][e.from] != at[parity][e.to]; }
+  int busy_streams() const;               // distinct streams of the roles other than ROLE_WIPE, both parities
+};
+// queues: GPU_MAX_HW_QUEUES as the process got it (hw_queues_from_env).  SHAPE_AUTO never keeps more streams busy than
+// the process has queues: wide at 8 queues and more, compact at COMPACT_MIN_QUEUES .. 7, and wide -- the map every
+// queue count had before there were two -- below that, where no four-stream map fits either.  SHAPE_COMPACT asked for
+// by name is the four-stream map whatever `queues` is.  No HIP call.
+constexpr int COMPACT_MIN_QUEUES = 4;
+StreamPlan stream_plan(int queues, int nslot, int shape = SHAPE_AUTO);
+int hw_queues_from_env(const char* value);   // the variable's text (or null): 4, HIP's default, when absent or unparsable
+int stream_shape_from_name(const char* name);   // "auto" / "wide" / "compact" -> StreamShape; -1: none of them
+const char* stream_shape_name(int shape);
 
 }  // namespace rlnamd

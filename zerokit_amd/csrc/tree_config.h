@@ -76,6 +76,9 @@ struct TreeConfig {
   // "gather_window_us": how long the leader of a gathered batch waits for callers it saw within the last 20 ms
   // (500 unless given; 0: it takes what is queued)
   long gather_window_us = 500;
+  // "stream_shape": "auto" | "wide" | "compact" -- the streams a big batch keeps busy (prover.h: ProverTuning::stream_shape).
+  // -1: RLNAMD_STREAM_SHAPE or auto (by the process's GPU_MAX_HW_QUEUES)
+  int stream_shape = -1;
   bool persistent() const { return !temporary && has_path; }
   ProverConfig prover_config() const {
     ProverConfig cfg;
@@ -85,6 +88,7 @@ struct TreeConfig {
     else if (profile == "small") { pw = 8; pb = 64; }
     cfg.max_batch = max_batch > 0 ? (size_t)max_batch : pb > 0 ? (size_t)pb : (mb && *mb ? (size_t)atoll(mb) : 256);
     cfg.window_bits = window_bits > 0 ? (int)window_bits : (int)pw;   // 0: Prover takes RLNAMD_WINDOW_BITS or its default schedule
+    cfg.stream_shape = stream_shape;
     cfg.partial_cache = partial_cache >= 0 ? partial_cache : (auto_partial > 0 ? std::max(64l, auto_partial + 8) : -1);
     return cfg;
   }
@@ -132,6 +136,11 @@ inline TreeConfig parse_tree_config(const std::string& js) {
         if (v != "latency" && v != "throughput" && v != "small")
           throw Error("Configuration error: profile: expected \"latency\", \"throughput\" or \"small\", got \"" + v + "\"");
         c.profile = v;
+      }
+      if (key == "stream_shape") {
+        c.stream_shape = v == "auto" ? 0 : v == "wide" ? 1 : v == "compact" ? 2 : -1;
+        if (c.stream_shape < 0)
+          throw Error("Configuration error: stream_shape: expected \"auto\", \"wide\" or \"compact\", got \"" + v + "\"");
       }
     } else if (!js.compare(i, 4, "true") || !js.compare(i, 5, "false")) {
       bool v = js[i] == 't';
