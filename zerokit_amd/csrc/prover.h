@@ -3,7 +3,7 @@
 // Device-side replacement for the path below generate_zk_proof_with_rs
 // (/root/reference/rln/src/protocol/proof.rs:753-777):
 //   calc_witness            (circuit/iden3calc.rs:20-60, iden3calc/graph.rs:246-272)  -> k_witness29, k_witness_lanes
-//   CircomReduction         (circuit/qap.rs:30-98)                                     -> k_matvec, k_ntt_pass, k_hquot
+//   CircomReduction         (circuit/qap.rs:30-98)                                     -> k_matvec, k_ntt_pass, k_ntt_turn
 //   create_proof_with_...   (ark-groth16 0.5.0; restated in partial_proof.rs:182-274)  -> k_recode, k_msm_*, k_finalize
 //   proof_values_from_witness (protocol/witness.rs:759-828)                            -> k_proof_values
 //

@@ -200,6 +200,7 @@ struct Prover::Impl {
   uint32_t n_mv_long = 0;
   DevBuf<Fr> a_coef, b_coef;
   DevBuf<Fr> tw_f, tw_i, coset;
+  std::vector<NttPass> ntt_passes;   // the launches of the transforms with lanes = proofs (prover_plan.h)
   // MSM: the comb tables in the packed 9 x 29-bit form (one 64-byte line per G1 entry)
   DevBuf<G1Affine29> t1_29;
   DevBuf<G2Affine29> t2_29;
@@ -454,12 +455,6 @@ std::string ProverTuning::describe() const {
 const ProverTuning& Prover::tuning() const { return d_->tune; }
 int Prover::device_shared() const { return (d_->device.dev >= 0 && g_provers_on_device[d_->device.dev] > 1 ? 1 : 0) | (d_->device.other_process() ? 2 : 0); }
 
-static uint32_t bitrev(uint32_t x, int bits) {
-  uint32_t r = 0;
-  for (int i = 0; i < bits; i++) r |= ((x >> i) & 1u) << (bits - 1 - i);
-  return r;
-}
-
 // G1 table in the 9 x 29 form: slabs are built in the 8 x 32 form (k_table_build reads its own rows back) and
 // converted into place
 // where the constructor's time goes (Prover::init_ms): [0] parsing the arkzkey / graph + the verifier's precomputation,
@@ -661,32 +656,13 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     RLN_HIP(hipStreamSynchronize(s));
   }
 
-  // ---- NTT tables: w = W^(2^(28-logn)), g = root of the doubled domain, coset[pos] = g^bitrev(pos) / n
+  // ---- NTT tables and the launches of the big batches' transforms (prover_plan.h)
   {
-    Fr root28 = Fr::from_canonical(FR_ROOT_2_28);
-    Fr g = root28;
-    for (int i = 0; i < 28 - (D.logn + 1); i++) g = g.sqr();  // order 2n
-    Fr w = g.sqr();                                           // order n
-    Fr wi = w.inv();
-    std::vector<Fr> tf(D.n / 2), ti(D.n / 2), cs(D.n);
-    Fr a = Fr::one(), b = Fr::one();
-    for (uint32_t k = 0; k < D.n / 2; k++) {
-      tf[k] = a;
-      ti[k] = b;
-      a = a * w;
-      b = b * wi;
-    }
-    Fr ninv = Fr::from_u32(D.n).inv();
-    std::vector<Fr> gp(D.n);
-    Fr acc = ninv;
-    for (uint32_t i = 0; i < D.n; i++) {
-      gp[i] = acc;
-      acc = acc * g;
-    }
-    for (uint32_t pos = 0; pos < D.n; pos++) cs[pos] = gp[bitrev(pos, D.logn)];
-    D.tw_f.assign(tf, s);
-    D.tw_i.assign(ti, s);
-    D.coset.assign(cs, s);
+    const NttTables T = ntt_tables(D.logn);
+    D.ntt_passes = ntt_pass_list(D.logn);
+    D.tw_f.assign(T.tw_f, s);
+    D.tw_i.assign(T.tw_i, s);
+    D.coset.assign(T.coset, s);
     RLN_HIP(hipStreamSynchronize(s));
   }
 
@@ -911,24 +887,27 @@ void Prover::upload_witness(size_t n, const uint8_t* w_le) {
   D.wgiven_n = n;
 }
 
-template <bool DIF>
-static void launch_ntt(Fr* data, const Fr* tw, int logn, const Fr* final_scale, uint32_t B, uint32_t nb, hipStream_t s) {
-  int s0 = 0;
-  while (s0 < logn) {
-    const int rem = logn - s0;
-    const int K = rem > 3 ? 3 : rem;  // 13 -> 3,3,3,3,1 (a 16-point block spills; measured 6.7 -> 5.0 ms)
-    const uint32_t groups = (1u << logn) >> K;
+// iNTT (DIF) + g^i / n + NTT (DIT) over the three vectors with lanes = proofs, by the pass list of prover_plan.h
+static void launch_ntt(const std::vector<NttPass>& passes, Fr* data, const Fr* tw_i, const Fr* tw_f, int logn, const Fr* scale,
+                       uint32_t B, uint32_t nb, hipStream_t s) {
+  for (const NttPass& ps : passes) {
     // one wave per workgroup: a 4-wave workgroup needs four free wave slots on one CU at the same moment, which the
     // single-wave MSM workgroups streaming through the chip never leave (measured: mat-vec 0.6 -> 32 ms, NTT 5 -> 19 ms)
-    dim3 block(64, 1), grid(div_up(nb, 64), groups, 3);
-    const Fr* sc = (s0 + K == logn) ? final_scale : nullptr;
-    switch (K) {
-      case 1: hipLaunchKernelGGL((k_ntt_pass<1, DIF>), grid, block, 0, s, data, tw, logn, s0, sc, B, nb); break;
-      case 2: hipLaunchKernelGGL((k_ntt_pass<2, DIF>), grid, block, 0, s, data, tw, logn, s0, sc, B, nb); break;
-      default: hipLaunchKernelGGL((k_ntt_pass<3, DIF>), grid, block, 0, s, data, tw, logn, s0, sc, B, nb); break;
+    const dim3 block(64, 1), grid(div_up(nb, 64), (1u << logn) >> ps.k, 3);
+    if (ps.kind == NTT_TURN) {
+      switch (ps.k) {
+        case 1: hipLaunchKernelGGL(k_ntt_turn<1>, grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+        case 2: hipLaunchKernelGGL(k_ntt_turn<2>, grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+        default: hipLaunchKernelGGL(k_ntt_turn<3>, grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+      }
+    } else if (ps.k != NTT_MAX_K) {
+      throw Error("NTT pass list: a pass that is not the turn has NTT_MAX_K levels");
+    } else if (ps.kind == NTT_DIF) {
+      hipLaunchKernelGGL((k_ntt_pass<NTT_MAX_K, true>), grid, block, 0, s, data, tw_i, logn, (int)ps.s0, B, nb);
+    } else {
+      hipLaunchKernelGGL((k_ntt_pass<NTT_MAX_K, false>), grid, block, 0, s, data, tw_f, logn, (int)ps.s0, B, nb);
     }
     RLN_HIP(hipGetLastError());
-    s0 += K;
   }
 }
 
@@ -1481,14 +1460,14 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     // and both walks wait for them on their own streams.
     hipStream_t sR1 = sA, sR3 = lone ? D.sB : sA;
     hipLaunchKernelGGL(k_recode, dim3(div_up(D.NS + 3, 64), nb), dim3(64, 1), 0, sR1, S.V.p, D.sig2node.p, D.NS,
-                       S.abc.p, D.n, rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nb, 1u, 1u, dB);
+                       S.abc.p, D.n, rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nb, 1u, 1u, 0u, dB);
     if (lone) {
       RLN_HIP(hipEventRecord(S.evW, sA));
       RLN_HIP(hipStreamWaitEvent(D.sB, S.evW, 0));
     }
     if (fused)
       hipLaunchKernelGGL(k_recode, dim3(div_up(2 * D.NS + 1, 64), nb), dim3(64, 1), 0, sR3, S.V.p, D.sig2node.p, D.NS,
-                         S.abc.p, D.n, rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nb, 3u, 1u, dB);
+                         S.abc.p, D.n, rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nb, 3u, 1u, 0u, dB);
     if (!lone) {
       RLN_HIP(hipEventRecord(S.evW, sA));
       RLN_HIP(hipStreamWaitEvent(D.sB, S.evW, 0));
@@ -1534,11 +1513,9 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
       if (D.logn > 9) hipLaunchKernelGGL(k_ntt_edge<false>, grid, dim3(256), 0, sA2, S.abc.p, D.tw_f.p, D.logn, B, nb);
       RLN_HIP(hipGetLastError());
     } else {
-      launch_ntt<true>(S.abc.p, D.tw_i.p, D.logn, D.coset.p, B, nbp, sA2);   // iNTT (DIF) + g^i / n
-      launch_ntt<false>(S.abc.p, D.tw_f.p, D.logn, nullptr, B, nbp, sA2);    // NTT (DIT)
+      launch_ntt(D.ntt_passes, S.abc.p, D.tw_i.p, D.tw_f.p, D.logn, D.coset.p, B, nbp, sA2);
     }
-    if (!early)   // (early: the recode below forms h = a o b - c itself)
-      hipLaunchKernelGGL(k_hquot, dim3(pg, D.n), dim3(64, 1), 0, sA2, S.abc.p, D.n, B, nbp, 0u);
+    // (the recode below forms h = a o b - c itself)
   }
   MARK(4, sA2);
   // digit recoding closes the front end: the MSM streams carry nothing but the two table walks
@@ -1546,10 +1523,11 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   MARK(5, sR);
   if (early)
     hipLaunchKernelGGL(k_recode, dim3(div_up(D.n, 64), nb), dim3(64, 1), 0, sR, S.V.p, D.sig2node.p, D.NS, S.abc.p, D.n,
-                       rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nb, 2u, 2u, dB);
+                       rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nb, 2u, 1u, 1u, dB);
   else
     hipLaunchKernelGGL(k_recode, dim3(pg, D.NS + D.n + 3), dim3(64, 1), 0, sR, S.V.p, D.sig2node.p, D.NS,
-                       S.abc.p, D.n, rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nbp, 0u, 0u, dB);
+                       S.abc.p, D.n, rs_p, D.ws, D.ws2, S.digits.p, S.digits2.p, B, nbp, 0u, 0u,
+                       mode != PROVE_PARTIAL ? 1u : 0u, dB);
   MARK(6, sR);
   // ---------------- stage B
   if (!early) {

@@ -21,6 +21,7 @@ struct GNode29 {
 
 constexpr uint32_t MV_LONG = 8;   // mat-vec: rows with more entries in A or B get a wave each (k_matvec)
 constexpr uint32_t SUM_TREE_LANES = 512;
+constexpr int NTT_MAX_K = 3;      // levels of one k_ntt_pass: eight points per lane (a 16-point block spills; measured 6.7 -> 5.0 ms)
 struct InputSlots {
   uint32_t secret, limit, msg_id, path, path_idx, x, ext, depth;
 };

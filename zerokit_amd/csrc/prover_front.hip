@@ -325,9 +325,15 @@ __global__ void __launch_bounds__(256) k_consts_to29(const Fr* __restrict__ src,
 }
 // (Small batches do not come here: k_ntt_edge / k_ntt_mid below; a circuit with fewer than 512 constraints would, with its
 // proofs in the lanes like any batch.)
+// Which pass takes which levels: ntt_pass_list (prover_plan.h).  The lowest levels of both directions and the scaling
+// between them are k_ntt_turn's, so a pass here never has stride 1 and never scales.
+// A butterfly whose twiddle index j is 0 multiplies by tw[0], the Montgomery one (checked where the tables are built), and
+// the product would return its operand -- sums, differences and products of Fr are canonical -- so it is left out: 8 191
+// of a 2^13-point transform's 53 248 products, ~375 instructions each.  j = (m & (half - 1)) stride + lo: the first
+// term is known at compile time, lo is the same for the whole wave (a scalar branch).
 template <int K, bool DIF>
 __global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0,
-                                                  const Fr* __restrict__ scale, uint32_t B, uint32_t nb) {
+                                                  uint32_t B, uint32_t nb) {
   // (twiddle products through Fr29::mul_mont -- ~290 instead of ~375 instructions -- were measured neutral twice: beside the
   // table walks the passes are bound by HBM and by waiting for SIMD slots; that variant is gone)
   auto tmul = [&](const Fr& a, const Fr* __restrict__ tab, uint32_t idx) -> Fr { return a * tab[idx]; };
@@ -359,6 +365,7 @@ __global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict_
 #pragma unroll
     for (int m = 0; m < R; m++) {
       if (m & half) continue;
+      const bool unit = (m & (half - 1)) == 0 && lo == 0;   // j == 0 (wave-uniform)
       uint32_t j = (uint32_t)(m & (half - 1)) * stride + lo;
       uint32_t ti = DIF ? (j << (s0 + t)) : (j << (logn - 1 - (s0 + t)));
       // the twiddle index is the same for all 64 lanes (lanes = proofs): force the scalar path so the
@@ -367,21 +374,73 @@ __global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict_
       if (DIF) {
         Fr u = e[m], v = e[m + half];
         e[m] = u + v;
-        e[m + half] = tmul(u - v, tw, tix);
+        Fr d = u - v;
+        if (!unit) d = tmul(d, tw, tix);
+        e[m + half] = d;
       } else {
-        Fr u = e[m], v = tmul(e[m + half], tw, tix);
+        Fr u = e[m], v = e[m + half];
+        if (!unit) v = tmul(v, tw, tix);
         e[m] = u + v;
         e[m + half] = u - v;
       }
     }
   }
 #pragma unroll
-  for (int m = 0; m < R; m++) {
-    uint32_t pos = base + m * stride;
-    Fr o = e[m];
-    if (scale) o = tmul(o, scale, uni(pos));
-    x[(size_t)pos * B] = o;
+  for (int m = 0; m < R; m++) x[(size_t)(base + m * stride) * B] = e[m];
+}
+
+// The turn: the lowest KT levels of the inverse transform (DIF levels logn - KT .. logn - 1), the coset / 1/n scaling and
+// the lowest KT levels of the forward one (DIT levels 0 .. KT - 1) over the same 2^KT contiguous points -- DIF leaves
+// bit-reversed order and DIT starts from it, so both close over the positions (g << KT) + m, as in k_ntt_mid.  One trip
+// through HBM where two one-level passes around the scaling made two.  Same butterflies, same twiddles, same products per
+// point as k_ntt_pass over those levels (stride 1, lo 0): j = m & (half - 1) is known at compile time and the products by
+// tw[0] are left out -- KT = 1 has no twiddle product at all.
+template <int KT>
+__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_turn(Fr* __restrict__ data, const Fr* __restrict__ tw_i,
+                                                  const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale,
+                                                  uint32_t B, uint32_t nb) {
+  constexpr int R = 1 << KT;
+  const uint32_t n = 1u << logn;
+  uint32_t p = blockIdx.x * 64 + threadIdx.x;
+  uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.y * blockDim.y + threadIdx.y);  // one group per wave
+  if (g >= (n >> KT)) return;
+  if (p >= nb) return;
+  const uint32_t base = g << KT;
+  Fr* x = data + ((size_t)blockIdx.z * n + base) * B + p;
+  Fr e[R];
+#pragma unroll
+  for (int m = 0; m < R; m++) e[m] = x[(size_t)m * B];
+#pragma unroll
+  for (int t = 0; t < KT; t++) {   // inverse level logn - KT + t
+    const int half = R >> (t + 1);
+#pragma unroll
+    for (int m = 0; m < R; m++) {
+      if (m & half) continue;
+      const uint32_t j = (uint32_t)(m & (half - 1));
+      Fr u = e[m], v = e[m + half];
+      e[m] = u + v;
+      Fr d = u - v;
+      if (j) d = d * tw_i[(size_t)j << (logn - KT + t)];
+      e[m + half] = d;
+    }
   }
+#pragma unroll
+  for (int m = 0; m < R; m++) e[m] = e[m] * scale[base + m];   // (wave-uniform index: the factor rides in SGPRs)
+#pragma unroll
+  for (int t = 0; t < KT; t++) {   // forward level t
+    const int half = 1 << t;
+#pragma unroll
+    for (int m = 0; m < R; m++) {
+      if (m & half) continue;
+      const uint32_t j = (uint32_t)(m & (half - 1));
+      Fr u = e[m], v = e[m + half];
+      if (j) v = v * tw_f[(size_t)j << (logn - 1 - t)];
+      e[m] = u + v;
+      e[m + half] = u - v;
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < R; m++) x[(size_t)m * B] = e[m];
 }
 
 // Small batches (lanes = groups), logn >= 9: the three transforms of the quotient in THREE kernels, one butterfly per lane
@@ -482,16 +541,6 @@ __global__ void __launch_bounds__(256) k_ntt_edge(Fr* __restrict__ data, const F
   }
 }
 
-// h = a o b - c  (qap.rs:84-95), written over the `a` vector
-__global__ void __launch_bounds__(256) k_hquot(Fr* __restrict__ abc, uint32_t n, uint32_t B, uint32_t nb, uint32_t lg) {
-  if (lg) __builtin_amdgcn_s_setprio(3);   // small batches: a link of the latency chain (see k_ntt_mid)
-  uint32_t p = lg ? blockIdx.y : blockIdx.x * 64 + threadIdx.x;   // lg: lanes = coefficients of one proof
-  uint32_t i = lg ? blockIdx.x * 64 + threadIdx.x : blockIdx.y * blockDim.y + threadIdx.y;
-  if (p >= nb || i >= n) return;
-  size_t o = (size_t)i * B + p;
-  abc[o] = abc[o] * abc[(size_t)n * B + o] - abc[2 * (size_t)n * B + o];
-}
-
 // =====================================================================================================
 // 4. scalars -> signed digits (window j: cw[j] bits), layout [scalar][half][window][proof] (int16)
 // =====================================================================================================
@@ -527,7 +576,7 @@ __global__ void __launch_bounds__(256) k_recode(const Fr* __restrict__ V, const 
                                                 uint32_t ns, const Fr* H, uint32_t n,
                                                 const uint32_t* __restrict__ rs, WinSched ws1, WinSched ws2,
                                                 int16_t* __restrict__ dig1, int16_t* __restrict__ dig2, uint32_t B,
-                                                uint32_t nb, uint32_t part, uint32_t lg, uint32_t dB) {
+                                                uint32_t nb, uint32_t part, uint32_t lg, uint32_t hq, uint32_t dB) {
   // dB: the proof stride of the digit arrays ([scalar][half][window][dB]).  The batch capacity B in the throughput
   // shapes; the batch SIZE for small batches -- with B = 64 a lone proof's digits sat one per 128-byte line (64 scattered
   // two-byte stores per lane here, a miss per step in the walks); compact, a scalar's windows share one line.
@@ -562,10 +611,12 @@ __global__ void __launch_bounds__(256) k_recode(const Fr* __restrict__ V, const 
     x = V[(size_t)sig2node[sid] * B + p];
   } else if (sid < ns + n) {
     const size_t o = (size_t)(sid - ns) * B + p;
-    // lg == 2 (small batches): the quotient on the fly, h = a o b - c (k_hquot's line: same products, same bytes) -- one
-    // kernel and one boundary less on the chain the h rows wait for
-    x = lg == 2 ? H[o] * H[(size_t)n * B + o] - H[2 * (size_t)n * B + o] : H[o];
-    if (lg == 2) const_cast<Fr*>(H)[o] = x;   // where k_hquot leaves it (Prover::fetch_h reads it there); one lane per element
+    // hq (every full proof and finish; a flag of its own: lg also selects the lane mapping): the quotient on the fly,
+    // h = a o b - c (qap.rs:84-95), from the three transformed vectors -- no kernel of its own that reads a, b, c and
+    // writes h for this one to read back, and for small batches one boundary less on the chain the h rows wait for.
+    // Without it (a partial proof: no quotient, its h rows are not walked) the row is read as it is.
+    x = hq ? H[o] * H[(size_t)n * B + o] - H[2 * (size_t)n * B + o] : H[o];
+    if (hq) const_cast<Fr*>(H)[o] = x;   // over the `a` vector, where Prover::fetch_h reads it; one lane per element
   } else {
     Fr r = Fr::from_canonical(rs + (size_t)p * 16);
     Fr s = Fr::from_canonical(rs + (size_t)p * 16 + 8);
@@ -595,12 +646,11 @@ __global__ void __launch_bounds__(256) k_recode(const Fr* __restrict__ V, const 
 template __global__ void k_witness29<false>(const GNode29* __restrict__ nodes, uint32_t n_nodes, const uint32_t* __restrict__ consts29, uint32_t n_consts, const uint32_t* __restrict__ inputs, uint32_t n_inputs, uint4* __restrict__ V29, uint32_t* __restrict__ err, uint32_t B, uint32_t nb, unsigned long long* __restrict__ prof);
 template __global__ void k_matvec<true>(CsrView A, CsrView Bm, const Fr* __restrict__ V, const uint32_t* __restrict__ sig2node, uint32_t nc, uint32_t ni, uint32_t n, Fr* __restrict__ abc, uint32_t B, uint32_t nb, const uint32_t* __restrict__ long_rows, uint32_t nshort);
 template __global__ void k_matvec<false>(CsrView A, CsrView Bm, const Fr* __restrict__ V, const uint32_t* __restrict__ sig2node, uint32_t nc, uint32_t ni, uint32_t n, Fr* __restrict__ abc, uint32_t B, uint32_t nb, const uint32_t* __restrict__ long_rows, uint32_t nshort);
-template __global__ void k_ntt_pass<1, true>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
-template __global__ void k_ntt_pass<1, false>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
-template __global__ void k_ntt_pass<2, true>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
-template __global__ void k_ntt_pass<2, false>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
-template __global__ void k_ntt_pass<3, true>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
-template __global__ void k_ntt_pass<3, false>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
+template __global__ void k_ntt_pass<NTT_MAX_K, true>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, uint32_t B, uint32_t nb);
+template __global__ void k_ntt_pass<NTT_MAX_K, false>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, uint32_t B, uint32_t nb);
+template __global__ void k_ntt_turn<1>(Fr* __restrict__ data, const Fr* __restrict__ tw_i, const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
+template __global__ void k_ntt_turn<2>(Fr* __restrict__ data, const Fr* __restrict__ tw_i, const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
+template __global__ void k_ntt_turn<3>(Fr* __restrict__ data, const Fr* __restrict__ tw_i, const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
 template __global__ void k_ntt_edge<true>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, uint32_t B, uint32_t nb);
 template __global__ void k_ntt_edge<false>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, uint32_t B, uint32_t nb);
 

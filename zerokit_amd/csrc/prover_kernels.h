@@ -61,19 +61,22 @@ __global__ void __launch_bounds__(256) k_matvec(CsrView A, CsrView Bm, const Fr*
 __global__ void __launch_bounds__(256) k_consts_to29(const Fr* __restrict__ src, uint32_t* __restrict__ dst, uint32_t n);
 template <int K, bool DIF>
 __global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0,
-                                                  const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
+                                                  uint32_t B, uint32_t nb);
+template <int KT>
+__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_turn(Fr* __restrict__ data, const Fr* __restrict__ tw_i,
+                                                  const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale,
+                                                  uint32_t B, uint32_t nb);
 __global__ void __launch_bounds__(256) k_ntt_mid(Fr* __restrict__ data, const Fr* __restrict__ tw_i,
                                                  const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale,
                                                  uint32_t B, uint32_t nb);
 template <bool DIF>
 __global__ void __launch_bounds__(256) k_ntt_edge(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, uint32_t B,
                                                   uint32_t nb);
-__global__ void __launch_bounds__(256) k_hquot(Fr* __restrict__ abc, uint32_t n, uint32_t B, uint32_t nb, uint32_t lg);
 __global__ void __launch_bounds__(256) k_recode(const Fr* __restrict__ V, const uint32_t* __restrict__ sig2node,
                                                 uint32_t ns, const Fr* H, uint32_t n,
                                                 const uint32_t* __restrict__ rs, WinSched ws1, WinSched ws2,
                                                 int16_t* __restrict__ dig1, int16_t* __restrict__ dig2, uint32_t B,
-                                                uint32_t nb, uint32_t part, uint32_t lg, uint32_t dB);
+                                                uint32_t nb, uint32_t part, uint32_t lg, uint32_t hq, uint32_t dB);
 
 // ---- kernels of prover_walks.hip (k_msm29 itself is declared in walk29.h)
 template <class A, class E>

@@ -608,6 +608,54 @@ BatchShape batch_shape(const BatchQuery& q, const ProverTuning& T) {
   return S;
 }
 
+// ------------------------------------------------------------------------------------------------- the transforms of a big batch
+static uint32_t bitrev(uint32_t x, int bits) {
+  uint32_t r = 0;
+  for (int i = 0; i < bits; i++) r |= ((x >> i) & 1u) << (bits - 1 - i);
+  return r;
+}
+
+NttTables ntt_tables(int logn) {
+  if (logn < 1 || logn > 27) throw Error("NTT tables: domain size out of range");
+  const uint32_t n = 1u << logn;
+  Fr g = Fr::from_canonical(FR_ROOT_2_28);
+  for (int i = 0; i < 28 - (logn + 1); i++) g = g.sqr();  // order 2n
+  const Fr w = g.sqr();                                   // order n
+  const Fr wi = w.inv();
+  NttTables T;
+  T.tw_f.resize(n / 2);
+  T.tw_i.resize(n / 2);
+  T.coset.resize(n);
+  Fr a = Fr::one(), b = Fr::one();
+  for (uint32_t k = 0; k < n / 2; k++) {
+    T.tw_f[k] = a;
+    T.tw_i[k] = b;
+    a = a * w;
+    b = b * wi;
+  }
+  if (T.tw_f[0] != Fr::one() || T.tw_i[0] != Fr::one()) throw Error("NTT tables: tw[0] is not one");
+  std::vector<Fr> gp(n);
+  Fr acc = Fr::from_u32(n).inv();
+  for (uint32_t i = 0; i < n; i++) {
+    gp[i] = acc;
+    acc = acc * g;
+  }
+  for (uint32_t pos = 0; pos < n; pos++) T.coset[pos] = gp[bitrev(pos, logn)];
+  return T;
+}
+
+int ntt_turn_width(int logn) { return logn < 1 ? 0 : (logn - 1) % NTT_MAX_K + 1; }
+
+std::vector<NttPass> ntt_pass_list(int logn) {
+  std::vector<NttPass> L;
+  if (logn < 1) return L;
+  const int kt = ntt_turn_width(logn);   // logn - kt is a multiple of NTT_MAX_K
+  for (int s0 = 0; s0 < logn - kt; s0 += NTT_MAX_K) L.push_back({NTT_DIF, (uint8_t)NTT_MAX_K, (uint8_t)s0});
+  L.push_back({NTT_TURN, (uint8_t)kt, (uint8_t)(logn - kt)});
+  for (int s0 = kt; s0 < logn; s0 += NTT_MAX_K) L.push_back({NTT_DIT, (uint8_t)NTT_MAX_K, (uint8_t)s0});
+  return L;
+}
+
 // ------------------------------------------------------------------------------------------------- the streams of a big batch
 const StreamEdge StreamPlan::edges[StreamPlan::NEDGE] = {
     {ROLE_INTERP, ROLE_VALUES}, {ROLE_INTERP, ROLE_QUOTIENT}, {ROLE_QUOTIENT, ROLE_WALK1}, {ROLE_QUOTIENT, ROLE_WALK2},

@@ -160,6 +160,28 @@ struct BatchShape {
 };
 BatchShape batch_shape(const BatchQuery& q, const ProverTuning& T);
 
+// ---- the transforms of the quotient with lanes = proofs (prover_front.hip: k_ntt_pass, k_ntt_turn): iNTT as DIF levels
+// 0 .. logn - 1 (level t pairs points n >> (t + 1) apart), the coset scaling, NTT as DIT levels 0 .. logn - 1 (level t
+// pairs points 1 << t apart).  A launch holds a block of 2^k points per lane, k <= NTT_MAX_K (a 16-point block spills).
+// The lowest kt DIF levels, the scaling and the lowest kt DIT levels close over the same 2^kt contiguous points: one
+// launch, the turn.  kt = ((logn - 1) mod 3) + 1, so that the levels on either side of it split into threes (and a
+// transform of at most three levels is the turn alone): 13 levels are 3, 3, 3, 3 | turn(1) | 3, 3, 3, 3.
+enum NttPassKind : uint8_t { NTT_DIF = 0, NTT_TURN, NTT_DIT };
+struct NttPass {
+  uint8_t kind;   // NttPassKind
+  uint8_t k;      // levels: points per block = 1 << k
+  uint8_t s0;     // first level (NTT_TURN: its first DIF level, logn - k; its DIT levels start at 0)
+};
+// The tables of a 2^logn-point domain: tw_f[k] = w^k and tw_i[k] = w^-k for k < n / 2 (w = W^(2^(28 - logn))), and
+// coset[pos] = g^bitrev(pos) / n, g the root of the doubled domain -- the scaling between the transforms acts on
+// bit-reversed order.  Throws unless tw_f[0] and tw_i[0] are the Montgomery one: the kernels leave those products out.
+struct NttTables {
+  std::vector<Fr> tw_f, tw_i, coset;
+};
+NttTables ntt_tables(int logn);
+int ntt_turn_width(int logn);                  // kt; 0 for logn < 1
+std::vector<NttPass> ntt_pass_list(int logn);  // in launch order; empty for logn < 1
+
 // ---- which stream every role of a BIG batch (!BatchShape::small) takes: Prover::enqueue, wipe_slot.  ROCclr maps streams
 // onto GPU_MAX_HW_QUEUES hardware queues; streams that share a queue run their kernels in submission order, and a wait at
 // the head of one holds up what the other submitted behind it.  So a big batch keeps no more streams busy than the process
