@@ -113,6 +113,20 @@ CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t*
 CBoolResult_t ffi_finish_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNPartialProof_t* const* partials,
                                           FFI_RLNWitnessInput_t* const* witnesses, size_t n, const CFr_t* rs,
                                           FFI_RLNProof_t** out);
+/* EXT: n proofs for members of the object's own tree, named by leaf index (single message-id circuits only; a
+ * multi-message-id object returns an error naming this function).  What ffi_get_merkle_proof + the witness constructor +
+ * ffi_generate_rln_proofs_batch do with n path round trips through the caller, without them: the members' paths are read
+ * from the tree on the device, straight into the batch's inputs, at the root the tree has when the call is made (all n
+ * proofs at that one root; the object's tree is locked for the call).  Every CFr array holds n contiguous elements; rs:
+ * NULL (random blinding) or 2n CFr (r_0, s_0, r_1, ...); out: n proof pointers filled on success.  The range checks and
+ * error texts are the witness constructor's (a zero limit, a message_id that is not below the limit); a leaf index
+ * >= 2^depth and a tree whose depth is not the circuit's are errors before anything runs.  n above max_batch is streamed
+ * in chunks through the object's own prover (replica 0 of a "devices" pool) -- it is NOT dealt to the pool, because the
+ * other replicas do not hold the tree.  n = 0 succeeds. */
+CBoolResult_t ffi_generate_rln_proofs_for_members(FFI_RLN_t* const* rln, const size_t* leaf_indices, size_t n,
+                                                  const CFr_t* identity_secrets, const CFr_t* user_message_limits,
+                                                  const CFr_t* message_ids, const CFr_t* xs,
+                                                  const CFr_t* external_nullifiers, const CFr_t* rs, FFI_RLNProof_t** out);
 
 FFI_RLNProofValues_t* ffi_rln_proof_get_values(FFI_RLNProof_t* const* proof);                 /* ffi_rln.rs:158 */
 uint8_t ffi_rln_proof_get_version_byte(FFI_RLNProof_t* const* proof);                         /* ffi_rln.rs:165 */

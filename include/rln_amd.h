@@ -58,6 +58,10 @@ int rlnamd_tree_get_leaf(rlnamd_tree* t, size_t index, uint8_t out_le[32]);     
 int rlnamd_tree_proof(rlnamd_tree* t, size_t index, uint8_t* elems_le, uint8_t* bits);
 /* `count` proofs for leaves [first, first+count) copied back to host buffers */
 int rlnamd_tree_proofs(rlnamd_tree* t, size_t first, size_t count, uint8_t* elems_le, uint8_t* bits);
+/* the batch form of rlnamd_tree_proof for k leaves in any order (repeats allowed): one launch and one wait for all of
+ * them; elems_le = k*depth*32 bytes, bits = k*depth bytes, proof i at index i.  An index >= 2^depth fails the call before
+ * anything is enqueued; k = 0 succeeds and writes nothing. */
+int rlnamd_tree_proofs_at(rlnamd_tree* t, const uint64_t* indices, size_t k, uint8_t* elems_le, uint8_t* bits);
 /* Device-resident workload of BASELINE config 3: leaves first_value + i generated in HBM, full rebuild,
  * all `count` proofs emitted into an internal HBM buffer and (if verify != 0) every proof recomputed to
  * the root on the device.  ms[0] = build, ms[1] = proof emission (HIP events); bad = failed proofs. */
@@ -161,6 +165,26 @@ int rlnamd_prover_describe(rlnamd_prover* p, char* buf, size_t cap);
 int rlnamd_prover_init_ms(rlnamd_prover* p, float ms[4]);
 int rlnamd_prover_prove_stream(rlnamd_prover* p, size_t n, const uint8_t* inputs_le, const uint8_t* rs_le,
                                uint8_t* proofs, uint8_t* values, uint32_t* errors);
+/* ---- prove for members of a tree by leaf index.  rlnamd_prover_submit_members is rlnamd_prover_submit for n members of
+ * `t`: inputs_le is what submit takes, but its pathElements / identityPathIndex slots are ignored -- the members' paths at
+ * the tree's current root are read from the tree's nodes on the device, straight into the batch's staged inputs (the path
+ * index as the field element 0 / 1).  Nothing waits on the host: the gather is ordered behind everything already enqueued
+ * on the tree (every rlnamd_tree_set_* that has returned) and a later write to the tree is ordered behind the gather, so
+ * all n proofs are at ONE root, the one the tree had when the call was made.  mode: RLNAMD_MODE_FULL or
+ * RLNAMD_MODE_PARTIAL (a partial proof's inputs are secret, limit and path); RLNAMD_MODE_FINISH is an error.  The ticket
+ * is collected, read (collect_public, collect_partial_cached) and wiped as any other; the leaf indices -- who proves is a
+ * secret as the inputs are -- are staged in pinned memory, copied to the device and overwritten with the inputs (entry
+ * [5] of rlnamd_prover_residue counts them).  A lone batch of at most RLNAMD_HINTS proofs, whose hints are hashed from the
+ * path on the host, fetches its paths with one rlnamd_tree_proofs_at-like call instead and then takes submit's way; the
+ * bytes are the same.  Errors, each before anything is enqueued: the witness graph names no pathElements /
+ * identityPathIndex, the tree's depth is not the circuit's, tree and prover are on different devices, an index >= 2^depth.
+ * rlnamd_prover_prove_stream_members: the chunked form over `capacity` (full proofs), the tree locked for the whole
+ * call: all n proofs at one root. */
+int rlnamd_prover_submit_members(rlnamd_prover* p, rlnamd_tree* t, size_t n, const uint64_t* leaf_indices,
+                                 const uint8_t* inputs_le, const uint8_t* rs_le, int mode, uint64_t* ticket);
+int rlnamd_prover_prove_stream_members(rlnamd_prover* p, rlnamd_tree* t, size_t n, const uint64_t* leaf_indices,
+                                       const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* proofs,
+                                       uint8_t* values, uint32_t* errors);
 int rlnamd_prover_stage_ms(rlnamd_prover* p, float ms[RLNAMD_PROVER_STAGES]);
 const char* rlnamd_prover_stage_name(int i);
 /* mean shader clock (MHz) under the G1 / G2 table walks since the previous call (the walks are VALU-issue bound: their
@@ -172,7 +196,8 @@ int rlnamd_prover_fetch_h(rlnamd_prover* p, size_t index, uint8_t* out_le);
 /* tap of the wipes: the number of 16-byte words that are not zero in the buffers of the slot the last batch used, whole
  * buffers: [0] G1 window digits, [1] G2 window digits, [2] a | b | c (the quotient's operands, then h), [3] / [4] partial
  * sums of the G1 / G2 walks and everything their reduction leaves behind (block sums, the unblinded A / B / C sums, the
- * affine points, the ladder's products and tables), [5] staged inputs + (r, s).  All zero behind a collect that wipes. */
+ * affine points, the ladder's products and tables), [5] staged inputs + (r, s) + the leaf indices of a batch submitted
+ * by member (device and pinned copy).  All zero behind a collect that wipes. */
 int rlnamd_prover_residue(rlnamd_prover* p, uint64_t out[6]);
 /* ---- partial proofs (generate_partial_zk_proof / finish_zk_proof_with_rs, protocol/proof.rs:783-849;
  * Groth16Partial, partial_proof.rs:108-274).  mode: 0 full proof, 1 partial (inputs hold only identitySecret,

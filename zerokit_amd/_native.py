@@ -98,6 +98,11 @@ SIGNATURES = {
     "rlnamd_tree_get_leaf": (C.c_int, [P, C.c_size_t, C.c_char_p]),
     "rlnamd_tree_proof": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p]),
     "rlnamd_tree_proofs": (C.c_int, [P, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p]),
+    "rlnamd_tree_proofs_at": (C.c_int, [P, C.POINTER(C.c_uint64), C.c_size_t, C.c_char_p, C.c_char_p]),
+    "rlnamd_prover_submit_members": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p, C.c_int,
+                                               C.POINTER(C.c_uint64)]),
+    "rlnamd_prover_prove_stream_members": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
+                                                     C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
     "rlnamd_tree_fill_sequential": (C.c_int, [P, C.c_size_t, C.c_size_t, C.c_uint64]),
     "rlnamd_tree_bench": (C.c_int, [P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_size_t)]),
     "rlnamd_prover_new": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, PP]),
@@ -213,6 +218,8 @@ SIGNATURES = {
     "ffi_generate_rln_proof_with_rs": (CResultPtr, [PP, PP, CFRP, CFRP]),
     "ffi_generate_rln_proofs_batch": (CBoolResult, [PP, PP, C.c_size_t, CFRP, PP]),
     "ffi_finish_rln_proofs_batch": (CBoolResult, [PP, PP, PP, C.c_size_t, CFRP, PP]),
+    "ffi_generate_rln_proofs_for_members": (CBoolResult, [PP, C.POINTER(C.c_size_t), C.c_size_t, CFRP, CFRP, CFRP, CFRP,
+                                                          CFRP, CFRP, PP]),
     "ffi_verify_rln_proof": (CBoolResult, [PP, PP, CFRP]),
     "ffi_verify_rln_proofs_batch": (CBoolResult, [PP, PP, C.c_size_t, CFRP, C.POINTER(VecCFr), C.POINTER(C.c_bool)]),
     "ffi_verify_with_roots": (CBoolResult, [PP, PP, C.POINTER(VecCFr), CFRP]),

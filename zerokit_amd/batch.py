@@ -187,6 +187,40 @@ class BatchProver:
         check(lib().rlnamd_prover_submit(self._h, n, inputs, rsb, mode, pp, C.byref(t)))
         return int(t.value), n
 
+    def submit_members(self, tree: "PoseidonTree", leaf_indices, inputs: bytes, rsb: bytes, mode=0):
+        """submit() for members of `tree` named by leaf index: the pathElements / identityPathIndex slots of `inputs` are
+        ignored, the paths are read from the tree on the device at its current root (rlnamd_prover_submit_members).
+        mode 0 (full) or 1 (partial); returns (ticket, n)."""
+        n = len(inputs) // (self.inputs_size * 32)
+        if len(inputs) != n * self.inputs_size * 32 or len(rsb) != 64 * n or len(leaf_indices) != n:
+            raise RLNError("submit_members: leaf indices / inputs / rs sizes do not match")
+        idx = (C.c_uint64 * max(n, 1))(*[int(i) for i in leaf_indices])
+        t = C.c_uint64()
+        check(lib().rlnamd_prover_submit_members(self._h, tree._h, n, idx, inputs, rsb, mode, C.byref(t)))
+        return int(t.value), n
+
+    def prove_members_raw(self, tree: "PoseidonTree", leaf_indices, inputs: bytes, rsb: bytes):
+        """any n members through rlnamd_prover_prove_stream_members: chunks of `capacity`, all of them at one root"""
+        n = len(inputs) // (self.inputs_size * 32)
+        if len(inputs) != n * self.inputs_size * 32 or len(rsb) != 64 * n or len(leaf_indices) != n:
+            raise RLNError("prove_members: leaf indices / inputs / rs sizes do not match")
+        idx = (C.c_uint64 * max(n, 1))(*[int(i) for i in leaf_indices])
+        proofs = C.create_string_buffer(128 * n)
+        values = C.create_string_buffer(160 * n)
+        errs = (C.c_uint32 * max(n, 1))()
+        check(lib().rlnamd_prover_prove_stream_members(self._h, tree._h, n, idx, inputs, rsb, proofs, values, errs))
+        return proofs.raw, values.raw, list(errs)[:n]
+
+    def pack_member_inputs(self, witnesses):
+        """pack_inputs for witnesses without a path (submit_members fills it in): the two path inputs stay zero"""
+        d = int(self.info.tree_depth)
+        return self.pack_inputs([dict(w, path_elements=[0] * d, identity_path_index=[0] * d) for w in witnesses])
+
+    def prove_members(self, tree: "PoseidonTree", leaf_indices, witnesses, rs):
+        """witnesses: pack_inputs' dicts without path_elements / identity_path_index, one per leaf index"""
+        return _unpack_results(*self.prove_members_raw(tree, leaf_indices, self.pack_member_inputs(witnesses),
+                                                       self.pack_rs(rs)))
+
     def hints_for(self, inputs: bytes):
         """the hints of the proofs packed in `inputs`, one proof at a time on this thread (rlnamd_prover_hints_for): a list
         of ctypes arrays, or None when the circuit has no segments form"""
@@ -620,6 +654,24 @@ class PoseidonTree:
             o = p * self.depth
             out.append(([int.from_bytes(e.raw[32 * (o + i):32 * (o + i + 1)], "little") for i in range(self.depth)],
                         list(b.raw[o:o + self.depth])))
+        return out
+
+    def proofs_at_raw(self, indices):
+        """the paths of the listed leaves (any order, repeats allowed) in one call -> (elems k*depth*32 bytes, bits k*depth)"""
+        k = len(indices)
+        idx = (C.c_uint64 * max(k, 1))(*[int(i) for i in indices])
+        e = C.create_string_buffer(max(32 * self.depth * k, 1))
+        b = C.create_string_buffer(max(self.depth * k, 1))
+        check(lib().rlnamd_tree_proofs_at(self._h, idx, k, e, b))
+        return e.raw[:32 * self.depth * k], b.raw[:self.depth * k]
+
+    def proofs_at(self, indices):
+        e, b = self.proofs_at_raw(indices)
+        out = []
+        for p in range(len(indices)):
+            o = p * self.depth
+            out.append(([int.from_bytes(e[32 * (o + i):32 * (o + i + 1)], "little") for i in range(self.depth)],
+                        list(b[o:o + self.depth])))
         return out
 
     def fill_sequential(self, start, n, first_value):

@@ -189,6 +189,14 @@ int rlnamd_tree_proofs(rlnamd_tree* t, size_t first, size_t count, uint8_t* elem
   RLN_HIP(hipStreamSynchronize(t->t.stream));
   RLN_CATCH
 }
+int rlnamd_tree_proofs_at(rlnamd_tree* t, const uint64_t* indices, size_t k, uint8_t* elems_le, uint8_t* bits) {
+  RLN_TRY
+  std::lock_guard<std::mutex> tree_lk(t->mu);
+  if (k == 0) return RLNAMD_OK;
+  if (!indices || !elems_le || !bits) throw Error("rlnamd_tree_proofs_at: null pointer");
+  t->t.proofs_at_host(indices, k, elems_le, bits);
+  RLN_CATCH
+}
 int rlnamd_tree_fill_sequential(rlnamd_tree* t, size_t start, size_t n, uint64_t first_value) {
   RLN_TRY
   std::lock_guard<std::mutex> tree_lk(t->mu);
@@ -364,6 +372,30 @@ int rlnamd_prover_prove_stream(rlnamd_prover* p, size_t n, const uint8_t* inputs
                                uint8_t* proofs, uint8_t* values, uint32_t* errors) {
   RLN_TRY
   p->p->prove_stream(n, inputs_le, rs_le, proofs, values, errors);
+  RLN_CATCH
+}
+// (the tree's lock is held from the gather's first event to its last: see Prover::submit_members)
+static MemberTree member_tree(rlnamd_tree* t) {
+  MemberTree mt;
+  mt.dense = &t->t;
+  mt.depth = t->t.depth;
+  return mt;
+}
+int rlnamd_prover_submit_members(rlnamd_prover* p, rlnamd_tree* t, size_t n, const uint64_t* leaf_indices,
+                                 const uint8_t* inputs_le, const uint8_t* rs_le, int mode, uint64_t* ticket) {
+  RLN_TRY
+  if (!p || !t || !ticket) throw Error("rlnamd_prover_submit_members: null pointer");
+  std::lock_guard<std::mutex> tree_lk(t->mu);
+  *ticket = p->p->submit_members(member_tree(t), n, leaf_indices, inputs_le, rs_le, mode);
+  RLN_CATCH
+}
+int rlnamd_prover_prove_stream_members(rlnamd_prover* p, rlnamd_tree* t, size_t n, const uint64_t* leaf_indices,
+                                       const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* proofs, uint8_t* values,
+                                       uint32_t* errors) {
+  RLN_TRY
+  if (!p || !t) throw Error("rlnamd_prover_prove_stream_members: null pointer");
+  std::lock_guard<std::mutex> tree_lk(t->mu);
+  p->p->prove_stream_members(member_tree(t), n, leaf_indices, inputs_le, rs_le, proofs, values, errors);
   RLN_CATCH
 }
 int rlnamd_prover_run_mode(rlnamd_prover* p, size_t n, int mode) {

@@ -1494,6 +1494,82 @@ CBoolResult_t ffi_generate_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNWitnes
     return true;
   });
 }
+// EXT: n proofs for members of the object's OWN tree, named by leaf index -- no Merkle path crosses the boundary.  The paths
+// are read from the tree on the device into the batch's staged inputs (Prover::submit_members); replica 0 proves, with
+// the tree locked for the whole call, so all n proofs are at one root.
+CBoolResult_t ffi_generate_rln_proofs_for_members(FFI_RLN_t* const* rln, const size_t* leaf_indices, size_t n,
+                                                  const CFr_t* identity_secrets, const CFr_t* user_message_limits,
+                                                  const CFr_t* message_ids, const CFr_t* xs,
+                                                  const CFr_t* external_nullifiers, const CFr_t* rs, FFI_RLNProof_t** out) {
+  return guard_bool([&]() {
+    if (n == 0) return true;
+    if (!rln || !*rln) throw Error("ffi_generate_rln_proofs_for_members: null RLN object");
+    if (!leaf_indices || !identity_secrets || !user_message_limits || !message_ids || !xs || !external_nullifiers || !out)
+      throw Error("ffi_generate_rln_proofs_for_members: null argument");
+    FFI_RLN& r = *(FFI_RLN*)*rln;
+    if (r.stateless) throw Error("ffi_generate_rln_proofs_for_members: the object has no tree");
+    std::lock_guard<std::mutex> guard(*r.prove_mu);
+    Prover& P = *r.prover;
+    if (P.graph().max_out != 1 || P.graph().input_mapping.count("selectorUsed"))
+      throw Error("ffi_generate_rln_proofs_for_members: single message-id circuits only");
+    if (r.auto_partial) r.memo_adopt_pending();
+    const size_t cap = P.capacity(), ni = P.inputs_per_proof(), d = P.graph().tree_depth;
+    std::vector<uint8_t> inputs(n * ni * 32), rsb(n * 64), idx8(n * 8);
+    ZeroOnExit z1{inputs}, z2{rsb}, z3{idx8};   // (who proves is a secret as well)
+    uint64_t* idx = reinterpret_cast<uint64_t*>(idx8.data());
+    {
+      FFI_RLNWitnessInput w;   // the witness constructor's checks and texts (validate_witness), the path left to the device
+      w.path_elements.assign(d, cfr_from_u64(0));
+      w.identity_path_index.assign(d, 0);
+      for (size_t i = 0; i < n; i++) {
+        w.identity_secret = R(&identity_secrets[i]);
+        w.user_message_limit = R(&user_message_limits[i]);
+        w.message_id = R(&message_ids[i]);
+        w.x = R(&xs[i]);
+        w.external_nullifier = R(&external_nullifiers[i]);
+        validate_witness(w);
+        fill_inputs(P, w, inputs.data() + i * ni * 32);
+        const CFr rr = rs ? R(&rs[2 * i]) : random_fr(), ss = rs ? R(&rs[2 * i + 1]) : random_fr();
+        memcpy(rsb.data() + i * 64, rr.le, 32);
+        memcpy(rsb.data() + i * 64 + 32, ss.le, 32);
+        idx[i] = leaf_indices[i];
+      }
+    }
+    std::vector<uint8_t> proofs(n * 128), values(n * 160);
+    std::vector<uint32_t> errs(n);
+    {
+      // the tree's lock, from the flush of its pending writes to the event that orders later writes behind the gather
+      std::lock_guard<std::mutex> tree_lk(r.tree.pend->mu);
+      r.tree.flush_pending_locked();
+      MemberTree mt;
+      mt.dense = r.tree.sparse ? nullptr : &r.tree.dense;
+      mt.depth = r.tree.depth;
+      mt.proofs_at = [&](const uint64_t* ix, size_t k, uint8_t* e, uint8_t* b) { r.tree.proofs_at_locked(ix, k, e, b); };
+      if (n <= cap) {
+        const uint64_t ticket = P.submit_members(mt, n, idx, inputs.data(), rsb.data(), PROVE_FULL);
+        P.collect(ticket, n, proofs.data(), values.data(), errs.data());
+      } else {   // streamed on this prover: the replicas of a pool hold no tree
+        P.prove_stream_members(mt, n, idx, inputs.data(), rsb.data(), proofs.data(), values.data(), errs.data());
+      }
+    }
+    for (size_t i = 0; i < n; i++)
+      if (errs[i]) throw Error("Error calculating witness: graph evaluation failed (code " + std::to_string(errs[i]) + ")");
+    std::vector<std::unique_ptr<FFI_RLNProof>> made;
+    for (size_t i = 0; i < n; i++) {
+      std::unique_ptr<FFI_RLNProof> pr(new FFI_RLNProof);
+      memcpy(pr->proof, proofs.data() + 128 * i, 128);
+      const uint8_t* v = values.data() + 160 * i;
+      memcpy(pr->values.y.le, v, 32);
+      memcpy(pr->values.root.le, v + 32, 32);
+      memcpy(pr->values.nullifier.le, v + 64, 32);
+      memcpy(pr->values.x.le, v + 96, 32);
+      memcpy(pr->values.external_nullifier.le, v + 128, 32);
+      made.push_back(std::move(pr));
+    }
+    for (size_t i = 0; i < n; i++) out[i] = (FFI_RLNProof_t*)made[i].release();
+    return true;
+  });
+}
 CBoolResult_t ffi_verify_rln_proof(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proof, const CFr_t* x) {
   return guard_bool([&]() {  // public.rs:725-745: proof -> root -> signal, first failure is an error
     FFI_RLN& r = *(FFI_RLN*)*rln;

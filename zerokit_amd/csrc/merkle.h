@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "field.h"
+#include "merkle_paths.h"
 
 namespace rlnamd {
 
@@ -25,6 +26,7 @@ struct MerkleTreeDev {
   bool root_known = false;      // root_host is the root of what the stream will have written (set_few)
   Fr root_host;
   DevBuf<uint8_t> proof_dev;    // proof_host's device scratch (depth * 33 bytes), allocated once
+  int device = 0;               // the HIP device init() ran on: where `nodes` lives
   void reserve_staging(size_t words);
 
   MerkleTreeDev() = default;
@@ -69,6 +71,13 @@ struct MerkleTreeDev {
   // `count` proofs for leaves [first, first+count) written to device buffers
   // d_elems: [count][depth][32] canonical LE, d_bits: [count][depth]
   void proofs_device(size_t first, size_t count, uint8_t* d_elems, uint8_t* d_bits);
+  // proofs of the k leaves listed at d_idx (device memory; any order, repeats allowed, every index below capacity()),
+  // written where `dest` says (merkle_paths.h: packed, or into a prover's staged inputs), by one launch on stream `on`.
+  // Only enqueues; ordering against the tree's own stream is the caller's business.
+  void proofs_at_device(const uint64_t* d_idx, size_t k, const PathDest& dest, hipStream_t on);
+  // the batch form of proof_host: one launch and one copy for all k; an index >= capacity() throws before anything is
+  // enqueued.  elems: [k][depth][32], bits: [k][depth]
+  void proofs_at_host(const uint64_t* idx, size_t k, uint8_t* elems_le, uint8_t* bits);
   // recompute the root from each emitted proof + its leaf on the device (compute_root_from :441-446);
   // returns the number of proofs whose root differs from the tree root.
   size_t verify_proofs_device(size_t first, size_t count, const uint8_t* d_elems, const uint8_t* d_bits);

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "poseidon.h"
@@ -161,6 +162,33 @@ __global__ void __launch_bounds__(256) k_proofs(const Fr* __restrict__ nodes, in
   bits[t] = right ? 1 : 0;
 }
 
+// The same for k leaves named by a device list (any order, repeats allowed): one lane per (proof, level); the sibling is
+// read from `nodes`, brought to canonical form and leaves as two 16-byte stores.  Where it lands is the caller's layout
+// (merkle_paths.h: PathDest): a packed proof buffer, or the staged inputs of a prover batch, where the path bit is the
+// field element 0 / 1.  The host has checked every index against 2^depth (proofs_at_device's caller).
+__global__ void __launch_bounds__(256) k_proofs_at(const Fr* __restrict__ nodes, uint32_t depth, const uint64_t* __restrict__ idx,
+                                                   uint32_t k, PathDest d) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= k * depth) return;
+  const uint32_t pi = t / depth, lvl = t - pi * depth;
+  const uint64_t leaf = idx[pi];
+  if (leaf >> depth) return;   // (never taken: a stale or foreign index list must not read outside the tree)
+  const PathStep s = merkle_path_step(depth, leaf, lvl);
+  uint32_t c[8];
+  nodes[s.sibling].to_canonical(c);
+  uint4* o = reinterpret_cast<uint4*>(d.elem_base + path_elem_offset(d, pi, lvl));
+  o[0] = make_uint4(c[0], c[1], c[2], c[3]);
+  o[1] = make_uint4(c[4], c[5], c[6], c[7]);
+  uint8_t* b = d.bit_base + path_bit_offset(d, pi, lvl);
+  if (d.bit_as_field) {
+    uint4* bo = reinterpret_cast<uint4*>(b);
+    bo[0] = make_uint4(s.bit, 0, 0, 0);
+    bo[1] = make_uint4(0, 0, 0, 0);
+  } else {
+    *b = (uint8_t)s.bit;
+  }
+}
+
 constexpr uint32_t PROOFS_PER_BLOCK = 64;
 // Bulk emission.  A gather -> store loop (round 2: canonical copies of all nodes, then one gather per 16 bytes) makes every
 // 16-byte store wait for an L2 round trip, and with 32 waves per CU that caps the chip near 4 TB/s (0.19 ms for 692 MB; a
@@ -271,6 +299,7 @@ void MerkleTreeDev::init(int depth_, const uint8_t default_leaf_le[32]) {
   if (depth_ < 0 || depth_ > 30) throw Error("InvalidDepth: tree depth must be in [0, 30] for the HBM-resident tree");
   depth = depth_;
   root_known = false;
+  RLN_HIP(hipGetDevice(&device));
   nodes.alloc(num_nodes());
   PoseidonView pv = poseidon_view(3);
   DevBuf<Fr> zh(depth + 1);
@@ -501,6 +530,7 @@ MerkleTreeDev& MerkleTreeDev::operator=(MerkleTreeDev&& o) noexcept {
     root_known = o.root_known;
     root_host = o.root_host;
     proof_dev = std::move(o.proof_dev);
+    device = o.device;
     o.root_known = false;
     o.scat_host = nullptr;
     o.scat_cap = 0;
@@ -560,6 +590,34 @@ void MerkleTreeDev::proofs_device(size_t first, size_t count, uint8_t* d_elems, 
                        (uint32_t*)d_elems, d_bits);
   }
   RLN_HIP(hipGetLastError());
+}
+
+void MerkleTreeDev::proofs_at_device(const uint64_t* d_idx, size_t k, const PathDest& dest, hipStream_t on) {
+  if (k == 0 || depth == 0) return;
+  if (k * (size_t)depth > 0xFFFFFFFFull) throw Error("proofs_at_device: too many paths for one launch");
+  if (((uintptr_t)dest.elem_base | dest.proof_stride | dest.elem_stride) & 15)
+    throw Error("proofs_at_device: path elements must land 16-byte aligned");
+  if (dest.bit_as_field && (((uintptr_t)dest.bit_base | dest.bit_proof_stride | dest.bit_stride) & 15))
+    throw Error("proofs_at_device: path bits written as field elements must land 16-byte aligned");
+  const uint32_t total = (uint32_t)(k * (size_t)depth);
+  hipLaunchKernelGGL(k_proofs_at, dim3(div_up(total, 256)), dim3(256), 0, on, nodes.p, (uint32_t)depth, d_idx, (uint32_t)k, dest);
+  RLN_HIP(hipGetLastError());
+}
+
+void MerkleTreeDev::proofs_at_host(const uint64_t* idx, size_t k, uint8_t* elems_le, uint8_t* bits) {
+  for (size_t i = 0; i < k; i++)
+    if (idx[i] >= capacity()) throw Error("InvalidLeaf: leaf index " + std::to_string(idx[i]) + " is outside a tree of depth " + std::to_string(depth));
+  if (k == 0 || depth == 0) return;
+  // proof_host's device scratch, grown when a call needs more: [k][depth][32] elements | [k][depth] bits | [k] indices
+  const size_t d = (size_t)depth, eb = k * d * 32, bb = (k * d + 15) / 16 * 16;
+  if (proof_dev.n < eb + bb + k * 8) proof_dev.alloc(eb + bb + k * 8);
+  uint8_t* tmp = proof_dev.p;
+  RLN_HIP(hipMemcpyAsync(tmp + eb + bb, idx, k * 8, hipMemcpyHostToDevice, stream));
+  const PathDest dest{tmp, tmp + eb, d * 32, 32, d, 1, 0};
+  proofs_at_device((const uint64_t*)(tmp + eb + bb), k, dest, stream);
+  RLN_HIP(hipMemcpyAsync(elems_le, tmp, eb, hipMemcpyDeviceToHost, stream));
+  RLN_HIP(hipMemcpyAsync(bits, tmp + eb, k * d, hipMemcpyDeviceToHost, stream));
+  RLN_HIP(hipStreamSynchronize(stream));
 }
 
 void MerkleTreeDev::proof_host(size_t leaf, uint8_t* elems_le, uint8_t* bits) {

@@ -96,6 +96,19 @@ struct ProofOut {            // one proof, host side
 };
 
 class GpuVerifier;
+struct MerkleTreeDev;
+
+// The tree of a batch submitted by member, as the prover sees it.  The caller holds the tree's lock for the call.
+struct MemberTree {
+  MerkleTreeDev* dense = nullptr;   // the HBM-resident tree, every pending write flushed; null: a sparse tree (host route at any n)
+  int depth = 0;
+  // the paths of k leaves on the host ([k][depth][32] + [k][depth]); null: dense->proofs_at_host
+  std::function<void(const uint64_t* idx, size_t k, uint8_t* elems_le, uint8_t* bits)> proofs_at;
+};
+struct MemberGather {   // enqueue's view of a device-route members batch
+  MerkleTreeDev* tree;
+  const uint64_t* leaf;
+};
 
 class Prover {
  public:
@@ -145,6 +158,19 @@ class Prover {
   // submits later.  This is the path of SURVEY 8(d)'s timed region: H2D of witness inputs -> D2H of proofs.
   uint64_t submit(size_t n, const uint8_t* inputs, const uint8_t* rs, int mode = PROVE_FULL,
                   const uint8_t* partial320 = nullptr);
+  // submit() for members of a tree named by leaf index: the pathElements / identityPathIndex slots of `inputs` are ignored
+  // and overwritten with the members' paths at the tree's current root -- on the device, read from the tree's nodes into
+  // the slot's staged inputs, ordered against the tree's stream by events (no host wait): a write enqueued on the tree
+  // before the call is seen by the whole batch, one made after it returns by none of it.  mode: PROVE_FULL or
+  // PROVE_PARTIAL.  Lone batches of at most hint_max proofs and batches against a sparse tree fetch the paths to the host
+  // instead (one call) and go through submit(); the bytes are the same.  Refused before anything is enqueued, each with
+  // its own text: a graph without the two path inputs, a tree of another depth or on another device, an index >= 2^depth.
+  // The ticket is collected like any other.  prove_stream_members: the chunked form (prove_stream); the caller keeps the
+  // tree's lock for the whole call, so all n proofs are at one root.
+  uint64_t submit_members(const MemberTree& tree, size_t n, const uint64_t* leaf_indices, const uint8_t* inputs,
+                          const uint8_t* rs, int mode = PROVE_FULL);
+  void prove_stream_members(const MemberTree& tree, size_t n, const uint64_t* leaf_indices, const uint8_t* inputs,
+                            const uint8_t* rs, uint8_t* proofs, uint8_t* values, uint32_t* errors);
   // The hints of a lone small batch (the values between the circuit's chained hashes: prover_plan.h, HintChains) may be
   // computed ahead of the call, by any thread, one proof at a time: hint_words() 32-bit words per proof (0: this circuit
   // has no such form), hints_for() fills them from one proof's packed inputs.  submit_hinted() is submit() for a full
@@ -170,7 +196,8 @@ class Prover {
   // shared with the other replicas gives it (rlnamd_pool, dynamic assignment).  max_in_flight 0 = every workspace slot.
   typedef std::function<bool(size_t* off, size_t* cnt)> ChunkSource;
   void prove_stream_from(const ChunkSource& next, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs, uint8_t* values,
-                         uint32_t* errors, int max_in_flight = 0);
+                         uint32_t* errors, int max_in_flight = 0, const MemberTree* tree = nullptr,
+                         const uint64_t* leaf_indices = nullptr);
   void prove_stream(size_t n, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs, uint8_t* values,
                     uint32_t* errors);
   // Partial proofs.  PROVE_PARTIAL: inputs carry only the partial witness (unknown slots zero); the result is
@@ -226,7 +253,8 @@ class Prover {
   void fetch_witness(size_t p, std::vector<uint8_t>* w_le);
   void fetch_h(size_t p, std::vector<uint8_t>* h_le);
   // tap of the wipes: 16-byte words of the last batch's slot that are not zero, whole buffers --
-  // [G1 digits, G2 digits, a|b|c (h), G1 partial sums, G2 partial sums, staged inputs + (r, s)]
+  // [G1 digits, G2 digits, a|b|c (h), G1 partial sums, G2 partial sums, staged inputs + (r, s) + the leaf indices of a
+  // batch submitted by member (device and pinned copy)]
   static constexpr int RESIDUE_FIELDS = 6;
   void residue(uint64_t out[RESIDUE_FIELDS]);
   // the device Groth16 verifier of this prover's key (verify.h), made on first use; independent of the proving pipeline
@@ -235,7 +263,9 @@ class Prover {
  private:
   uint64_t settle_hints(uint64_t ticket);
   uint64_t enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint8_t* h_rs, const uint8_t* h_pp320,
-                   const uint64_t* cone_handles = nullptr, const uint32_t* pre_hints = nullptr);
+                   const uint64_t* cone_handles = nullptr, const uint32_t* pre_hints = nullptr,
+                   const MemberGather* members = nullptr);
+  void check_members(const MemberTree& tree, size_t n, const uint64_t* leaf_indices) const;
   void fetch_public_slot(void* slot, size_t n, std::vector<uint8_t>* out_le);
   struct Impl;
   std::unique_ptr<Impl> d_;

@@ -29,6 +29,7 @@
 #include "witness_lanes.h"
 #include "witness_sched.h"
 #include "fin29.h"
+#include "merkle.h"
 
 namespace rlnamd {
 
@@ -80,6 +81,12 @@ struct Slot {
   size_t n = 0;
   // what the batch's walks used (wipe_slot): proof stride of the digit rows, stride and row counts of the partial sums
   uint32_t dB = 0, PB = 0, nch1 = 0, nch2 = 0;
+  // a batch submitted by member (Prover::submit_members): the leaf indices, pinned and on the device -- who proves is a
+  // secret as the inputs are -- and the event behind the gather that fills the path slots of `inputs`
+  DevBuf<uint64_t> idx;
+  uint64_t* h_idx = nullptr;
+  hipEvent_t evT = nullptr, evG = nullptr;   // the tree's stream up to the gather; the gather done
+  bool members = false;
   uint32_t seq = 0;             // the batch's sequence number (Impl::seq) and whether it took the big-batch streams
   bool big = false;             // (prover_plan.h: stream_plan): which stream its wipe goes to
 };
@@ -287,6 +294,8 @@ struct Prover::Impl {
   DevBuf<uint32_t> wgiven;     // externally calculated witnesses for the next run (upload_witness), else empty
   size_t wgiven_n = 0;
   InputSlots slots{};
+  bool have_path_slots = false;           // the graph names pathElements and identityPathIndex (submit_members)
+  uint32_t path_off = 0, path_idx_off = 0;
   bool have_values_kernel = false;
   // resident inputs (shared by both slots; upload() drains the pipeline first)
   DevBuf<uint32_t> inputs, rs;
@@ -343,6 +352,12 @@ struct Prover::Impl {
       __asm__ __volatile__("" : : "r"(S.h_in) : "memory");
       zero(S.inputs.p, n * (size_t)NI * 32);
       zero(S.rs.p, n * 64);
+      if (S.members) {   // the leaf indices of a batch submitted by member
+        memset(S.h_idx, 0, B * 8);
+        __asm__ __volatile__("" : : "r"(S.h_idx) : "memory");
+        zero(S.idx.p, S.idx.bytes());
+        S.members = false;
+      }
     }
     const uint32_t pg = div_up(n, 64);
     hipLaunchKernelGGL(k_wipe_cols, dim3(pg, nstore29), dim3(64), 0, sW, S.V.p, slot2node.p, nstore29, (uint32_t)B, (uint32_t)n);
@@ -380,6 +395,32 @@ struct Prover::Impl {
     RLN_HIP(hipGetLastError());
     RLN_HIP(hipEventRecord(S.evZ, sW));
     S.wiped = true;
+  }
+
+  // what batch_shape asks about a batch of n proofs in `mode` (the caller adds what it brings: points, handles, hints)
+  BatchQuery query(size_t n, int mode, bool streamed) {
+    BatchQuery q;
+    q.n = n;
+    q.mode = mode;
+    q.inputs = streamed;
+    q.partial_points = false;
+    q.handles = false;
+    q.pre_hints = false;
+    // nothing of this prover in flight?  (asked only where the answer decides `lone`)
+    q.idle = tune.lone >= 0 || n <= tune.lone_small_max || !last || hipEventQuery(last->evC) == hipSuccess;
+    (void)hipGetLastError();   // hipErrorNotReady is not an error here
+    q.shared = device.shared();
+    q.no_hints_now = no_hints_now;
+    q.witlanes_ok = witlanes.ok;
+    q.segs_ok = segs.ok;
+    q.cone_ok = cone.ok;
+    q.have_values_kernel = have_values_kernel;
+    q.ni = ni;
+    q.logn = logn;
+    q.capacity = batch_cap;
+    q.small_stride = small_stride;
+    q.compact = splan.shape == SHAPE_COMPACT;
+    return q;
   }
 
   void sync_all() {
@@ -585,6 +626,9 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
   const NamedInputs named = find_named_inputs(graph_, D.ni);
   D.slots = named.slots;
   D.have_values_kernel = named.have_values_kernel;
+  D.have_path_slots = named.have_path_slots;
+  D.path_off = named.path_off;
+  D.path_idx_off = named.path_idx_off;
   D.hints.configure(named, D.tune.hint_chains);
   // ---- where the graph can be cut (segments behind hints; find_hint_cuts): a circuit on which a hint matches no node
   //      keeps the whole-graph interpreter
@@ -797,6 +841,14 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     RLN_HIP(hipMemsetAsync(S.pp_in.p, 0, S.pp_in.bytes(), s));
     RLN_HIP(hipHostMalloc((void**)&S.h_in, B * ((size_t)D.NI * 32 + 64 + 320), hipHostMallocDefault));
     RLN_HIP(hipHostMalloc((void**)&S.h_cone, B * 4, hipHostMallocDefault));
+    static_assert(sizeof(uint64_t) == 8, "two leaf indices per 16-byte word");
+    if (B % 2) throw Error("internal: the workspace capacity is a multiple of 64");   // idx / h_idx are staged and counted in 16-byte words
+    S.idx.alloc(B);
+    RLN_HIP(hipMemsetAsync(S.idx.p, 0, S.idx.bytes(), s));
+    RLN_HIP(hipHostMalloc((void**)&S.h_idx, B * 8, hipHostMallocDefault));
+    memset(S.h_idx, 0, B * 8);
+    RLN_HIP(hipEventCreateWithFlags(&S.evT, hipEventDisableTiming));
+    RLN_HIP(hipEventCreateWithFlags(&S.evG, hipEventDisableTiming));
     RLN_HIP(hipHostMalloc((void**)&S.h_hints, (size_t)HINT_PROOFS * 64 * 32, hipHostMallocDefault));
     RLN_HIP(hipEventCreateWithFlags(&S.evU, hipEventDisableTiming));
     RLN_HIP(hipEventCreateWithFlags(&S.evE, hipEventDisableTiming));
@@ -846,6 +898,9 @@ Prover::~Prover() {
     if (S.h_pp) (void)hipHostFree(S.h_pp);
     if (S.h_in) (void)hipHostFree(S.h_in);
     if (S.h_cone) (void)hipHostFree(S.h_cone);
+    if (S.h_idx) (void)hipHostFree(S.h_idx);
+    if (S.evT) (void)hipEventDestroy(S.evT);
+    if (S.evG) (void)hipEventDestroy(S.evG);
     if (S.h_hints) (void)hipHostFree(S.h_hints);
     if (S.evU) (void)hipEventDestroy(S.evU);
     if (S.evE) (void)hipEventDestroy(S.evE);
@@ -932,6 +987,65 @@ uint64_t Prover::submit_finish(size_t n, const uint8_t* inputs, const uint8_t* r
   if (n == 0) throw Error("empty batch");
   if (!inputs || !rs || !partial320) throw Error("submit_finish: inputs, rs and the partial points are required");
   return enqueue(n, PROVE_FINISH, inputs, rs, partial320, handles);
+}
+
+// Submit by member: the Merkle paths are read on the device, where the tree already holds them (k_proofs_at into the
+// slot's staged inputs, ordered against the tree's stream by two events: enqueue).  A batch that would be interpreted as
+// segments behind hints needs the paths on the host -- the hints are hashed from them -- and so does a sparse tree: those
+// fetch the paths with one proofs_at call, fill the path slots of a copy of the inputs and go through enqueue as any
+// submit does.  The path slots of `inputs` are ignored on both routes and the staged bytes are the same.
+void Prover::check_members(const MemberTree& t, size_t n, const uint64_t* leaf) const {
+  const Impl& D = *d_;
+  if (!D.have_path_slots) throw Error("submit_members: the witness graph names no pathElements / identityPathIndex inputs");
+  if (t.depth != (int)graph_.tree_depth)
+    throw Error("submit_members: the tree's depth (" + std::to_string(t.depth) + ") is not the circuit's (" +
+                std::to_string(graph_.tree_depth) + ")");
+  if (t.dense && t.dense->device != D.device.dev) throw Error("submit_members: the tree and the prover are on different devices");
+  if (!t.dense && !t.proofs_at) throw Error("submit_members: no tree");
+  for (size_t i = 0; i < n; i++)
+    if (leaf[i] >> t.depth)
+      throw Error("submit_members: leaf index " + std::to_string(leaf[i]) + " is outside a tree of depth " + std::to_string(t.depth));
+}
+
+uint64_t Prover::submit_members(const MemberTree& t, size_t n, const uint64_t* leaf, const uint8_t* inputs, const uint8_t* rs,
+                                int mode) {
+  if (n == 0) throw Error("empty batch");
+  if (!leaf || !inputs || !rs) throw Error("submit_members: leaf indices, inputs and rs are required");
+  if (mode != PROVE_FULL && mode != PROVE_PARTIAL)
+    throw Error("submit_members: full and partial proofs only (a finish brings its path with its inputs: submit)");
+  if (n > B_) throw Error("batch larger than the prover workspace (max_batch)");
+  check_members(t, n, leaf);
+  Impl& D = *d_;
+  bool host = !t.dense;
+  if (!host && n <= D.tune.hint_max) host = batch_shape(D.query(n, mode, true), D.tune).hinted;
+  if (!host) {
+    const MemberGather g{t.dense, leaf};
+    return enqueue(n, mode, inputs, rs, nullptr, nullptr, nullptr, &g);
+  }
+  const size_t d = (size_t)t.depth, NIB = (size_t)D.NI * 32;
+  std::vector<uint8_t> elems(n * d * 32), bits(n * d), in(inputs, inputs + n * NIB);
+  auto scrub = [&]() {   // the copy holds what the caller's inputs hold: the identity secret among it
+    for (std::vector<uint8_t>* v : {&in, &elems, &bits}) {   // (the path bits are the member's leaf index)
+      memset(v->data(), 0, v->size());
+      __asm__ __volatile__("" : : "r"(v->data()) : "memory");
+    }
+  };
+  try {
+    if (t.proofs_at) t.proofs_at(leaf, n, elems.data(), bits.data());
+    else t.dense->proofs_at_host(leaf, n, elems.data(), bits.data());
+    for (size_t i = 0; i < n; i++) {
+      uint8_t* row = in.data() + i * NIB;
+      memcpy(row + (size_t)D.path_off * 32, elems.data() + i * d * 32, d * 32);
+      memset(row + (size_t)D.path_idx_off * 32, 0, d * 32);
+      for (size_t l = 0; l < d; l++) row[((size_t)D.path_idx_off + l) * 32] = bits[i * d + l];
+    }
+    const uint64_t ticket = enqueue(n, mode, in.data(), rs, nullptr);
+    scrub();
+    return ticket;
+  } catch (...) {
+    scrub();
+    throw;
+  }
 }
 
 uint32_t Prover::hint_words() const {
@@ -1165,8 +1279,23 @@ void Prover::prove_stream(size_t n, const uint8_t* inputs, const uint8_t* rs, ui
   }, inputs, rs, proofs, values, errors);
 }
 
+void Prover::prove_stream_members(const MemberTree& tree, size_t n, const uint64_t* leaf, const uint8_t* inputs,
+                                  const uint8_t* rs, uint8_t* proofs, uint8_t* values, uint32_t* errors) {
+  if (n && (!leaf || !inputs || !rs)) throw Error("prove_stream_members: leaf indices, inputs and rs are required");
+  check_members(tree, n, leaf);   // all of it before the first chunk is enqueued
+  size_t at = 0;
+  prove_stream_from([&](size_t* off, size_t* cnt) {
+    if (at >= n) return false;
+    *off = at;
+    *cnt = std::min(B_, n - at);
+    at += *cnt;
+    return true;
+  }, inputs, rs, proofs, values, errors, 0, &tree, leaf);
+}
+
 void Prover::prove_stream_from(const ChunkSource& next, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs,
-                               uint8_t* values, uint32_t* errors, int max_in_flight) {
+                               uint8_t* values, uint32_t* errors, int max_in_flight, const MemberTree* tree,
+                               const uint64_t* leaf) {
   Impl& D = *d_;
   struct Pending { uint64_t ticket; size_t off, cnt; };
   std::deque<Pending> q;
@@ -1185,7 +1314,9 @@ void Prover::prove_stream_from(const ChunkSource& next, const uint8_t* inputs, c
       if (!next(&off, &cnt)) break;         // (asked only when a slot is free: a shared cursor hands out no chunk early)
       if (cnt == 0) continue;
       if (cnt > B_) throw Error("prove_stream: a chunk larger than the prover workspace (max_batch)");
-      q.push_back({submit(cnt, inputs + off * NIB, rs + off * 64), off, cnt});
+      q.push_back({tree ? submit_members(*tree, cnt, leaf + off, inputs + off * NIB, rs + off * 64, PROVE_FULL)
+                        : submit(cnt, inputs + off * NIB, rs + off * 64),
+                   off, cnt});
     }
     while (!q.empty()) take();
   } catch (...) {
@@ -1221,34 +1352,19 @@ static void on_hint_threads(size_t n, size_t nth, F&& per_proof) {
 }
 
 uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint8_t* h_rs, const uint8_t* h_pp320,
-                         const uint64_t* cone_handles, const uint32_t* pre_hints) {
+                         const uint64_t* cone_handles, const uint32_t* pre_hints, const MemberGather* members) {
   if (n == 0) return 0;
   if (n > B_) throw Error("batch larger than the prover workspace (max_batch)");
   if (mode < PROVE_FULL || mode > PROVE_FINISH) throw Error("unknown prover mode");
   Impl& D = *d_;
   const ProverTuning& T = D.tune;
   // ---- the shape of the batch (prover_plan.h: batch_shape), decided before anything is launched
-  BatchQuery q;
-  q.n = n;
-  q.mode = mode;
-  q.inputs = h_inputs != nullptr;
+  BatchQuery q = D.query(n, mode, h_inputs != nullptr);
   q.partial_points = h_pp320 != nullptr;
   q.handles = cone_handles != nullptr;
   q.pre_hints = pre_hints != nullptr;
-  // nothing of this prover in flight?  (asked only where the answer decides `lone`)
-  q.idle = T.lone >= 0 || n <= T.lone_small_max || !D.last || hipEventQuery(D.last->evC) == hipSuccess;
-  (void)hipGetLastError();   // hipErrorNotReady is not an error here
-  q.shared = D.device.shared();
-  q.no_hints_now = D.no_hints_now;
-  q.witlanes_ok = D.witlanes.ok;
-  q.segs_ok = D.segs.ok;
-  q.cone_ok = D.cone.ok;
-  q.have_values_kernel = D.have_values_kernel;
-  q.ni = D.ni;
-  q.logn = D.logn;
-  q.capacity = B_;
-  q.small_stride = D.small_stride;
-  q.compact = D.splan.shape == SHAPE_COMPACT;
+  // a batch whose paths are gathered on the device has no path on the host to hash hints from
+  q.no_hints_now = D.no_hints_now || members != nullptr;
   BatchShape sh = batch_shape(q, T);
   // the cone needs a live cache entry for every proof: a dead handle walks the whole graph
   std::vector<uint32_t> cone_entries;
@@ -1300,6 +1416,10 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     memcpy(S.h_in, h_inputs, n * (size_t)D.NI * 32);
     memcpy(S.h_in + B_ * (size_t)D.NI * 32, h_rs, n * 64);
     if (h_pp320) memcpy(S.h_in + B_ * ((size_t)D.NI * 32 + 64), h_pp320, n * 320);
+    if (members) {
+      memcpy(S.h_idx, members->leaf, n * 8);
+      S.members = true;
+    }
   }
   const uint32_t* in_p = streamed ? S.inputs.p : D.inputs.p;
   const uint32_t* rs_p = streamed ? S.rs.p : D.rs.p;
@@ -1375,6 +1495,22 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     h2d(S.inputs.p, S.h_in, n * (size_t)D.NI * 32);
     h2d(S.rs.p, S.h_in + B_ * (size_t)D.NI * 32, n * 64);
     if (h_pp320) h2d(S.pp_in.p, S.h_in + B_ * ((size_t)D.NI * 32 + 64), n * 320);
+    if (members) {
+      // The paths, read where the tree holds them, land in the path slots of the inputs just staged -- behind that staging
+      // on this stream, before evU and so before every reader.  Events only: the gather waits for whatever the tree's
+      // stream holds so far (a scatter that set_few left behind included), and the tree's stream waits for the gather, so a
+      // write made after this call finds the batch's paths read.  The caller holds the tree's lock across both.
+      MerkleTreeDev& tree = *members->tree;
+      h2d(S.idx.p, (const uint8_t*)S.h_idx, (n * 8 + 15) / 16 * 16);
+      RLN_HIP(hipEventRecord(S.evT, tree.stream));
+      RLN_HIP(hipStreamWaitEvent(sA, S.evT, 0));
+      uint8_t* in8 = reinterpret_cast<uint8_t*>(S.inputs.p);
+      const uint64_t NIB = (uint64_t)D.NI * 32;
+      const PathDest dest{in8 + (size_t)D.path_off * 32, in8 + (size_t)D.path_idx_off * 32, NIB, 32, NIB, 32, 1};
+      tree.proofs_at_device(S.idx.p, n, dest, sA);
+      RLN_HIP(hipEventRecord(S.evG, sA));
+      RLN_HIP(hipStreamWaitEvent(tree.stream, S.evG, 0));
+    }
     RLN_HIP(hipGetLastError());
     RLN_HIP(hipEventRecord(S.evU, sA));
   }
@@ -1920,11 +2056,13 @@ void Prover::residue(uint64_t out[RESIDUE_FIELDS]) {
   count(4, S.affB2.p, S.affB2.bytes());
   count(5, S.inputs.p, S.inputs.bytes());
   count(5, S.rs.p, S.rs.bytes());
+  count(5, S.idx.p, S.idx.bytes());   // the leaf indices of a batch submitted by member, device and (below) pinned copy
   RLN_HIP(hipGetLastError());
   unsigned long long h[RESIDUE_FIELDS];
   RLN_HIP(hipMemcpyAsync(h, cnt.p, sizeof h, hipMemcpyDeviceToHost, D.sC));
   RLN_HIP(hipStreamSynchronize(D.sC));
   for (int k = 0; k < RESIDUE_FIELDS; k++) out[k] = h[k];
+  for (size_t i = 0; i + 1 < B_; i += 2) out[5] += (S.h_idx[i] | S.h_idx[i + 1]) ? 1 : 0;
 }
 
 }  // namespace rlnamd

@@ -42,6 +42,8 @@ NamedInputs find_named_inputs(const Graph& graph, uint32_t ni) {
   };
   InputSlots& sl = R.slots;
   sl.depth = graph.tree_depth;
+  R.have_path_slots = graph.tree_depth > 0 && find("pathElements", graph.tree_depth, &R.path_off) &&
+                      find("identityPathIndex", graph.tree_depth, &R.path_idx_off);
   // the hints need one message id per message slot (the multi-message-id circuit: max_out of them)
   uint32_t unused = 0;
   R.hint_msgs = graph.max_out;

@@ -27,6 +27,9 @@ struct NamedInputs {
   bool have_values_kernel = false;   // single message id, six instance variables, every shipped name
   bool have_hint_slots = false;      // the names the hints read, with one message id per message slot (max_out of them)
   uint32_t hint_msg_off = 0, hint_msgs = 1;
+  // the Merkle path by itself (Prover::submit_members writes it on the device): both names, tree_depth elements each
+  bool have_path_slots = false;
+  uint32_t path_off = 0, path_idx_off = 0;
 };
 NamedInputs find_named_inputs(const Graph& graph, uint32_t ni);
 

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <string>
 
 #include "common.h"
 #include "poseidon.h"
@@ -224,5 +225,15 @@ void TreeAny::proof_host(size_t leaf, uint8_t* elems_le, uint8_t* bits) {
   flush_locked(*this);
   if (sparse) sp.proof(leaf, elems_le, bits); else dense.proof_host(leaf, elems_le, bits);
 }
+
+void TreeAny::proofs_at_locked(const uint64_t* idx, size_t k, uint8_t* elems_le, uint8_t* bits) {
+  for (size_t i = 0; i < k; i++)
+    if (idx[i] >= capacity()) throw Error("InvalidLeaf: leaf index " + std::to_string(idx[i]) + " is outside a tree of depth " + std::to_string(depth));
+  flush_locked(*this);
+  if (!sparse) return dense.proofs_at_host(idx, k, elems_le, bits);
+  for (size_t i = 0; i < k; i++) sp.proof(idx[i], elems_le + i * (size_t)depth * 32, bits + i * (size_t)depth);
+}
+
+void TreeAny::flush_pending_locked() { flush_locked(*this); }
 
 }  // namespace rlnamd

@@ -73,6 +73,11 @@ struct TreeAny {
   void get_node_host(size_t node, uint8_t out_le[32]);
   void get_leaves_host(size_t first, size_t n, uint8_t* out_le);
   void proof_host(size_t leaf, uint8_t* elems_le, uint8_t* bits);
+  // the paths of k leaves in any order ([k][depth][32] + [k][depth]): one launch and one wait on the dense tree, a host loop
+  // on the sparse one.  An index >= capacity() throws first.  _locked: the caller holds pend->mu (a members batch keeps it
+  // from the gather to the event that orders later writes behind it)
+  void proofs_at_locked(const uint64_t* idx, size_t k, uint8_t* elems_le, uint8_t* bits);
+  void flush_pending_locked();
 };
 
 }  // namespace rlnamd

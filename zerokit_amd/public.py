@@ -460,6 +460,24 @@ class RLN:
         _ok_bool(lib().ffi_generate_rln_proofs_batch(C.byref(self._h), hs, n, rsp, outs))
         return [RLNProof(C.c_void_p(outs[i])) for i in range(n)]
 
+    def generate_rln_proofs_for_members(self, leaf_indices, identity_secrets, user_message_limits, message_ids, xs,
+                                        external_nullifiers, rs=None):
+        """EXT: n proofs for members of this object's tree named by leaf index; the Merkle paths are read on the device
+        (ffi_generate_rln_proofs_for_members).  Every list holds n ints; rs: None or n (r, s) pairs."""
+        n = len(leaf_indices)
+        cols = (identity_secrets, user_message_limits, message_ids, xs, external_nullifiers)
+        if any(len(c) != n for c in cols) or (rs is not None and len(rs) != n):
+            raise RLNError("generate_rln_proofs_for_members: every argument holds one entry per leaf index")
+        idx = (C.c_size_t * max(n, 1))(*[int(i) for i in leaf_indices])
+        vecs = [_vec_cfr(list(c)) for c in cols]          # (kept alive until the call has returned)
+        outs = (C.c_void_p * max(n, 1))()
+        rsp, flat = None, None
+        if rs is not None:
+            flat = _vec_cfr([v for pair in rs for v in pair])
+            rsp = flat[0].ptr
+        _ok_bool(lib().ffi_generate_rln_proofs_for_members(C.byref(self._h), idx, n, *[v[0].ptr for v in vecs], rsp, outs))
+        return [RLNProof(C.c_void_p(outs[i])) for i in range(n)]
+
     def finish_rln_proofs_batch(self, partials, witnesses, rs=None):
         """EXT: n finishes in one call; partials[i] (the same object may repeat) is what witnesses[i] is finished from"""
         n = len(witnesses)
