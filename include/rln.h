@@ -88,6 +88,21 @@ CResult_CFr_ptr_Vec_uint8_t ffi_compute_id_secret(const CFr_t* share1_x, const C
                                                   const CFr_t* share2_y);                       /* ffi_rln.rs:1015 */
 CResult_CFr_ptr_Vec_uint8_t ffi_recover_id_secret(FFI_RLNProofValues_t* const* proof_values_1,
                                                   FFI_RLNProofValues_t* const* proof_values_2); /* ffi_rln.rs:1036 */
+/* EXT: the step of a relay loop behind ffi_verify_rln_proofs_batch: the shares of n proof values through a nullifier
+ * log kept on the device (rln_amd.h: rlnamd_nullifier_log_new makes it, the RLNAMD_SHARE_* codes and what a log refuses
+ * are described there).  take: NULL, or the `ok` array of the verification -- a proof with take[i] == false is
+ * RLNAMD_SHARE_SKIPPED and uses no record (so is a proof without a single share).  A single-message proof is one share
+ * (nullifier, x, y, external_nullifier); a multi-message proof is one share per slot whose selector_used is set, in slot
+ * order, all with the proof's x, external nullifier and tag (tags[i]; tags NULL: every share's own sequence number in
+ * the log).  status[i] is the first of SPAM, FOREIGN, DUPLICATE, NEW that any share of proof i has; secrets[i] (n
+ * contiguous CFr, or NULL) and first_tag[i] (or NULL) come from the lowest slot with that status: for SPAM the identity
+ * secret recover_id_secret would return for the two proofs, zero otherwise.  Shares do not know which variant they came
+ * from: a single-message and a multi-message proof with one nullifier do meet.  All shares of the call go to the log in
+ * one observe; an error (null pointers, no room left in the log) leaves the log as it was. */
+struct rlnamd_nullifier_log;
+CBoolResult_t ffi_nullifier_log_observe(struct rlnamd_nullifier_log* log, FFI_RLNProofValues_t* const* values, size_t n,
+                                        const bool* take, const uint64_t* tags, uint8_t* status, CFr_t* secrets,
+                                        uint64_t* first_tag);
 /* EXT: generate_zk_proof_with_rs (protocol/proof.rs:753-777) -- explicit blinding scalars r, s */
 CResult_FFI_RLNProof_ptr_Vec_uint8_t ffi_generate_rln_proof_with_rs(FFI_RLN_t* const* rln,
                                                                     FFI_RLNWitnessInput_t* const* witness,
@@ -355,6 +370,7 @@ CResult_FFI_RLNV3ProofValues_ptr_Vec_uint8_t ffi_bytes_be_to_rln_v3_proof_values
 void ffi_rln_v3_proof_values_free(FFI_RLNV3ProofValues_t* pv); /* ffi_rln_v3.rs:1319 */
 CResult_CFr_ptr_Vec_uint8_t ffi_rln_v3_compute_id_secret(const CFr_t* share1_x, const CFr_t* share1_y, const CFr_t* share2_x, const CFr_t* share2_y); /* ffi_rln_v3.rs:1324 */
 CResult_CFr_ptr_Vec_uint8_t ffi_rln_v3_recover_id_secret(FFI_RLNV3ProofValues_t* const* pv1, FFI_RLNV3ProofValues_t* const* pv2); /* ffi_rln_v3.rs:1345 */
+CBoolResult_t ffi_rln_v3_nullifier_log_observe(struct rlnamd_nullifier_log* log, FFI_RLNV3ProofValues_t* const* values, size_t n, const bool* take, const uint64_t* tags, uint8_t* status, CFr_t* secrets, uint64_t* first_tag); /* EXT: ffi_nullifier_log_observe over V3 values */
 void ffi_rln_v3_merkle_proof_free(FFI_RLNV3MerkleProof_t* proof); /* ffi_rln_v3.rs:1371 */
 CBoolResult_t ffi_rln_v3_delete_leaf(FFI_RLNV3_t** rln, size_t index); /* ffi_rln_v3.rs:1376 */
 CBoolResult_t ffi_rln_v3_set_leaf(FFI_RLNV3_t** rln, size_t index, const CFr_t* leaf); /* ffi_rln_v3.rs:1390 */

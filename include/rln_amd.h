@@ -68,6 +68,44 @@ int rlnamd_tree_proofs_at(rlnamd_tree* t, const uint64_t* indices, size_t k, uin
 int rlnamd_tree_fill_sequential(rlnamd_tree* t, size_t start, size_t n, uint64_t first_value);
 int rlnamd_tree_bench(rlnamd_tree* t, size_t n_leaves, uint64_t first_value, int verify, float ms[2], size_t* bad);
 
+/* ---- nullifier log on the device: find double signalling in batches --------------------------------------
+ * The step of a relay loop behind verification: the log keeps every share (nullifier | x | y | external_nullifier, four
+ * canonical little-endian Fr, 128 bytes) seen in an epoch, in HBM, and says of each new one whether its nullifier is new,
+ * a repeat of the same message, or a second message of one member -- and then returns the member's identity secret
+ * (compute_id_secret / recover_id_secret, protocol/slashing.rs:12-100).  Every observed share gets a record, repeats
+ * included; a record's id is its sequence number, and `tags` are the caller's own names for the messages.
+ *   NEW        the first record with this nullifier is the share itself
+ *   FOREIGN    the first record has another external nullifier (recover_id_secret's ExternalNullifierMismatch)
+ *   DUPLICATE  the first record has the same x: the same message again (compute_id_secret's DivisionByZero)
+ *   SPAM       otherwise: secrets_le[i] is a0 of the line through the two shares; it is all zero for every other status
+ * first_tag[i] is the tag of the first record with the share's nullifier (for NEW the share's own).  The meaning of a
+ * call is that of observing its shares one by one in index order: a call of n shares gives what any split of it into
+ * consecutive smaller calls gives.  observe refuses, each with its own text, before anything is enqueued and with the log
+ * left exactly as it was: a null pointer with n > 0, n larger than the room left (capacity counts shares observed), a
+ * field element >= r (the text names the first such share).  n = 0 succeeds and writes nothing.  The buffers that carried
+ * a call's results back, recovered secrets among them, are overwritten on the device and in pinned memory before observe
+ * returns.  Calls on one handle are
+ * serialised by the handle's own mutex; different handles do not wait for each other.  The log lives on the device that
+ * is current when it is made.
+ * info: [0] capacity, [1] shares recorded, [2] table slots, [3] distinct nullifiers (shares judged NEW since the last
+ * clear), [4] observe calls, [5] longest probe walk so far, [6] non-zero 16-byte words in those result buffers,
+ * device and pinned (0 expected), [7] the seed in use.  [4] and [5] run over the life of the handle. */
+typedef struct rlnamd_nullifier_log rlnamd_nullifier_log;
+#define RLNAMD_SHARE_NEW 0
+#define RLNAMD_SHARE_DUPLICATE 1
+#define RLNAMD_SHARE_SPAM 2
+#define RLNAMD_SHARE_FOREIGN 3
+#define RLNAMD_SHARE_SKIPPED 4   /* FFI layer only (rln.h: ffi_nullifier_log_observe): take[i] was false */
+int rlnamd_nullifier_log_new(size_t capacity, uint64_t seed, rlnamd_nullifier_log** out);  /* 1 <= capacity <= 2^31; seed 0 = random */
+void rlnamd_nullifier_log_free(rlnamd_nullifier_log* l);
+int rlnamd_nullifier_log_observe(rlnamd_nullifier_log* l, size_t n, const uint8_t* shares_le /* n*128 */,
+                                 const uint64_t* tags /* NULL: the sequence numbers */, uint8_t* status /* n */,
+                                 uint8_t* secrets_le /* n*32 or NULL */, uint64_t* first_tag /* n or NULL */);
+int rlnamd_nullifier_log_clear(rlnamd_nullifier_log* l);      /* a new epoch: empty table, count 0, same seed */
+int rlnamd_nullifier_log_get(rlnamd_nullifier_log* l, uint64_t seq, uint8_t share_le[128], uint64_t* tag);
+int rlnamd_nullifier_log_home_slot(rlnamd_nullifier_log* l, const uint8_t nullifier_le[32], uint64_t* slot); /* host only */
+int rlnamd_nullifier_log_info(rlnamd_nullifier_log* l, uint64_t out[8]);
+
 /* ---- batched Groth16 prover --------------------------------------------------------------------------
  * Replaces generate_zk_proof_with_rs (rln/src/protocol/proof.rs:753-777) + proof_values_from_witness
  * (protocol/witness.rs:759-804) for n independent proofs at once. */

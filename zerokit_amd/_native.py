@@ -103,6 +103,14 @@ SIGNATURES = {
                                                C.POINTER(C.c_uint64)]),
     "rlnamd_prover_prove_stream_members": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
                                                      C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
+    "rlnamd_nullifier_log_new": (C.c_int, [C.c_size_t, C.c_uint64, PP]),
+    "rlnamd_nullifier_log_free": (None, [P]),
+    "rlnamd_nullifier_log_observe": (C.c_int, [P, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
+                                              C.POINTER(C.c_uint64)]),
+    "rlnamd_nullifier_log_clear": (C.c_int, [P]),
+    "rlnamd_nullifier_log_get": (C.c_int, [P, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "rlnamd_nullifier_log_home_slot": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "rlnamd_nullifier_log_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_tree_fill_sequential": (C.c_int, [P, C.c_size_t, C.c_size_t, C.c_uint64]),
     "rlnamd_tree_bench": (C.c_int, [P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_size_t)]),
     "rlnamd_prover_new": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, PP]),
@@ -265,6 +273,8 @@ SIGNATURES = {
     "ffi_generate_rln_proof_with_witness": (CResultPtr, [PP, C.POINTER(VecString), PP]),
     "ffi_compute_id_secret": (CResultPtr, [CFRP, CFRP, CFRP, CFRP]),
     "ffi_recover_id_secret": (CResultPtr, [PP, PP]),
+    "ffi_nullifier_log_observe": (CBoolResult, [P, PP, C.c_size_t, C.POINTER(C.c_bool), C.POINTER(C.c_uint64), C.c_char_p,
+                                                CFRP, C.POINTER(C.c_uint64)]),
     "ffi_seeded_key_gen": (VecCFr, [C.POINTER(VecU8)]),
     "ffi_extended_key_gen": (VecCFr, []),
     "ffi_seeded_extended_key_gen": (VecCFr, [C.POINTER(VecU8)]),
@@ -404,6 +414,8 @@ SIGNATURES = {
     "ffi_rln_v3_proof_values_free": (None, [P]),
     "ffi_rln_v3_compute_id_secret": (CResultPtr, [CFRP, CFRP, CFRP, CFRP]),
     "ffi_rln_v3_recover_id_secret": (CResultPtr, [PP, PP]),
+    "ffi_rln_v3_nullifier_log_observe": (CBoolResult, [P, PP, C.c_size_t, C.POINTER(C.c_bool), C.POINTER(C.c_uint64),
+                                                       C.c_char_p, CFRP, C.POINTER(C.c_uint64)]),
     "ffi_rln_v3_merkle_proof_free": (None, [P]),
     "ffi_rln_v3_delete_leaf": (CBoolResult, [PP, C.c_size_t]),
     "ffi_rln_v3_set_leaf": (CBoolResult, [PP, C.c_size_t, CFRP]),

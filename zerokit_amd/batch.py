@@ -684,6 +684,67 @@ class PoseidonTree:
         return dict(build_ms=float(ms[0]), proofs_ms=float(ms[1]), bad=int(bad.value))
 
 
+class NullifierLog:
+    """Device-resident log of the rate-limiting shares of one epoch (rlnamd_nullifier_log_*): for each observed share,
+    whether its nullifier is new, a repeat of the same message or a second message of one member -- and then that
+    member's identity secret (compute_id_secret, rln/src/protocol/slashing.rs:12-36)."""
+    NEW, DUPLICATE, SPAM, FOREIGN, SKIPPED = range(5)
+
+    def __init__(self, capacity, seed=0):
+        self._h = C.c_void_p()
+        check(lib().rlnamd_nullifier_log_new(capacity, seed, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rlnamd_nullifier_log_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def observe_raw(self, shares: bytes, tags=None):
+        """n packed shares (128 bytes each: nullifier | x | y | external_nullifier, canonical LE) ->
+        (status n bytes, secrets n * 32 bytes, first tags: list of n ints)"""
+        n = len(shares) // 128
+        if len(shares) != 128 * n or (tags is not None and len(tags) != n):
+            raise RLNError("NullifierLog.observe: %d bytes of shares and %s tags" % (len(shares), "no" if tags is None else len(tags)))
+        tg = None if tags is None else (C.c_uint64 * max(n, 1))(*[int(t) for t in tags])
+        status = C.create_string_buffer(max(n, 1))
+        secrets = C.create_string_buffer(max(32 * n, 1))
+        first = (C.c_uint64 * max(n, 1))()
+        check(lib().rlnamd_nullifier_log_observe(self._h, n, shares, tg, status, secrets, first))
+        return status.raw[:n], secrets.raw[:32 * n], list(first[:n])
+
+    def observe(self, shares, tags=None):
+        """shares: [(nullifier, x, y, external_nullifier)] as ints -> (status, secrets, first_tag), three lists of ints"""
+        status, secrets, first = self.observe_raw(b"".join(_b(v) for s in shares for v in s), tags)
+        return (list(status), [int.from_bytes(secrets[32 * i:32 * i + 32], "little") for i in range(len(status))], first)
+
+    def clear(self):
+        """a new epoch: the table empty, no records, the same seed"""
+        check(lib().rlnamd_nullifier_log_clear(self._h))
+
+    def get(self, seq):
+        """record `seq` -> ((nullifier, x, y, external_nullifier), tag)"""
+        out = C.create_string_buffer(128)
+        tag = C.c_uint64()
+        check(lib().rlnamd_nullifier_log_get(self._h, seq, out, C.byref(tag)))
+        return tuple(int.from_bytes(out.raw[32 * k:32 * k + 32], "little") for k in range(4)), int(tag.value)
+
+    def home_slot(self, nullifier):
+        slot = C.c_uint64()
+        check(lib().rlnamd_nullifier_log_home_slot(self._h, _b(nullifier), C.byref(slot)))
+        return int(slot.value)
+
+    def info(self):
+        out = (C.c_uint64 * 8)()
+        check(lib().rlnamd_nullifier_log_info(self._h, out))
+        return [int(v) for v in out]
+
+
 class MsmG1:
     """Variable-base MSM (VariableBaseMSM::msm_bigint, ark-ec 0.5.0; BASELINE config 5) on G1; MsmG2 below is the same
     object on the twist: points are (x, y) ints for G1, ((x.c0, x.c1), (y.c0, y.c1)) for G2, None = infinity."""

@@ -15,6 +15,7 @@
 #include "keccak.h"
 #include "merkle.h"
 #include "msm.h"
+#include "nullifier_log.h"
 #include "pairing.h"
 #include "poseidon.h"
 #include "prover.h"
@@ -38,6 +39,13 @@ struct rlnamd_tree {
   MerkleTreeDev t;
   size_t host_max = 0;   // rlnamd_tree_set_leaves: up to this many distinct leaves take MerkleTreeDev::set_few
   DevBuf<uint8_t> bench_elems, bench_bits;
+};
+
+struct rlnamd_nullifier_log {
+  // one stream and one staging block per log: every call on a handle takes this
+  std::mutex mu;
+  NullifierLogDev log;
+  rlnamd_nullifier_log(uint64_t capacity, uint64_t seed) : log(capacity, seed) {}
 };
 
 static void verify_common(const Zkey& zk, const uint8_t proof[128], const uint8_t* values_le, int* ok, size_t nv = 5);
@@ -228,6 +236,50 @@ int rlnamd_tree_bench(rlnamd_tree* t, size_t n_leaves, uint64_t first_value, int
   (void)hipEventDestroy(e1);
   (void)hipEventDestroy(e2);
   if (bad) *bad = verify ? T.verify_proofs_device(0, n_leaves, t->bench_elems.p, t->bench_bits.p) : 0;
+  RLN_CATCH
+}
+
+// ------------------------------------------------------------------------------------ nullifier log
+int rlnamd_nullifier_log_new(size_t capacity, uint64_t seed, rlnamd_nullifier_log** out) {
+  RLN_TRY
+  if (!out) throw Error("rlnamd_nullifier_log_new: null pointer");
+  *out = new rlnamd_nullifier_log(capacity, seed);
+  RLN_CATCH
+}
+void rlnamd_nullifier_log_free(rlnamd_nullifier_log* l) { delete l; }
+int rlnamd_nullifier_log_observe(rlnamd_nullifier_log* l, size_t n, const uint8_t* shares_le, const uint64_t* tags,
+                                 uint8_t* status, uint8_t* secrets_le, uint64_t* first_tag) {
+  RLN_TRY
+  if (!l) throw Error("rlnamd_nullifier_log_observe: null log");
+  std::lock_guard<std::mutex> lk(l->mu);
+  l->log.observe(n, shares_le, tags, status, secrets_le, first_tag);
+  RLN_CATCH
+}
+int rlnamd_nullifier_log_clear(rlnamd_nullifier_log* l) {
+  RLN_TRY
+  if (!l) throw Error("rlnamd_nullifier_log_clear: null log");
+  std::lock_guard<std::mutex> lk(l->mu);
+  l->log.clear();
+  RLN_CATCH
+}
+int rlnamd_nullifier_log_get(rlnamd_nullifier_log* l, uint64_t seq, uint8_t share_le[128], uint64_t* tag) {
+  RLN_TRY
+  if (!l) throw Error("rlnamd_nullifier_log_get: null log");
+  std::lock_guard<std::mutex> lk(l->mu);
+  l->log.get(seq, share_le, tag);
+  RLN_CATCH
+}
+int rlnamd_nullifier_log_home_slot(rlnamd_nullifier_log* l, const uint8_t nullifier_le[32], uint64_t* slot) {
+  RLN_TRY
+  if (!l || !nullifier_le || !slot) throw Error("rlnamd_nullifier_log_home_slot: null pointer");
+  *slot = l->log.home_slot(nullifier_le);
+  RLN_CATCH
+}
+int rlnamd_nullifier_log_info(rlnamd_nullifier_log* l, uint64_t out[8]) {
+  RLN_TRY
+  if (!l || !out) throw Error("rlnamd_nullifier_log_info: null pointer");
+  std::lock_guard<std::mutex> lk(l->mu);
+  l->log.info(out);
   RLN_CATCH
 }
 

@@ -2217,6 +2217,66 @@ CResult_CFr_ptr_Vec_uint8_t ffi_recover_id_secret(FFI_RLNProofValues_t* const* p
   });
 }
 
+// EXT: the shares of n proof values through a nullifier log on the device (rln.h).  One observe for the whole call; a
+// proof's verdict is the first of SPAM, FOREIGN, DUPLICATE, NEW among its shares, taken from the lowest such slot.
+static bool nullifier_log_observe_values(rlnamd_nullifier_log* log, void* const* values, size_t n, const bool* take,
+                                         const uint64_t* tags, uint8_t* status, CFr_t* secrets, uint64_t* first_tag) {
+  if (!log) throw Error("nullifier log: null log");
+  if (n == 0) return true;
+  if (!values || !status) throw Error("nullifier log: null argument");
+  std::vector<uint8_t> shares;
+  std::vector<uint64_t> share_tags;
+  std::vector<size_t> first_share(n + 1, 0);
+  auto put = [&](const FFI_RLNProofValues& v, const CFr& nullifier, const CFr& y, size_t i) {
+    const CFr* parts[4] = {&nullifier, &v.x, &y, &v.external_nullifier};
+    for (const CFr* p : parts) shares.insert(shares.end(), p->le, p->le + 32);
+    if (tags) share_tags.push_back(tags[i]);
+  };
+  for (size_t i = 0; i < n; i++) {
+    first_share[i] = shares.size() / 128;
+    if (take && !take[i]) continue;
+    if (!values[i]) throw Error("nullifier log: null proof values");
+    const FFI_RLNProofValues& v = *(const FFI_RLNProofValues*)values[i];
+    if (!v.multi) {
+      put(v, v.nullifier, v.y, i);
+    } else {
+      for (size_t k = 0; k < v.nullifiers.size(); k++)
+        if (v.selector_used[k]) put(v, v.nullifiers[k], v.ys[k], i);
+    }
+  }
+  const size_t m = shares.size() / 128;
+  first_share[n] = m;
+  std::vector<uint8_t> st(m), sec(32 * m);
+  std::vector<uint64_t> ft(m);
+  ZeroOnExit wipe{sec};
+  if (rlnamd_nullifier_log_observe(log, m, shares.data(), tags ? share_tags.data() : nullptr, st.data(), sec.data(),
+                                   ft.data()) != RLNAMD_OK)
+    throw Error(rlnamd_last_error());
+  static const uint8_t kOrder[4] = {RLNAMD_SHARE_SPAM, RLNAMD_SHARE_FOREIGN, RLNAMD_SHARE_DUPLICATE, RLNAMD_SHARE_NEW};
+  for (size_t i = 0; i < n; i++) {
+    status[i] = RLNAMD_SHARE_SKIPPED;
+    if (secrets) memset((CFr*)secrets + i, 0, 32);
+    if (first_tag) first_tag[i] = 0;
+    size_t pick = m;
+    for (uint8_t want : kOrder) {
+      for (size_t k = first_share[i]; k < first_share[i + 1] && pick == m; k++)
+        if (st[k] == want) pick = k;
+      if (pick != m) break;
+    }
+    if (pick == m) continue;
+    status[i] = st[pick];
+    if (secrets) memcpy((CFr*)secrets + i, &sec[32 * pick], 32);
+    if (first_tag) first_tag[i] = ft[pick];
+  }
+  return true;
+}
+CBoolResult_t ffi_nullifier_log_observe(struct rlnamd_nullifier_log* log, FFI_RLNProofValues_t* const* values, size_t n,
+                                        const bool* take, const uint64_t* tags, uint8_t* status, CFr_t* secrets,
+                                        uint64_t* first_tag) {
+  return guard_bool(
+      [&]() { return nullifier_log_observe_values(log, (void* const*)values, n, take, tags, status, secrets, first_tag); });
+}
+
 CResult_Vec_uint8_Vec_uint8_t ffi_rln_witness_to_bigint_json(FFI_RLNWitnessInput_t* const* wp) {
   // rln_witness_to_bigint_json (witness.rs:317-366); serde_json's default map is a BTreeMap: keys sorted, compact
   const FFI_RLNWitnessInput& w = W(wp);

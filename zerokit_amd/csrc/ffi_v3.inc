@@ -421,6 +421,13 @@ CResult_CFr_ptr_Vec_uint8_t ffi_rln_v3_recover_id_secret(FFI_RLNV3ProofValues_t*
   });
 }
 
+CBoolResult_t ffi_rln_v3_nullifier_log_observe(struct rlnamd_nullifier_log* log, FFI_RLNV3ProofValues_t* const* values,
+                                               size_t n, const bool* take, const uint64_t* tags, uint8_t* status,
+                                               CFr_t* secrets, uint64_t* first_tag) {   // EXT: the V3 values are the same record
+  return guard_bool(
+      [&]() { return nullifier_log_observe_values(log, (void* const*)values, n, take, tags, status, secrets, first_tag); });
+}
+
 // ================================================================================ tree (:1363-1609)
 void ffi_rln_v3_merkle_proof_free(FFI_RLNV3MerkleProof_t* proof) { ffi_merkle_proof_free((FFI_MerkleProof_t*)proof); }
 CBoolResult_t ffi_rln_v3_delete_leaf(FFI_RLNV3_t** rln, size_t index) {

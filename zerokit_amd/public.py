@@ -560,6 +560,29 @@ def recover_id_secret(values_1: RLNProofValues, values_2: RLNProofValues) -> int
     return _take_cfr(C.cast(_ok_ptr(r), C.POINTER(CFr)))
 
 
+def _observe_proof_values(fn, log, values, take, tags):
+    n = len(values)
+    if (take is not None and len(take) != n) or (tags is not None and len(tags) != n):
+        raise RLNError("observe_proof_values: %d proof values, but take or tags of another length" % n)
+    hs = (C.c_void_p * max(n, 1))(*[v._h.value for v in values])
+    tk = None if take is None else (C.c_bool * max(n, 1))(*[bool(t) for t in take])
+    tg = None if tags is None else (C.c_uint64 * max(n, 1))(*[int(t) for t in tags])
+    status = C.create_string_buffer(max(n, 1))
+    secrets = (CFr * max(n, 1))()
+    first = (C.c_uint64 * max(n, 1))()
+    _ok_bool(fn(log._h, hs, n, tk, tg, status, secrets, first))
+    return (list(status.raw[:n]), [int.from_bytes(bytes(secrets[i].le), "little") for i in range(n)], list(first[:n]))
+
+
+def observe_proof_values(log, values, take=None, tags=None):
+    """EXT: the shares of n RLNProofValues through a batch.NullifierLog (ffi_nullifier_log_observe): one share per
+    single-message proof, one per used slot of a multi-message proof.  take: None, or the list verify_rln_proofs_batch
+    returned (a proof that did not pass is SKIPPED and leaves no record).  Returns (status, secrets, first_tag), one
+    entry per proof: the first of SPAM, FOREIGN, DUPLICATE, NEW among the proof's shares, the recovered identity secret
+    for SPAM (else 0), and the tag of the first message that carried the nullifier."""
+    return _observe_proof_values(lib().ffi_nullifier_log_observe, log, values, take, tags)
+
+
 def seeded_keygen(seed: bytes):
     """protocol/keygen.rs:50-65 -> (identity_secret, id_commitment)"""
     v, _k = _vec_u8(seed)

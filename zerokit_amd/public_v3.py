@@ -4,8 +4,8 @@ Field elements are Python ints; errors are RLNError with the text the ABI return
 import ctypes as C
 
 from ._native import CFr, RLNError, VecSize, lib
-from .public import (_cfr, _err, _ok_bool, _ok_ptr, _take_bytes, _take_cfr, _take_vec_bool, _take_vec_cfr, _vec_bool,
-                     _vec_cfr, _vec_u8)
+from .public import (_cfr, _err, _observe_proof_values, _ok_bool, _ok_ptr, _take_bytes, _take_cfr, _take_vec_bool,
+                     _take_vec_cfr, _vec_bool, _vec_cfr, _vec_u8)
 
 
 def _res_vec(res, take):
@@ -205,6 +205,11 @@ class PartialProofV3(_Handle):
 def compute_id_secret(share1, share2) -> int:
     return _res_cfr(lib().ffi_rln_v3_compute_id_secret(C.byref(_cfr(share1[0])), C.byref(_cfr(share1[1])),
                                                        C.byref(_cfr(share2[0])), C.byref(_cfr(share2[1]))))
+
+
+def observe_proof_values(log, values, take=None, tags=None):
+    """EXT: public.observe_proof_values over RLNProofValuesV3 (ffi_rln_v3_nullifier_log_observe)"""
+    return _observe_proof_values(lib().ffi_rln_v3_nullifier_log_observe, log, values, take, tags)
 
 
 class RLNV3(_Handle):
