@@ -120,6 +120,12 @@ CBoolResult_t ffi_generate_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNWitnes
  * call). */
 CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
                                           const CFr_t* xs, const Vec_CFr_t* roots, bool* ok);
+/* EXT: ffi_verify_rln_proofs_batch from the messages themselves: exactly that call with xs[i] =
+ * hash_to_field(signals[i]), the n signals hashed in one call -- on the device when n is at least the object's
+ * "hash_gpu_min" (config JSON; rln_amd.h: rlnamd_hasher_*), one by one on the calling thread below it.  A null
+ * signals[i].ptr with length 0 is the empty message. */
+CBoolResult_t ffi_verify_rln_signals_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
+                                           const Vec_uint8_t* signals, const Vec_CFr_t* roots, bool* ok);
 
 /* EXT: n finishes in one call (single message-id): partials[i] is the partial proof witnesses[i] is finished from -- the
  * same pointer may repeat, one member's partial proof finished for n messages being what partial proofs are for
@@ -274,6 +280,11 @@ Vec_uint8_t ffi_vec_u8_debug(const Vec_uint8_t* v);                             
 void ffi_vec_u8_free(Vec_uint8_t v);                                                           /* ffi_utils.rs:343 */
 CFr_t* ffi_hash_to_field_le(const Vec_uint8_t* input);                                         /* ffi_utils.rs:349 */
 CFr_t* ffi_hash_to_field_be(const Vec_uint8_t* input);                                         /* ffi_utils.rs:354 */
+/* EXT: ffi_hash_to_field_le / _be of n signals in one call; out: n CFr.  Over one hasher per device for the whole process,
+ * made on first use (rln_amd.h: rlnamd_hasher_*); small calls are hashed on the calling thread.  Both give the same
+ * result, as the single calls do. */
+CBoolResult_t ffi_hash_to_field_batch_le(const Vec_uint8_t* signals, size_t n, CFr_t* out);
+CBoolResult_t ffi_hash_to_field_batch_be(const Vec_uint8_t* signals, size_t n, CFr_t* out);
 /* The five functions below have no error channel in the reference ABI.  A device failure (no GPU, out of memory)
  * is reported on stderr and by a NULL pointer / an empty vector {NULL, 0, 0} -- never by a zero "result". */
 CFr_t* ffi_poseidon_hash_pair(const CFr_t* a, const CFr_t* b);                                 /* ffi_utils.rs:359 */

@@ -37,7 +37,8 @@ int rlnamd_device_name(char* buf, size_t cap);
  * Batched Poseidon: poseidon_hash / poseidon_hash_pair (rln/src/hashers.rs:32-54) over n independent
  * inputs.  inputs: n * arity * 32 bytes, out: n * 32 bytes (host memory). arity 1..8 (t = 2..9). */
 int rlnamd_poseidon_hash(const uint8_t* inputs_le, size_t n, size_t arity, uint8_t* out_le);
-/* hash_to_field_le / _be (rln/src/hashers.rs:73-93): Keccak-256 then reduction mod r.  Host only. */
+/* hash_to_field_le / _be (rln/src/hashers.rs:73-93): Keccak-256 then reduction mod r.  Host only; many messages at
+ * once, on the device: rlnamd_hasher_* below. */
 int rlnamd_hash_to_field_le(const uint8_t* data, size_t len, uint8_t out_le[32]);
 int rlnamd_hash_to_field_be(const uint8_t* data, size_t len, uint8_t out_le[32]);
 
@@ -105,6 +106,28 @@ int rlnamd_nullifier_log_clear(rlnamd_nullifier_log* l);      /* a new epoch: em
 int rlnamd_nullifier_log_get(rlnamd_nullifier_log* l, uint64_t seq, uint8_t share_le[128], uint64_t* tag);
 int rlnamd_nullifier_log_home_slot(rlnamd_nullifier_log* l, const uint8_t nullifier_le[32], uint64_t* slot); /* host only */
 int rlnamd_nullifier_log_info(rlnamd_nullifier_log* l, uint64_t out[8]);
+
+/* ---- signals to field elements on the device, in batches ------------------------------------------------------
+ * The step of a relay loop in front of verification: x = hash_to_field(signal) (rln/src/hashers.rs:73-93: Keccak-256,
+ * read little-endian, mod r) of n messages in one call, a lane per message.  Message i is data[offsets[i],
+ * offsets[i + 1]); out_le row i is its field element, 32 canonical little-endian bytes -- what rlnamd_hash_to_field_le
+ * (and _be) gives for it.  Messages are dealt to lanes by descending length.  A message larger than one half of the
+ * staging is hashed on the calling thread while the device works, and so are the longest of the messages of more than
+ * lane_max_blocks 136-byte blocks, for as long as the host is done with them before a lane would be (a lone long
+ * message, a few among many short ones).  A call larger than the staging (stage_bytes: two pinned halves) goes through
+ * it in chunks.  hash_to_field refuses, each
+ * with its own text and before anything is enqueued: null pointers with n > 0, decreasing offsets, offsets[n] >
+ * data_len, sizes that overflow (n >= 2^32).  n = 0 succeeds and writes nothing.  Signals are public: nothing is wiped.
+ * Calls on one handle are serialised by the handle's own mutex; the hasher lives on the device that is current when
+ * it is made.
+ * info, of the last call: [0] messages hashed on the device, [1] on the host, [2] chunks, [3] blocks on the device,
+ * [4] the longest lane in blocks; of the handle: [5] blocks per staging half, [6] lane_max_blocks, [7] calls so far. */
+typedef struct rlnamd_hasher rlnamd_hasher;
+int rlnamd_hasher_new(size_t stage_bytes /* 0: default */, size_t lane_max_blocks /* 0: default */, rlnamd_hasher** out);
+void rlnamd_hasher_free(rlnamd_hasher* h);
+int rlnamd_hasher_hash_to_field(rlnamd_hasher* h, const uint8_t* data, size_t data_len,
+                                const uint64_t* offsets /* n + 1 */, size_t n, uint8_t* out_le /* n * 32 */);
+int rlnamd_hasher_info(rlnamd_hasher* h, uint64_t out[8]);
 
 /* ---- batched Groth16 prover --------------------------------------------------------------------------
  * Replaces generate_zk_proof_with_rs (rln/src/protocol/proof.rs:753-777) + proof_values_from_witness

@@ -111,6 +111,10 @@ SIGNATURES = {
     "rlnamd_nullifier_log_get": (C.c_int, [P, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_home_slot": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "rlnamd_hasher_new": (C.c_int, [C.c_size_t, C.c_size_t, PP]),
+    "rlnamd_hasher_free": (None, [P]),
+    "rlnamd_hasher_hash_to_field": (C.c_int, [P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_char_p]),
+    "rlnamd_hasher_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_tree_fill_sequential": (C.c_int, [P, C.c_size_t, C.c_size_t, C.c_uint64]),
     "rlnamd_tree_bench": (C.c_int, [P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_size_t)]),
     "rlnamd_prover_new": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, PP]),
@@ -230,6 +234,8 @@ SIGNATURES = {
                                                           CFRP, CFRP, PP]),
     "ffi_verify_rln_proof": (CBoolResult, [PP, PP, CFRP]),
     "ffi_verify_rln_proofs_batch": (CBoolResult, [PP, PP, C.c_size_t, CFRP, C.POINTER(VecCFr), C.POINTER(C.c_bool)]),
+    "ffi_verify_rln_signals_batch": (CBoolResult, [PP, PP, C.c_size_t, C.POINTER(VecU8), C.POINTER(VecCFr),
+                                                   C.POINTER(C.c_bool)]),
     "ffi_verify_with_roots": (CBoolResult, [PP, PP, C.POINTER(VecCFr), CFRP]),
     "ffi_rln_proof_get_values": (P, [PP]),
     "ffi_rln_proof_get_version_byte": (C.c_uint8, [PP]),
@@ -345,6 +351,8 @@ SIGNATURES = {
     "ffi_vec_u8_free": (None, [VecU8]),
     "ffi_hash_to_field_le": (CFRP, [C.POINTER(VecU8)]),
     "ffi_hash_to_field_be": (CFRP, [C.POINTER(VecU8)]),
+    "ffi_hash_to_field_batch_le": (CBoolResult, [C.POINTER(VecU8), C.c_size_t, CFRP]),
+    "ffi_hash_to_field_batch_be": (CBoolResult, [C.POINTER(VecU8), C.c_size_t, CFRP]),
     "ffi_poseidon_hash_pair": (CFRP, [CFRP, CFRP]),
     "ffi_key_gen": (VecCFr, []),
     # ---- V3 mirror (include/rln.h, ffi_rln_v3.rs:323-1609)

@@ -745,6 +745,55 @@ class NullifierLog:
         return [int(v) for v in out]
 
 
+class Hasher:
+    """hash_to_field (rln/src/hashers.rs:73-93) of many messages in one call on the device (rlnamd_hasher_*): a lane per
+    message, the lanes dealt by descending length; the longest of the messages of more than lane_max_blocks 136-byte
+    blocks are hashed on the calling thread meanwhile (as many as it is done with before a lane would be), and a call
+    larger than stage_bytes of pinned staging goes through it in chunks."""
+    INFO = ("device_messages", "host_messages", "chunks", "device_blocks", "longest_lane_blocks", "half_blocks",
+            "lane_max_blocks", "calls")
+
+    def __init__(self, stage_bytes=0, lane_max_blocks=0):
+        self._h = C.c_void_p()
+        check(lib().rlnamd_hasher_new(stage_bytes, lane_max_blocks, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rlnamd_hasher_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def hash_to_field_raw(self, data: bytes, offsets) -> bytes:
+        """message i is data[offsets[i]:offsets[i + 1]] -> n * 32 bytes, row i its field element (canonical LE)"""
+        n = len(offsets) - 1
+        if n < 0:
+            raise RLNError("Hasher.hash_to_field: offsets must hold n + 1 entries")
+        off = (C.c_uint64 * (n + 1))(*[int(o) for o in offsets])
+        out = C.create_string_buffer(max(32 * n, 1))
+        check(lib().rlnamd_hasher_hash_to_field(self._h, data, len(data), off, n, out))
+        return out.raw[:32 * n]
+
+    def hash_to_field(self, messages):
+        """messages: a list of bytes -> a list of ints"""
+        offsets = [0]
+        for m in messages:
+            offsets.append(offsets[-1] + len(m))
+        out = self.hash_to_field_raw(b"".join(messages), offsets)
+        return [int.from_bytes(out[32 * i:32 * i + 32], "little") for i in range(len(messages))]
+
+    def info(self):
+        """of the last call: messages on the device and on the host, chunks, blocks on the device, the longest lane;
+        of the hasher: blocks per staging half, lane_max_blocks, calls so far"""
+        out = (C.c_uint64 * 8)()
+        check(lib().rlnamd_hasher_info(self._h, out))
+        return dict(zip(self.INFO, (int(v) for v in out)))
+
+
 class MsmG1:
     """Variable-base MSM (VariableBaseMSM::msm_bigint, ark-ec 0.5.0; BASELINE config 5) on G1; MsmG2 below is the same
     object on the twist: points are (x, y) ints for G1, ((x.c0, x.c1), (y.c0, y.c1)) for G2, None = infinity."""

@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "keccak.h"
+#include "keccak_batch.h"
 #include "merkle.h"
 #include "msm.h"
 #include "nullifier_log.h"
@@ -46,6 +47,13 @@ struct rlnamd_nullifier_log {
   std::mutex mu;
   NullifierLogDev log;
   rlnamd_nullifier_log(uint64_t capacity, uint64_t seed) : log(capacity, seed) {}
+};
+
+struct rlnamd_hasher {
+  // one stream and one pair of staging halves per hasher: every call on a handle takes this
+  std::mutex mu;
+  HasherDev hasher;
+  rlnamd_hasher(size_t stage_bytes, size_t lane_max_blocks) : hasher(stage_bytes, lane_max_blocks) {}
 };
 
 static void verify_common(const Zkey& zk, const uint8_t proof[128], const uint8_t* values_le, int* ok, size_t nv = 5);
@@ -280,6 +288,30 @@ int rlnamd_nullifier_log_info(rlnamd_nullifier_log* l, uint64_t out[8]) {
   if (!l || !out) throw Error("rlnamd_nullifier_log_info: null pointer");
   std::lock_guard<std::mutex> lk(l->mu);
   l->log.info(out);
+  RLN_CATCH
+}
+
+// ------------------------------------------------------------------------------------------- hasher
+int rlnamd_hasher_new(size_t stage_bytes, size_t lane_max_blocks, rlnamd_hasher** out) {
+  RLN_TRY
+  if (!out) throw Error("rlnamd_hasher_new: null pointer");
+  *out = new rlnamd_hasher(stage_bytes, lane_max_blocks);
+  RLN_CATCH
+}
+void rlnamd_hasher_free(rlnamd_hasher* h) { delete h; }
+int rlnamd_hasher_hash_to_field(rlnamd_hasher* h, const uint8_t* data, size_t data_len, const uint64_t* offsets, size_t n,
+                                uint8_t* out_le) {
+  RLN_TRY
+  if (!h) throw Error("rlnamd_hasher_hash_to_field: null hasher");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->hasher.hash_to_field(data, data_len, offsets, n, out_le);
+  RLN_CATCH
+}
+int rlnamd_hasher_info(rlnamd_hasher* h, uint64_t out[8]) {
+  RLN_TRY
+  if (!h || !out) throw Error("rlnamd_hasher_info: null pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->hasher.info(out);
   RLN_CATCH
 }
 

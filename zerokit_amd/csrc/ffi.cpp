@@ -31,6 +31,7 @@
 #include "capi_util.h"
 #include "common.h"
 #include "keccak.h"
+#include "keccak_batch.h"
 #include "merkle.h"
 #include "tree_any.h"
 #include "tree_config.h"   // TreeConfig, parse_tree_config, tree_config_from_file
@@ -274,6 +275,57 @@ std::string json_str_array(const std::vector<std::string>& v) {
 // 512 is the smallest measured n where the device wins (and a power of two already).
 static constexpr size_t VERIFY_GPU_MIN_DEFAULT = 512;
 
+// Smallest call that ffi_hash_to_field_batch_le / _be and ffi_verify_rln_signals_batch hash on the device unless the
+// config says otherwise ("hash_gpu_min"); smaller calls are hashed on the calling thread with keccak.h.  The smallest
+// measured n at which the device call beats one host thread at 32-byte messages, rounded up to a power of two
+// (tools/hash_to_field_throughput.py, profiles/hash_to_field_batch.md: a device call costs 0.04 - 0.06 ms up to 1 024
+// messages; the host takes 0.043 ms for 128 messages, against 0.045 ms, and 0.085 ms for 256, against 0.046 ms)
+static constexpr size_t HASH_GPU_MIN_DEFAULT = 256;
+
+// one hasher per device for the whole process, made on first use and never freed (it would outlive the HIP runtime's
+// own teardown otherwise); calls on one device take turns
+namespace {
+struct SharedHasher {
+  std::mutex mu;
+  std::unique_ptr<HasherDev> h;
+};
+SharedHasher& shared_hasher() {
+  static std::mutex reg_mu;
+  static std::vector<SharedHasher*>* reg = new std::vector<SharedHasher*>();
+  require_gpu();
+  int dev = 0;
+  RLN_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(reg_mu);
+  if (reg->size() <= (size_t)dev) reg->resize((size_t)dev + 1, nullptr);
+  if (!(*reg)[dev]) (*reg)[dev] = new SharedHasher;
+  return *(*reg)[dev];
+}
+
+// out[i] = hash_to_field(signals[i]); a null ptr with length 0 is the empty message.  From gpu_min signals on, on the
+// current device's shared hasher; below, one by one on this thread.
+void hash_signals(const Vec_uint8_t* signals, size_t n, size_t gpu_min, CFr* out) {
+  for (size_t i = 0; i < n; i++)
+    if (!signals[i].ptr && signals[i].len) throw Error("hash_to_field: signal " + std::to_string(i) + " is a null pointer with a length");
+  if (n < gpu_min) {
+    for (size_t i = 0; i < n; i++) hash_to_field_le(signals[i].ptr, signals[i].len, out[i].le);
+    return;
+  }
+  std::vector<uint64_t> offsets(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    if (signals[i].len > UINT64_MAX - offsets[i]) throw Error("hash_to_field: sizes overflow");
+    offsets[i + 1] = offsets[i] + signals[i].len;
+  }
+  std::vector<uint8_t> data((size_t)offsets[n]);
+  for (size_t i = 0; i < n; i++)
+    if (signals[i].len) memcpy(&data[(size_t)offsets[i]], signals[i].ptr, signals[i].len);
+  static_assert(sizeof(CFr) == 32, "rows of 32 bytes");
+  SharedHasher& sh = shared_hasher();
+  std::lock_guard<std::mutex> lk(sh.mu);
+  if (!sh.h) sh.h.reset(new HasherDev(0, 0));
+  sh.h->hash_to_field(data.data(), data.size(), offsets.data(), n, (uint8_t*)out);
+}
+}  // namespace
+
 struct FFI_RLN {
   // generate / verify take &self in the reference and may be called from several threads (SURVEY section 8b,
   // "Threading"); the prover owns one set of device workspaces, so proving calls on one object take turns
@@ -295,6 +347,8 @@ struct FFI_RLN {
   size_t auto_partial = 0;
   // ffi_verify_rln_proofs_batch: calls of at least this many proofs are verified on the device ("verify_gpu_min")
   size_t verify_gpu_min = VERIFY_GPU_MIN_DEFAULT;
+  // ffi_verify_rln_signals_batch: calls of at least this many signals are hashed on the device ("hash_gpu_min")
+  size_t hash_gpu_min = HASH_GPU_MIN_DEFAULT;
   int verify_lanes = 0;   // "verify_lanes": lanes per proof of those passes (0: the verifier chooses)
   // single calls from several threads gathered into batches: gather.h
   struct GatherReq {
@@ -379,6 +433,7 @@ struct FFI_RLN {
     const ProverConfig cfg = tcfg.prover_config();
     auto_partial = tcfg.auto_partial > 0 ? (size_t)tcfg.auto_partial : 0;
     verify_gpu_min = tcfg.verify_gpu_min >= 0 ? (size_t)tcfg.verify_gpu_min : VERIFY_GPU_MIN_DEFAULT;
+    hash_gpu_min = tcfg.hash_gpu_min >= 0 ? (size_t)tcfg.hash_gpu_min : HASH_GPU_MIN_DEFAULT;
     verify_lanes = (int)tcfg.verify_lanes;
     gather_wanted = tcfg.gather_calls;
     if (const char* e = getenv("RLNAMD_GATHER_CALLS"))
@@ -1651,6 +1706,21 @@ CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t*
     return true;
   });
 }
+// EXT: ffi_verify_rln_proofs_batch with xs[i] = hash_to_field(signals[i]), hashed in one call
+CBoolResult_t ffi_verify_rln_signals_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
+                                           const Vec_uint8_t* signals, const Vec_CFr_t* roots, bool* ok) {
+  std::vector<CFr> xs;
+  CBoolResult_t hashed = guard_bool([&]() {
+    if (!rln || !*rln) throw Error("Verification error: null RLN object");
+    if (n == 0) return true;
+    if (!proofs || !signals || !ok) throw Error("Verification error: null argument");
+    xs.resize(n);
+    hash_signals(signals, n, ((FFI_RLN*)*rln)->hash_gpu_min, xs.data());
+    return true;
+  });
+  if (!hashed.ok || n == 0) return hashed;
+  return ffi_verify_rln_proofs_batch(rln, proofs, n, (const CFr_t*)xs.data(), roots, ok);
+}
 FFI_RLNProofValues_t* ffi_rln_proof_get_values(FFI_RLNProof_t* const* proof) {
   return (FFI_RLNProofValues_t*)new FFI_RLNProofValues(((FFI_RLNProof*)*proof)->values);
 }
@@ -2156,6 +2226,19 @@ CFr_t* ffi_hash_to_field_be(const Vec_uint8_t* input) {
   CFr r;
   hash_to_field_be(input->ptr, input->len, r.le);
   return box_cfr(r);
+}
+// EXT: n signals in one call, on the device from HASH_GPU_MIN_DEFAULT signals on; out: n CFr.  _be gives what _le gives,
+// as the single calls do (hashers.rs:84-93).
+CBoolResult_t ffi_hash_to_field_batch_le(const Vec_uint8_t* signals, size_t n, CFr_t* out) {
+  return guard_bool([&]() {
+    if (n == 0) return true;
+    if (!signals || !out) throw Error("hash_to_field: null argument");
+    hash_signals(signals, n, HASH_GPU_MIN_DEFAULT, (CFr*)out);
+    return true;
+  });
+}
+CBoolResult_t ffi_hash_to_field_batch_be(const Vec_uint8_t* signals, size_t n, CFr_t* out) {
+  return ffi_hash_to_field_batch_le(signals, n, out);
 }
 // The hash / keygen entry points below return bare values in the reference (ffi_utils.rs:359-392: no CResult), so a
 // device failure (no GPU, out of memory, lost device) has no error channel.  It must not look like a result: the

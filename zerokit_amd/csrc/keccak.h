@@ -1,5 +1,7 @@
 // Keccak-256 (original 0x01 padding == tiny-keccak `Keccak::v256`) and the reference's hash_to_field
-// (/root/reference/rln/src/hashers.rs:73-93).  Host helper: O(1) per call, not on the proving path.
+// (/root/reference/rln/src/hashers.rs:73-93).  Host helper: O(1) per call, not on the proving path.  In front of a
+// batch verifier it is a message at a time on one thread: many messages at once go through keccak_batch.h / HasherDev
+// (rlnamd_hasher_*, ffi_hash_to_field_batch_le), which this file judges in the tests.
 #pragma once
 #include <stdint.h>
 #include <string.h>

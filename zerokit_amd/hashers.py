@@ -1,7 +1,7 @@
 """rln::hashers (/root/reference/rln/src/hashers.rs:32-93) over the C ABI.  Field elements are Python ints."""
 import ctypes as C
 
-from ._native import check, lib
+from ._native import CFr, RLNError, VecU8, check, lib
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -45,3 +45,21 @@ def hash_to_field_be(signal: bytes) -> int:
     out = C.create_string_buffer(32)
     check(lib().rlnamd_hash_to_field_be(signal, len(signal), out))
     return int.from_bytes(out.raw, "little")
+
+
+def hash_to_field_many(messages):
+    """EXT: hash_to_field_le of every message in one call (ffi_hash_to_field_batch_le): on the device from
+    HASH_GPU_MIN_DEFAULT messages on, on the calling thread below.  -> a list of ints"""
+    n = len(messages)
+    if n == 0:
+        return []
+    keep = [(C.c_uint8 * max(len(m), 1)).from_buffer_copy(bytes(m) or b"\0") for m in messages]
+    vecs = (VecU8 * n)(*[VecU8(C.cast(k, C.POINTER(C.c_uint8)) if len(m) else None, len(m), len(m))
+                         for k, m in zip(keep, messages)])
+    out = (CFr * n)()
+    r = lib().ffi_hash_to_field_batch_le(vecs, n, out)
+    if r.err.ptr:
+        err = C.string_at(r.err.ptr, r.err.len).decode("utf-8", "replace")
+        lib().ffi_c_string_free(r.err)
+        raise RLNError(err)
+    return [int.from_bytes(bytes(out[i].le), "little") for i in range(n)]

@@ -546,6 +546,26 @@ class RLN:
         _ok_bool(lib().ffi_verify_rln_proofs_batch(C.byref(self._h), hs, n, flat.ptr, rp, ok))
         return [bool(b) for b in ok]
 
+    def verify_rln_signals_batch(self, proofs, signals, roots=None):
+        """EXT: verify_rln_proofs_batch from the messages themselves (ffi_verify_rln_signals_batch): xs[i] =
+        hash_to_field(signals[i]), hashed in one call -- on the device when n is at least the object's "hash_gpu_min".
+        signals: a list of bytes.  Returns a list of bools."""
+        n = len(proofs)
+        if len(signals) != n:
+            raise RLNError("verify_rln_signals_batch: %d proofs but %d signals" % (n, len(signals)))
+        if n == 0:
+            return []
+        hs = (C.c_void_p * n)(*[p._h.value for p in proofs])
+        keep = [_vec_u8(s) for s in signals]
+        vecs = (VecU8 * n)(*[v if len(s) else VecU8(None, 0, 0) for (v, _k), s in zip(keep, signals)])
+        rp = None
+        if roots is not None:
+            v, _k2 = _vec_cfr(list(roots))
+            rp = C.byref(v)
+        ok = (C.c_bool * n)()
+        _ok_bool(lib().ffi_verify_rln_signals_batch(C.byref(self._h), hs, n, vecs, rp, ok))
+        return [bool(b) for b in ok]
+
 
 def compute_id_secret(share1, share2) -> int:
     """protocol/slashing.rs:12-36: shares are (x, y) pairs"""
