@@ -403,6 +403,55 @@ size_t rlnamd_msm_window_sums_bytes_of(rlnamd_msm* m);
  * kernels use -- so the CPU test suite can compare both with the oracle. */
 int rlnamd_poseidon_params_check(const uint8_t* inputs_le, size_t arity, uint8_t out_dense_le[32], uint8_t out_sparse_le[32]);
 int rlnamd_selftest_fq29(int group, uint32_t threads, uint32_t iters, const uint8_t* g2_gen_xy_le, uint32_t* mismatches);
+/* Arithmetic probes (test support): ONE device function per call, run on n operand tuples of the caller's choosing, one
+ * lane per tuple; in = n x in_words and out = n x out_words 32-bit words in host memory, copied to the device and back
+ * unchanged (no conversion, no reduction: the caller judges the raw words).  in_words / out_words are the words per tuple
+ * and must be the operation's own (checked).  n = 0 returns RLNAMD_OK without a launch.
+ *
+ * rlnamd_probe_field: the 8 x 32-bit Montgomery field of csrc/field.h, field 0 = Fr, 1 = Fq; operands and results are
+ * 8-word elements as the kernels hold them (in_words = 8 x operands, out_words = 8 x results):
+ *   add sub mul (a, b); neg dbl sqr inv from_canonical to_canonical (a); dot2 dot2_sub (a, b, c, d: ab +- cd);
+ *   dot3, dot4 (a0, b0, a1, b1, ...); Fq only: Fq2 mul (a.c0, a.c1, b.c0, b.c1 -> c0, c1), sqr, inv (a.c0, a.c1 -> c0, c1). */
+enum {
+  RLNAMD_PROBE_FP_ADD = 0, RLNAMD_PROBE_FP_SUB, RLNAMD_PROBE_FP_NEG, RLNAMD_PROBE_FP_DBL, RLNAMD_PROBE_FP_MUL,
+  RLNAMD_PROBE_FP_SQR, RLNAMD_PROBE_FP_DOT2, RLNAMD_PROBE_FP_DOT3, RLNAMD_PROBE_FP_DOT4, RLNAMD_PROBE_FP_DOT2_SUB,
+  RLNAMD_PROBE_FP_FROM_CANONICAL, RLNAMD_PROBE_FP_TO_CANONICAL, RLNAMD_PROBE_FP_INV,
+  RLNAMD_PROBE_FQ2_MUL, RLNAMD_PROBE_FQ2_SQR, RLNAMD_PROBE_FQ2_INV, RLNAMD_PROBE_FP_OPS
+};
+int rlnamd_probe_field(int field, uint32_t op, uint32_t in_words, uint32_t out_words, size_t n, const uint32_t* in, uint32_t* out);
+/* rlnamd_probe_f29: the 9 x 29-bit limb form of csrc/fq29.h, field 0 = Fr29, 1 = Fq29; a 9 x 29 element is 9 raw limb
+ * words, an 8 x 32 element 8 words.  Per tuple:
+ *   MUL (a, b)  MUL_ADD (a, b, add)  SQR (a)  SQR_ADD (a, add)  DOT2 (a0, b0, a1, b1)  DOT2_ADD (a0, b0, a1, b1, add)
+ *   DOT3 / DOT3_WIDE / DOT4 / DOT4_WIDE (a0, b0, a1, b1, ...: masked / wide reduction rounds)
+ *   DOTN5 (a0, b0, ... a4, b4: poseidon.h's poseidon_dotn29<5>, Fr29 only)
+ *   SUB_K2 .. SUB_K8 (a, b -> a + K - b, normalised)   NEG_K2 .. NEG_K8 (b -> K - b, limb by limb)   NORMALIZE (a)
+ *   IS_ZERO (a -> 1 word)   SLICE (8 words -> 9)   PACK_REDUCED (9 -> 8)   FROM_FQ (8 -> 9)   TO_FQ (9 -> 8)
+ *   MUL_MONT (a: 8 words, w29: 9 words -> 8)   FROM_CANONICAL (8 -> 9: mul(slice(x), FROM_CANON), the witness
+ *   interpreters' input conversion)   UNPACK29 (8 -> 9) and PACK29_REDUCED (9 -> 8), Fq29 only
+ * and the lane forms of the group law, Fq29 only:
+ *   G1_WALK / G2_WALK   a lane starts from infinity and applies madd for each of 1 .. 32 steps, the same count for every
+ *                       lane: in_words = steps x (1 + 16 | 32): a flag word (bit 0: negate, bit 1: no entry at this step)
+ *                       and a table entry (G1Affine29 x | y, G2Affine29 x0 | x1 | y0 | y1); out_words = steps x (36 | 72):
+ *                       the raw accumulator X | Y | ZZ | ZZZ (G2: c0 | c1 each) after every step
+ *   G1_ADD / G2_ADD     two raw accumulators -> a.add(b)
+ *   G1_TABLE / G2_TABLE to_table29 of an affine point in the 8 x 32 Montgomery form (16 | 32 words in and out) */
+enum {
+  RLNAMD_PROBE_F29_MUL = 0, RLNAMD_PROBE_F29_MUL_ADD, RLNAMD_PROBE_F29_SQR, RLNAMD_PROBE_F29_SQR_ADD,
+  RLNAMD_PROBE_F29_DOT2, RLNAMD_PROBE_F29_DOT2_ADD, RLNAMD_PROBE_F29_DOT3, RLNAMD_PROBE_F29_DOT3_WIDE,
+  RLNAMD_PROBE_F29_DOT4, RLNAMD_PROBE_F29_DOT4_WIDE, RLNAMD_PROBE_F29_DOTN5,
+  RLNAMD_PROBE_F29_SUB_K2, RLNAMD_PROBE_F29_SUB_K4, RLNAMD_PROBE_F29_SUB_K6, RLNAMD_PROBE_F29_SUB_K8,
+  RLNAMD_PROBE_F29_NEG_K2, RLNAMD_PROBE_F29_NEG_K4, RLNAMD_PROBE_F29_NEG_K6, RLNAMD_PROBE_F29_NEG_K8,
+  RLNAMD_PROBE_F29_NORMALIZE, RLNAMD_PROBE_F29_IS_ZERO, RLNAMD_PROBE_F29_SLICE, RLNAMD_PROBE_F29_PACK_REDUCED,
+  RLNAMD_PROBE_F29_FROM_FQ, RLNAMD_PROBE_F29_TO_FQ, RLNAMD_PROBE_F29_MUL_MONT, RLNAMD_PROBE_F29_FROM_CANONICAL,
+  RLNAMD_PROBE_F29_UNPACK29, RLNAMD_PROBE_F29_PACK29_REDUCED,
+  RLNAMD_PROBE_G1_WALK, RLNAMD_PROBE_G2_WALK, RLNAMD_PROBE_G1_ADD, RLNAMD_PROBE_G2_ADD, RLNAMD_PROBE_G1_TABLE,
+  RLNAMD_PROBE_G2_TABLE, RLNAMD_PROBE_F29_OPS
+};
+int rlnamd_probe_f29(int field, uint32_t op, uint32_t in_words, uint32_t out_words, size_t n, const uint32_t* in, uint32_t* out);
+/* rlnamd_probe_witness_op: csrc/witness_ops.h.  in: n x 17 words (graph opcode, a, b: Fr in the 8 x 32 form), out: n x 9
+ * (witness_slow_op's value, its error word).  Mul / Add / Sub, which the interpreters never hand to witness_slow_op,
+ * are answered with the 8 x 32 operators. */
+int rlnamd_probe_witness_op(size_t n, const uint32_t* in, uint32_t* out);
 /* points: n x (x || y) canonical LE affine, all-zero = infinity; scalars: n x 32 bytes canonical LE */
 int rlnamd_msm_set(rlnamd_msm* m, const uint8_t* points_xy_le, const uint8_t* scalars_le, size_t n);
 /* synthetic config-5 workload generated in HBM: P_i = k_i G, scalars s_i, SplitMix64(seed) at index first+i */

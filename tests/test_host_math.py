@@ -1,5 +1,11 @@
-"""CPU build of the product's __host__ __device__ field / curve code (zerokit_amd/csrc/{field,curve}.h, the
-same functions the HIP kernels inline) checked against the Python oracle.  No GPU needed."""
+"""CPU build of the product's __host__ __device__ field / curve code (zerokit_amd/csrc/{field,curve}.h) checked
+against the Python oracle.  No GPU needed.
+
+g++ compiles the host branches only: CIOS on 4 x 64-bit limbs (and the mulx / adcx / adox form) for the product, the C
+carry loops for +, - and reduce_once, the plain sums for dot2 / dot3 / dot4, Karatsuba for Fq2.  The curve formulas,
+inv (modinv30.h) and pow above them are the code the HIP kernels inline; the device branches of those field operations
+(the inline-asm carry chains, the product-scanning mont_dot1..4 of mont_mac.inc) are separate code and are compared with
+Python integers on the device by tests/test_gpu_field_ops.py."""
 import ctypes
 import os
 import random

@@ -11,6 +11,7 @@
 #include <thread>
 #include <string>
 
+#include "arith_probe.h"
 #include "common.h"
 #include "keccak.h"
 #include "keccak_batch.h"
@@ -628,6 +629,21 @@ int rlnamd_poseidon_params_check(const uint8_t* inputs_le, size_t arity, uint8_t
 int rlnamd_selftest_fq29(int group, uint32_t threads, uint32_t iters, const uint8_t* g2_gen_xy_le, uint32_t* mismatches) {
   RLN_TRY
   *mismatches = selftest_fq29(group, threads, iters, g2_gen_xy_le);
+  RLN_CATCH
+}
+int rlnamd_probe_field(int field, uint32_t op, uint32_t in_words, uint32_t out_words, size_t n, const uint32_t* in, uint32_t* out) {
+  RLN_TRY
+  probe_field(field, op, in_words, out_words, n, in, out);
+  RLN_CATCH
+}
+int rlnamd_probe_f29(int field, uint32_t op, uint32_t in_words, uint32_t out_words, size_t n, const uint32_t* in, uint32_t* out) {
+  RLN_TRY
+  probe_f29(field, op, in_words, out_words, n, in, out);
+  RLN_CATCH
+}
+int rlnamd_probe_witness_op(size_t n, const uint32_t* in, uint32_t* out) {
+  RLN_TRY
+  probe_witness_op(n, in, out);
   RLN_CATCH
 }
 int rlnamd_msm_set(rlnamd_msm* m, const uint8_t* points_xy_le, const uint8_t* scalars_le, size_t n) {
