@@ -14,9 +14,11 @@
  *    (ffi_utils.rs:183-185).  In this implementation a CFr is the 32-byte little-endian canonical value.
  *
  * Scope: single and multi message-id circuits, full and partial proofs, the HBM-resident tree with the
- * PmTreeConfig semantics of config_path (path / temporary / tree_depth; a persistent tree is one snapshot file
- * <path>/rlnamd_tree.bin written by ffi_flush and when the object is freed -- not sled's on-disk format, which belongs
- * to a third-party crate).  Depth <= 30: the dense tree in HBM; depth 31 .. 63: a sparse tree (only written nodes are
+ * PmTreeConfig semantics of config_path (path / temporary / tree_depth / flush_every_ms; a persistent tree is the directory
+ * <path>: a checksummed snapshot rlnamd_tree.bin plus a write-ahead journal rlnamd_tree.wal.  Every mutating tree call
+ * appends one record before it is applied, ffi_flush is an fdatasync of the journal, a flusher thread syncs every
+ * flush_every_ms, the journal is folded into a new snapshot as it grows and when the object is freed, and one object at
+ * a time may hold a path -- not sled's on-disk format, which belongs to a third-party crate).  Depth <= 30: the dense tree in HBM; depth 31 .. 63: a sparse tree (only written nodes are
  * kept, hashes in device batches -- OptimalMerkleTree's semantics, utils/src/merkle_tree/optimal_merkle_tree.rs);
  * depth >= 64 is the reference's InvalidDepth.  Replacing a dense tree (ffi_set_tree, ffi_init_tree_with_leaves) builds
  * the new one beside the old when the device can hold both and releases the old one first otherwise.  config_path may also carry "window_bits" and "max_batch" (prover sizing, see

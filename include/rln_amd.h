@@ -164,6 +164,13 @@ int rlnamd_ffi_prover_info(const void* ffi_rln, rlnamd_prover_info* info);
  * (identity secret included) in host memory until the entry is evicted, or the object freed.
  * out: [0] members remembered, [1] proofs that were finishes, [2] proofs from scratch, [3] 1 while a partial proof is pending */
 int rlnamd_ffi_memo_stats(const void* ffi_rln, uint64_t out[4]);
+/* The durable store of a persistent tree (config_path: "temporary": false + "path"): the directory `path`
+ * holds a checksummed snapshot and a write-ahead journal, every mutating tree call appends ONE record before it is applied,
+ * ffi_flush is an fdatasync of the journal and a flusher thread does the same every "flush_every_ms".
+ * out: [0] snapshot generation, [1] journal bytes (header included), [2] records since the snapshot, [3] syncs so far,
+ * [4] compactions so far, [5] records replayed at open, [6] torn bytes discarded at open, [7] appended bytes not yet
+ * synced.  A temporary tree returns all zero. */
+int rlnamd_ffi_tree_store_info(const void* ffi_rln, uint64_t out[8]);
 /* Concurrent callers.  generate_rln_proof takes &self in the reference (rln/src/public.rs:624) and an RLN object may be
  * shared by threads; the prover proves one batch at a time, so the single-proof calls (ffi_generate_rln_proof,
  * ffi_rln_v3_generate_proof and their _with_rs twins) that arrive while a proof is on the device are gathered and go out

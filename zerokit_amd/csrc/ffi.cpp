@@ -35,6 +35,7 @@
 #include "merkle.h"
 #include "tree_any.h"
 #include "tree_config.h"   // TreeConfig, parse_tree_config, tree_config_from_file
+#include "tree_store.h"    // tstore::TreeStore: snapshot + journal of a persistent tree (host only)
 #include "pairing.h"
 #include "poseidon.h"
 #include "prover.h"
@@ -493,11 +494,12 @@ struct FFI_RLN {
   size_t next_index = 0;
   std::vector<uint8_t> leaf_set;  // cached_leaves_indices
   std::vector<uint8_t> metadata;
-  std::string store;              // snapshot file of a persistent tree ("" = temporary tree)
+  // the durable store of a persistent tree (tree_store.h: snapshot + write-ahead journal); null for a temporary tree
+  std::unique_ptr<tstore::TreeStore> st;
 
   ~FFI_RLN() {
     try {
-      flush();  // sled flushes when the database is dropped
+      detach_store();  // sled flushes when the database is dropped
     } catch (...) {
     }
     try {
@@ -547,18 +549,25 @@ struct FFI_RLN {
     next_index = 0;
     metadata.clear();
   }
-  // ffi_set_tree / ffi_init_tree_with_leaves: the stored tree is flushed and replaced by a default (temporary) one
+  // ffi_set_tree / ffi_init_tree_with_leaves: the stored tree is closed (compacted when its journal holds a record) and
+  // replaced by a default (temporary) one
   void replace_with_default_tree(size_t depth) {
-    flush();
-    new_tree(depth);  // throws before anything is dropped
-    store.clear();
+    if (st && st->records() > 0) compact_store();
+    const int old_depth = tree.depth;
+    try {
+      new_tree(depth);  // throws before anything is dropped
+    } catch (...) {
+      if (tree.depth != old_depth) st.reset();   // (new_tree's non-atomic case: the object holds an empty depth-0 tree)
+      throw;
+    }
+    st.reset();   // stops and joins the flusher, releases the lock
   }
   // PmTree::new (pm_tree_adapter.rs:191-239): depth check against the config, load the stored tree when there is
   // one (its depth must match), else start empty; cached_leaves_indices rebuilt from the leaves below next_index
   void open_tree(size_t depth, const TreeConfig& cfg) {
     if (cfg.tree_depth >= 0 && (size_t)cfg.tree_depth != depth)
       throw Error("Merkle tree error: Tree depth exceeds maximum allowed (must be < 64)");  // InvalidDepth
-    store.clear();
+    st.reset();
     // a snapshot holds the dense prefix of leaves below next_index; the sparse tree of depths 31 .. 63 has no such prefix
     // (one leaf at index 2^35 would make it terabytes), so persistence stops at the dense tree
     if (cfg.persistent() && depth > (size_t)TreeAny::MAX_DENSE_DEPTH)
@@ -567,80 +576,141 @@ struct FFI_RLN {
                   " takes the sparse in-memory tree, which has no snapshot form");
     new_tree(depth);
     if (!cfg.persistent()) return;
-    if (mkdir(cfg.path.c_str(), 0777) != 0 && errno != EEXIST)
-      throw Error("Merkle tree error: cannot create " + cfg.path + ": " + strerror(errno));
-    std::string file = cfg.path + "/rlnamd_tree.bin";
-    FILE* f = fopen(file.c_str(), "rb");
-    if (f) {
-      struct { char magic[8]; uint64_t depth, next, meta_len; } h;
-      std::vector<uint8_t> meta, leaves;
-      bool ok = fread(&h, sizeof h, 1, f) == 1 && !memcmp(h.magic, "RLNAMDT1", 8) && h.depth < 64 &&
-                h.next <= ((uint64_t)1 << h.depth) && h.meta_len <= (1u << 30);
-      if (ok) {
-        meta.resize(h.meta_len);
-        leaves.resize(h.next * 32);
-        ok = (meta.empty() || fread(meta.data(), meta.size(), 1, f) == 1) &&
-             (leaves.empty() || fread(leaves.data(), leaves.size(), 1, f) == 1);
-      }
-      fclose(f);
-      if (!ok) throw Error("Merkle tree error: " + file + " is not a tree snapshot of this library");
-      if (h.depth != depth) throw Error("Merkle tree error: Tree depth exceeds maximum allowed (must be < 64)");
-      if (h.next) {
-        tree.set_range_host(0, leaves.data(), h.next);
-        static const uint8_t zero[32] = {0};
-        for (size_t i = 0; i < h.next && !leaf_set.empty(); i++) leaf_set[i] = memcmp(leaves.data() + 32 * i, zero, 32) != 0;
-      }
-      next_index = h.next;
-      metadata = meta;
+    // snapshot + replayed journal arrive as ONE host image and go up in one pass (tree_store.h); a failure below closes
+    // the store again, which releases its lock
+    std::unique_ptr<tstore::TreeStore> opened(new tstore::TreeStore);
+    tstore::Options opt;
+    opt.flush_every_ms = (uint64_t)cfg.flush_every_ms;
+    opt.journal_max_bytes = (uint64_t)cfg.journal_max_bytes;
+    tstore::Image im;
+    opened->open(cfg.path, depth, opt, im);
+    if (im.next) {
+      tree.set_range_host(0, im.leaves.data(), im.next);
+      static const uint8_t zero[32] = {0};
+      for (size_t i = 0; i < im.next && !leaf_set.empty(); i++) leaf_set[i] = memcmp(im.leaves.data() + 32 * i, zero, 32) != 0;
     }
-    store = file;
+    if (im.has_root) {   // nothing was replayed: the tree just built must hash to what the snapshot recorded
+      uint8_t root[32];
+      tree.get_node_host(0, root);
+      if (memcmp(root, im.root, 32)) throw Error("Merkle tree error: " + opened->snap_path() + " is corrupt (root)");
+    }
+    next_index = im.next;
+    metadata = im.meta;
+    opened->start_flusher();
+    st = std::move(opened);
   }
-  void flush() {  // written to a sibling file, then renamed over the snapshot
-    if (store.empty()) return;
+  void flush() {  // ffi_flush: one fdatasync of the journal, whatever the size of the tree
+    if (st) st->sync();
+  }
+  // the tree as it stands becomes the snapshot of the next generation; the journal starts empty
+  void compact_store() {
+    tree.flush_pending();
     std::vector<uint8_t> leaves(next_index * 32);
     if (next_index) tree.get_leaves_host(0, next_index, leaves.data());
-    struct { char magic[8]; uint64_t depth, next, meta_len; } h;
-    memcpy(h.magic, "RLNAMDT1", 8);
-    h.depth = (uint64_t)tree.depth;
-    h.next = next_index;
-    h.meta_len = metadata.size();
-    std::string tmp = store + ".tmp";
-    FILE* f = fopen(tmp.c_str(), "wb");
-    if (!f) throw Error("Merkle tree error: cannot write " + tmp + ": " + strerror(errno));
-    bool ok = fwrite(&h, sizeof h, 1, f) == 1 && (metadata.empty() || fwrite(metadata.data(), metadata.size(), 1, f) == 1) &&
-              (leaves.empty() || fwrite(leaves.data(), leaves.size(), 1, f) == 1);
-    ok = fclose(f) == 0 && ok;
-    if (!ok || rename(tmp.c_str(), store.c_str()) != 0)
-      throw Error("Merkle tree error: cannot write " + store + ": " + strerror(errno));
+    uint8_t root[32];
+    tree.get_node_host(0, root);
+    st->compact(next_index, metadata.data(), metadata.size(), leaves.data(), root);
   }
-  void set_range(size_t start, const std::vector<CFr>& leaves) {  // full_merkle_tree.rs:197-223
+  // freeing the object: a cleanly closed store is one snapshot plus an empty journal.  Should the compaction fail, the
+  // journal still holds every record and the next open replays it; the store is released either way.
+  void detach_store() {
+    if (!st) return;
+    struct Release {
+      std::unique_ptr<tstore::TreeStore>& s;
+      ~Release() { s.reset(); }
+    } release{st};
+    if (st->records() > 0) compact_store();
+  }
+
+  // One write to the tree, as every mutating call ends up: a single leaf (deferred: TreeAny::set_leaf) or a range, then
+  // the cached_leaves_indices marks on top of the written leaves' own.  The mutators below validate and plan; commit()
+  // journals the plan (ONE record per call, so a call is all or nothing after a crash) and only then applies it.
+  struct TreeWrite {
+    bool nothing = true, single = false;
+    size_t start = 0;
+    std::vector<CFr> leaves;
+    size_t clear_lo = 0, clear_hi = 0;   // [lo, hi) unmarked
+    std::vector<size_t> clear_idx;       // then these
+    size_t mark_lo = 0, mark_hi = 0;     // then [lo, hi) marked
+  };
+  void commit(const TreeWrite& w) {
+    if (w.nothing) return;
+    const size_t next_after = std::max(next_index, w.start + w.leaves.size());
+    uint64_t before = 0;
+    if (st) {   // write-ahead: a failing append fails the call with nothing applied
+      before = st->journal_bytes();
+      const uint64_t at = w.start;
+      if (w.single) st->append_scatter(1, &at, w.leaves[0].le, next_after);
+      else st->append_range(w.start, w.leaves.size(), (const uint8_t*)w.leaves.data(), next_after);
+    }
+    try {
+      if (w.single) tree.set_leaf(w.start, w.leaves[0].le);
+      else tree.set_range_host(w.start, (const uint8_t*)w.leaves.data(), w.leaves.size());
+    } catch (...) {
+      if (st) st->rollback(before);
+      throw;
+    }
+    for (size_t i = 0; i < w.leaves.size() && !leaf_set.empty(); i++) leaf_set[w.start + i] = 1;
+    next_index = next_after;
+    if (!leaf_set.empty()) {
+      for (size_t i = w.clear_lo; i < w.clear_hi; i++) leaf_set[i] = 0;
+      for (size_t i : w.clear_idx) leaf_set[i] = 0;
+      for (size_t i = w.mark_lo; i < w.mark_hi; i++) leaf_set[i] = 1;
+    }
+    after_append();
+  }
+  // The journal is compacted once it outgrows its bound.  The call that tipped it over has been journalled and applied, so
+  // a compaction that fails does not fail the call: the journal stays valid and the store itself refuses later appends
+  // if it could not be carried over.
+  void after_append() {
+    if (!st || !st->wants_compaction()) return;
+    try {
+      compact_store();
+    } catch (const std::exception& e) {
+      fprintf(stderr, "librln: tree store: %s\n", e.what());
+    }
+  }
+  void set_metadata(const uint8_t* bytes, size_t len) {
+    if (st) st->append_metadata(bytes, len, next_index);
+    metadata.assign(bytes, bytes + len);
+    after_append();
+  }
+  TreeWrite plan_range(size_t start, const std::vector<CFr>& leaves) {  // full_merkle_tree.rs:197-223
     if (start + leaves.size() > tree.capacity() || start + leaves.size() < start)
       throw Error("set_range got too many leaves");
-    if (leaves.empty()) return;
-    tree.set_range_host(start, (const uint8_t*)leaves.data(), leaves.size());
-    for (size_t i = 0; i < leaves.size() && !leaf_set.empty(); i++) leaf_set[start + i] = 1;
-    next_index = std::max(next_index, start + leaves.size());
+    TreeWrite w;
+    if (leaves.empty()) return w;
+    w.nothing = false;
+    w.start = start;
+    w.leaves = leaves;
+    return w;
   }
   // one leaf (:141-147).  The write is recorded and hashed by the first reader, together with every other write made
   // until then (TreeAny::set_leaf): ONE pass over the union of the dirty paths instead of `depth` dependent hashes per call
-  void set(size_t index, const CFr& leaf) {
+  TreeWrite plan_set(size_t index, const CFr& leaf) {
     if (index >= tree.capacity()) throw Error("set_range got too many leaves");
-    tree.set_leaf(index, leaf.le);
-    if (!leaf_set.empty()) leaf_set[index] = 1;
-    next_index = std::max(next_index, index + 1);
+    TreeWrite w;
+    w.nothing = false;
+    w.single = true;
+    w.start = index;
+    w.leaves.assign(1, leaf);
+    return w;
   }
+  TreeWrite plan_del(size_t index) {  // :271-285; out-of-capacity indices are an error (rln/tests/ffi.rs:1087-1089)
+    if (index >= tree.capacity()) throw Error("Leaf index out of bounds");
+    if (index >= next_index) return TreeWrite();
+    TreeWrite w = plan_set(index, cfr_from_u64(0));
+    w.clear_idx.assign(1, index);
+    return w;
+  }
+  void set_range(size_t start, const std::vector<CFr>& leaves) { commit(plan_range(start, leaves)); }
+  void set(size_t index, const CFr& leaf) { commit(plan_set(index, leaf)); }
+  void del(size_t index) { commit(plan_del(index)); }
   CFr get(size_t index) {
     if (index >= tree.capacity()) throw Error("Leaf index out of bounds");
     CFr r;
     tree.get_node_host(tree.capacity() - 1 + index, r.le);
     return r;
-  }
-  void del(size_t index) {  // :271-285; out-of-capacity indices are an error (rln/tests/ffi.rs:1087-1089)
-    if (index >= tree.capacity()) throw Error("Leaf index out of bounds");
-    if (index < next_index) {
-      set(index, cfr_from_u64(0));
-      if (!leaf_set.empty()) leaf_set[index] = 0;
-    }
   }
   // override_range with the default (pmtree-ft) build's behaviour: empty `indices` allowed
   // (pm_tree_adapter.rs:320-356, validation override_range_validation.rs:20-65)
@@ -659,18 +729,20 @@ struct FFI_RLN {
     if (!indices.empty() && have_end && (indices[0] > start || indices[0] >= end)) throw Error("Invalid indices");
     if (leaves.empty() && indices.empty()) throw Error("Leaf index out of bounds");
     if (indices.empty()) {
-      if (leaves.size() == 1) set(start, leaves[0]); else set_range(start, leaves);
+      commit(leaves.size() == 1 ? plan_set(start, leaves[0]) : plan_range(start, leaves));
       return;
     }
     if (leaves.empty()) {
       if (indices.size() == 1) {
-        del(indices[0]);
+        commit(plan_del(indices[0]));
         return;
       }
       // remove_indices (pm_tree_adapter.rs:417-435): the whole span [first, last] is reset
       size_t s = indices.front(), e = indices.back() + 1;
-      set_range(s, std::vector<CFr>(e - s, cfr_from_u64(0)));
-      for (size_t i = s; i < e && !leaf_set.empty(); i++) leaf_set[i] = 0;
+      TreeWrite w = plan_range(s, std::vector<CFr>(e - s, cfr_from_u64(0)));
+      w.clear_lo = s;
+      w.clear_hi = e;
+      commit(w);
       return;
     }
     // remove_indices_and_set_leaves (pm_tree_adapter.rs:437-480); the merged buffer is written at `start`
@@ -681,10 +753,11 @@ struct FFI_RLN {
       if (!std::binary_search(indices.begin(), indices.end(), i)) vals[i - min_index] = get(i);
     for (size_t i = 0; i < leaves.size(); i++) vals[start - min_index + i] = leaves[i];
     if (start + vals.size() > cap) throw Error("set_range got too many leaves");
-    set_range(start, vals);
-    for (size_t i : indices)
-      if (!leaf_set.empty()) leaf_set[i] = 0;
-    for (size_t i = start; i < end - min_index && i < cap && !leaf_set.empty(); i++) leaf_set[i] = 1;
+    TreeWrite w = plan_range(start, vals);
+    w.clear_idx = indices;
+    w.mark_lo = start;
+    w.mark_hi = std::min(end - min_index, cap);
+    commit(w);
   }
 };
 
@@ -1504,6 +1577,17 @@ int rlnamd_ffi_memo_stats(const void* ffi_rln, uint64_t out[4]) {
   out[3] = r.pending_ticket ? 1 : 0;
   return RLNAMD_OK;
 }
+// EXT (include/rln_amd.h): the durable store of a persistent tree (tree_store.h): [0] snapshot generation, [1] journal
+// bytes, [2] records since the snapshot, [3] syncs so far, [4] compactions so far, [5] records replayed at open, [6] torn
+// bytes discarded at open, [7] appended bytes not yet synced.  A temporary tree: all zero.  The store answers under its
+// own mutex, so the call may run beside tree reads and leaf writes of other threads (not beside one that replaces the tree).
+int rlnamd_ffi_tree_store_info(const void* ffi_rln, uint64_t out[8]) {
+  if (!ffi_rln || !out) return RLNAMD_ERR;
+  const FFI_RLN& r = *(const FFI_RLN*)ffi_rln;
+  memset(out, 0, 8 * sizeof(uint64_t));
+  if (r.st) r.st->info(out);
+  return RLNAMD_OK;
+}
 // EXT (include/rln_amd.h): the gathering of concurrent single-proof calls: [0] batches led, [1] calls that went out in
 // them, [2] the largest batch, [3] the most calls one batch may take (0: off), [4] batches whose leader waited for a
 // recent caller, [5] nanoseconds the leaders spent proving their batches, [6] / [7] batches and calls of the finish queue
@@ -2107,12 +2191,12 @@ void ffi_merkle_proof_free(FFI_MerkleProof_t* proof) {
   free(proof);
 }
 CBoolResult_t ffi_set_metadata(FFI_RLN_t** rln, const Vec_uint8_t* metadata) {
-  return guard_bool([&]() { RLNM(rln).metadata.assign(metadata->ptr, metadata->ptr + metadata->len); return true; });
+  return guard_bool([&]() { RLNM(rln).set_metadata(metadata->ptr, metadata->len); return true; });
 }
 CResult_Vec_uint8_Vec_uint8_t ffi_get_metadata(FFI_RLN_t* const* rln) {
   return guard_bytes([&]() { return RLNM(rln).metadata; });
 }
-CBoolResult_t ffi_flush(FFI_RLN_t** rln) {  // deferred leaf writes are hashed now; persistent trees write their snapshot
+CBoolResult_t ffi_flush(FFI_RLN_t** rln) {  // deferred leaf writes are hashed now; persistent trees sync their journal
   return guard_bool([&]() { RLNM(rln).tree.flush_pending(); RLNM(rln).flush(); return true; });
 }
 

@@ -4,8 +4,9 @@
 // (error.rs:104-208) and the wire formats (enum tag + arkworks field order, protocol/serialize.rs:63-714).
 //
 // Tree flavours: FullMerkleTree, OptimalMerkleTree and PmTree all map to the one HBM-resident tree of merkle.hip
-// (identical roots and proofs, rln/tests/poseidon_tree.rs:14-41); the pm-tree constructors keep no on-disk state
-// (sled persistence is out of scope, SURVEY.md section 8f rank 4) and `flush` is a no-op.
+// (identical roots and proofs, rln/tests/poseidon_tree.rs:14-41); the pm-tree constructor that takes a config file
+// shares FFI_RLN::open_tree and so the durable store of tree_store.h (sled's own on-disk format stays out of scope,
+// SURVEY.md section 8f rank 4); `flush` syncs that store's journal and is a no-op for a temporary tree.
 
 namespace {
 

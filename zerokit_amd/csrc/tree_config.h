@@ -21,14 +21,21 @@ namespace rlnamd {
 // ---- tree persistence --------------------------------------------------------------------------------------------
 // The reference keeps the default (pmtree-ft) tree in a sled database under `path` (pm_tree_adapter.rs:71-176,
 // 191-239).  sled's on-disk format belongs to a third-party crate (sled 0.34.7) that is not in the tree, so the state is
-// kept in ONE snapshot file of our own, `<path>/rlnamd_tree.bin`: the same config keys and lifecycle (load when
-// present, otherwise start empty; written by ffi_flush and when the object is freed), not readable by sled.  The
-// tree itself stays in HBM; a snapshot holds depth, next_index, the metadata bytes and the leaves below next_index.
+// kept in a store of our own (tree_store.h): the DIRECTORY `path`, holding a checksummed snapshot `rlnamd_tree.bin` and a
+// write-ahead journal `rlnamd_tree.wal`.  The same config keys and lifecycle (load when present, otherwise start empty;
+// every mutating call journalled before it is applied, synced by ffi_flush and every "flush_every_ms"), not readable by
+// sled.  The tree itself stays in HBM; a snapshot holds depth, next_index, the metadata bytes and the leaves below
+// next_index.  "cache_capacity", "mode" and "use_compression" tune sled itself: parsed (any value is accepted) and ignored.
 struct TreeConfig {
   std::string path;
   bool has_path = false;
   bool temporary = true;   // DEFAULT_TEMPORARY (pm_tree_adapter.rs:67)
   long tree_depth = -1;
+  // "flush_every_ms": the period of the store's timed journal syncs (absent: 500, the reference's default,
+  // pm_tree_adapter.rs:69; 0: every mutating call syncs before it returns).  "journal_max_bytes": the journal size above
+  // which the store is compacted into a new snapshot (0 / absent: max(1 MiB, bytes of the current snapshot))
+  long flush_every_ms = 500;
+  long journal_max_bytes = 0;
   // prover sizing, keys of THIS backend in the same JSON object (the reference's PmTreeConfig::from_str picks its keys
   // out of a serde_json::Value and ignores the rest, so one config file serves both): "window_bits" = the comb schedule
   // of rlnamd_prover_new (7150114 = the 228 GiB bench schedule), "max_batch" = workspace capacity in proofs.
@@ -205,6 +212,14 @@ inline TreeConfig parse_tree_config(const std::string& js) {
       if (key == "tree_depth") c.tree_depth = num;
       if (key == "window_bits") c.window_bits = num;
       if (key == "max_batch") c.max_batch = num;
+      if (key == "flush_every_ms") {
+        if (num < 0 || num > 3600000) throw Error("Configuration error: flush_every_ms: expected 0 .. 3600000 milliseconds");
+        c.flush_every_ms = num;
+      }
+      if (key == "journal_max_bytes") {
+        if (num < 0) throw Error("Configuration error: journal_max_bytes: expected 0 or a positive number of bytes");
+        c.journal_max_bytes = num;
+      }
       if (key == "failover") {
         if (num < 0 || num > 64) throw Error("Configuration error: failover: expected 0 .. 64 rounds");
         c.failover = num;

@@ -363,6 +363,15 @@ class RLN:
             raise RLNError("rlnamd_ffi_memo_stats failed")
         return dict(zip(("members", "finishes", "from_scratch", "pending"), [int(v) for v in out]))
 
+    def tree_store_info(self):
+        """the durable store of a persistent tree (rlnamd_ffi_tree_store_info): [0] snapshot generation, [1] journal
+        bytes, [2] records since the snapshot, [3] syncs, [4] compactions, [5] records replayed at open, [6] torn bytes
+        discarded at open, [7] appended bytes not yet synced; all zero for a temporary tree"""
+        out = (C.c_uint64 * 8)()
+        if lib().rlnamd_ffi_tree_store_info(self._h, out) != 0:
+            raise RLNError("rlnamd_ffi_tree_store_info failed")
+        return [int(v) for v in out]
+
     def gather_stats(self):
         """concurrent single-proof calls gathered into batches (rlnamd_ffi_gather_stats)"""
         out = (C.c_uint64 * 8)()
@@ -432,11 +441,11 @@ class RLN:
         return _take_bytes(lib().ffi_get_metadata(C.byref(self._h)))
 
     def flush(self):
-        """ffi_flush (ffi_tree.rs): writes a persistent tree's snapshot; nothing to do for a temporary tree"""
+        """ffi_flush (ffi_tree.rs): syncs a persistent tree's journal; nothing to do for a temporary tree"""
         _ok_bool(lib().ffi_flush(C.byref(self._h)))
 
     def close(self):
-        """drop the object now (a persistent tree is flushed, as sled does when the database is dropped)"""
+        """drop the object now (a persistent tree's store is compacted and released, as sled flushes when the database is dropped)"""
         self.__del__()
 
     # ---- zkSNARK APIs (public.rs:595-771)

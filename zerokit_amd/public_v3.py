@@ -320,3 +320,10 @@ class RLNV3(_Handle):
 
     def flush(self):
         _ok_bool(lib().ffi_rln_v3_flush(self._ref()))
+
+    def tree_store_info(self):
+        """the durable store of a persistent tree (rlnamd_ffi_tree_store_info, as RLN.tree_store_info)"""
+        out = (C.c_uint64 * 8)()
+        if lib().rlnamd_ffi_tree_store_info(self._h, out) != 0:
+            raise RLNError("rlnamd_ffi_tree_store_info failed")
+        return [int(v) for v in out]
