@@ -265,7 +265,8 @@ int rlnamd_prover_fetch_h(rlnamd_prover* p, size_t index, uint8_t* out_le);
  * buffers: [0] G1 window digits, [1] G2 window digits, [2] a | b | c (the quotient's operands, then h), [3] / [4] partial
  * sums of the G1 / G2 walks and everything their reduction leaves behind (block sums, the unblinded A / B / C sums, the
  * affine points, the ladder's products and tables), [5] staged inputs + (r, s) + the leaf indices of a batch submitted
- * by member (device and pinned copy).  All zero behind a collect that wipes. */
+ * by member (device and pinned copy) + the witness given with rlnamd_prover_upload_witness.  All zero behind a collect
+ * that wipes, and behind rlnamd_prover_wipe after a resident run. */
 int rlnamd_prover_residue(rlnamd_prover* p, uint64_t out[6]);
 /* ---- partial proofs (generate_partial_zk_proof / finish_zk_proof_with_rs, protocol/proof.rs:783-849;
  * Groth16Partial, partial_proof.rs:108-274).  mode: 0 full proof, 1 partial (inputs hold only identitySecret,
@@ -459,6 +460,15 @@ int rlnamd_probe_f29(int field, uint32_t op, uint32_t in_words, uint32_t out_wor
  * (witness_slow_op's value, its error word).  Mul / Add / Sub, which the interpreters never hand to witness_slow_op,
  * are answered with the 8 x 32 operators. */
 int rlnamd_probe_witness_op(size_t n, const uint32_t* in, uint32_t* out);
+/* rlnamd_probe_quotient_transform: the three steps every vector of the quotient goes through -- inverse transform, x g^i
+ * (g the root of the doubled domain), forward transform (circuit/qap.rs:60-90) -- launched by the function the prover
+ * itself launches them with, at ANY domain size: lds = 0 the passes of ntt_pass_list(logn) (k_ntt_pass / k_ntt_turn, what
+ * a big batch takes), lds = 1 the edge / mid / edge kernels of a small batch.  in / out: vectors x 2^logn x nb canonical
+ * values of 8 words ([vector][index][lane], dense); on the device they sit in the prover's [index][B] layout, nb of the B
+ * lanes live.  An error, before anything is launched: logn outside 1 .. 18, lds with logn outside 9 .. 18, nb = 0 or
+ * nb > B, vectors outside 1 .. 3, more than 2^26 elements in the layout. */
+int rlnamd_probe_quotient_transform(int logn, int lds, uint32_t B, uint32_t nb, uint32_t vectors, const uint32_t* in,
+                                    uint32_t* out);
 /* points: n x (x || y) canonical LE affine, all-zero = infinity; scalars: n x 32 bytes canonical LE */
 int rlnamd_msm_set(rlnamd_msm* m, const uint8_t* points_xy_le, const uint8_t* scalars_le, size_t n);
 /* synthetic config-5 workload generated in HBM: P_i = k_i G, scalars s_i, SplitMix64(seed) at index first+i */

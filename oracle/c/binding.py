@@ -43,6 +43,15 @@ def lib():
         L.oracle_prove_many.restype = C.c_double
         L.oracle_prove_many.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_char_p, C.c_char_p,
                                         C.POINTER(C.c_int)]
+        L.oracle_witness.restype = C.c_int
+        L.oracle_witness.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+        L.oracle_prove_witness.restype = C.c_int
+        L.oracle_prove_witness.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p] + [C.c_char_p] * 3
+        L.oracle_prove_witness_many.restype = C.c_double
+        L.oracle_prove_witness_many.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_char_p,
+                                                C.c_char_p, C.POINTER(C.c_int)]
+        L.oracle_coset_transform.restype = C.c_int
+        L.oracle_coset_transform.argtypes = [C.c_int, C.c_char_p]
         L.oracle_known_mask.restype = None
         L.oracle_known_mask.argtypes = [C.c_void_p, C.c_char_p]
         L.oracle_prove_partial.restype = C.c_int
@@ -230,6 +239,46 @@ class Circuit:
             out["h"] = [int.from_bytes(hb.raw[32 * i:32 * i + 32], "little") for i in range(self.domain)]
         return out
 
+    def witness_packed(self, packed):
+        """the full witness (n_signals ints) of a packed inputs buffer: the graph evaluation alone"""
+        wit = C.create_string_buffer(32 * self.n_signals)
+        rc = lib().oracle_witness(self.h, packed, wit)
+        if rc:
+            raise RuntimeError("oracle_witness rc=%d" % rc)
+        return [int.from_bytes(wit.raw[32 * i:32 * i + 32], "little") for i in range(self.n_signals)]
+
+    def prove_witness(self, witness, r, s, want_h=False):
+        """generate_zk_proof_with_witness: the proof of a supplied witness (n_signals ints below 2^256, reduced mod r;
+        it need not satisfy the circuit).  w_0 is used as given in the witness map; query[0], alpha and beta are added
+        whatever it is.  -> dict(proof, coords[, h])"""
+        assert len(witness) == self.n_signals
+        proof, coords = C.create_string_buffer(128), C.create_string_buffer(256)
+        hb = C.create_string_buffer(32 * self.domain) if want_h else None
+        rc = lib().oracle_prove_witness(self.h, b"".join(_b(v) for v in witness), _b(r) + _b(s), proof, coords, hb)
+        if rc:
+            raise RuntimeError("oracle_prove_witness rc=%d" % rc)
+        out = dict(proof=proof.raw, coords=[int.from_bytes(coords.raw[32 * i:32 * i + 32], "little") for i in range(8)])
+        if hb is not None:
+            out["h"] = [int.from_bytes(hb.raw[32 * i:32 * i + 32], "little") for i in range(self.domain)]
+        return out
+
+    def prove_many_witness(self, witnesses, rs, threads=None, want_h=False):
+        """n proofs of supplied witnesses on host threads -> (seconds, [proof128], [h as bytes, domain x 32] or None)"""
+        n = len(witnesses)
+        assert len(rs) == n and all(len(w) == self.n_signals for w in witnesses)
+        threads = threads or usable_cores()
+        blob = b"".join(_b(v) for w in witnesses for v in w)
+        rsb = b"".join(_b(r) + _b(s) for r, s in rs)
+        proofs = C.create_string_buffer(128 * n)
+        hs = C.create_string_buffer(32 * self.domain * n) if want_h else None
+        rc = C.c_int(0)
+        secs = lib().oracle_prove_witness_many(self.h, blob, rsb, n, threads, proofs, hs, C.byref(rc))
+        if rc.value:
+            raise RuntimeError("oracle_prove_witness_many rc=%d" % rc.value)
+        hb = 32 * self.domain
+        return (secs, [proofs.raw[128 * i:128 * (i + 1)] for i in range(n)],
+                [hs.raw[hb * i:hb * (i + 1)] for i in range(n)] if want_h else None)
+
     def prove_many(self, ws, rs, threads=None):
         """-> (seconds, [proof128], [public_inputs])"""
         n = len(ws)
@@ -253,6 +302,16 @@ def poseidon_batch(rows):
     out = C.create_string_buffer(32 * len(rows))
     lib().oracle_poseidon(buf, len(rows), arity, out)
     return [int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(len(rows))]
+
+
+def coset_transform(logn, values):
+    """iNTT, x g^i, NTT of 2^logn values with the oracle's own transform (oracle_coset_transform) -> list of ints"""
+    assert len(values) == 1 << logn
+    buf = C.create_string_buffer(b"".join(_b(v) for v in values), 32 << logn)
+    if lib().oracle_coset_transform(logn, buf):
+        raise RuntimeError("oracle_coset_transform: logn out of range")
+    raw = buf.raw
+    return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(1 << logn)]
 
 
 def tree_root(depth, leaves):

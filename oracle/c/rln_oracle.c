@@ -604,15 +604,11 @@ static void public_values(const circuit* C, const uint8_t* in, uint8_t* out) {
 /* the public values alone (num_public x 32 B): what a verifier is handed beside the proof */
 void oracle_public_values(void* h, const uint8_t* inputs_le, uint8_t* out) { public_values((const circuit*)h, inputs_le, out); }
 
-/* One proof.  inputs: n_inputs x 32 B (slot 0 = 1); rs: r|s; outputs optional. Returns 0 on success. */
-int oracle_prove(void* hnd, const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* proof128, uint8_t* coords256,
-                 uint8_t* values160, uint8_t* witness_le, uint8_t* h_le) {
-  const circuit* C = (const circuit*)hnd;
+/* The proof of a full assignment w (n_signals values, taken over; freed here): the witness map over all of w, w_0
+ * included as it stands, and query[0], alpha, beta added unconditionally -- ark-groth16's
+ * create_proof_with_reduction_and_matrices, which reads full_assignment[0] inside the witness map only. */
+static int prove_assignment(const circuit* C, fe* w, const uint8_t* rs_le, uint8_t* proof128, uint8_t* coords256, uint8_t* h_le) {
   size_t ns = C->n_signals, n = C->n, nc = C->n_cons, ni = C->n_inst;
-  fe* vals = (fe*)malloc(sizeof(fe) * C->n_nodes); fe* w = (fe*)malloc(sizeof(fe) * ns);
-  int rc = eval_graph(C, inputs_le, vals, w); free(vals);
-  if (rc) { free(w); return rc; }
-  if (witness_le) for (size_t i = 0; i < ns; i++) fe_to_bytes(&FR, witness_le + 32 * i, &w[i]);
   /* qap.rs:30-98 */
   fe* a = (fe*)calloc(n, sizeof(fe)); fe* b = (fe*)calloc(n, sizeof(fe)); fe* c = (fe*)calloc(n, sizeof(fe));
   for (size_t r = 0; r < nc; r++) {
@@ -650,8 +646,59 @@ int oracle_prove(void* hnd, const uint8_t* inputs_le, const uint8_t* rs_le, uint
   if (proof128) { g1_compress(&A, proof128); g2_compress(&B2, proof128 + 32); g1_compress(&Cc, proof128 + 96); }
   if (coords256) { fe_to_bytes(&FQ, coords256, &A.x); fe_to_bytes(&FQ, coords256 + 32, &A.y); fe_to_bytes(&FQ, coords256 + 64, &B2.x.c0); fe_to_bytes(&FQ, coords256 + 96, &B2.x.c1);
     fe_to_bytes(&FQ, coords256 + 128, &B2.y.c0); fe_to_bytes(&FQ, coords256 + 160, &B2.y.c1); fe_to_bytes(&FQ, coords256 + 192, &Cc.x); fe_to_bytes(&FQ, coords256 + 224, &Cc.y); }
-  if (values160) proof_values(C, inputs_le, values160); /* single-message circuits; oracle_public_values serves both */
   free(w); free(a); free(b); free(c); free(ws); free(hs);
+  return 0;
+}
+/* One proof.  inputs: n_inputs x 32 B (slot 0 = 1); rs: r|s; outputs optional. Returns 0 on success. */
+int oracle_prove(void* hnd, const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* proof128, uint8_t* coords256,
+                 uint8_t* values160, uint8_t* witness_le, uint8_t* h_le) {
+  const circuit* C = (const circuit*)hnd;
+  size_t ns = C->n_signals;
+  fe* vals = (fe*)malloc(sizeof(fe) * C->n_nodes); fe* w = (fe*)malloc(sizeof(fe) * ns);
+  int rc = eval_graph(C, inputs_le, vals, w); free(vals);
+  if (rc) { free(w); return rc; }
+  if (witness_le) for (size_t i = 0; i < ns; i++) fe_to_bytes(&FR, witness_le + 32 * i, &w[i]);
+  rc = prove_assignment(C, w, rs_le, proof128, coords256, h_le);
+  if (!rc && values160) proof_values(C, inputs_le, values160); /* single-message circuits; oracle_public_values serves both */
+  return rc;
+}
+/* The graph evaluation alone (calc_witness, circuit/iden3calc.rs:20-60): the full witness of packed inputs, n_signals x 32 B */
+int oracle_witness(void* hnd, const uint8_t* inputs_le, uint8_t* witness_le) {
+  const circuit* C = (const circuit*)hnd;
+  fe* vals = (fe*)malloc(sizeof(fe) * C->n_nodes); fe* w = (fe*)malloc(sizeof(fe) * C->n_signals);
+  int rc = eval_graph(C, inputs_le, vals, w); free(vals);
+  if (!rc) for (size_t i = 0; i < C->n_signals; i++) fe_to_bytes(&FR, witness_le + 32 * i, &w[i]);
+  free(w);
+  return rc;
+}
+/* a 256-bit value mod r, as ark's Fr::from(BigUint) takes it (2^256 < 6 r: at most five subtractions) */
+static void fr_from_bytes_mod(fe* r, const uint8_t* le) {
+  u64 c[4]; memcpy(c, le, 32);
+  while (!gt4(FR.p, c)) sub4(c, c, FR.p);
+  fe_from_u64x4(&FR, r, c);
+}
+/* generate_zk_proof_with_witness (protocol/proof.rs:705-732): the proof of a witness calculated elsewhere -- n_signals x
+ * 32 B, any 256-bit values (reduced mod r), which need not satisfy the circuit.  r and s are reduced the same way. */
+int oracle_prove_witness(void* hnd, const uint8_t* witness_le, const uint8_t* rs_le, uint8_t* proof128, uint8_t* coords256,
+                         uint8_t* h_le) {
+  const circuit* C = (const circuit*)hnd;
+  fe* w = (fe*)malloc(sizeof(fe) * C->n_signals);
+  for (size_t i = 0; i < C->n_signals; i++) fr_from_bytes_mod(&w[i], witness_le + 32 * i);
+  uint8_t rs[64];
+  for (int k = 0; k < 2; k++) { fe t; fr_from_bytes_mod(&t, rs_le + 32 * k); fe_to_bytes(&FR, rs + 32 * k, &t); }
+  return prove_assignment(C, w, rs, proof128, coords256, h_le);
+}
+/* iNTT, x g^i (g of order 2n), NTT over 2^logn values (32 B LE each, reduced mod r), in place: one vector's way through
+ * the witness map (qap.rs:60-90), with the transform the proofs use.  0 on success. */
+int oracle_coset_transform(int logn, uint8_t* data_le) {
+  if (logn < 1 || logn > 27) return 1;
+  circuit* C = (circuit*)calloc(1, sizeof(circuit));
+  C->n_cons = (size_t)1 << logn; C->n_inst = 0; ntt_init(C);
+  fe* v = (fe*)malloc(sizeof(fe) * C->n);
+  for (size_t i = 0; i < C->n; i++) fr_from_bytes_mod(&v[i], data_le + 32 * i);
+  ntt(C, v, 1); for (size_t i = 0; i < C->n; i++) fe_mul(&FR, &v[i], &v[i], &C->coset[i]); ntt(C, v, 0);
+  for (size_t i = 0; i < C->n; i++) fe_to_bytes(&FR, data_le + 32 * i, &v[i]);
+  free(v); free(C->tw); free(C->twi); free(C->coset); free(C);
   return 0;
 }
 
@@ -798,12 +845,18 @@ int oracle_selftest_mul(u64 seed, size_t iters) {
 }
 const char* oracle_mul_kind(void) { return ORACLE_MUL_KIND; }
 
-typedef struct { void* h; const uint8_t *in, *rs; uint8_t *proofs, *values; size_t n, next; pthread_mutex_t* mu; int rc; const uint8_t* partial; } job;
+typedef struct { void* h; const uint8_t *in, *rs; uint8_t *proofs, *values; size_t n, next; pthread_mutex_t* mu; int rc; const uint8_t* partial; int given; uint8_t* hs; } job;
 static void* worker(void* arg) {
   job* J = (job*)arg; size_t ni = oracle_num_inputs(J->h), np = oracle_num_public(J->h);
   for (;;) {
     pthread_mutex_lock(J->mu); size_t i = J->next++; pthread_mutex_unlock(J->mu);
     if (i >= J->n) break;
+    if (J->given) {   /* in: n x n_signals x 32 B of supplied witnesses; hs: optional n x domain x 32 B */
+      size_t ns = oracle_num_signals(J->h), dn = oracle_domain(J->h);
+      int rc = oracle_prove_witness(J->h, J->in + i * ns * 32, J->rs + i * 64, J->proofs ? J->proofs + i * 128 : NULL, NULL, J->hs ? J->hs + i * dn * 32 : NULL);
+      if (rc) J->rc = rc;
+      continue;
+    }
     /* values: num_public x 32 B per proof (160 B for the single-message circuits) */
     int rc = J->partial ? oracle_finish(J->h, J->in + i * ni * 32, J->rs + i * 64, J->partial + i * 320, J->proofs ? J->proofs + i * 128 : NULL)
                         : oracle_prove(J->h, J->in + i * ni * 32, J->rs + i * 64, J->proofs ? J->proofs + i * 128 : NULL, NULL, NULL, NULL, NULL);
@@ -821,14 +874,24 @@ double oracle_prove_many(void* h, const uint8_t* inputs, const uint8_t* rs, size
 double oracle_finish_many(void* h, const uint8_t* inputs, const uint8_t* rs, const uint8_t* partial320, size_t n, int threads, uint8_t* proofs, int* rc_out) {
   return run_many(h, inputs, rs, partial320, n, threads, proofs, NULL, rc_out);
 }
+static double run_job(job* J, int threads, int* rc_out);
 static double run_many(void* h, const uint8_t* inputs, const uint8_t* rs, const uint8_t* partial, size_t n, int threads, uint8_t* proofs, uint8_t* values, int* rc_out) {
-  pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER; job J = {h, inputs, rs, proofs, values, n, 0, &mu, 0, partial};
+  pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER; job J = {h, inputs, rs, proofs, values, n, 0, &mu, 0, partial, 0, NULL};
+  return run_job(&J, threads, rc_out);
+}
+/* n x oracle_prove_witness, one proof per host thread; hs (n x domain x 32 B) may be NULL; returns seconds */
+double oracle_prove_witness_many(void* h, const uint8_t* witnesses, const uint8_t* rs, size_t n, int threads, uint8_t* proofs, uint8_t* hs, int* rc_out) {
+  pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER; job J = {h, witnesses, rs, proofs, NULL, n, 0, &mu, 0, NULL, 1, hs};
+  return run_job(&J, threads, rc_out);
+}
+static double run_job(job* Jp, int threads, int* rc_out) {
+  if (threads < 1) threads = 1;
   struct timespec t0, t1; clock_gettime(CLOCK_MONOTONIC, &t0);
   pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * threads);
-  for (int i = 0; i < threads; i++) pthread_create(&th[i], NULL, worker, &J);
+  for (int i = 0; i < threads; i++) pthread_create(&th[i], NULL, worker, Jp);
   for (int i = 0; i < threads; i++) pthread_join(th[i], NULL);
   clock_gettime(CLOCK_MONOTONIC, &t1); free(th);
-  if (rc_out) *rc_out = J.rc;
+  if (rc_out) *rc_out = Jp->rc;
   return (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
 }
 

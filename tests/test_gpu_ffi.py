@@ -337,6 +337,46 @@ def test_generate_rln_proof_with_witness_ffi():
         rln.generate_rln_proof_with_witness(strs[:-1], w)
 
 
+def test_generate_rln_proof_with_witness_ffi_follows_the_reference_for_w0():
+    """A supplied witness with w_0 = 2: the reference (protocol/proof.rs:705-732 -> ark-groth16's
+    create_proof_with_reduction_and_matrices) adds query[0], alpha and beta unconditionally and uses w_0 only in the witness
+    map, so A and B are those of the honest witness and C moves by D = sum_k (h'_k - h_k) H_k, h' the quotient with
+    w_0 = 2.  The call draws its own (r, s), so the bytes cannot be compared; instead C - D, with D from the oracle (the
+    difference of its two C points at one fixed (r, s)), must verify as the honest proof does -- which holds exactly when
+    the constant row was walked under the scalar one and the quotient used w_0 = 2."""
+    from oracle.c import binding as ob
+    from oracle.pyref import arkzkey
+    from oracle.pyref.bn254 import G1
+    from zerokit_amd import hashers
+    from zerokit_amd.batch import BatchProver
+    from zerokit_amd.public import RLN, RLNWitnessInput
+    rln = RLN(20)
+    secret = 977
+    rln.set_leaf(5, hashers.poseidon_hash_pair(hashers.poseidon_hash([secret]), 20))
+    elems, bits = rln.get_merkle_proof(5)
+    w = RLNWitnessInput(secret, 20, 3, elems, bits, 8642, 9753)
+    wd = dict(identity_secret=secret, user_message_limit=20, message_id=3, path_elements=elems, identity_path_index=bits,
+              x=8642, external_nullifier=9753)
+    o = ob.Circuit(20)
+    calc = o.witness_packed(o.pack(wd))
+    pub = calc[1:6]
+    one = o.prove_witness(calc, 11, 13)["coords"]
+    two = o.prove_witness([2] + calc[1:], 11, 13)["coords"]
+    assert one[:6] == two[:6] and one[6:] != two[6:]
+    D = G1.add((two[6], two[7]), G1.neg((one[6], one[7])))
+    bp = BatchProver(max_batch=64, window_bits=8)
+    try:
+        honest = rln.generate_rln_proof_with_witness([str(v) for v in calc], w).to_bytes_le()[1:129]   # (version byte, proof, values)
+        assert bp.verify_public(honest, pub)
+        got = rln.generate_rln_proof_with_witness(["2"] + [str(v) for v in calc[1:]], w).to_bytes_le()[1:129]
+        assert not bp.verify_public(got, pub)
+        A, Bp, Cp = arkzkey.proof_decompress(got)
+        moved = arkzkey.proof_compress(A, Bp, G1.add(Cp, G1.neg(D)))
+        assert bp.verify_public(moved, pub)
+    finally:
+        bp.close()
+
+
 def test_seeded_keygen_ffi():
     """rln/tests/ffi_utils.rs:8-66 and rln/tests/protocol.rs:463-540"""
     from zerokit_amd import hashers

@@ -4,9 +4,9 @@ those shapes: 129 proofs -- above lanechunk_max = 128 and ntt_lg_max = 96 -- whi
 live lane.  Default tables, max_batch 192, every shipped circuit.  Bit-exact everywhere (integer arithmetic).
 
 Turn widths: a circuit's domain has 2^logn points and the turn takes ((logn - 1) mod 3) + 1 levels; each test prints the
-logn and the width it ran.  A width that no shipped circuit reaches is covered by the host replay only
-(tests/test_ntt_plan_host.py: logn 3, 4, 5 are widths 3, 1, 2) -- test_the_turn_widths_the_shipped_circuits_reach says
-which."""
+logn and the width it ran.  A width that no shipped circuit reaches runs on the device in the transform probe
+(tests/test_gpu_transform_probe.py: the same launches at logn 1 .. 14, against Python integers) and in the host replay of
+the index formulas (tests/test_ntt_plan_host.py) -- test_the_turn_widths_the_shipped_circuits_reach says which."""
 import ctypes as C
 import json
 import os
@@ -173,7 +173,8 @@ def test_h_of_the_golden_cases_in_a_big_batch_equals_the_golden_digest():
 
 
 def test_the_turn_widths_the_shipped_circuits_reach():
-    """which widths the tests above ran on the device; the rest is the host replay's (tests/test_ntt_plan_host.py)"""
+    """which widths the tests above ran on the device inside whole proofs; the probe runs every width on the device
+    (tests/test_gpu_transform_probe.py), the host replay every index formula (tests/test_ntt_plan_host.py)"""
     from zerokit_amd.batch import BatchProver
     seen = {}
     for depth, multi in CIRCUITS:
@@ -184,6 +185,6 @@ def test_the_turn_widths_the_shipped_circuits_reach():
         if not c:
             p.close()
     widths = {w for _, w in seen.values()}
-    print("logn and turn width per circuit:", seen, "-- widths covered by the host replay only:", sorted({1, 2, 3} - widths))
+    print("logn and turn width per circuit:", seen, "-- widths no shipped circuit reaches (run on the device by the transform probe):", sorted({1, 2, 3} - widths))
     assert seen[(20, False)] == (13, 1)     # the headline circuit: 3, 3, 3, 3 | turn(1) | 3, 3, 3, 3
     assert widths <= {1, 2, 3}

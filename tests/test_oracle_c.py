@@ -185,3 +185,69 @@ def test_c_field_product_forms_agree():
     it replaced, both fields, random and edge operands"""
     assert ob.lib().oracle_selftest_mul(0xC0FFEE, 300000) == 1
     assert ob.lib().oracle_mul_kind() in (b"mulx/adcx/adox", b"portable (unsigned __int128)")
+
+
+def _honest_witness_depth10(c):
+    from zerokit_amd import workload
+    named, rs = workload.circuit_range(7, 1, 10, False)
+    packed = c.pack_named(named[0])
+    w = c.witness_packed(packed)
+    assert w == c.prove_packed(packed, rs[0][0], rs[0][1], want_witness=True)["witness"]
+    return w, rs[0], packed
+
+
+def test_c_prove_witness_vs_pyref_on_adversarial_witnesses():
+    """oracle_prove_witness (generate_zk_proof_with_witness: the proof of a SUPPLIED witness, which need not satisfy the
+    circuit) against oracle.pyref.groth16.prove + arkzkey.proof_compress on the depth-10 circuit: the all-zero witness with
+    r = s = 0 (A, B from the constant terms alone, C the point at infinity: the 0x40 flag byte), every value r - 1 with
+    (r, s) = (r - 1, 1), an honest witness, and the honest witness with w_0 = 2 -- w_0 enters the witness map as given,
+    query[0], alpha and beta are added whatever it is (ark-groth16's create_proof_with_reduction_and_matrices).  h too.
+    The threaded form returns the same bytes; values of 2^256 - 1 and r + 5 are taken mod r."""
+    from oracle.pyref import arkzkey, groth16
+    zk, _ = o_rln.load_circuit(10)
+    c = ob.Circuit(10)
+    ns = c.n_signals
+    honest, hrs, packed = _honest_witness_depth10(c)
+    assert honest[0] == 1
+    cases = [("zero", [0] * ns, (0, 0)), ("r-1", [R - 1] * ns, (R - 1, 1)), ("honest", honest, hrs),
+             ("honest_w0_2", [2] + honest[1:], hrs)]
+    got = {}
+    for name, w, (r, s) in cases:
+        o = c.prove_witness(w, r, s, want_h=True)
+        A, B, Cc = groth16.prove(zk, w, r, s)
+        assert o["proof"] == arkzkey.proof_compress(A, B, Cc), name
+        assert o["h"] == groth16.witness_map(zk, w), name
+        if name == "zero":
+            assert Cc is None and o["proof"][96:] == bytes(31) + b"\x40" and not any(o["h"])
+        got[name] = o
+    # an honest witness proved from its values is the proof made from its inputs; w_0 = 2 changes h and the bytes
+    assert got["honest"]["proof"] == c.prove_packed(packed, hrs[0], hrs[1])["proof"]
+    assert got["honest_w0_2"]["proof"] != got["honest"]["proof"] and got["honest_w0_2"]["h"] != got["honest"]["h"]
+    _, many, hs = c.prove_many_witness([w for _, w, _ in cases], [rs for _, _, rs in cases], threads=3, want_h=True)
+    assert many == [got[name]["proof"] for name, _, _ in cases]
+    assert [[int.from_bytes(h[32 * i:32 * i + 32], "little") for i in range(c.domain)] for h in hs] == \
+        [got[name]["h"] for name, _, _ in cases]
+    big = [(1 << 256) - 1 if i % 3 == 0 else v + R if v + R < 1 << 256 else v for i, v in enumerate(honest)]
+    assert c.prove_witness(big, hrs[0] + R, hrs[1])["proof"] == \
+        c.prove_witness([v % R for v in big], hrs[0], hrs[1])["proof"]
+
+
+def test_c_coset_transform_vs_pyref():
+    """oracle_coset_transform (iNTT, x g^i, NTT with the oracle's own ntt) against pyref's ntt in Python integers, logn
+    1 .. 12: random vectors, all r - 1, a single r - 1"""
+    from oracle.pyref import groth16
+    rnd = random.Random(18)
+    for logn in range(1, 13):
+        n = 1 << logn
+        g = groth16.root_of_unity(2 * n)
+        vecs = [[rnd.randrange(R) for _ in range(n)]]
+        if logn <= 8:
+            vecs += [[R - 1] * n, [0] * (n - 1) + [R - 1]]
+        for v in vecs:
+            t = groth16.ntt(v, inverse=True)
+            p = 1
+            for i in range(n):
+                t[i] = t[i] * p % R
+                p = p * g % R
+            assert ob.coset_transform(logn, v) == groth16.ntt(t), logn
+    assert ob.lib().oracle_coset_transform(0, b"") == 1 and ob.lib().oracle_coset_transform(28, b"") == 1

@@ -176,6 +176,8 @@ SIGNATURES = {
     "rlnamd_probe_field": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rlnamd_probe_f29": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rlnamd_probe_witness_op": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rlnamd_probe_quotient_transform": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                  C.c_void_p]),
     "rlnamd_msm_free": (None, [P]),
     "rlnamd_msm_set": (C.c_int, [P, C.c_char_p, C.c_char_p, C.c_size_t]),
     "rlnamd_msm_generate": (C.c_int, [P, C.c_uint64, C.c_uint64, C.c_size_t]),

@@ -353,9 +353,15 @@ class BatchProver:
         check(lib().rlnamd_prover_upload_partial(self._h, len(partials), b"".join(partials)))
 
     def prove_with_witness(self, witnesses, rs, calculated):
-        """generate_zk_proof_with_witness for a batch: `calculated` = per proof the full witness (ints)"""
-        n = self.upload(self.pack_inputs(witnesses), rs)
-        blob = b"".join(int(v).to_bytes(32, "little") for w in calculated for v in w)
+        """generate_zk_proof_with_witness for a batch: `calculated` = per proof the full witness (ints below 2^256, taken
+        mod r; or all of them as bytes, 32 little-endian bytes per value).  The witness need not satisfy the circuit: w_0
+        enters the quotient as given, the constant row (query[0], alpha, beta) is added whatever it is.  `witnesses`: the
+        inputs (pack_inputs' dicts, or packed bytes) -- the proof values of a single-message circuit come from them."""
+        n = self.upload(witnesses if isinstance(witnesses, (bytes, bytearray)) else self.pack_inputs(witnesses), rs)
+        blob = bytes(calculated) if isinstance(calculated, (bytes, bytearray)) else \
+            b"".join(int(v).to_bytes(32, "little") for w in calculated for v in w)
+        if len(blob) != n * int(self.info.num_signals) * 32:
+            raise RLNError("prove_with_witness: one full witness per proof expected")
         check(lib().rlnamd_prover_upload_witness(self._h, n, blob))
         check(lib().rlnamd_prover_run_mode(self._h, n, 0))
         return self.download(n)

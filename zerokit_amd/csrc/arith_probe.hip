@@ -18,6 +18,8 @@
 #include "curve.h"
 #include "fq29.h"
 #include "poseidon.h"
+#include "prover_kernels.h"
+#include "prover_plan.h"
 #include "witness_ops.h"
 
 namespace rlnamd {
@@ -327,6 +329,26 @@ __global__ void __launch_bounds__(64) k_probe_witness_op(size_t n, const uint32_
   out[t * 9 + 8] = err;
 }
 
+// ---- the quotient's transforms ------------------------------------------------------------------------------------
+// canonical values, dense [vector][index][lane] with nb lanes <-> Montgomery, [vector][index][B] (the prover's layout);
+// one thread per value, lanes of a wave on consecutive lanes of the layout
+__global__ void __launch_bounds__(64) k_probe_lanes_in(const uint32_t* __restrict__ in, Fr* __restrict__ data, size_t rows,
+                                                        uint32_t B, uint32_t nb) {
+  const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (t >= rows * nb) return;
+  const size_t row = t / nb;
+  const uint32_t p = (uint32_t)(t % nb);
+  data[row * B + p] = Fr::from_canonical(in + t * 8);
+}
+__global__ void __launch_bounds__(64) k_probe_lanes_out(const Fr* __restrict__ data, uint32_t* __restrict__ out, size_t rows,
+                                                         uint32_t B, uint32_t nb) {
+  const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (t >= rows * nb) return;
+  const size_t row = t / nb;
+  const uint32_t p = (uint32_t)(t % nb);
+  data[row * B + p].to_canonical(out + t * 8);
+}
+
 constexpr size_t PROBE_MAX_TUPLES = (size_t)1 << 22;
 
 template <class L>
@@ -383,6 +405,33 @@ void probe_f29(int field, uint32_t op, uint32_t in_words, uint32_t out_words, si
     else if (field == 0) hipLaunchKernelGGL((k_probe_f29<Fr29, Fr, Fr29C>), g, b, 0, 0, op, in_words, out_words, n, di, dq);
     else hipLaunchKernelGGL((k_probe_f29<Fq29, Fq, Fq29C>), g, b, 0, 0, op, in_words, out_words, n, di, dq);
   });
+}
+
+void probe_quotient_transform(int logn, int lds, uint32_t B, uint32_t nb, uint32_t vectors, const uint32_t* in, uint32_t* out) {
+  if (logn < 1 || logn > 18) throw Error("probe_quotient_transform: logn is 1 .. 18");
+  if (lds && logn < 9) throw Error("probe_quotient_transform: the LDS kernels take logn 9 .. 18");
+  if (nb < 1 || nb > B) throw Error("probe_quotient_transform: 1 <= nb <= B");
+  if (vectors < 1 || vectors > 3) throw Error("probe_quotient_transform: 1 .. 3 vectors");
+  if (!in || !out) throw Error("probe: null buffer");
+  const size_t n = (size_t)1 << logn, rows = (size_t)vectors * n;
+  if (rows * B > ((size_t)1 << 26)) throw Error("probe_quotient_transform: more than 2^26 elements in the layout");
+  require_gpu();
+  const NttTables T = ntt_tables(logn);
+  const std::vector<NttPass> passes = ntt_pass_list(logn);
+  DevBuf<Fr> tw_i(T.tw_i.size()), tw_f(T.tw_f.size()), coset(T.coset.size()), data(rows * B);
+  DevBuf<uint32_t> din(rows * nb * 8), dout(rows * nb * 8);
+  RLN_HIP(hipMemcpy(tw_i.p, T.tw_i.data(), T.tw_i.size() * sizeof(Fr), hipMemcpyHostToDevice));
+  RLN_HIP(hipMemcpy(tw_f.p, T.tw_f.data(), T.tw_f.size() * sizeof(Fr), hipMemcpyHostToDevice));
+  RLN_HIP(hipMemcpy(coset.p, T.coset.data(), T.coset.size() * sizeof(Fr), hipMemcpyHostToDevice));
+  RLN_HIP(hipMemcpy(din.p, in, rows * nb * 32, hipMemcpyHostToDevice));
+  RLN_HIP(hipMemset(data.p, 0, rows * B * sizeof(Fr)));
+  const dim3 grid((uint32_t)div_up(rows * nb, 64));
+  hipLaunchKernelGGL(k_probe_lanes_in, grid, dim3(64), 0, 0, (const uint32_t*)din.p, data.p, rows, B, nb);
+  RLN_HIP(hipGetLastError());
+  launch_quotient_transform(lds != 0, passes, data.p, tw_i.p, tw_f.p, logn, coset.p, B, nb, vectors, 0);
+  hipLaunchKernelGGL(k_probe_lanes_out, grid, dim3(64), 0, 0, (const Fr*)data.p, dout.p, rows, B, nb);
+  RLN_HIP(hipGetLastError());
+  RLN_HIP(hipMemcpy(out, dout.p, rows * nb * 32, hipMemcpyDeviceToHost));
 }
 
 void probe_witness_op(size_t n, const uint32_t* in, uint32_t* out) {

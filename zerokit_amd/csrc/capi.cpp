@@ -641,6 +641,12 @@ int rlnamd_probe_f29(int field, uint32_t op, uint32_t in_words, uint32_t out_wor
   probe_f29(field, op, in_words, out_words, n, in, out);
   RLN_CATCH
 }
+int rlnamd_probe_quotient_transform(int logn, int lds, uint32_t B, uint32_t nb, uint32_t vectors, const uint32_t* in,
+                                    uint32_t* out) {
+  RLN_TRY
+  probe_quotient_transform(logn, lds, B, nb, vectors, in, out);
+  RLN_CATCH
+}
 int rlnamd_probe_witness_op(size_t n, const uint32_t* in, uint32_t* out) {
   RLN_TRY
   probe_witness_op(n, in, out);

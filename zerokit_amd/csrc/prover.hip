@@ -201,7 +201,9 @@ struct Prover::Impl {
 
   uint32_t N = 0, NS = 0, NI = 0, nc = 0, ni = 0, n = 0;
   int logn = 0;
-  DevBuf<uint32_t> sig2node;
+  DevBuf<uint32_t> sig2node;     // witness signal -> its row of V (the node's row; a row behind them for a later signal of an aliased node)
+  DevBuf<uint32_t> alias_src, alias_dst;
+  uint32_t n_alias = 0;
   DevBuf<uint32_t> a_ptr, a_col, b_ptr, b_col;
   DevBuf<uint32_t> mv_long;       // rows with more than MV_LONG entries in A or B
   uint32_t n_mv_long = 0;
@@ -671,7 +673,30 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
       RLN_HIP(hipStreamSynchronize(s));
     }
   }
-  D.sig2node.assign(graph_.signals, s);
+  // One row of V per witness SIGNAL.  Signals that alias one graph node (the multi-message-id circuit: six nodes under
+  // four signals each) hold one value in a calculated witness, but a supplied one (upload_witness) may give each its own,
+  // and the reference reads the assignment by signal: the later signals of such a node get rows of their own behind the
+  // nodes' rows, filled from the node's row behind the interpreter (k_alias_rows) and overwritten by a supplied witness.
+  std::vector<uint32_t> sig_row = graph_.signals;
+  {
+    std::vector<uint8_t> taken(D.N, 0);
+    std::vector<uint32_t> src, dst;
+    for (uint32_t j = 0; j < D.NS; j++) {
+      const uint32_t node = graph_.signals[j];
+      if (taken[node]) {
+        sig_row[j] = D.N + (uint32_t)dst.size();
+        src.push_back(node);
+        dst.push_back(sig_row[j]);
+      }
+      taken[node] = 1;
+    }
+    D.n_alias = (uint32_t)dst.size();
+    if (D.n_alias) {
+      D.alias_src.assign(src, s);
+      D.alias_dst.assign(dst, s);
+    }
+  }
+  D.sig2node.assign(sig_row, s);
 
   // ---- matrices as CSR over graph node ids
   auto csr = [&](const std::vector<SparseRow>& m, DevBuf<uint32_t>& ptr, DevBuf<uint32_t>& col, DevBuf<Fr>& coef) {
@@ -679,7 +704,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     std::vector<Fr> hv;
     for (uint32_t r = 0; r < D.nc; r++) {
       for (size_t k = 0; k < m[r].col.size(); k++) {
-        hc.push_back(graph_.signals[m[r].col[k]]);
+        hc.push_back(sig_row[m[r].col[k]]);
         hv.push_back(m[r].coeff[k]);
       }
       hp[r + 1] = (uint32_t)hc.size();
@@ -814,7 +839,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     S.coords.alloc(B * 64);
     S.values.alloc(B * 40);
     S.comp.alloc(B * 128);
-    S.V.alloc((size_t)D.N * B);
+    S.V.alloc((size_t)(D.N + D.n_alias) * B);
     S.V29.alloc(((size_t)D.nstore29 + 1) * 3 * B);   // + the trash row of k_witness_lanes
     S.abc.alloc(3 * (size_t)D.n * B);
     S.digits.alloc((size_t)(3 * D.NS + D.n + 4) * D.nh * D.ws.W * B);   // + s w_i, r w_i, r s of the fused small-batch plan
@@ -942,13 +967,13 @@ void Prover::upload_witness(size_t n, const uint8_t* w_le) {
   D.wgiven_n = n;
 }
 
-// iNTT (DIF) + g^i / n + NTT (DIT) over the three vectors with lanes = proofs, by the pass list of prover_plan.h
+// iNTT (DIF) + g^i / n + NTT (DIT) over `vectors` vectors with lanes = proofs, by the pass list of prover_plan.h
 static void launch_ntt(const std::vector<NttPass>& passes, Fr* data, const Fr* tw_i, const Fr* tw_f, int logn, const Fr* scale,
-                       uint32_t B, uint32_t nb, hipStream_t s) {
+                       uint32_t B, uint32_t nb, uint32_t vectors, hipStream_t s) {
   for (const NttPass& ps : passes) {
     // one wave per workgroup: a 4-wave workgroup needs four free wave slots on one CU at the same moment, which the
     // single-wave MSM workgroups streaming through the chip never leave (measured: mat-vec 0.6 -> 32 ms, NTT 5 -> 19 ms)
-    const dim3 block(64, 1), grid(div_up(nb, 64), (1u << logn) >> ps.k, 3);
+    const dim3 block(64, 1), grid(div_up(nb, 64), (1u << logn) >> ps.k, vectors);
     if (ps.kind == NTT_TURN) {
       switch (ps.k) {
         case 1: hipLaunchKernelGGL(k_ntt_turn<1>, grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
@@ -964,6 +989,23 @@ static void launch_ntt(const std::vector<NttPass>& passes, Fr* data, const Fr* t
     }
     RLN_HIP(hipGetLastError());
   }
+}
+
+// The transforms of the quotient, either way the prover launches them (prover_kernels.h): Prover::enqueue and the probe
+// of arith_probe.hip (rlnamd_probe_quotient_transform) both come through here.
+void launch_quotient_transform(bool lds, const std::vector<NttPass>& passes, Fr* data, const Fr* tw_i, const Fr* tw_f,
+                               int logn, const Fr* coset, uint32_t B, uint32_t nb, uint32_t vectors, hipStream_t s) {
+  if (!lds) {
+    launch_ntt(passes, data, tw_i, tw_f, logn, coset, B, nb, vectors, s);
+    return;
+  }
+  if (logn < 9 || logn > 18) throw Error("the LDS transforms take domains of 2^9 .. 2^18 points");
+  // iNTT, coset scaling and NTT as edge / mid / edge: one butterfly per lane per level (prover_front.hip: k_ntt_mid)
+  const dim3 grid(nb, (1u << logn) >> 9, vectors);
+  if (logn > 9) hipLaunchKernelGGL(k_ntt_edge<true>, grid, dim3(256), 0, s, data, tw_i, logn, B, nb);
+  hipLaunchKernelGGL(k_ntt_mid, grid, dim3(256), 0, s, data, tw_i, tw_f, logn, coset, B, nb);
+  if (logn > 9) hipLaunchKernelGGL(k_ntt_edge<false>, grid, dim3(256), 0, s, data, tw_f, logn, B, nb);
+  RLN_HIP(hipGetLastError());
 }
 
 // Enqueue one batch; returns as soon as the work is queued.  Stage A (stream sA): proof values, witness,
@@ -1576,6 +1618,9 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   else
     hipLaunchKernelGGL(k_v29_to_fr, dim3(pg, D.nstore29), dim3(64, 1), 0, sA, S.V29.p, D.slot2node.p, D.nstore29, S.V.p,
                        B, nbp);
+  if (D.n_alias)   // (the lanes k_v29_to_fr filled: the padded lanes of a big batch hold valid values too, their digits are read)
+    hipLaunchKernelGGL(k_alias_rows, dim3(pg, D.n_alias), dim3(64), 0, sA, S.V.p, D.alias_src.p, D.alias_dst.p, D.n_alias, B,
+                       small ? nb : nbp);
   if (hinted)
     hipLaunchKernelGGL(k_hint_check, dim3(div_up(D.n_cut, 64), nb), dim3(64), 0, sA, S.V.p, D.cut_node.p, D.cut_hint.p, D.n_cut,
                        S.h_hints, D.n_hints, B, S.err.p);
@@ -1641,16 +1686,9 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     // (above ~100 proofs the walks beside the quotient chain leave the 4-wave workgroups of the LDS kernels waiting for
     // four free wave slots on one CU: the single-wave passes then finish earlier -- 128 proofs 13.3 -> 12.6 ms, 96 and
     // below no better or worse; RLNAMD_NTT_LG_MAX)
-    if (sh.ntt_lds) {
-      // iNTT, coset scaling and NTT as edge / mid / edge: one butterfly per lane per level (prover_front.hip: k_ntt_mid)
-      const dim3 grid(nb, D.n >> 9, 3);
-      if (D.logn > 9) hipLaunchKernelGGL(k_ntt_edge<true>, grid, dim3(256), 0, sA2, S.abc.p, D.tw_i.p, D.logn, B, nb);
-      hipLaunchKernelGGL(k_ntt_mid, grid, dim3(256), 0, sA2, S.abc.p, D.tw_i.p, D.tw_f.p, D.logn, D.coset.p, B, nb);
-      if (D.logn > 9) hipLaunchKernelGGL(k_ntt_edge<false>, grid, dim3(256), 0, sA2, S.abc.p, D.tw_f.p, D.logn, B, nb);
-      RLN_HIP(hipGetLastError());
-    } else {
-      launch_ntt(D.ntt_passes, S.abc.p, D.tw_i.p, D.tw_f.p, D.logn, D.coset.p, B, nbp, sA2);
-    }
+    // (the LDS kernels have one lane per butterfly and take the batch's size; the passes, lanes = proofs, its padded size)
+    launch_quotient_transform(sh.ntt_lds, D.ntt_passes, S.abc.p, D.tw_i.p, D.tw_f.p, D.logn, D.coset.p, B,
+                              sh.ntt_lds ? nb : nbp, 3, sA2);
     // (the recode below forms h = a o b - c itself)
   }
   MARK(4, sA2);
@@ -2056,6 +2094,7 @@ void Prover::residue(uint64_t out[RESIDUE_FIELDS]) {
   count(4, S.affB2.p, S.affB2.bytes());
   count(5, S.inputs.p, S.inputs.bytes());
   count(5, S.rs.p, S.rs.bytes());
+  count(5, D.wgiven.p, D.wgiven.bytes());   // a supplied witness (upload_witness): wiped with the resident inputs
   count(5, S.idx.p, S.idx.bytes());   // the leaf indices of a batch submitted by member, device and (below) pinned copy
   RLN_HIP(hipGetLastError());
   unsigned long long h[RESIDUE_FIELDS];

@@ -368,7 +368,8 @@ __global__ void k_gather_col(const Fr* __restrict__ src, const uint32_t* __restr
 }
 
 // generate_zk_proof_with_witness (protocol/proof.rs:705-732): an externally calculated witness replaces the
-// graph interpreter's.  given = [proof][signal] canonical LE; each signal is stored at the node it aliases.
+// graph interpreter's.  given = [proof][signal] canonical LE (any 256-bit value: taken mod r); each signal is stored at
+// its own row (sig2node).
 __global__ void k_scatter_witness(const uint32_t* __restrict__ given, const uint32_t* __restrict__ sig2node,
                                   uint32_t NS, Fr* __restrict__ V, uint32_t* __restrict__ err, uint32_t B, uint32_t nb) {
   uint32_t p = blockIdx.x * 64 + threadIdx.x;
@@ -376,6 +377,14 @@ __global__ void k_scatter_witness(const uint32_t* __restrict__ given, const uint
   if (p >= nb || j >= NS) return;
   V[(size_t)sig2node[j] * B + p] = Fr::from_canonical(given + ((size_t)p * NS + j) * 8);
   if (j == 0) err[p] = WERR_NONE;
+}
+
+// the rows of the later signals of an aliased node (prover.hip: sig2node), from the node's row
+__global__ void __launch_bounds__(64) k_alias_rows(Fr* __restrict__ V, const uint32_t* __restrict__ src,
+                                                   const uint32_t* __restrict__ dst, uint32_t count, uint32_t B, uint32_t nb) {
+  const uint32_t p = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y;
+  if (p >= nb || k >= count) return;
+  V[(size_t)dst[k] * B + p] = V[(size_t)src[k] * B + p];
 }
 
 // Streamed inputs: the batch's inputs, (r, s) and partial points move from the slot's pinned staging buffer to its device

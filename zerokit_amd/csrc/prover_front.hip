@@ -569,8 +569,9 @@ __device__ __forceinline__ void emit_digits(uint32_t* l, bool neg, const WinSche
     out[(size_t)j * B] = (int16_t)(neg ? -d : d);
   }
 }
-// Scalar ids: [0, ns) witness signals, [ns, ns + n) quotient coefficients h, then r, s, -(r s).  dig1 holds the G1
-// schedule for all of them; dig2 the G2 schedule for the ones the G2 walk uses (witness, r, s, -(r s): id - n).
+// Scalar ids: [0, ns) witness signals (id 0: the constant one, not w_0), [ns, ns + n) quotient coefficients h, then
+// r, s, -(r s).  dig1 holds the G1 schedule for all of them; dig2 the G2 schedule for the ones the G2 walk uses
+// (witness, r, s, -(r s): id - n).
 // Every scalar is split as k1 + lambda k2 (glv.h) and both halves are recoded.
 __global__ void __launch_bounds__(256) k_recode(const Fr* __restrict__ V, const uint32_t* __restrict__ sig2node,
                                                 uint32_t ns, const Fr* H, uint32_t n,
@@ -601,14 +602,18 @@ __global__ void __launch_bounds__(256) k_recode(const Fr* __restrict__ V, const 
   if (sid >= ns + n + 3) {
     const uint32_t q = sid - (ns + n + 3);
     const Fr r = Fr::from_canonical(rs + (size_t)p * 16), s = Fr::from_canonical(rs + (size_t)p * 16 + 8);
+    // (id 0: the constant row, see below -- s and r themselves)
     if (q < ns)
-      x = s * V[(size_t)sig2node[q] * B + p];
+      x = q == 0 ? s : s * V[(size_t)sig2node[q] * B + p];
     else if (q < 2 * ns)
-      x = r * V[(size_t)sig2node[q - ns] * B + p];
+      x = q == ns ? r : r * V[(size_t)sig2node[q - ns] * B + p];
     else
       x = r * s;
   } else if (sid < ns) {
-    x = V[(size_t)sig2node[sid] * B + p];
+    // id 0 is the scalar of the constant row -- query[0], alpha, beta -- which the reference adds unconditionally
+    // (ark-groth16 create_proof_with_reduction_and_matrices): ONE, whatever a supplied witness holds in w_0.  The mat-vec
+    // reads w_0 from the witness as given (the witness map's full_assignment[0]).
+    x = sid == 0 ? Fr::one() : V[(size_t)sig2node[sid] * B + p];
   } else if (sid < ns + n) {
     const size_t o = (size_t)(sid - ns) * B + p;
     // hq (every full proof and finish; a flag of its own: lg also selects the lane mapping): the quotient on the fly,

@@ -14,6 +14,7 @@
 #include "poseidon.h"
 #include "prover.h"
 #include "prover_desc.h"
+#include "prover_plan.h"
 #include "walk29.h"
 #include "witness_ops.h"
 
@@ -42,6 +43,12 @@ constexpr uint32_t SUM_TREE_LDS_G1 = SUM_TREE_LANES / 2 * 4 * 9 * 4, SUM_TREE_LD
 #ifndef RLN_NTT_WAVES
 #define RLN_NTT_WAVES 1
 #endif
+
+// ---- the quotient's transforms (prover.hip): iNTT, coset scaling, NTT over `vectors` vectors of 2^logn points in the
+// [index][B] layout, nb live lanes -- lds: k_ntt_edge / k_ntt_mid / k_ntt_edge (2^9 .. 2^18 points); otherwise the pass list
+// (ntt_pass_list(logn)) through k_ntt_pass / k_ntt_turn.  The one place either form is launched from.
+void launch_quotient_transform(bool lds, const std::vector<NttPass>& passes, Fr* data, const Fr* tw_i, const Fr* tw_f,
+                               int logn, const Fr* coset, uint32_t B, uint32_t nb, uint32_t vectors, hipStream_t s);
 
 // ---- kernels of prover_front.hip
 template <bool PROF>
@@ -133,6 +140,8 @@ __global__ void k_gather_col(const Fr* __restrict__ src, const uint32_t* __restr
                              uint32_t p, uint32_t* __restrict__ out);
 __global__ void k_scatter_witness(const uint32_t* __restrict__ given, const uint32_t* __restrict__ sig2node,
                                   uint32_t NS, Fr* __restrict__ V, uint32_t* __restrict__ err, uint32_t B, uint32_t nb);
+__global__ void __launch_bounds__(64) k_alias_rows(Fr* __restrict__ V, const uint32_t* __restrict__ src,
+                                                   const uint32_t* __restrict__ dst, uint32_t count, uint32_t B, uint32_t nb);
 // partial-proof cache (Prover::collect_partial_cached / submit_finish): rows[k] = stored slot of the k-th known value;
 // entry_of[p] (pinned host memory) = cache entry of proof p; an entry is [nk][3] uint4 in the 9 x 29 form of V29
 __global__ void __launch_bounds__(64) k_hint_check(const Fr* __restrict__ V, const uint32_t* __restrict__ cut_node,

@@ -362,7 +362,7 @@ G1Rows g1_walk_rows(const Zkey& zk, uint32_t NS, uint32_t n, uint32_t ni) {
     sids.push_back(sid);
     row_seg.push_back(seg);
   };
-  // seg 0: A = alpha + sum_i w_i A_i + r delta      (w_0 = 1 carries a_query[0] and alpha)
+  // seg 0: A = alpha + sum_i w_i A_i + r delta      (scalar id 0 carries a_query[0] and alpha: k_recode makes it ONE whatever w_0 is)
   for (uint32_t i = 0; i < NS; i++) push(zk.a_query[i], i, 0);
   push(zk.alpha_g1, 0, 0);
   push(zk.delta_g1, SID_R, 0);
