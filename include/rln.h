@@ -105,6 +105,12 @@ struct rlnamd_nullifier_log;
 CBoolResult_t ffi_nullifier_log_observe(struct rlnamd_nullifier_log* log, FFI_RLNProofValues_t* const* values, size_t n,
                                         const bool* take, const uint64_t* tags, uint8_t* status, CFr_t* secrets,
                                         uint64_t* first_tag);
+/* EXT: one log serves the whole window of epochs a relay accepts; when epochs leave it, every record under their k
+ * external nullifiers (1 .. RLNAMD_LOG_RETIRE_MAX of them) goes, the rest stays as if those shares had never been
+ * observed, and the log has room for *removed (may be NULL) more shares (rln_amd.h: rlnamd_nullifier_log_retire, where
+ * the semantics and the refusals are described).  One function for V1 and V3 callers: shares do not know which variant
+ * they came from. */
+CBoolResult_t ffi_nullifier_log_retire(struct rlnamd_nullifier_log* log, const CFr_t* external_nullifiers, size_t k, size_t* removed); /* EXT */
 /* EXT: generate_zk_proof_with_rs (protocol/proof.rs:753-777) -- explicit blinding scalars r, s */
 CResult_FFI_RLNProof_ptr_Vec_uint8_t ffi_generate_rln_proof_with_rs(FFI_RLN_t* const* rln,
                                                                     FFI_RLNWitnessInput_t* const* witness,

@@ -71,10 +71,11 @@ int rlnamd_tree_bench(rlnamd_tree* t, size_t n_leaves, uint64_t first_value, int
 
 /* ---- nullifier log on the device: find double signalling in batches --------------------------------------
  * The step of a relay loop behind verification: the log keeps every share (nullifier | x | y | external_nullifier, four
- * canonical little-endian Fr, 128 bytes) seen in an epoch, in HBM, and says of each new one whether its nullifier is new,
+ * canonical little-endian Fr, 128 bytes) seen in the epochs of a relay's window, in HBM, and says of each new one whether its nullifier is new,
  * a repeat of the same message, or a second message of one member -- and then returns the member's identity secret
  * (compute_id_secret / recover_id_secret, protocol/slashing.rs:12-100).  Every observed share gets a record, repeats
- * included; a record's id is its sequence number, and `tags` are the caller's own names for the messages.
+ * included; a record's sequence number is its arrival index since the last clear, and `tags` are the caller's own names
+ * for the messages (tags == NULL: the sequence numbers).
  *   NEW        the first record with this nullifier is the share itself
  *   FOREIGN    the first record has another external nullifier (recover_id_secret's ExternalNullifierMismatch)
  *   DUPLICATE  the first record has the same x: the same message again (compute_id_secret's DivisionByZero)
@@ -90,7 +91,29 @@ int rlnamd_tree_bench(rlnamd_tree* t, size_t n_leaves, uint64_t first_value, int
  * is current when it is made.
  * info: [0] capacity, [1] shares recorded, [2] table slots, [3] distinct nullifiers (shares judged NEW since the last
  * clear), [4] observe calls, [5] longest probe walk so far, [6] non-zero 16-byte words in those result buffers,
- * device and pinned (0 expected), [7] the seed in use.  [4] and [5] run over the life of the handle. */
+ * device and pinned (0 expected), [7] the seed in use.  [4] and [5] run over the life of the handle.
+ *
+ * Retiring.  One log serves a whole window of epochs: nullifiers of different epochs do not collide, and
+ * retire(E), E a set of 1 .. RLNAMD_LOG_RETIRE_MAX external nullifiers, removes every record whose external nullifier
+ * is in E when those epochs leave the window.  The survivors keep their arrival order, their tags and their sequence
+ * numbers.  Afterwards every observe returns the statuses, secrets and first tags that a fresh log with the same seed
+ * would return, had it been fed only the surviving shares with their stored tags in their original order; what differs
+ * from that fresh log is default tags and the counters that run over the life of the handle.  "The first record with
+ * this nullifier" becomes the first surviving one: a nullifier seen under two external nullifiers survives under the
+ * one that was not retired, and that record is then the first.  capacity counts records held: after a retire info[1]
+ * is the number of survivors, info[3] the number of distinct nullifiers among them, and observe has capacity - info[1]
+ * rows of room.  A sequence number is never reused before the next clear: with tags == NULL a share's tag stays its
+ * sequence number, the counter behind it is not lowered by a retire, and clear resets it.  rlnamd_nullifier_log_get
+ * takes the sequence number; one that was retired is an error whose text says so, one never issued is the error it was.
+ * A log that never retires behaves exactly as before.  retire refuses, each with its own text, before anything is
+ * enqueued and with the log unchanged: a null pointer with k > 0, k > RLNAMD_LOG_RETIRE_MAX, an external nullifier >= r
+ * (the text names the first such one).  A duplicate in E is not an error.  k = 0, or a set no record matches: removed =
+ * 0 and nothing moves.  Retiring everything leaves what clear leaves, except that the default-tag counter is not reset.
+ * A failed allocation during a retire leaves the log as it was.  From a log's first retire on its record memory doubles
+ * (the survivors are moved into a spare set of record arrays, which then becomes the live one); a log that never
+ * retires pays nothing.
+ * retire_info: [0] retire calls, [1] records removed over the life of the handle, [2] next default tag, [3] records
+ * held, [4] longest probe walk of the last rebuild, [5] 1 once the spare arrays exist, [6..7] reserved 0. */
 typedef struct rlnamd_nullifier_log rlnamd_nullifier_log;
 #define RLNAMD_SHARE_NEW 0
 #define RLNAMD_SHARE_DUPLICATE 1
@@ -102,7 +125,11 @@ void rlnamd_nullifier_log_free(rlnamd_nullifier_log* l);
 int rlnamd_nullifier_log_observe(rlnamd_nullifier_log* l, size_t n, const uint8_t* shares_le /* n*128 */,
                                  const uint64_t* tags /* NULL: the sequence numbers */, uint8_t* status /* n */,
                                  uint8_t* secrets_le /* n*32 or NULL */, uint64_t* first_tag /* n or NULL */);
-int rlnamd_nullifier_log_clear(rlnamd_nullifier_log* l);      /* a new epoch: empty table, count 0, same seed */
+int rlnamd_nullifier_log_clear(rlnamd_nullifier_log* l);      /* everything goes: empty table, count 0, same seed */
+#define RLNAMD_LOG_RETIRE_MAX 64
+int rlnamd_nullifier_log_retire(rlnamd_nullifier_log* l, const uint8_t* external_nullifiers_le /* k*32 */, size_t k,
+                                uint64_t* removed /* or NULL */);
+int rlnamd_nullifier_log_retire_info(rlnamd_nullifier_log* l, uint64_t out[8]);
 int rlnamd_nullifier_log_get(rlnamd_nullifier_log* l, uint64_t seq, uint8_t share_le[128], uint64_t* tag);
 int rlnamd_nullifier_log_home_slot(rlnamd_nullifier_log* l, const uint8_t nullifier_le[32], uint64_t* slot); /* host only */
 int rlnamd_nullifier_log_info(rlnamd_nullifier_log* l, uint64_t out[8]);
@@ -460,6 +487,10 @@ int rlnamd_probe_f29(int field, uint32_t op, uint32_t in_words, uint32_t out_wor
  * (witness_slow_op's value, its error word).  Mul / Add / Sub, which the interpreters never hand to witness_slow_op,
  * are answered with the 8 x 32 operators. */
 int rlnamd_probe_witness_op(size_t n, const uint32_t* in, uint32_t* out);
+/* rlnamd_probe_log_positions: the position pass of rlnamd_nullifier_log_retire alone -- keep: n bytes (0 / non-zero) ->
+ * pos: n exclusive positions, *kept: the number of non-zero bytes.  Runs the same kernels the retire runs, on buffers of
+ * its own; n = 0 succeeds without a launch. */
+int rlnamd_probe_log_positions(const uint8_t* keep, size_t n, uint32_t* pos, uint64_t* kept);
 /* rlnamd_probe_quotient_transform: the three steps every vector of the quotient goes through -- inverse transform, x g^i
  * (g the root of the doubled domain), forward transform (circuit/qap.rs:60-90) -- launched by the function the prover
  * itself launches them with, at ANY domain size: lds = 0 the passes of ntt_pass_list(logn) (k_ntt_pass / k_ntt_turn, what

@@ -108,6 +108,8 @@ SIGNATURES = {
     "rlnamd_nullifier_log_observe": (C.c_int, [P, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
                                               C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_clear": (C.c_int, [P]),
+    "rlnamd_nullifier_log_retire": (C.c_int, [P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "rlnamd_nullifier_log_retire_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_get": (C.c_int, [P, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_home_slot": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
@@ -176,6 +178,7 @@ SIGNATURES = {
     "rlnamd_probe_field": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rlnamd_probe_f29": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rlnamd_probe_witness_op": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rlnamd_probe_log_positions": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rlnamd_probe_quotient_transform": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                                   C.c_void_p]),
     "rlnamd_msm_free": (None, [P]),
@@ -287,6 +290,7 @@ SIGNATURES = {
     "ffi_recover_id_secret": (CResultPtr, [PP, PP]),
     "ffi_nullifier_log_observe": (CBoolResult, [P, PP, C.c_size_t, C.POINTER(C.c_bool), C.POINTER(C.c_uint64), C.c_char_p,
                                                 CFRP, C.POINTER(C.c_uint64)]),
+    "ffi_nullifier_log_retire": (CBoolResult, [P, CFRP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ffi_seeded_key_gen": (VecCFr, [C.POINTER(VecU8)]),
     "ffi_extended_key_gen": (VecCFr, []),
     "ffi_seeded_extended_key_gen": (VecCFr, [C.POINTER(VecU8)]),

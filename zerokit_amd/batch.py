@@ -691,9 +691,17 @@ class PoseidonTree:
 
 
 class NullifierLog:
-    """Device-resident log of the rate-limiting shares of one epoch (rlnamd_nullifier_log_*): for each observed share,
-    whether its nullifier is new, a repeat of the same message or a second message of one member -- and then that
-    member's identity secret (compute_id_secret, rln/src/protocol/slashing.rs:12-36)."""
+    """Device-resident log of the rate-limiting shares of the epochs in a relay's window (rlnamd_nullifier_log_*): for
+    each observed share, whether its nullifier is new, a repeat of the same message or a second message of one member --
+    and then that member's identity secret (compute_id_secret, rln/src/protocol/slashing.rs:12-36).
+
+    One log serves the whole window: nullifiers of different epochs do not collide, shares of two or three epochs may
+    arrive interleaved, and retire() drops the records of the epochs that have left the window -- the log is then what
+    it would have been had those shares never been observed, and their room is free again.  `capacity` counts records
+    held.  A record is named by its sequence number, its arrival index since the last clear(); that is also a share's
+    tag when observe gets no tags, it survives a retire unchanged and is never issued twice.  clear() drops everything.
+    From its first retire on a log holds a spare set of record arrays, so its record memory doubles; a log that never
+    retires pays nothing."""
     NEW, DUPLICATE, SPAM, FOREIGN, SKIPPED = range(5)
 
     def __init__(self, capacity, seed=0):
@@ -730,11 +738,26 @@ class NullifierLog:
         return (list(status), [int.from_bytes(secrets[32 * i:32 * i + 32], "little") for i in range(len(status))], first)
 
     def clear(self):
-        """a new epoch: the table empty, no records, the same seed"""
+        """everything goes: the table empty, no records, sequence numbers from 0 again, the same seed"""
         check(lib().rlnamd_nullifier_log_clear(self._h))
 
+    def retire(self, external_nullifiers):
+        """0 .. 64 external nullifiers (ints): every record under one of them is removed -> how many"""
+        k = len(external_nullifiers)
+        removed = C.c_uint64()
+        check(lib().rlnamd_nullifier_log_retire(self._h, b"".join(_b(e) for e in external_nullifiers), k, C.byref(removed)))
+        return int(removed.value)
+
+    def retire_info(self):
+        """[retire calls, records removed so far, next default tag, records held, longest probe walk of the last
+        rebuild, 1 once the spare record arrays exist, 0, 0]"""
+        out = (C.c_uint64 * 8)()
+        check(lib().rlnamd_nullifier_log_retire_info(self._h, out))
+        return [int(v) for v in out]
+
     def get(self, seq):
-        """record `seq` -> ((nullifier, x, y, external_nullifier), tag)"""
+        """the record with sequence number `seq` -> ((nullifier, x, y, external_nullifier), tag); an error that says so
+        if it was retired"""
         out = C.create_string_buffer(128)
         tag = C.c_uint64()
         check(lib().rlnamd_nullifier_log_get(self._h, seq, out, C.byref(tag)))

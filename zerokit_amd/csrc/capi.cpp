@@ -271,6 +271,21 @@ int rlnamd_nullifier_log_clear(rlnamd_nullifier_log* l) {
   l->log.clear();
   RLN_CATCH
 }
+int rlnamd_nullifier_log_retire(rlnamd_nullifier_log* l, const uint8_t* external_nullifiers_le, size_t k, uint64_t* removed) {
+  RLN_TRY
+  if (!l) throw Error("rlnamd_nullifier_log_retire: null log");
+  std::lock_guard<std::mutex> lk(l->mu);
+  const uint64_t gone = l->log.retire(k, external_nullifiers_le);
+  if (removed) *removed = gone;
+  RLN_CATCH
+}
+int rlnamd_nullifier_log_retire_info(rlnamd_nullifier_log* l, uint64_t out[8]) {
+  RLN_TRY
+  if (!l || !out) throw Error("rlnamd_nullifier_log_retire_info: null pointer");
+  std::lock_guard<std::mutex> lk(l->mu);
+  l->log.retire_info(out);
+  RLN_CATCH
+}
 int rlnamd_nullifier_log_get(rlnamd_nullifier_log* l, uint64_t seq, uint8_t share_le[128], uint64_t* tag) {
   RLN_TRY
   if (!l) throw Error("rlnamd_nullifier_log_get: null log");
@@ -645,6 +660,11 @@ int rlnamd_probe_quotient_transform(int logn, int lds, uint32_t B, uint32_t nb, 
                                     uint32_t* out) {
   RLN_TRY
   probe_quotient_transform(logn, lds, B, nb, vectors, in, out);
+  RLN_CATCH
+}
+int rlnamd_probe_log_positions(const uint8_t* keep, size_t n, uint32_t* pos, uint64_t* kept) {
+  RLN_TRY
+  probe_log_positions(keep, n, pos, kept);
   RLN_CATCH
 }
 int rlnamd_probe_witness_op(size_t n, const uint32_t* in, uint32_t* out) {

@@ -2443,6 +2443,18 @@ CBoolResult_t ffi_nullifier_log_observe(struct rlnamd_nullifier_log* log, FFI_RL
   return guard_bool(
       [&]() { return nullifier_log_observe_values(log, (void* const*)values, n, take, tags, status, secrets, first_tag); });
 }
+// EXT: the epochs that have left the window go from the log (rln.h); one function for V1 and V3 callers
+CBoolResult_t ffi_nullifier_log_retire(struct rlnamd_nullifier_log* log, const CFr_t* external_nullifiers, size_t k,
+                                       size_t* removed) {
+  return guard_bool([&]() {
+    if (!log) throw Error("nullifier log: null log");
+    uint64_t gone = 0;
+    if (rlnamd_nullifier_log_retire(log, (const uint8_t*)external_nullifiers, k, &gone) != RLNAMD_OK)
+      throw Error(rlnamd_last_error());
+    if (removed) *removed = (size_t)gone;
+    return true;
+  });
+}
 
 CResult_Vec_uint8_Vec_uint8_t ffi_rln_witness_to_bigint_json(FFI_RLNWitnessInput_t* const* wp) {
   // rln_witness_to_bigint_json (witness.rs:317-366); serde_json's default map is a BTreeMap: keys sorted, compact

@@ -1,11 +1,11 @@
-// Nullifier log: every rate-limiting share seen in an epoch, keyed by its nullifier, and the verdict on each new one --
-// the first sight of a nullifier, the same message again, or a second message of one member, whose identity secret the
-// two shares give away (compute_id_secret / recover_id_secret, protocol/slashing.rs:12-100).  Everything the kernels of
-// nullifier_log.hip inline is here, and there is no HIP call in here: a plain C++ compiler builds the same source for
-// the CPU tests (tests/host/nullifierlog.cpp).
+// Nullifier log: every rate-limiting share seen in the epochs of a relay's window, keyed by its nullifier, and the
+// verdict on each new one -- the first sight of a nullifier, the same message again, or a second message of one member,
+// whose identity secret the two shares give away (compute_id_secret / recover_id_secret, protocol/slashing.rs:12-100).
+// Everything the kernels of nullifier_log.hip inline is here, and there is no HIP call in here: a plain C++ compiler
+// builds the same source for the CPU tests (tests/host/nullifierlog.cpp, tests/host/nullifierretire.cpp).
 //
 // Layout.  A share is 128 bytes, nullifier | x | y | external_nullifier, four canonical little-endian Fr.  Record `id`
-// (the sequence number of the share: every observed share gets one, repeats included) is row `id` of three arrays:
+// (every observed share gets one, repeats included; its sequence number until a retire, see below) is row `id` of:
 //   nul[id]   32 B   the key, in an array of its own: a probe's key compare reads one row
 //   rest[id]  96 B   x | y | external_nullifier
 //   tags[id]   8 B   the caller's name for the message
@@ -20,6 +20,27 @@
 // the key is the same for all of them from the moment one of them takes it: a key owns exactly one slot, and after the
 // insert pass that slot holds the lowest id that ever carried the key.  judge() runs in a later pass, walks to that slot
 // and compares the share with record f found there.
+//
+// Retiring.  retire(E), E a set of 1 .. 64 external nullifiers, removes every record whose external nullifier is in E:
+// the epochs that have left a relay's window go, the ones still open stay.  The survivors keep their arrival order,
+// their tags and their sequence numbers, and from then on every observe returns the statuses, secrets and first tags a
+// fresh log with the same seed would return had it been fed only the surviving shares, with their stored tags, in
+// their original order (what differs from that fresh log: default tags, and the counters that run over the life of
+// the handle).  "The first record with this nullifier" is the first SURVIVING one: a nullifier seen under two external
+// nullifiers survives under the one that was not retired, and that record becomes the first.  `capacity` counts
+// records held, so a retire hands back the room of what it removed.
+//
+// Rows and sequence numbers.  A record's sequence number is its arrival index since the last clear; it never changes
+// and is not issued again before the next clear, and a share observed without a tag is tagged with it (a retire does
+// not lower that counter).  The table holds ROWS.  Until the first retire that removes something, row == sequence
+// number and nothing is stored for it; from then on a fourth record array, seqs[row], ascending, names them, and
+// find_seq() is the way from a sequence number to its row.  The survivors are moved in order, so the lowest row with a
+// key is still the earliest arrival with it, which is all insert() and judge() ask of an id.
+//
+// The device keeps a spare set of the record arrays from a log's first retire on (the move is not in place: a
+// destination row can be another lane's source) and swaps it with the live set: record memory doubles then, from 136
+// to 2 * 144 bytes per record of capacity, plus 5 bytes per record of keep marks and positions.  A log that never
+// retires pays nothing.  retire() below is the one-thread form, which can move in place.
 //
 // The atomics are a policy type A, so that the kernels and the CPU build compile the same source:
 //   A::cas(p, expect, v)  compare-and-swap, returns what was there      A::min(p, v)  atomic minimum
@@ -212,16 +233,82 @@ RLN_HD Verdict judge(const View& L, uint32_t id) {
   return v;
 }
 
-// one share's four field elements: all canonical?
-inline bool share_is_canonical(const uint8_t share_le[128]) {
-  for (int k = 0; k < 4; k++) {
-    uint32_t w[8];
-    for (int i = 0; i < 8; i++) {
-      const uint8_t* b = share_le + 32 * k + 4 * i;
-      w[i] = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-    }
-    if (limbs_geq(w, FrParams::MOD)) return false;
+// ---- retiring
+constexpr uint32_t RETIRE_MAX = 64;
+struct RetireSet {   // the external nullifiers of one retire call, canonical; duplicates do no harm
+  Row32 e[RETIRE_MAX];
+  uint32_t k;
+};
+
+// the keep predicate: the record stays unless its external nullifier is one of set[0 .. k)
+RLN_HD bool keeps(const Row32& ext, const Row32* set, uint32_t k) {
+  bool hit = false;
+  for (uint32_t j = 0; j < k; j++) hit |= same(ext, set[j]);
+  return !hit;
+}
+
+// sequence number -> row: binary search over the ascending seqs[0 .. count); `count` if no record carries it
+RLN_HD uint64_t find_seq(const uint64_t* seqs, uint64_t count, uint64_t seq) {
+  uint64_t lo = 0, hi = count;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (seqs[mid] < seq) lo = mid + 1;
+    else hi = mid;
   }
+  return lo < count && seqs[lo] == seq ? lo : count;
+}
+
+// the record arrays as something a retire may write
+struct Records {
+  Row32* nul;
+  Row96* rest;
+  uint64_t* tags;
+  uint64_t* seqs;
+};
+
+// The sequential retire: mark, move, rebuild on one thread.  Row i goes to row (kept rows below i) <= i, so in
+// ascending order the move is in place here; the device, one lane per record, moves into a spare set.  Then the table
+// is emptied and the survivors are inserted again, which leaves the lowest surviving row of each key in the key's
+// slot.  Returns the number of survivors; *distinct: taken slots, *longest: the longest walk of the rebuild.
+template <class A>
+inline uint64_t retire(const Records& R, uint32_t* table, uint64_t slots, uint64_t seed, uint64_t count, const RetireSet& E,
+                       uint64_t* distinct, uint32_t* longest) {
+  uint64_t kept = 0;
+  for (uint64_t i = 0; i < count; i++) {
+    if (!keeps(R.rest[i].ext, E.e, E.k)) continue;
+    if (kept != i) {
+      R.nul[kept] = R.nul[i];
+      R.rest[kept] = R.rest[i];
+      R.tags[kept] = R.tags[i];
+      R.seqs[kept] = R.seqs[i];
+    }
+    kept++;
+  }
+  if (kept == count) return kept;   // nothing removed: the table stands, *distinct and *longest are not touched
+  *distinct = 0;
+  *longest = 0;
+  for (uint64_t s = 0; s < slots; s++) table[s] = EMPTY;
+  const View L{R.nul, R.rest, R.tags, table, slots, seed};
+  for (uint64_t id = 0; id < kept; id++) {
+    const uint32_t walk = insert<A>(L, (uint32_t)id);
+    if (walk > *longest) *longest = walk;
+  }
+  for (uint64_t s = 0; s < slots; s++) *distinct += table[s] != EMPTY;
+  return kept;
+}
+
+// one field element, and one share's four: canonical?
+inline bool element_is_canonical(const uint8_t le[32]) {
+  uint32_t w[8];
+  for (int i = 0; i < 8; i++) {
+    const uint8_t* b = le + 4 * i;
+    w[i] = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+  }
+  return !limbs_geq(w, FrParams::MOD);
+}
+inline bool share_is_canonical(const uint8_t share_le[128]) {
+  for (int k = 0; k < 4; k++)
+    if (!element_is_canonical(share_le + 32 * k)) return false;
   return true;
 }
 
@@ -243,10 +330,21 @@ struct NullifierLogDev {
   // the room left, a field element >= r.
   void observe(size_t n, const uint8_t* shares_le, const uint64_t* tags, uint8_t* status, uint8_t* secrets_le,
                uint64_t* first_tag);
-  void clear();   // a new epoch: empty table, no records, the same seed
+  void clear();   // everything goes: empty table, no records, sequence numbers from 0 again, the same seed
+  // k external nullifiers of 32 bytes, 0 <= k <= RETIRE_MAX: every record under one of them goes (the semantics are at
+  // the top of this file); returns how many.  Refused before anything is enqueued, the log left as it was: a null
+  // pointer with k > 0, k > RETIRE_MAX, an element >= r.  k = 0 and a set no record matches return 0 and move nothing.
+  // A failed allocation leaves the log as it was.
+  uint64_t retire(size_t k, const uint8_t* external_nullifiers_le);
+  // by sequence number; one that was retired and one that was never issued are two different errors
   void get(uint64_t seq, uint8_t share_le[128], uint64_t* tag);
   uint64_t home_slot(const uint8_t nullifier_le[32]) const;   // host only
   void info(uint64_t out[8]);
+  void retire_info(uint64_t out[8]);   // include/rln_amd.h: rlnamd_nullifier_log_retire_info
 };
+
+// test support (rlnamd_probe_log_positions): the position pass of a retire on buffers of its own -- keep: n bytes,
+// pos: n exclusive counts of the non-zero bytes before each, *kept: their number
+void probe_log_positions(const uint8_t* keep, size_t n, uint32_t* pos, uint64_t* kept);
 
 }  // namespace rlnamd

@@ -612,6 +612,17 @@ def observe_proof_values(log, values, take=None, tags=None):
     return _observe_proof_values(lib().ffi_nullifier_log_observe, log, values, take, tags)
 
 
+def retire_external_nullifiers(log, external_nullifiers) -> int:
+    """EXT: the epochs that have left the window go from a batch.NullifierLog (ffi_nullifier_log_retire): every record
+    under one of the 1 .. 64 external nullifiers is removed, the rest stays as if those shares had never been observed.
+    Serves V1 and V3 proof values alike.  Returns the number of records removed, which is the room handed back."""
+    k = len(external_nullifiers)
+    ext = (CFr * max(k, 1))(*[_cfr(e) for e in external_nullifiers])
+    removed = C.c_size_t()
+    _ok_bool(lib().ffi_nullifier_log_retire(log._h, ext, k, C.byref(removed)))
+    return int(removed.value)
+
+
 def seeded_keygen(seed: bytes):
     """protocol/keygen.rs:50-65 -> (identity_secret, id_commitment)"""
     v, _k = _vec_u8(seed)
