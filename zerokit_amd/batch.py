@@ -651,6 +651,13 @@ class PoseidonTree:
         return ([int.from_bytes(e.raw[32 * i:32 * i + 32], "little") for i in range(self.depth)],
                 list(b.raw[:self.depth]))
 
+    def proofs_raw(self, first, count):
+        """the paths of leaves [first, first + count) in one call -> (elems count*depth*32 bytes, bits count*depth)"""
+        e = C.create_string_buffer(max(32 * self.depth * count, 1))
+        b = C.create_string_buffer(max(self.depth * count, 1))
+        check(lib().rlnamd_tree_proofs(self._h, first, count, e, b))
+        return e.raw[:32 * self.depth * count], b.raw[:self.depth * count]
+
     def proofs(self, first, count):
         e = C.create_string_buffer(32 * self.depth * count)
         b = C.create_string_buffer(max(self.depth * count, 1))

@@ -540,7 +540,7 @@ MerkleTreeDev& MerkleTreeDev::operator=(MerkleTreeDev&& o) noexcept {
 }
 
 void MerkleTreeDev::fill_sequential_device(size_t start, size_t n, uint64_t first_value) {
-  if (start + n > capacity()) throw Error("TooManySet");
+  if (start + n > capacity() || start + n < start) throw Error("TooManySet");
   if (n == 0) return;
   size_t first = capacity() - 1 + start;
   hipLaunchKernelGGL(k_fill_seq, dim3(div_up(n, 256)), dim3(256), 0, stream, nodes.p, first, n, first_value);
@@ -575,7 +575,7 @@ void MerkleTreeDev::get_leaves_host(size_t first, size_t n, uint8_t* out_le) {
 }
 
 void MerkleTreeDev::proofs_device(size_t first, size_t count, uint8_t* d_elems, uint8_t* d_bits) {
-  if (first + count > capacity()) throw Error("InvalidLeaf");
+  if (first + count > capacity() || first + count < first) throw Error("InvalidLeaf");
   if (count == 0 || depth == 0) return;
   if ((uintptr_t)d_elems & 15) throw Error("proofs_device: the path-element buffer must be 16-byte aligned");
   size_t total = count * (size_t)depth;
