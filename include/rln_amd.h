@@ -191,6 +191,10 @@ int rlnamd_ffi_prover_info(const void* ffi_rln, rlnamd_prover_info* info);
  * (identity secret included) in host memory until the entry is evicted, or the object freed.
  * out: [0] members remembered, [1] proofs that were finishes, [2] proofs from scratch, [3] 1 while a partial proof is pending */
 int rlnamd_ffi_memo_stats(const void* ffi_rln, uint64_t out[4]);
+/* The device verifier behind an FFI object (ffi_verify_rln_proofs_batch, ffi_verify_rln_signals_batch; config keys
+ * "verify_gpu_min", "verify_lanes", "verify_optimistic", "verify_optimistic_cooldown"): out[0..7] as
+ * rlnamd_verify_gpu_optimistic_stats, out[8] chunks run exactly with a lane per proof, out[9] in team form. */
+int rlnamd_ffi_verify_stats(const void* ffi_rln, uint64_t out[10]);
 /* The durable store of a persistent tree (config_path: "temporary": false + "path"): the directory `path`
  * holds a checksummed snapshot and a write-ahead journal, every mutating tree call appends ONE record before it is applied,
  * ffi_flush is an fdatasync of the journal and a flusher thread does the same every "flush_every_ms".
@@ -398,6 +402,37 @@ int rlnamd_verify_many_gpu_ex(rlnamd_prover* p, size_t n, const uint8_t* proofs,
 /* test / diagnosis: chunks the device verifier has run so far with a lane per proof (passes[0]) and in team form
  * (passes[1]) */
 int rlnamd_verify_gpu_passes(rlnamd_prover* p, size_t passes[2]);
+/* EXT: rlnamd_verify_many_gpu with an optimistic first pass (verify_agg.hip).  Same inputs, and the same verdicts up to
+ * the probability below.  Per chunk of 65 536 proofs: the proofs that the per-proof checks refuse (a non-canonical
+ * encoding, a point off its curve, B outside the order-r subgroup, an input >= r) get ok = 0 at once; every other
+ * proof i gets a scalar r_i, uniform in [1, 2^128) and drawn inside the call (getrandom), after the proofs are fixed;
+ * and ONE pairing check decides prod_i GT_i^(r_i) == 1 for the per-proof pairing products GT_i, at the cost of one
+ * single-pair Miller loop per proof and one final exponentiation per chunk.  If it accepts, all those proofs get
+ * ok = 1: since every GT_i lies in the order-r group, a chunk that holds an invalid proof is accepted with
+ * probability about 2^-128 over the scalars.  If it rejects, the chunk runs through the exact pass of
+ * rlnamd_verify_many_gpu, which names the bad proofs, and the next `cooldown` chunks (rlnamd_verify_gpu_set_cooldown;
+ * default 16, a policy bound on the wasted work and not a measured optimum; 0 = none) go straight to the exact pass.
+ * Taken only where the verifier would run a lane per proof (n > 1 024 unless RLNAMD_VERIFY_LANES says otherwise);
+ * smaller calls are rlnamd_verify_many_gpu unchanged.  n = 0 succeeds; null pointers with n > 0, a wrong n_values and
+ * a zero scalar in scalars16 are errors.  scalars16: NULL (drawn), or n x 16 bytes little-endian -- a test hook:
+ * scalars known to the sender of the proofs void the bound. */
+int rlnamd_verify_many_gpu_optimistic(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                      size_t n_values, const uint8_t* scalars16, uint8_t* ok);
+/* out[0] chunks checked combined, [1] accepted, [2] fell back to the exact pass, [3] chunks that skipped the combined
+ * check during a cool-down, [4] proofs the per-proof checks refused in combined checks, [5] cool-down chunks left,
+ * [6] the cool-down setting, [7] reserved, 0 */
+int rlnamd_verify_gpu_optimistic_stats(rlnamd_prover* p, uint64_t out[8]);
+int rlnamd_verify_gpu_set_cooldown(rlnamd_prover* p, size_t chunks);
+/* test / diagnosis: the final-exponentiated combined value prod_i GT_i^(r_i) of all n proofs, 12 x 32 bytes canonical
+ * LE in pairing.h's coefficient order (1 = accept), with no fallback; rejected[i] = 1 where the per-proof checks
+ * refuse proof i (it counts as 1 in the product).  scalars16 as above. */
+int rlnamd_verify_gpu_aggregate(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                size_t n_values, const uint8_t* scalars16, uint8_t gt384[384], uint8_t* rejected);
+/* its host-only twin from pairing.h alone (no GPU, none of the device form's folding): the product of the exact
+ * per-proof pairing products raised to the scalars.  scalars16 must be given.  The value the device is judged by. */
+int rlnamd_verify_aggregate_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n, const uint8_t* proofs,
+                                      const uint8_t* values_le, size_t n_values, const uint8_t* scalars16,
+                                      uint8_t gt384[384], uint8_t* rejected);
 int rlnamd_verify_many_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n, const uint8_t* proofs,
                                  const uint8_t* values_le, size_t n_values, int threads, uint8_t* ok);
 /* same check straight from arkzkey bytes; needs no GPU (host parser + host pairing only) */

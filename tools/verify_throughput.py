@@ -3,7 +3,7 @@
 per proof, against 16 host threads (rlnamd_verify_many), compressed proof bytes in, verdicts out, copies to and from the
 device inside the timed region.
 
-    python tools/verify_throughput.py [--calls 9] [--lanes 1,8] [--out FILE]
+    python tools/verify_throughput.py [--calls 9] [--lanes 1,8] [--optimistic] [--out FILE]
 
 prints ONE JSON line.  Torch-free (ctypes through zerokit_amd).  Each of the two steps runs in a child process of its
 own under a time limit; a step that fails or runs out of time ends the run there.
@@ -14,6 +14,9 @@ own under a time limit; a step that fails or runs out of time ends the run there
               n where the device's median beats the host's at that n); with both shapes measured, team_max: the largest
               measured n at which the teams' median is below the minimum of a lane per proof
   concurrent  device verification at n = 8 192 while a proving stream runs, and the proving rate alone and meanwhile
+  optimistic  (with --optimistic) rlnamd_verify_many_gpu_optimistic against the exact lane-per-proof call of the same
+              build at n = 8 192 and 65 536, alternated call by call: all rows valid, and the worst case of one damaged
+              proof in every chunk with cool-down 0 (a combined check and an exact pass per chunk)
 """
 import argparse
 import collections
@@ -32,7 +35,8 @@ sys.path.insert(0, ROOT)
 HOST_THREADS = 16
 DEVICE_N = (1, 8, 64, 96, 128, 192, 256, 384, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536)
 HOST_N = (1, 8, 64, 96, 128, 192, 256, 384, 512, 1024, 8192)
-STEP_LIMIT_S = {"sweep": 540, "concurrent": 240}
+STEP_LIMIT_S = {"sweep": 540, "concurrent": 240, "optimistic": 240}
+OPTIMISTIC_N = (8192, 65536)
 
 
 def setup():
@@ -156,7 +160,45 @@ def step_concurrent(calls, shapes=(0,)):
             "prove_meanwhile_per_s": round(res["rate"], 1), "verify_meanwhile": row(8192, ts) if ts else None}
 
 
-STEPS = {"sweep": step_sweep, "concurrent": step_concurrent}
+def step_optimistic(calls, shapes=(1,)):
+    from zerokit_amd import lib
+    from zerokit_amd._native import check
+    p, _inp, _rsb, proofs, values = setup()
+    out = {"all_valid": [], "one_damaged_per_chunk_cooldown_0": []}
+    for n in OPTIMISTIC_N:
+        pr, va = tiled(proofs, values, n)
+        bad = bytearray(va)
+        bad[0] ^= 1                      # one changed public input: the pairing rejects row 0
+        bad = bytes(bad)
+        ok = C.create_string_buffer(n)
+
+        def exact(vals=va):
+            check(lib().rlnamd_verify_many_gpu_ex(p._h, n, pr, vals, 5, 1, ok, None))
+
+        def optimistic(vals=va):
+            check(lib().rlnamd_verify_many_gpu_optimistic(p._h, n, pr, vals, 5, None, ok))
+        for key, vals, want in (("all_valid", va, b"\x01" * n),
+                                ("one_damaged_per_chunk_cooldown_0", bad, b"\x00" + b"\x01" * (n - 1))):
+            p.verify_set_cooldown(0)
+            ts = {"optimistic": [], "exact": []}
+            for fn in (optimistic, exact):   # warm-up: code objects, buffers at their size
+                fn(vals)
+                assert ok.raw == want
+            for _ in range(calls):
+                for name, fn in (("optimistic", optimistic), ("exact", exact)):
+                    t0 = time.perf_counter()
+                    fn(vals)
+                    ts[name].append(time.perf_counter() - t0)
+            r = {"n": n, "optimistic": row(n, ts["optimistic"]), "exact": row(n, ts["exact"])}
+            r["optimistic_over_exact"] = round(r["optimistic"]["median_ms"] / r["exact"]["median_ms"], 3)
+            out[key].append(r)
+    out["stats"] = p.verify_optimistic_stats()
+    p.verify_set_cooldown(16)
+    p.close()
+    return out
+
+
+STEPS = {"sweep": step_sweep, "concurrent": step_concurrent, "optimistic": step_optimistic}
 
 
 def main():
@@ -164,6 +206,7 @@ def main():
     ap.add_argument("--calls", type=int, default=9)
     ap.add_argument("--lanes", default="1,8", help="shapes to measure, of 1 (a lane per proof), 8 (teams), 0 (the "
                     "verifier's choice): a column each in the sweep; the concurrent step takes a single one, else 0")
+    ap.add_argument("--optimistic", action="store_true", help="add the optimistic step")
     ap.add_argument("--out")
     ap.add_argument("--step", choices=sorted(STEPS))
     a = ap.parse_args()
@@ -176,7 +219,7 @@ def main():
         print(json.dumps(STEPS[a.step](a.calls, shapes)))
         return 0
     out = {"tool": "verify_throughput", "calls": a.calls, "lanes": list(shapes)}
-    for name in ("sweep", "concurrent"):
+    for name in ("sweep", "concurrent") + (("optimistic",) if a.optimistic else ()):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--calls", str(a.calls), "--lanes",
                                 a.lanes],
@@ -193,7 +236,8 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             f.write(line + "\n")
-    return 0 if all("error" not in out.get(k, {"error": 1}) for k in ("sweep", "concurrent")) else 1
+    wanted = ("sweep", "concurrent") + (("optimistic",) if a.optimistic else ())
+    return 0 if all("error" not in out.get(k, {"error": 1}) for k in wanted) else 1
 
 
 if __name__ == "__main__":

@@ -164,6 +164,14 @@ SIGNATURES = {
     "rlnamd_verify_many_gpu_ex": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_char_p,
                                             C.c_char_p]),
     "rlnamd_verify_gpu_passes": (C.c_int, [P, C.POINTER(C.c_size_t)]),
+    "rlnamd_verify_many_gpu_optimistic": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p,
+                                                    C.c_char_p]),
+    "rlnamd_verify_gpu_optimistic_stats": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "rlnamd_verify_gpu_set_cooldown": (C.c_int, [P, C.c_size_t]),
+    "rlnamd_verify_gpu_aggregate": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p,
+                                              C.c_char_p]),
+    "rlnamd_verify_aggregate_with_zkey": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p,
+                                                    C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rlnamd_verify_many_with_zkey": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t,
                                                C.c_int, C.c_char_p]),
     "rlnamd_parse_resources": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)]),
@@ -191,6 +199,7 @@ SIGNATURES = {
     "rlnamd_msm_combine": (C.c_int, [P, C.c_char_p, C.c_size_t, C.c_char_p]),
     "rlnamd_ffi_prover_info": (C.c_int, [P, C.POINTER(ProverInfo)]),
     "rlnamd_ffi_memo_stats": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "rlnamd_ffi_verify_stats": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_ffi_tree_store_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_ffi_gather_stats": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_prover_slots": (C.c_int, [P]),

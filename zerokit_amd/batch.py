@@ -467,6 +467,42 @@ class BatchProver:
         check(lib().rlnamd_verify_gpu_passes(self._h, out))
         return int(out[0]), int(out[1])
 
+    def verify_many_gpu_optimistic(self, proofs, public_inputs, scalars=None):
+        """verify_many_gpu with one combined pairing check per chunk first and the exact pass only for a chunk it
+        rejects (rlnamd_verify_many_gpu_optimistic): the same verdicts, up to about 2^-128 per chunk.  scalars: None
+        (drawn inside the call) or n non-zero ints below 2^128, a test hook"""
+        n = len(proofs)
+        if n == 0:
+            return []
+        nv = _check_verify_shapes(proofs, public_inputs)
+        ok = C.create_string_buffer(n)
+        sc = None if scalars is None else b"".join(int(r).to_bytes(16, "little") for r in scalars)
+        check(lib().rlnamd_verify_many_gpu_optimistic(self._h, n, b"".join(proofs),
+                                                      b"".join(_b(v) for pi in public_inputs for v in pi), nv, sc, ok))
+        return [bool(x) for x in ok.raw]
+
+    def verify_aggregate(self, proofs, public_inputs, scalars=None):
+        """test / diagnosis (rlnamd_verify_gpu_aggregate): (the final-exponentiated combined value of all n proofs as
+        384 bytes in pairing.h's coefficient order, the encoding of 1 = accept; a list of bools, True where the
+        per-proof checks refuse a proof).  No fallback."""
+        n = len(proofs)
+        nv = _check_verify_shapes(proofs, public_inputs) if n else self.num_public
+        gt, rej = C.create_string_buffer(384), C.create_string_buffer(max(n, 1))
+        sc = None if scalars is None else b"".join(int(r).to_bytes(16, "little") for r in scalars)
+        check(lib().rlnamd_verify_gpu_aggregate(self._h, n, b"".join(proofs),
+                                                b"".join(_b(v) for pi in public_inputs for v in pi), nv, sc, gt, rej))
+        return gt.raw, [bool(x) for x in rej.raw[:n]]
+
+    def verify_optimistic_stats(self):
+        """rlnamd_verify_gpu_optimistic_stats as a dict"""
+        out = (C.c_uint64 * 8)()
+        check(lib().rlnamd_verify_gpu_optimistic_stats(self._h, out))
+        keys = ("combined", "accepted", "fell_back", "skipped_in_cooldown", "refused_proofs", "cooldown_left", "cooldown")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def verify_set_cooldown(self, chunks):
+        check(lib().rlnamd_verify_gpu_set_cooldown(self._h, chunks))
+
     def verify(self, proof: bytes, public_inputs):
         """verify_zk_proof (protocol/proof.rs:856-894); public_inputs = [y, root, nullifier, x, ext]."""
         ok = C.c_int()

@@ -10,6 +10,7 @@
 #include <mutex>
 #include <thread>
 #include <string>
+#include <unordered_map>
 
 #include "arith_probe.h"
 #include "common.h"
@@ -814,6 +815,133 @@ int rlnamd_verify_many_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n,
   Zkey zk = parse_arkzkey(zkey, zkey_len);
   if (n_values + 1 != zk.gamma_abc_g1.size()) throw Error("MalformedVerifyingKey");
   verify_many_common(zk, n, proofs, values_le, n_values, threads, ok);
+  RLN_CATCH
+}
+
+int rlnamd_verify_many_gpu_optimistic(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                      size_t n_values, const uint8_t* scalars16, uint8_t* ok) {
+  RLN_TRY
+  if (n_values + 1 != p->p->zkey().gamma_abc_g1.size())
+    throw Error("MalformedVerifyingKey: rlnamd_verify_many_gpu_optimistic: n_values is not the key's input count");
+  if (n && (!proofs || !values_le || !ok)) throw Error("rlnamd_verify_many_gpu_optimistic: null argument with n > 0");
+  if (n) p->p->gpu_verifier().verify_optimistic(n, proofs, values_le, n_values, scalars16, ok);
+  RLN_CATCH
+}
+int rlnamd_verify_gpu_optimistic_stats(rlnamd_prover* p, uint64_t out[8]) {
+  RLN_TRY
+  p->p->gpu_verifier().optimistic_stats(out);
+  RLN_CATCH
+}
+int rlnamd_verify_gpu_set_cooldown(rlnamd_prover* p, size_t chunks) {
+  RLN_TRY
+  p->p->gpu_verifier().set_cooldown(chunks);
+  RLN_CATCH
+}
+int rlnamd_verify_gpu_aggregate(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                size_t n_values, const uint8_t* scalars16, uint8_t gt384[384], uint8_t* rejected) {
+  RLN_TRY
+  if (n_values + 1 != p->p->zkey().gamma_abc_g1.size())
+    throw Error("MalformedVerifyingKey: rlnamd_verify_gpu_aggregate: n_values is not the key's input count");
+  p->p->gpu_verifier().aggregate(n, proofs, values_le, n_values, scalars16, gt384, rejected);
+  RLN_CATCH
+}
+}  // extern "C"
+namespace rlnamd {
+// f(i) for i < n on host threads
+template <class F>
+static void parallel_for(size_t n, F f) {
+  unsigned hw = std::thread::hardware_concurrency();
+  const size_t nt = std::max<size_t>(1, std::min<size_t>(hw ? hw : 1, n));
+  std::atomic<size_t> next{0};
+  auto work = [&](size_t t) {
+    for (size_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) f(i, t);
+  };
+  std::vector<std::thread> pool;
+  for (size_t t = 1; t < nt; t++) {
+    try {
+      pool.emplace_back(work, t);
+    } catch (const std::system_error&) {
+      break;
+    }
+  }
+  work(0);
+  for (auto& t : pool) t.join();
+}
+// The yardstick of the combined check, from pairing.h alone: prod_i GT_i^(r_i) over the exact per-proof pairing
+// products GT_i = final_exponentiation(miller_loop_3(..) alpha_beta); a proof the host rules refuse counts as 1 and
+// gets rejected[i] = 1.  Rows that repeat byte for byte share one pairing product.
+static void aggregate_host(const Zkey& zk, size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv,
+                           const uint8_t* scalars16, uint8_t gt384[384], uint8_t* rejected) {
+  const PreparedVk& pv = prepared(zk);
+  std::unordered_map<std::string, size_t> seen;
+  std::vector<size_t> row_of(n), first;
+  for (size_t i = 0; i < n; i++) {
+    std::string key((const char*)proofs + 128 * i, 128);
+    key.append((const char*)values_le + 32 * nv * i, 32 * nv);
+    auto it = seen.emplace(std::move(key), first.size());
+    if (it.second) first.push_back(i);
+    row_of[i] = it.first->second;
+  }
+  std::vector<Fq12> gt(first.size(), Fq12::one());
+  std::vector<uint8_t> refused(first.size(), 0);
+  parallel_for(first.size(), [&](size_t d, size_t) {
+    const uint8_t *proof = proofs + 128 * first[d], *vals = values_le + 32 * nv * first[d];
+    G1Affine A, C;
+    G2Affine B;
+    bool ok = g1_decompress(proof, &A) && g2_decompress(proof + 32, &B) && g1_decompress(proof + 96, &C) &&
+              g2_in_subgroup(B);
+    std::vector<Fr> x(nv);
+    for (size_t j = 0; ok && j < nv; j++) {
+      uint32_t c[8];
+      memcpy(c, vals + 32 * j, 32);
+      ok = !limbs_geq(c, FrParams::MOD);
+      if (ok) x[j] = Fr::from_canonical(c);
+    }
+    refused[d] = ok ? 0 : 1;
+    if (!ok) return;
+    const G1Affine ic = ic_combination(zk, pv, x).to_affine();
+    gt[d] = final_exponentiation(f12_mul(miller_loop_3(A, B, ic.neg(), pv.gamma, C.neg(), pv.delta), pv.alpha_beta));
+  });
+  unsigned hw = std::thread::hardware_concurrency();
+  std::vector<Fq12> part(hw ? hw : 1, Fq12::one());
+  parallel_for(n, [&](size_t i, size_t t) {
+    rejected[i] = refused[row_of[i]];
+    if (rejected[i]) return;
+    uint32_t k[4];
+    memcpy(k, scalars16 + 16 * i, 16);
+    const Fq12& g = gt[row_of[i]];   // in the cyclotomic subgroup: its squaring applies
+    Fq12 r = Fq12::one();
+    bool started = false;
+    for (int b = 127; b >= 0; b--) {
+      if (started) r = f12_cyclotomic_sqr(r);
+      if ((k[b >> 5] >> (b & 31)) & 1) {
+        r = started ? f12_mul(r, g) : g;
+        started = true;
+      }
+    }
+    part[t] = f12_mul(part[t], r);
+  });
+  Fq12 all = Fq12::one();
+  for (const Fq12& f : part) all = f12_mul(all, f);
+  for (int i = 0; i < 6; i++) {
+    uint32_t a[8], b[8];
+    all.c[i].c0.to_canonical(a);
+    all.c[i].c1.to_canonical(b);
+    memcpy(gt384 + 64 * i, a, 32);
+    memcpy(gt384 + 64 * i + 32, b, 32);
+  }
+}
+}  // namespace rlnamd
+extern "C" {
+int rlnamd_verify_aggregate_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n, const uint8_t* proofs,
+                                      const uint8_t* values_le, size_t n_values, const uint8_t* scalars16,
+                                      uint8_t gt384[384], uint8_t* rejected) {
+  RLN_TRY
+  Zkey zk = parse_arkzkey(zkey, zkey_len);
+  if (n_values + 1 != zk.gamma_abc_g1.size()) throw Error("MalformedVerifyingKey");
+  if (!gt384 || (n && (!proofs || !values_le || !scalars16 || !rejected)))
+    throw Error("rlnamd_verify_aggregate_with_zkey: null argument");
+  aggregate_host(zk, n, proofs, values_le, n_values, scalars16, gt384, rejected);
   RLN_CATCH
 }
 

@@ -351,6 +351,8 @@ struct FFI_RLN {
   // ffi_verify_rln_signals_batch: calls of at least this many signals are hashed on the device ("hash_gpu_min")
   size_t hash_gpu_min = HASH_GPU_MIN_DEFAULT;
   int verify_lanes = 0;   // "verify_lanes": lanes per proof of those passes (0: the verifier chooses)
+  bool verify_optimistic = false;        // "verify_optimistic": a combined check per chunk first (verify_agg.hip)
+  long verify_optimistic_cooldown = -1;  // "verify_optimistic_cooldown": -1 leaves the verifier's setting
   // single calls from several threads gathered into batches: gather.h
   struct GatherReq {
     FFI_RLNWitnessInput* w = nullptr;
@@ -436,6 +438,8 @@ struct FFI_RLN {
     verify_gpu_min = tcfg.verify_gpu_min >= 0 ? (size_t)tcfg.verify_gpu_min : VERIFY_GPU_MIN_DEFAULT;
     hash_gpu_min = tcfg.hash_gpu_min >= 0 ? (size_t)tcfg.hash_gpu_min : HASH_GPU_MIN_DEFAULT;
     verify_lanes = (int)tcfg.verify_lanes;
+    verify_optimistic = tcfg.verify_optimistic;
+    verify_optimistic_cooldown = tcfg.verify_optimistic_cooldown;
     gather_wanted = tcfg.gather_calls;
     if (const char* e = getenv("RLNAMD_GATHER_CALLS"))
       if (*e) gather_wanted = atol(e);
@@ -1565,6 +1569,23 @@ int rlnamd_ffi_prover_info(const void* ffi_rln, rlnamd_prover_info* info) {
   }
   return RLNAMD_OK;
 }
+// EXT (include/rln_amd.h): the device verifier behind this object: rlnamd_verify_gpu_optimistic_stats' eight values,
+// then rlnamd_verify_gpu_passes' two
+int rlnamd_ffi_verify_stats(const void* ffi_rln, uint64_t out[10]) {
+  if (!ffi_rln || !out) return RLNAMD_ERR;
+  FFI_RLN& r = *(FFI_RLN*)ffi_rln;
+  try {
+    size_t passes[2];
+    GpuVerifier& gv = r.prover->gpu_verifier();
+    gv.optimistic_stats(out);
+    gv.passes(passes);
+    out[8] = passes[0];
+    out[9] = passes[1];
+  } catch (const std::exception&) {
+    return RLNAMD_ERR;
+  }
+  return RLNAMD_OK;
+}
 // EXT (include/rln_amd.h): the member memo of an object built with "auto_partial": [0] members remembered, [1] proofs
 // that were finishes of a remembered partial proof, [2] proofs made from scratch, [3] 1 while a partial proof is pending
 int rlnamd_ffi_memo_stats(const void* ffi_rln, uint64_t out[4]) {
@@ -1737,7 +1758,8 @@ CBoolResult_t ffi_verify_with_roots(FFI_RLN_t* const* rln, FFI_RLNProof_t* const
   });
 }
 // EXT: n proofs in one call; the public-input rows are verify_zk's (proof.rs:863-885), the pairing checks run on the
-// device from verify_gpu_min proofs on and on host threads below
+// device from verify_gpu_min proofs on and on host threads below; with "verify_optimistic" the device passes try one
+// combined check per chunk first
 CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
                                           const CFr_t* xs, const Vec_CFr_t* roots, bool* ok) {
   return guard_bool([&]() {
@@ -1769,7 +1791,11 @@ CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t*
       memcpy(&bytes[128 * i], pr.proof, 128);
     }
     std::vector<uint8_t> pass(n);
-    if (n >= r.verify_gpu_min)
+    if (n >= r.verify_gpu_min && r.verify_optimistic) {
+      GpuVerifier& gv = r.prover->gpu_verifier();
+      if (r.verify_optimistic_cooldown >= 0) gv.set_cooldown((size_t)r.verify_optimistic_cooldown);
+      gv.verify_optimistic(n, bytes.data(), rows.data(), nv, nullptr, pass.data(), r.verify_lanes);
+    } else if (n >= r.verify_gpu_min)
       r.prover->gpu_verifier().verify(n, bytes.data(), rows.data(), nv, pass.data(), nullptr, r.verify_lanes);
     else
       verify_many_common(r.prover->zkey(), n, bytes.data(), rows.data(), nv, 0, pass.data());

@@ -79,6 +79,13 @@ struct TreeConfig {
   // "verify_lanes": 1 | 8 | 0 -- lanes per proof of those device passes: a lane, a team of 8 (verify_team.hip), or by the
   // size of the call (0, the default: RLNAMD_VERIFY_LANES if set, else teams up to GpuVerifier::TEAM_MAX proofs)
   long verify_lanes = 0;
+  // "verify_optimistic": true | false -- those device passes try one combined pairing check per chunk first and run the
+  // exact pass only for a chunk it rejects (GpuVerifier::verify_optimistic: verdicts equal up to about 2^-128 per
+  // chunk).  Default false.  Only calls that run a lane per proof take it; "verify_lanes": 8 keeps teams.
+  bool verify_optimistic = false;
+  // "verify_optimistic_cooldown": N -- chunks after a rejected combined check that go straight to the exact pass.
+  // -1 (default): GpuVerifier::COOLDOWN_DEFAULT; 0: none
+  long verify_optimistic_cooldown = -1;
   // "gather_calls": N -- single-proof calls that arrive from other threads while a proof is on the device go out together,
   // as one batch of up to N, when it returns (ffi.cpp: prove_one).  -1 (default): on, up to the workspace's capacity;
   // 0 or 1: every call is its own batch, one after the other
@@ -157,6 +164,7 @@ inline TreeConfig parse_tree_config(const std::string& js) {
       i += v ? 4 : 5;
       if (key == "temporary") c.temporary = v;
       if (key == "dynamic_shards") c.dynamic_shards = v;
+      if (key == "verify_optimistic") c.verify_optimistic = v;
     } else if (!js.compare(i, 4, "null")) {
       i += 4;
     } else if (js[i] == '[' && key == "devices") {
@@ -239,6 +247,11 @@ inline TreeConfig parse_tree_config(const std::string& js) {
       if (key == "verify_lanes") {
         if (num != 0 && num != 1 && num != 8) throw Error("Configuration error: verify_lanes: expected 0, 1 or 8");
         c.verify_lanes = num;
+      }
+      if (key == "verify_optimistic_cooldown") {
+        if (num < 0 || num > 1000000)
+          throw Error("Configuration error: verify_optimistic_cooldown: expected 0 .. 1000000 chunks");
+        c.verify_optimistic_cooldown = num;
       }
       if (key == "gather_calls") {
         if (num < 0 || num > 65536) throw Error("Configuration error: gather_calls: expected 0 .. 65536 calls");

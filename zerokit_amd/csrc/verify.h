@@ -16,6 +16,8 @@ namespace vm {
 struct PreparedKey;
 struct Prep;
 struct F12;
+struct PrepAgg;
+struct Partial;
 }  // namespace vm
 
 class GpuVerifier {
@@ -45,6 +47,29 @@ class GpuVerifier {
   // chunks run so far with a lane per proof ([0]) and in team form ([1]); for tests
   void passes(size_t out[2]);
 
+  // ---- the optimistic form (verify_agg.hip, verify_agg_math.h): the verdicts of verify(), up to the bound below.
+  // Per chunk of CHUNK proofs: the proofs that the reject rules of vm::prepare refuse get ok = 0 at once; the rest pass
+  // ONE combined pairing check under scalars r_i in [1, 2^128) drawn inside the call (getrandom), after the proofs are
+  // fixed.  If it accepts, they all get ok = 1: a chunk that holds an invalid proof is accepted with probability at
+  // most about 2^-128 over the scalars.  If it rejects, the chunk runs through the exact pass of verify(), which names
+  // the bad proofs, and the next `cooldown` chunks skip the combined check.  Taken only where verify() would run a lane
+  // per proof (n > TEAM_MAX, or lanes = 1); a call that takes teams is verify() unchanged.
+  // scalars16: null (drawn), or n x 16 bytes little-endian, none zero (a test hook: supplied scalars void the bound).
+  void verify_optimistic(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv, const uint8_t* scalars16,
+                         uint8_t* ok, int lanes = 0);
+  // test / diagnosis: the final-exponentiated combined value of all n proofs (the product over the chunks) as
+  // gt_words orders it, 1 = accept, and rejected[i] = 1 where the reject rules refuse proof i.  No fallback.
+  void aggregate(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv, const uint8_t* scalars16,
+                 uint8_t gt384[384], uint8_t* rejected);
+  // Chunks after a fallback that go straight to the exact pass.  A sender of one bad proof per chunk then costs at
+  // most one wasted combined check per cooldown + 1 chunks.  16 is a policy bound on that overhead, not a measured
+  // optimum; 0 means no cool-down.
+  static constexpr size_t COOLDOWN_DEFAULT = 16;
+  void set_cooldown(size_t chunks);
+  // [0] chunks checked combined, [1] accepted, [2] fell back, [3] chunks that skipped the check during a cool-down,
+  // [4] proofs the reject rules refused in combined checks, [5] cool-down chunks left, [6] the setting, [7] 0
+  void optimistic_stats(uint64_t out[8]);
+
  private:
   struct Impl;
   std::unique_ptr<Impl> d_;
@@ -53,5 +78,18 @@ class GpuVerifier {
 // verify_team.hip: the three team kernels over n <= TEAM_CHUNK proofs, enqueued on `stream` (a hipStream_t)
 void verify_team_enqueue(void* stream, const vm::PreparedKey* vk, const uint32_t* proofs, const uint32_t* vals,
                          vm::Prep* prep, vm::F12* f, uint8_t* ok, uint32_t* gt, uint32_t n);
+
+
+// verify_agg.hip: the kernels of one combined check over n <= CHUNK proofs, enqueued on `stream`.  part[0] and sums[0]
+// hold n entries (sums: rows of n_values + 1), part[1] and sums[1] ceil(n / 64); the levels of the fold alternate
+// between them.  Returns the index of the pair that holds the last partial in entry 0.
+struct AggBuffers {
+  vm::PrepAgg* prep;
+  vm::Partial* part[2];
+  Fr* sums[2];
+  uint8_t* rejected;
+};
+int verify_agg_enqueue(void* stream, const vm::PreparedKey* vk, const uint32_t* proofs, const uint32_t* vals,
+                       const uint32_t* scalars, const AggBuffers& b, uint32_t n, uint32_t n_values);
 
 }  // namespace rlnamd

@@ -12,12 +12,14 @@
 #include "verify.h"
 
 #include <string.h>
+#include <sys/random.h>
 
 #include <mutex>
 #include <vector>
 
 #include "common.h"
 #include "prover.h"
+#include "verify_agg_math.h"
 #include "verify_key.h"
 
 namespace rlnamd {
@@ -75,16 +77,25 @@ struct GpuVerifier::Impl {
   size_t cap = 0;           // proofs the buffers hold: grows to the largest chunk seen, at most CHUNK
   int forced_lanes = 0;     // 0: the shape follows the size of the call
   size_t n_passes[2] = {0, 0};   // chunks run with a lane per proof, in team form (under mu)
+  // the optimistic form: its buffers are made by the first call that takes it
+  vm::AggKey agg_key;
+  DevBuf<vm::PrepAgg> d_pa;
+  DevBuf<vm::Partial> d_part[2];
+  DevBuf<Fr> d_sums[2];
+  uint8_t* h_last = nullptr;     // pinned: the last partial, then its n_values + 1 sums
+  size_t agg_cap = 0;
+  uint64_t stats[5] = {0, 0, 0, 0, 0};
+  size_t cooldown = COOLDOWN_DEFAULT, cooldown_left = 0;
 
   void reserve(size_t n, bool want_gt) {
     if (n > cap) {
       release_host();
-      d_in.alloc(n * (32 + 8 * nv));
+      d_in.alloc(n * (32 + 8 * nv + 4));   // + 4 words: a proof's scalar in the optimistic form
       d_prep.alloc(n);
       d_f.alloc(n);
       d_ok.alloc(n);
       d_gt.release();
-      RLN_HIP(hipHostMalloc((void**)&h_in, n * (128 + 32 * nv), hipHostMallocDefault));
+      RLN_HIP(hipHostMalloc((void**)&h_in, n * (128 + 32 * nv + 16), hipHostMallocDefault));
       RLN_HIP(hipHostMalloc((void**)&h_ok, n, hipHostMallocDefault));
       cap = n;
     }
@@ -97,8 +108,72 @@ struct GpuVerifier::Impl {
     if (h_in) (void)hipHostFree(h_in);
     if (h_ok) (void)hipHostFree(h_ok);
     if (h_gt) (void)hipHostFree(h_gt);
-    h_in = h_ok = h_gt = nullptr;
-    cap = 0;
+    if (h_last) (void)hipHostFree(h_last);
+    h_in = h_ok = h_gt = h_last = nullptr;
+    cap = agg_cap = 0;
+  }
+  void reserve_agg(size_t n) {
+    reserve(n, false);
+    if (agg_cap >= cap) return;
+    const size_t groups = div_up(cap, (size_t)vm::FOLD);
+    d_pa.alloc(cap);
+    d_part[0].alloc(cap);
+    d_part[1].alloc(groups);
+    d_sums[0].alloc(cap * (nv + 1));
+    d_sums[1].alloc(groups * (nv + 1));
+    if (!h_last) RLN_HIP(hipHostMalloc((void**)&h_last, sizeof(vm::Partial) + (nv + 1) * sizeof(Fr), hipHostMallocDefault));
+    agg_cap = cap;
+  }
+  // One combined check over n <= CHUNK proofs: the final-exponentiated value, and rejected[i] = 1 where the reject
+  // rules refuse proof i.  scalars16: null (drawn here, after the proofs were copied into the staging buffer, which
+  // is what the device reads) or n x 16 bytes.
+  Fq12 agg_chunk(size_t n, const uint8_t* proofs, const uint8_t* values, const uint8_t* scalars16, uint8_t* rejected) {
+    reserve_agg(n);
+    memcpy(h_in, proofs, 128 * n);
+    memcpy(h_in + 128 * n, values, 32 * nv * n);
+    uint8_t* sc = h_in + (128 + 32 * nv) * n;
+    if (scalars16) {
+      memcpy(sc, scalars16, 16 * n);
+    } else {
+      for (size_t off = 0; off < 16 * n;) {   // getrandom returns at most 32 MiB - 1 bytes per call
+        const ssize_t got = getrandom(sc + off, 16 * n - off, 0);
+        if (got < 0) throw Error("verify_optimistic: getrandom failed");
+        off += (size_t)got;
+      }
+      static const uint8_t zero[16] = {0};
+      for (size_t i = 0; i < n; i++)
+        while (!memcmp(sc + 16 * i, zero, 16))
+          if (getrandom(sc + 16 * i, 16, 0) != 16) throw Error("verify_optimistic: getrandom failed");
+    }
+    RLN_HIP(hipMemcpyAsync(d_in.p, h_in, n * (128 + 32 * nv + 16), hipMemcpyHostToDevice, st));
+    const AggBuffers b{d_pa.p, {d_part[0].p, d_part[1].p}, {d_sums[0].p, d_sums[1].p}, d_ok.p};
+    const int at = verify_agg_enqueue(st, key.p, d_in.p, d_in.p + 32 * n, d_in.p + (32 + 8 * nv) * n, b, (uint32_t)n,
+                                      (uint32_t)nv);
+    RLN_HIP(hipGetLastError());
+    RLN_HIP(hipMemcpyAsync(h_last, d_part[at].p, sizeof(vm::Partial), hipMemcpyDeviceToHost, st));
+    RLN_HIP(hipMemcpyAsync(h_last + sizeof(vm::Partial), d_sums[at].p, (nv + 1) * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    RLN_HIP(hipMemcpyAsync(h_ok, d_ok.p, n, hipMemcpyDeviceToHost, st));
+    RLN_HIP(hipStreamSynchronize(st));
+    memcpy(rejected, h_ok, n);
+    vm::Partial last;
+    std::vector<Fr> sums(nv + 1);
+    memcpy(&last, h_last, sizeof(last));
+    memcpy(sums.data(), h_last + sizeof(last), (nv + 1) * sizeof(Fr));
+    return vm::finish_host(agg_key, last, sums.data());
+  }
+  // runs f with the verifier's device current
+  template <class F>
+  void on_device(F f) {
+    int cur = 0;
+    RLN_HIP(hipGetDevice(&cur));
+    if (cur != dev) RLN_HIP(hipSetDevice(dev));
+    try {
+      f();
+    } catch (...) {
+      if (cur != dev) (void)hipSetDevice(cur);
+      throw;
+    }
+    if (cur != dev) RLN_HIP(hipSetDevice(cur));
   }
   void chunk(size_t n, const uint8_t* proofs, const uint8_t* values, uint8_t* ok, uint8_t* gt384, bool team) {
     reserve(n, gt384 != nullptr);
@@ -136,6 +211,7 @@ GpuVerifier::GpuVerifier(const Zkey& zk, int forced_lanes) : d_(new Impl) {
   std::vector<G1Affine> rows;
   vm::prepare_key(zk, &K, &rows);
   D.nv = K.n_values;
+  D.agg_key = vm::agg_key(zk);
   D.ic.alloc(rows.size());
   D.key.alloc(1);
   K.ic_mult = D.ic.p;
@@ -165,20 +241,91 @@ void GpuVerifier::verify(size_t n, const uint8_t* proofs, const uint8_t* values_
   if (lanes == 0) lanes = D.forced_lanes ? D.forced_lanes : (n <= TEAM_MAX ? 8 : 1);
   const bool team = lanes == 8;
   const size_t step = team ? TEAM_CHUNK : CHUNK;
-  int cur = 0;
-  RLN_HIP(hipGetDevice(&cur));
-  if (cur != D.dev) RLN_HIP(hipSetDevice(D.dev));
-  try {
+  D.on_device([&]() {
     for (size_t off = 0; off < n; off += step) {
       const size_t m = n - off < step ? n - off : step;
       D.chunk(m, proofs + 128 * off, values_le + 32 * nv * off, ok ? ok + off : nullptr,
               gt384 ? gt384 + 384 * off : nullptr, team);
     }
-  } catch (...) {
-    if (cur != D.dev) (void)hipSetDevice(cur);
-    throw;
-  }
-  if (cur != D.dev) RLN_HIP(hipSetDevice(cur));
+  });
+}
+
+static void check_scalars(size_t n, const uint8_t* scalars16) {
+  static const uint8_t zero[16] = {0};
+  for (size_t i = 0; scalars16 && i < n; i++)
+    if (!memcmp(scalars16 + 16 * i, zero, 16)) throw Error("verify_optimistic: a supplied scalar is zero");
+}
+
+void GpuVerifier::verify_optimistic(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv,
+                                    const uint8_t* scalars16, uint8_t* ok, int lanes) {
+  Impl& D = *d_;
+  if (lanes != 0 && lanes != 1 && lanes != 8) throw Error("verify: lanes must be 0 (choose), 1 or 8");
+  if (nv != D.nv) throw Error("MalformedVerifyingKey");
+  if (n == 0) return;
+  if (!proofs || !values_le || !ok) throw Error("verify_optimistic: null argument");
+  check_scalars(n, scalars16);
+  if (lanes == 0) lanes = D.forced_lanes ? D.forced_lanes : (n <= TEAM_MAX ? 8 : 1);   // verify()'s choice
+  if (lanes == 8) return verify(n, proofs, values_le, nv, ok, nullptr, 8);   // teams: never aggregated
+  std::lock_guard<std::mutex> lk(D.mu);
+  D.on_device([&]() {
+    for (size_t off = 0; off < n; off += CHUNK) {
+      const size_t m = n - off < CHUNK ? n - off : CHUNK;
+      const uint8_t *pr = proofs + 128 * off, *va = values_le + 32 * nv * off;
+      if (D.cooldown_left) {
+        D.cooldown_left--;
+        D.stats[3]++;
+        D.chunk(m, pr, va, ok + off, nullptr, false);
+        continue;
+      }
+      D.stats[0]++;
+      const bool accept = D.agg_chunk(m, pr, va, scalars16 ? scalars16 + 16 * off : nullptr, ok + off).is_one();
+      size_t refused = 0;
+      for (size_t i = 0; i < m; i++) {
+        refused += ok[off + i];
+        ok[off + i] = ok[off + i] ? 0 : 1;
+      }
+      D.stats[4] += refused;
+      if (accept) {
+        D.stats[1]++;
+      } else {
+        D.stats[2]++;
+        D.cooldown_left = D.cooldown;
+        D.chunk(m, pr, va, ok + off, nullptr, false);   // the exact pass names the bad ones
+      }
+    }
+  });
+}
+
+void GpuVerifier::aggregate(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv,
+                            const uint8_t* scalars16, uint8_t gt384[384], uint8_t* rejected) {
+  Impl& D = *d_;
+  if (nv != D.nv) throw Error("MalformedVerifyingKey");
+  if (!gt384 || (n && (!proofs || !values_le || !rejected))) throw Error("verify_aggregate: null argument");
+  check_scalars(n, scalars16);
+  Fq12 all = Fq12::one();
+  std::lock_guard<std::mutex> lk(D.mu);
+  D.on_device([&]() {
+    for (size_t off = 0; off < n; off += CHUNK) {
+      const size_t m = n - off < CHUNK ? n - off : CHUNK;
+      all = f12_mul(all, D.agg_chunk(m, proofs + 128 * off, values_le + 32 * nv * off,
+                                     scalars16 ? scalars16 + 16 * off : nullptr, rejected + off));
+    }
+  });
+  vm::fq12_words(all, gt384);
+}
+
+void GpuVerifier::set_cooldown(size_t chunks) {
+  std::lock_guard<std::mutex> lk(d_->mu);
+  d_->cooldown = chunks;
+  if (d_->cooldown_left > chunks) d_->cooldown_left = chunks;
+}
+
+void GpuVerifier::optimistic_stats(uint64_t out[8]) {
+  std::lock_guard<std::mutex> lk(d_->mu);
+  for (int i = 0; i < 5; i++) out[i] = d_->stats[i];
+  out[5] = d_->cooldown_left;
+  out[6] = d_->cooldown;
+  out[7] = 0;
 }
 
 void GpuVerifier::passes(size_t out[2]) {

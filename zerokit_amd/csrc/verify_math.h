@@ -278,25 +278,39 @@ RLN_HD void proj_add(G2Proj* T, const Fq2& qx, const Fq2& qy, Fq2* l0, Fq2* l1, 
   T->Y = theta * (G - H) - E * T->Y;
   T->Z = T->Z * E;
 }
-// one line of each of the three pairs into f
-VM_FN void miller_step(const PreparedKey* vk, const Prep* p, F12* f, int k, const Fq2* l0, const Fq2* l1,
-                       const Fq2* l3) {
+// one line of each of the three pairs into f.  KEY_LINES = false leaves out the lines of gamma and delta (and never
+// reads icn / cn, so P may be a record without them: verify_agg_math.h's single pair)
+template <bool KEY_LINES, class P>
+RLN_HD void miller_step_t(const PreparedKey* vk, const P* p, F12* f, int k, const Fq2* l0, const Fq2* l1,
+                          const Fq2* l3) {
   if (p->flags & P_VARYING) {
     const Fq2 a0 = l0->mul_fq(p->A.y), a1 = l1->mul_fq(p->A.x);
     f12_mul_line2(f, &a0, &a1, l3);
   }
-  if (p->flags & P_GAMMA) {
-    const Fq2 g1 = vk->gamma[k].lam.mul_fq(p->icn.x).neg();
-    f12_mul_line1(f, &p->icn.y, &g1, &vk->gamma[k].c);
-  }
-  if (p->flags & P_DELTA) {
-    const Fq2 d1 = vk->delta[k].lam.mul_fq(p->cn.x).neg();
-    f12_mul_line1(f, &p->cn.y, &d1, &vk->delta[k].c);
+  if constexpr (KEY_LINES) {
+    if (p->flags & P_GAMMA) {
+      const Fq2 g1 = vk->gamma[k].lam.mul_fq(p->icn.x).neg();
+      f12_mul_line1(f, &p->icn.y, &g1, &vk->gamma[k].c);
+    }
+    if (p->flags & P_DELTA) {
+      const Fq2 d1 = vk->delta[k].lam.mul_fq(p->cn.x).neg();
+      f12_mul_line1(f, &p->cn.y, &d1, &vk->delta[k].c);
+    }
   }
 }
-// miller(A, B) miller(-IC, gamma) miller(-C, delta), up to factors of proper subfields (the caller multiplies by
-// vk->alpha_beta)
-VM_FN void miller_loop(const PreparedKey* vk, const Prep* p, F12* f) {
+VM_FN void miller_step(const PreparedKey* vk, const Prep* p, F12* f, int k, const Fq2* l0, const Fq2* l1,
+                       const Fq2* l3) {
+  miller_step_t<true>(vk, p, f, k, l0, l1, l3);
+}
+struct ThreePairStep {
+  RLN_HD void operator()(const PreparedKey* vk, const Prep* p, F12* f, int k, const Fq2* l0, const Fq2* l1,
+                         const Fq2* l3) const {
+    miller_step(vk, p, f, k, l0, l1, l3);
+  }
+};
+// The loop over the running point of (A, B); STEP folds the lines of one step into f
+template <class P, class STEP>
+RLN_HD void miller_loop_t(const PreparedKey* vk, const P* p, F12* f, STEP step) {
   f12_one(f);
   G2Proj T{p->B.x, p->B.y, Fq2::one()};
   Fq2 l0, l1, l3;
@@ -304,19 +318,24 @@ VM_FN void miller_loop(const PreparedKey* vk, const Prep* p, F12* f) {
   for (int i = ATE_LOOP_BITS - 2; i >= 0; i--) {
     f12_sqr(f, f);
     proj_double(vk, &T, &l0, &l1, &l3);
-    miller_step(vk, p, f, k++, &l0, &l1, &l3);
+    step(vk, p, f, k++, &l0, &l1, &l3);
     const uint32_t word = i >= 32 ? ATE_LOOP[1] : ATE_LOOP[0];   // bit 64 is the start value
     if ((word >> (i & 31)) & 1) {
       proj_add(&T, p->B.x, p->B.y, &l0, &l1, &l3);
-      miller_step(vk, p, f, k++, &l0, &l1, &l3);
+      step(vk, p, f, k++, &l0, &l1, &l3);
     }
   }
   const Fq2 q1x = p->B.x.conj() * vk->frob1[2], q1y = p->B.y.conj() * vk->frob1[3];   // pi(B)
   proj_add(&T, q1x, q1y, &l0, &l1, &l3);
-  miller_step(vk, p, f, k++, &l0, &l1, &l3);
+  step(vk, p, f, k++, &l0, &l1, &l3);
   const Fq2 q2x = p->B.x * vk->g22, q2y = (p->B.y * vk->g23).neg();                   // -pi^2(B)
   proj_add(&T, q2x, q2y, &l0, &l1, &l3);
-  miller_step(vk, p, f, k++, &l0, &l1, &l3);
+  step(vk, p, f, k++, &l0, &l1, &l3);
+}
+// miller(A, B) miller(-IC, gamma) miller(-C, delta), up to factors of proper subfields (the caller multiplies by
+// vk->alpha_beta)
+VM_FN void miller_loop(const PreparedKey* vk, const Prep* p, F12* f) {
+  miller_loop_t(vk, p, f, ThreePairStep{});
 }
 
 // ---------------------------------------------------------------- decompression (zkey.cpp's rules), subgroup, IC
@@ -465,12 +484,16 @@ VM_FN void ic_combination(const PreparedKey* vk, const uint32_t* vals, G1Affine*
 // Stage 1: proof bytes (32 little-endian words: A | B | C) and public inputs -> the operands of the Miller loop.
 // A rejected proof (bad encoding, B outside the subgroup, an input >= r) gets P_REJECT and harmless operands, so that
 // the later stages run the same instructions on it and its verdict is masked at the end.
-VM_FN void prepare(const PreparedKey* vk, const uint32_t* proof, const uint32_t* vals, Prep* out) {
-  bool ok = g1_decompress(vk, proof, &out->A);
-  ok = ok && g2_decompress(vk, proof + 8, &out->B);
-  G1Affine C = G1Affine::inf();
-  ok = ok && g1_decompress(vk, proof + 24, &C);
-  ok = ok && g2_in_subgroup(vk, &out->B);
+// The reject rules, one text for both forms of the verifier (prepare below, verify_agg_math.h's prepare_agg):
+// canonical encodings, points on their curves, B in the order-r subgroup, every input below r.  False: rejected; A, B
+// and C are then unspecified.
+VM_FN bool checked_points(const PreparedKey* vk, const uint32_t* proof, const uint32_t* vals, G1Affine* A, G2Affine* B,
+                          G1Affine* C) {
+  bool ok = g1_decompress(vk, proof, A);
+  ok = ok && g2_decompress(vk, proof + 8, B);
+  *C = G1Affine::inf();
+  ok = ok && g1_decompress(vk, proof + 24, C);
+  ok = ok && g2_in_subgroup(vk, B);
   for (uint32_t i = 0; ok && i < vk->n_values; i++) {
     bool lt = false, decided = false;
 #pragma unroll
@@ -483,6 +506,11 @@ VM_FN void prepare(const PreparedKey* vk, const uint32_t* proof, const uint32_t*
     }
     ok = lt;
   }
+  return ok;
+}
+VM_FN void prepare(const PreparedKey* vk, const uint32_t* proof, const uint32_t* vals, Prep* out) {
+  G1Affine C;
+  const bool ok = checked_points(vk, proof, vals, &out->A, &out->B, &C);
   if (!ok) {
     out->A = G1Affine::inf();
     out->B = G2Affine::inf();

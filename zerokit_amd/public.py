@@ -363,6 +363,16 @@ class RLN:
             raise RLNError("rlnamd_ffi_memo_stats failed")
         return dict(zip(("members", "finishes", "from_scratch", "pending"), [int(v) for v in out]))
 
+    def verify_stats(self):
+        """the device verifier behind this object (rlnamd_ffi_verify_stats): the optimistic form's counters and the
+        exact passes run so far"""
+        out = (C.c_uint64 * 10)()
+        if lib().rlnamd_ffi_verify_stats(self._h, out) != 0:
+            raise RLNError("rlnamd_ffi_verify_stats failed")
+        keys = ("combined", "accepted", "fell_back", "skipped_in_cooldown", "refused_proofs", "cooldown_left", "cooldown",
+                "reserved", "lane_passes", "team_passes")
+        return dict(zip(keys, (int(v) for v in out)))
+
     def tree_store_info(self):
         """the durable store of a persistent tree (rlnamd_ffi_tree_store_info): [0] snapshot generation, [1] journal
         bytes, [2] records since the snapshot, [3] syncs, [4] compactions, [5] records replayed at open, [6] torn bytes
