@@ -125,7 +125,9 @@ CBoolResult_t ffi_generate_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNWitnes
  * for a call-level error (null pointers, a proof of the other circuit kind).  The pairing checks run on the device
  * when n is at least the object's "verify_gpu_min" (config JSON), on host threads below it; "verify_lanes" (1 | 8 | 0)
  * names the shape of those device passes (rln_amd.h: rlnamd_verify_many_gpu_ex; 0, the default: by the size of the
- * call). */
+ * call).  With "verify_optimistic": true the passes that run a lane per proof try one combined pairing check per chunk
+ * first; with "verify_optimistic_teams": true as well, the passes that take teams do too
+ * (rln_amd.h: rlnamd_verify_many_gpu_optimistic_ex).  Both default to false. */
 CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
                                           const CFr_t* xs, const Vec_CFr_t* roots, bool* ok);
 /* EXT: ffi_verify_rln_proofs_batch from the messages themselves: exactly that call with xs[i] =

@@ -192,7 +192,7 @@ int rlnamd_ffi_prover_info(const void* ffi_rln, rlnamd_prover_info* info);
  * out: [0] members remembered, [1] proofs that were finishes, [2] proofs from scratch, [3] 1 while a partial proof is pending */
 int rlnamd_ffi_memo_stats(const void* ffi_rln, uint64_t out[4]);
 /* The device verifier behind an FFI object (ffi_verify_rln_proofs_batch, ffi_verify_rln_signals_batch; config keys
- * "verify_gpu_min", "verify_lanes", "verify_optimistic", "verify_optimistic_cooldown"): out[0..7] as
+ * "verify_gpu_min", "verify_lanes", "verify_optimistic", "verify_optimistic_teams", "verify_optimistic_cooldown"): out[0..7] as
  * rlnamd_verify_gpu_optimistic_stats, out[8] chunks run exactly with a lane per proof, out[9] in team form. */
 int rlnamd_ffi_verify_stats(const void* ffi_rln, uint64_t out[10]);
 /* The durable store of a persistent tree (config_path: "temporary": false + "path"): the directory `path`
@@ -418,16 +418,31 @@ int rlnamd_verify_gpu_passes(rlnamd_prover* p, size_t passes[2]);
  * scalars known to the sender of the proofs void the bound. */
 int rlnamd_verify_many_gpu_optimistic(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
                                       size_t n_values, const uint8_t* scalars16, uint8_t* ok);
+/* EXT: the same with the shape given and the combined check also in team form (verify_agg_team.hip).  lanes: 1 a lane
+ * per proof, 8 a team of 8 lanes per proof, 0 the verifier's choice (teams up to 1 024 proofs: the threshold measured
+ * for the exact forms); anything else is an error.  A call that takes teams runs the combined check with a team per
+ * proof in chunks of 8 192, and a chunk it rejects runs through the exact team pass; the cool-down is the one above.
+ * Everything else as rlnamd_verify_many_gpu_optimistic. */
+int rlnamd_verify_many_gpu_optimistic_ex(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                         size_t n_values, const uint8_t* scalars16, int lanes, uint8_t* ok);
 /* out[0] chunks checked combined, [1] accepted, [2] fell back to the exact pass, [3] chunks that skipped the combined
  * check during a cool-down, [4] proofs the per-proof checks refused in combined checks, [5] cool-down chunks left,
- * [6] the cool-down setting, [7] reserved, 0 */
+ * [6] the cool-down setting, [7] the chunks of [0] that were checked in team form */
 int rlnamd_verify_gpu_optimistic_stats(rlnamd_prover* p, uint64_t out[8]);
+/* diagnosis: out[0] nanoseconds the combined checks have spent in the host's finish (L, -R alpha, one Miller loop of
+ * three pairs and one final exponentiation per chunk; a host timer around it), out[1] the number of finishes */
+int rlnamd_verify_gpu_finish_time(rlnamd_prover* p, uint64_t out[2]);
 int rlnamd_verify_gpu_set_cooldown(rlnamd_prover* p, size_t chunks);
 /* test / diagnosis: the final-exponentiated combined value prod_i GT_i^(r_i) of all n proofs, 12 x 32 bytes canonical
  * LE in pairing.h's coefficient order (1 = accept), with no fallback; rejected[i] = 1 where the per-proof checks
  * refuse proof i (it counts as 1 in the product).  scalars16 as above. */
 int rlnamd_verify_gpu_aggregate(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
                                 size_t n_values, const uint8_t* scalars16, uint8_t gt384[384], uint8_t* rejected);
+/* the same with the shape given: lanes 1 (as above, chunks of 65 536) or 8 (a team per proof, chunks of 8 192); the
+ * chunk values are multiplied.  Anything else is an error. */
+int rlnamd_verify_gpu_aggregate_ex(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                   size_t n_values, const uint8_t* scalars16, int lanes, uint8_t gt384[384],
+                                   uint8_t* rejected);
 /* its host-only twin from pairing.h alone (no GPU, none of the device form's folding): the product of the exact
  * per-proof pairing products raised to the scalars.  scalars16 must be given.  The value the device is judged by. */
 int rlnamd_verify_aggregate_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n, const uint8_t* proofs,

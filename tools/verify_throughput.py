@@ -16,7 +16,11 @@ own under a time limit; a step that fails or runs out of time ends the run there
   concurrent  device verification at n = 8 192 while a proving stream runs, and the proving rate alone and meanwhile
   optimistic  (with --optimistic) rlnamd_verify_many_gpu_optimistic against the exact lane-per-proof call of the same
               build at n = 8 192 and 65 536, alternated call by call: all rows valid, and the worst case of one damaged
-              proof in every chunk with cool-down 0 (a combined check and an exact pass per chunk)
+              proof in every chunk with cool-down 0 (a combined check and an exact pass per chunk; left out when
+              --lanes names 8 alone).  With 8 among --lanes: rlnamd_verify_many_gpu_optimistic_ex(lanes = 8), the combined check in team form, against the
+              exact team call and beside the lane-per-proof combined check at n = 64, 256, 512, 1 024 and 8 192, all
+              rows valid, the three alternated call by call; and the share of the host's finish in a team-form call
+              (rlnamd_verify_gpu_finish_time)
 """
 import argparse
 import collections
@@ -37,6 +41,7 @@ DEVICE_N = (1, 8, 64, 96, 128, 192, 256, 384, 512, 1024, 2048, 4096, 8192, 16384
 HOST_N = (1, 8, 64, 96, 128, 192, 256, 384, 512, 1024, 8192)
 STEP_LIMIT_S = {"sweep": 540, "concurrent": 240, "optimistic": 240}
 OPTIMISTIC_N = (8192, 65536)
+OPTIMISTIC_TEAM_N = (64, 256, 512, 1024, 8192)
 
 
 def setup():
@@ -160,12 +165,50 @@ def step_concurrent(calls, shapes=(0,)):
             "prove_meanwhile_per_s": round(res["rate"], 1), "verify_meanwhile": row(8192, ts) if ts else None}
 
 
+def optimistic_teams(p, proofs, values, calls):
+    """the combined check in team form against the exact team call, the lane-per-proof combined check beside them"""
+    from zerokit_amd import lib
+    from zerokit_amd._native import check
+    out = []
+    for n in OPTIMISTIC_TEAM_N:
+        pr, va = tiled(proofs, values, n)
+        ok = C.create_string_buffer(n)
+        fns = (("optimistic_team", lambda: check(lib().rlnamd_verify_many_gpu_optimistic_ex(p._h, n, pr, va, 5, None, 8, ok))),
+               ("exact_team", lambda: check(lib().rlnamd_verify_many_gpu_ex(p._h, n, pr, va, 5, 8, ok, None))),
+               ("optimistic_lane", lambda: check(lib().rlnamd_verify_many_gpu_optimistic_ex(p._h, n, pr, va, 5, None, 1, ok))))
+        ts = {name: [] for name, _ in fns}
+        for _, fn in fns:   # warm-up: code objects, buffers at their size
+            fn()
+            assert ok.raw == b"\x01" * n
+        fin = {name: 0 for name, _ in fns}
+        ft = (C.c_uint64 * 2)()
+        for _ in range(calls):
+            for name, fn in fns:
+                check(lib().rlnamd_verify_gpu_finish_time(p._h, ft))
+                f0 = int(ft[0])
+                t0 = time.perf_counter()
+                fn()
+                ts[name].append(time.perf_counter() - t0)
+                check(lib().rlnamd_verify_gpu_finish_time(p._h, ft))
+                fin[name] += int(ft[0]) - f0
+        r = {"n": n}
+        for name, _ in fns:
+            r[name] = row(n, ts[name])
+            r[name]["finish_host_ms_mean"] = round(fin[name] / calls / 1e6, 3)
+        r["optimistic_team_over_exact_team"] = round(r["optimistic_team"]["median_ms"] / r["exact_team"]["median_ms"], 3)
+        out.append(r)
+    return out
+
+
 def step_optimistic(calls, shapes=(1,)):
     from zerokit_amd import lib
     from zerokit_amd._native import check
     p, _inp, _rsb, proofs, values = setup()
     out = {"all_valid": [], "one_damaged_per_chunk_cooldown_0": []}
-    for n in OPTIMISTIC_N:
+    if 8 in shapes:
+        p.verify_set_cooldown(0)
+        out["teams_all_valid"] = optimistic_teams(p, proofs, values, calls)
+    for n in OPTIMISTIC_N if 1 in shapes or 8 not in shapes else ():
         pr, va = tiled(proofs, values, n)
         bad = bytearray(va)
         bad[0] ^= 1                      # one changed public input: the pairing rejects row 0

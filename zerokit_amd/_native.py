@@ -166,10 +166,15 @@ SIGNATURES = {
     "rlnamd_verify_gpu_passes": (C.c_int, [P, C.POINTER(C.c_size_t)]),
     "rlnamd_verify_many_gpu_optimistic": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p,
                                                     C.c_char_p]),
+    "rlnamd_verify_many_gpu_optimistic_ex": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p,
+                                                       C.c_int, C.c_char_p]),
     "rlnamd_verify_gpu_optimistic_stats": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "rlnamd_verify_gpu_finish_time": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_verify_gpu_set_cooldown": (C.c_int, [P, C.c_size_t]),
     "rlnamd_verify_gpu_aggregate": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p,
                                               C.c_char_p]),
+    "rlnamd_verify_gpu_aggregate_ex": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_int,
+                                                 C.c_char_p, C.c_char_p]),
     "rlnamd_verify_aggregate_with_zkey": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p,
                                                     C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rlnamd_verify_many_with_zkey": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t,

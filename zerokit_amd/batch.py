@@ -467,37 +467,46 @@ class BatchProver:
         check(lib().rlnamd_verify_gpu_passes(self._h, out))
         return int(out[0]), int(out[1])
 
-    def verify_many_gpu_optimistic(self, proofs, public_inputs, scalars=None):
+    def verify_many_gpu_optimistic(self, proofs, public_inputs, scalars=None, lanes=None):
         """verify_many_gpu with one combined pairing check per chunk first and the exact pass only for a chunk it
         rejects (rlnamd_verify_many_gpu_optimistic): the same verdicts, up to about 2^-128 per chunk.  scalars: None
-        (drawn inside the call) or n non-zero ints below 2^128, a test hook"""
+        (drawn inside the call) or n non-zero ints below 2^128, a test hook.  lanes: None (calls that take teams are
+        verify_many_gpu unchanged), or 0 / 1 / 8 (rlnamd_verify_many_gpu_optimistic_ex: the shape as in
+        verify_many_gpu, and a call that takes teams is checked combined in team form)"""
         n = len(proofs)
         if n == 0:
             return []
         nv = _check_verify_shapes(proofs, public_inputs)
         ok = C.create_string_buffer(n)
         sc = None if scalars is None else b"".join(int(r).to_bytes(16, "little") for r in scalars)
-        check(lib().rlnamd_verify_many_gpu_optimistic(self._h, n, b"".join(proofs),
-                                                      b"".join(_b(v) for pi in public_inputs for v in pi), nv, sc, ok))
+        vals = b"".join(_b(v) for pi in public_inputs for v in pi)
+        if lanes is None:
+            check(lib().rlnamd_verify_many_gpu_optimistic(self._h, n, b"".join(proofs), vals, nv, sc, ok))
+        else:
+            check(lib().rlnamd_verify_many_gpu_optimistic_ex(self._h, n, b"".join(proofs), vals, nv, sc, int(lanes), ok))
         return [bool(x) for x in ok.raw]
 
-    def verify_aggregate(self, proofs, public_inputs, scalars=None):
-        """test / diagnosis (rlnamd_verify_gpu_aggregate): (the final-exponentiated combined value of all n proofs as
+    def verify_aggregate(self, proofs, public_inputs, scalars=None, lanes=1):
+        """test / diagnosis (rlnamd_verify_gpu_aggregate_ex): (the final-exponentiated combined value of all n proofs as
         384 bytes in pairing.h's coefficient order, the encoding of 1 = accept; a list of bools, True where the
-        per-proof checks refuse a proof).  No fallback."""
+        per-proof checks refuse a proof).  No fallback.  lanes: 1 a lane per proof, 8 a team of 8 lanes per proof"""
         n = len(proofs)
         nv = _check_verify_shapes(proofs, public_inputs) if n else self.num_public
         gt, rej = C.create_string_buffer(384), C.create_string_buffer(max(n, 1))
         sc = None if scalars is None else b"".join(int(r).to_bytes(16, "little") for r in scalars)
-        check(lib().rlnamd_verify_gpu_aggregate(self._h, n, b"".join(proofs),
-                                                b"".join(_b(v) for pi in public_inputs for v in pi), nv, sc, gt, rej))
+        check(lib().rlnamd_verify_gpu_aggregate_ex(self._h, n, b"".join(proofs),
+                                                   b"".join(_b(v) for pi in public_inputs for v in pi), nv, sc,
+                                                   int(lanes), gt, rej))
         return gt.raw, [bool(x) for x in rej.raw[:n]]
+
+    verify_gpu_aggregate = verify_aggregate
 
     def verify_optimistic_stats(self):
         """rlnamd_verify_gpu_optimistic_stats as a dict"""
         out = (C.c_uint64 * 8)()
         check(lib().rlnamd_verify_gpu_optimistic_stats(self._h, out))
-        keys = ("combined", "accepted", "fell_back", "skipped_in_cooldown", "refused_proofs", "cooldown_left", "cooldown")
+        keys = ("combined", "accepted", "fell_back", "skipped_in_cooldown", "refused_proofs", "cooldown_left", "cooldown",
+                "combined_team")
         return dict(zip(keys, (int(v) for v in out)))
 
     def verify_set_cooldown(self, chunks):

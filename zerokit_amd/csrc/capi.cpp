@@ -827,9 +827,25 @@ int rlnamd_verify_many_gpu_optimistic(rlnamd_prover* p, size_t n, const uint8_t*
   if (n) p->p->gpu_verifier().verify_optimistic(n, proofs, values_le, n_values, scalars16, ok);
   RLN_CATCH
 }
+int rlnamd_verify_many_gpu_optimistic_ex(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                         size_t n_values, const uint8_t* scalars16, int lanes, uint8_t* ok) {
+  RLN_TRY
+  if (lanes != 0 && lanes != 1 && lanes != 8)
+    throw Error("rlnamd_verify_many_gpu_optimistic_ex: lanes must be 0, 1 or 8");
+  if (n_values + 1 != p->p->zkey().gamma_abc_g1.size())
+    throw Error("MalformedVerifyingKey: rlnamd_verify_many_gpu_optimistic_ex: n_values is not the key's input count");
+  if (n && (!proofs || !values_le || !ok)) throw Error("rlnamd_verify_many_gpu_optimistic_ex: null argument with n > 0");
+  if (n) p->p->gpu_verifier().verify_optimistic(n, proofs, values_le, n_values, scalars16, ok, lanes, true);
+  RLN_CATCH
+}
 int rlnamd_verify_gpu_optimistic_stats(rlnamd_prover* p, uint64_t out[8]) {
   RLN_TRY
   p->p->gpu_verifier().optimistic_stats(out);
+  RLN_CATCH
+}
+int rlnamd_verify_gpu_finish_time(rlnamd_prover* p, uint64_t out[2]) {
+  RLN_TRY
+  p->p->gpu_verifier().finish_time(out);
   RLN_CATCH
 }
 int rlnamd_verify_gpu_set_cooldown(rlnamd_prover* p, size_t chunks) {
@@ -843,6 +859,16 @@ int rlnamd_verify_gpu_aggregate(rlnamd_prover* p, size_t n, const uint8_t* proof
   if (n_values + 1 != p->p->zkey().gamma_abc_g1.size())
     throw Error("MalformedVerifyingKey: rlnamd_verify_gpu_aggregate: n_values is not the key's input count");
   p->p->gpu_verifier().aggregate(n, proofs, values_le, n_values, scalars16, gt384, rejected);
+  RLN_CATCH
+}
+int rlnamd_verify_gpu_aggregate_ex(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                   size_t n_values, const uint8_t* scalars16, int lanes, uint8_t gt384[384],
+                                   uint8_t* rejected) {
+  RLN_TRY
+  if (lanes != 1 && lanes != 8) throw Error("rlnamd_verify_gpu_aggregate_ex: lanes must be 1 or 8");
+  if (n_values + 1 != p->p->zkey().gamma_abc_g1.size())
+    throw Error("MalformedVerifyingKey: rlnamd_verify_gpu_aggregate_ex: n_values is not the key's input count");
+  p->p->gpu_verifier().aggregate(n, proofs, values_le, n_values, scalars16, gt384, rejected, lanes);
   RLN_CATCH
 }
 }  // extern "C"

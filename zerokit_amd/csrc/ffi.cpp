@@ -352,6 +352,7 @@ struct FFI_RLN {
   size_t hash_gpu_min = HASH_GPU_MIN_DEFAULT;
   int verify_lanes = 0;   // "verify_lanes": lanes per proof of those passes (0: the verifier chooses)
   bool verify_optimistic = false;        // "verify_optimistic": a combined check per chunk first (verify_agg.hip)
+  bool verify_optimistic_teams = false;  // "verify_optimistic_teams": passes that take teams are checked combined too
   long verify_optimistic_cooldown = -1;  // "verify_optimistic_cooldown": -1 leaves the verifier's setting
   // single calls from several threads gathered into batches: gather.h
   struct GatherReq {
@@ -439,6 +440,7 @@ struct FFI_RLN {
     hash_gpu_min = tcfg.hash_gpu_min >= 0 ? (size_t)tcfg.hash_gpu_min : HASH_GPU_MIN_DEFAULT;
     verify_lanes = (int)tcfg.verify_lanes;
     verify_optimistic = tcfg.verify_optimistic;
+    verify_optimistic_teams = tcfg.verify_optimistic_teams;
     verify_optimistic_cooldown = tcfg.verify_optimistic_cooldown;
     gather_wanted = tcfg.gather_calls;
     if (const char* e = getenv("RLNAMD_GATHER_CALLS"))
@@ -1758,8 +1760,8 @@ CBoolResult_t ffi_verify_with_roots(FFI_RLN_t* const* rln, FFI_RLNProof_t* const
   });
 }
 // EXT: n proofs in one call; the public-input rows are verify_zk's (proof.rs:863-885), the pairing checks run on the
-// device from verify_gpu_min proofs on and on host threads below; with "verify_optimistic" the device passes try one
-// combined check per chunk first
+// device from verify_gpu_min proofs on and on host threads below; with "verify_optimistic" the device passes that run a
+// lane per proof try one combined check per chunk first, and with "verify_optimistic_teams" the passes in team form too
 CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
                                           const CFr_t* xs, const Vec_CFr_t* roots, bool* ok) {
   return guard_bool([&]() {
@@ -1794,7 +1796,8 @@ CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t*
     if (n >= r.verify_gpu_min && r.verify_optimistic) {
       GpuVerifier& gv = r.prover->gpu_verifier();
       if (r.verify_optimistic_cooldown >= 0) gv.set_cooldown((size_t)r.verify_optimistic_cooldown);
-      gv.verify_optimistic(n, bytes.data(), rows.data(), nv, nullptr, pass.data(), r.verify_lanes);
+      gv.verify_optimistic(n, bytes.data(), rows.data(), nv, nullptr, pass.data(), r.verify_lanes,
+                           r.verify_optimistic_teams);
     } else if (n >= r.verify_gpu_min)
       r.prover->gpu_verifier().verify(n, bytes.data(), rows.data(), nv, pass.data(), nullptr, r.verify_lanes);
     else

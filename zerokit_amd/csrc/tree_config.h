@@ -83,6 +83,10 @@ struct TreeConfig {
   // exact pass only for a chunk it rejects (GpuVerifier::verify_optimistic: verdicts equal up to about 2^-128 per
   // chunk).  Default false.  Only calls that run a lane per proof take it; "verify_lanes": 8 keeps teams.
   bool verify_optimistic = false;
+  // "verify_optimistic_teams": true | false -- with "verify_optimistic", the device passes that take teams try the
+  // combined check too, in team form (verify_agg_team.hip), and run the exact team pass for a chunk it rejects.
+  // Default false; alone it is a configuration error.
+  bool verify_optimistic_teams = false;
   // "verify_optimistic_cooldown": N -- chunks after a rejected combined check that go straight to the exact pass.
   // -1 (default): GpuVerifier::COOLDOWN_DEFAULT; 0: none
   long verify_optimistic_cooldown = -1;
@@ -165,6 +169,7 @@ inline TreeConfig parse_tree_config(const std::string& js) {
       if (key == "temporary") c.temporary = v;
       if (key == "dynamic_shards") c.dynamic_shards = v;
       if (key == "verify_optimistic") c.verify_optimistic = v;
+      if (key == "verify_optimistic_teams") c.verify_optimistic_teams = v;
     } else if (!js.compare(i, 4, "null")) {
       i += 4;
     } else if (js[i] == '[' && key == "devices") {
@@ -278,6 +283,8 @@ inline TreeConfig parse_tree_config(const std::string& js) {
     else if (i < js.size() && js[i] != '}') throw bad("expected `,` or `}`");
   }
   if (i >= js.size()) throw bad("EOF while parsing an object");
+  if (c.verify_optimistic_teams && !c.verify_optimistic)
+    throw Error("Configuration error: verify_optimistic_teams: needs \"verify_optimistic\": true as well");
   // resolve_path (pm_tree_adapter.rs:93-100)
   if (!c.temporary && !c.has_path) throw Error("Configuration error: Error while creating pmtree config: missing path");
   struct stat st;

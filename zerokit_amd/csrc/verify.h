@@ -52,23 +52,32 @@ class GpuVerifier {
   // ONE combined pairing check under scalars r_i in [1, 2^128) drawn inside the call (getrandom), after the proofs are
   // fixed.  If it accepts, they all get ok = 1: a chunk that holds an invalid proof is accepted with probability at
   // most about 2^-128 over the scalars.  If it rejects, the chunk runs through the exact pass of verify(), which names
-  // the bad proofs, and the next `cooldown` chunks skip the combined check.  Taken only where verify() would run a lane
-  // per proof (n > TEAM_MAX, or lanes = 1); a call that takes teams is verify() unchanged.
+  // the bad proofs, and the next `cooldown` chunks skip the combined check.
+  // team_checks false: taken only where verify() would run a lane per proof (n > TEAM_MAX, or lanes = 1); a call that
+  // takes teams is verify() unchanged.  team_checks true: a call that takes teams (lanes = 8, or lanes = 0 with
+  // n <= TEAM_MAX or teams forced) runs the combined check in team form (verify_agg_team.hip) per chunk of TEAM_CHUNK
+  // proofs, and a chunk it rejects runs through the exact team pass.  TEAM_MAX was measured for the exact forms only; it
+  // is the threshold of lanes = 0 here too, so that one call size means one shape.  One cool-down serves both shapes.
   // scalars16: null (drawn), or n x 16 bytes little-endian, none zero (a test hook: supplied scalars void the bound).
   void verify_optimistic(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv, const uint8_t* scalars16,
-                         uint8_t* ok, int lanes = 0);
+                         uint8_t* ok, int lanes = 0, bool team_checks = false);
   // test / diagnosis: the final-exponentiated combined value of all n proofs (the product over the chunks) as
   // gt_words orders it, 1 = accept, and rejected[i] = 1 where the reject rules refuse proof i.  No fallback.
+  // lanes: 1 a lane per proof (chunks of CHUNK), 8 a team per proof (chunks of TEAM_CHUNK); anything else throws.
   void aggregate(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv, const uint8_t* scalars16,
-                 uint8_t gt384[384], uint8_t* rejected);
+                 uint8_t gt384[384], uint8_t* rejected, int lanes = 1);
   // Chunks after a fallback that go straight to the exact pass.  A sender of one bad proof per chunk then costs at
   // most one wasted combined check per cooldown + 1 chunks.  16 is a policy bound on that overhead, not a measured
   // optimum; 0 means no cool-down.
   static constexpr size_t COOLDOWN_DEFAULT = 16;
   void set_cooldown(size_t chunks);
   // [0] chunks checked combined, [1] accepted, [2] fell back, [3] chunks that skipped the check during a cool-down,
-  // [4] proofs the reject rules refused in combined checks, [5] cool-down chunks left, [6] the setting, [7] 0
+  // [4] proofs the reject rules refused in combined checks, [5] cool-down chunks left, [6] the setting, [7] the
+  // chunks of [0] that were checked in team form
   void optimistic_stats(uint64_t out[8]);
+  // diagnosis: [0] nanoseconds the combined checks have spent in vm::finish_host (the host's three fixed pairs and the
+  // one final exponentiation per chunk), [1] the number of those calls
+  void finish_time(uint64_t out[2]);
 
  private:
   struct Impl;
@@ -91,5 +100,11 @@ struct AggBuffers {
 };
 int verify_agg_enqueue(void* stream, const vm::PreparedKey* vk, const uint32_t* proofs, const uint32_t* vals,
                        const uint32_t* scalars, const AggBuffers& b, uint32_t n, uint32_t n_values);
+// verify_agg.hip: the levels of the fold alone, over the n partials in part[0] / sums[0]; the same return value
+int verify_agg_reduce_enqueue(void* stream, const AggBuffers& b, uint32_t n, uint32_t n_values);
+// verify_agg_team.hip: the same combined check with a team of 8 lanes per proof, n <= TEAM_CHUNK: its two kernels, then
+// verify_agg_reduce_enqueue.  Returns what verify_agg_enqueue returns.
+int verify_agg_team_enqueue(void* stream, const vm::PreparedKey* vk, const uint32_t* proofs, const uint32_t* vals,
+                            const uint32_t* scalars, const AggBuffers& b, uint32_t n, uint32_t n_values);
 
 }  // namespace rlnamd

@@ -14,6 +14,7 @@
 #include <string.h>
 #include <sys/random.h>
 
+#include <chrono>
 #include <mutex>
 #include <vector>
 
@@ -84,8 +85,9 @@ struct GpuVerifier::Impl {
   DevBuf<Fr> d_sums[2];
   uint8_t* h_last = nullptr;     // pinned: the last partial, then its n_values + 1 sums
   size_t agg_cap = 0;
-  uint64_t stats[5] = {0, 0, 0, 0, 0};
+  uint64_t stats[6] = {0, 0, 0, 0, 0, 0};   // [5]: the chunks of [0] checked in team form
   size_t cooldown = COOLDOWN_DEFAULT, cooldown_left = 0;
+  uint64_t finish_ns = 0, finish_calls = 0;   // the host's share of the combined checks: time inside vm::finish_host
 
   void reserve(size_t n, bool want_gt) {
     if (n > cap) {
@@ -126,8 +128,9 @@ struct GpuVerifier::Impl {
   }
   // One combined check over n <= CHUNK proofs: the final-exponentiated value, and rejected[i] = 1 where the reject
   // rules refuse proof i.  scalars16: null (drawn here, after the proofs were copied into the staging buffer, which
-  // is what the device reads) or n x 16 bytes.
-  Fq12 agg_chunk(size_t n, const uint8_t* proofs, const uint8_t* values, const uint8_t* scalars16, uint8_t* rejected) {
+  // is what the device reads) or n x 16 bytes.  team: a team of 8 lanes per proof, n <= TEAM_CHUNK.
+  Fq12 agg_chunk(size_t n, const uint8_t* proofs, const uint8_t* values, const uint8_t* scalars16, uint8_t* rejected,
+                 bool team) {
     reserve_agg(n);
     memcpy(h_in, proofs, 128 * n);
     memcpy(h_in + 128 * n, values, 32 * nv * n);
@@ -147,8 +150,9 @@ struct GpuVerifier::Impl {
     }
     RLN_HIP(hipMemcpyAsync(d_in.p, h_in, n * (128 + 32 * nv + 16), hipMemcpyHostToDevice, st));
     const AggBuffers b{d_pa.p, {d_part[0].p, d_part[1].p}, {d_sums[0].p, d_sums[1].p}, d_ok.p};
-    const int at = verify_agg_enqueue(st, key.p, d_in.p, d_in.p + 32 * n, d_in.p + (32 + 8 * nv) * n, b, (uint32_t)n,
-                                      (uint32_t)nv);
+    const int at = (team ? verify_agg_team_enqueue : verify_agg_enqueue)(st, key.p, d_in.p, d_in.p + 32 * n,
+                                                                         d_in.p + (32 + 8 * nv) * n, b, (uint32_t)n,
+                                                                         (uint32_t)nv);
     RLN_HIP(hipGetLastError());
     RLN_HIP(hipMemcpyAsync(h_last, d_part[at].p, sizeof(vm::Partial), hipMemcpyDeviceToHost, st));
     RLN_HIP(hipMemcpyAsync(h_last + sizeof(vm::Partial), d_sums[at].p, (nv + 1) * sizeof(Fr), hipMemcpyDeviceToHost, st));
@@ -159,7 +163,11 @@ struct GpuVerifier::Impl {
     std::vector<Fr> sums(nv + 1);
     memcpy(&last, h_last, sizeof(last));
     memcpy(sums.data(), h_last + sizeof(last), (nv + 1) * sizeof(Fr));
-    return vm::finish_host(agg_key, last, sums.data());
+    const auto t0 = std::chrono::steady_clock::now();
+    const Fq12 value = vm::finish_host(agg_key, last, sums.data());
+    finish_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    finish_calls++;
+    return value;
   }
   // runs f with the verifier's device current
   template <class F>
@@ -257,28 +265,33 @@ static void check_scalars(size_t n, const uint8_t* scalars16) {
 }
 
 void GpuVerifier::verify_optimistic(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv,
-                                    const uint8_t* scalars16, uint8_t* ok, int lanes) {
+                                    const uint8_t* scalars16, uint8_t* ok, int lanes, bool team_checks) {
   Impl& D = *d_;
   if (lanes != 0 && lanes != 1 && lanes != 8) throw Error("verify: lanes must be 0 (choose), 1 or 8");
   if (nv != D.nv) throw Error("MalformedVerifyingKey");
   if (n == 0) return;
   if (!proofs || !values_le || !ok) throw Error("verify_optimistic: null argument");
   check_scalars(n, scalars16);
-  if (lanes == 0) lanes = D.forced_lanes ? D.forced_lanes : (n <= TEAM_MAX ? 8 : 1);   // verify()'s choice
-  if (lanes == 8) return verify(n, proofs, values_le, nv, ok, nullptr, 8);   // teams: never aggregated
+  // verify()'s choice.  TEAM_MAX was measured for the exact forms only; the combined check keeps it so that a call
+  // size means one shape, whichever form runs
+  if (lanes == 0) lanes = D.forced_lanes ? D.forced_lanes : (n <= TEAM_MAX ? 8 : 1);
+  const bool team = lanes == 8;
+  if (team && !team_checks) return verify(n, proofs, values_le, nv, ok, nullptr, 8);   // teams: not aggregated
+  const size_t step = team ? TEAM_CHUNK : CHUNK;
   std::lock_guard<std::mutex> lk(D.mu);
   D.on_device([&]() {
-    for (size_t off = 0; off < n; off += CHUNK) {
-      const size_t m = n - off < CHUNK ? n - off : CHUNK;
+    for (size_t off = 0; off < n; off += step) {
+      const size_t m = n - off < step ? n - off : step;
       const uint8_t *pr = proofs + 128 * off, *va = values_le + 32 * nv * off;
       if (D.cooldown_left) {
         D.cooldown_left--;
         D.stats[3]++;
-        D.chunk(m, pr, va, ok + off, nullptr, false);
+        D.chunk(m, pr, va, ok + off, nullptr, team);
         continue;
       }
       D.stats[0]++;
-      const bool accept = D.agg_chunk(m, pr, va, scalars16 ? scalars16 + 16 * off : nullptr, ok + off).is_one();
+      if (team) D.stats[5]++;
+      const bool accept = D.agg_chunk(m, pr, va, scalars16 ? scalars16 + 16 * off : nullptr, ok + off, team).is_one();
       size_t refused = 0;
       for (size_t i = 0; i < m; i++) {
         refused += ok[off + i];
@@ -290,25 +303,27 @@ void GpuVerifier::verify_optimistic(size_t n, const uint8_t* proofs, const uint8
       } else {
         D.stats[2]++;
         D.cooldown_left = D.cooldown;
-        D.chunk(m, pr, va, ok + off, nullptr, false);   // the exact pass names the bad ones
+        D.chunk(m, pr, va, ok + off, nullptr, team);   // the exact pass of the same shape names the bad ones
       }
     }
   });
 }
 
 void GpuVerifier::aggregate(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv,
-                            const uint8_t* scalars16, uint8_t gt384[384], uint8_t* rejected) {
+                            const uint8_t* scalars16, uint8_t gt384[384], uint8_t* rejected, int lanes) {
   Impl& D = *d_;
+  if (lanes != 1 && lanes != 8) throw Error("verify_aggregate: lanes must be 1 or 8");
   if (nv != D.nv) throw Error("MalformedVerifyingKey");
   if (!gt384 || (n && (!proofs || !values_le || !rejected))) throw Error("verify_aggregate: null argument");
   check_scalars(n, scalars16);
   Fq12 all = Fq12::one();
   std::lock_guard<std::mutex> lk(D.mu);
   D.on_device([&]() {
-    for (size_t off = 0; off < n; off += CHUNK) {
-      const size_t m = n - off < CHUNK ? n - off : CHUNK;
+    const size_t step = lanes == 8 ? TEAM_CHUNK : CHUNK;
+    for (size_t off = 0; off < n; off += step) {
+      const size_t m = n - off < step ? n - off : step;
       all = f12_mul(all, D.agg_chunk(m, proofs + 128 * off, values_le + 32 * nv * off,
-                                     scalars16 ? scalars16 + 16 * off : nullptr, rejected + off));
+                                     scalars16 ? scalars16 + 16 * off : nullptr, rejected + off, lanes == 8));
     }
   });
   vm::fq12_words(all, gt384);
@@ -325,7 +340,13 @@ void GpuVerifier::optimistic_stats(uint64_t out[8]) {
   for (int i = 0; i < 5; i++) out[i] = d_->stats[i];
   out[5] = d_->cooldown_left;
   out[6] = d_->cooldown;
-  out[7] = 0;
+  out[7] = d_->stats[5];
+}
+
+void GpuVerifier::finish_time(uint64_t out[2]) {
+  std::lock_guard<std::mutex> lk(d_->mu);
+  out[0] = d_->finish_ns;
+  out[1] = d_->finish_calls;
 }
 
 void GpuVerifier::passes(size_t out[2]) {

@@ -60,13 +60,9 @@ __global__ __launch_bounds__(64) void k_verify_reduce(const Partial* __restrict_
     out_sums[(size_t)blockIdx.x * n1 + j] = vm::sum_column(in_sums + (size_t)first * n1, count, n1, j);
 }
 
-int verify_agg_enqueue(void* stream, const PreparedKey* vk, const uint32_t* proofs, const uint32_t* vals,
-                       const uint32_t* scalars, const AggBuffers& b, uint32_t n, uint32_t n_values) {
+int verify_agg_reduce_enqueue(void* stream, const AggBuffers& b, uint32_t n, uint32_t n_values) {
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(div_up(n, 64)), block(64);
-  hipLaunchKernelGGL(k_verify_prepare_agg, grid, block, 0, st, vk, proofs, vals, scalars, b.prep, b.part[0], b.sums[0],
-                     b.rejected, n);
-  hipLaunchKernelGGL(k_verify_miller_agg, grid, block, 0, st, vk, b.prep, b.part[0], n);
+  const dim3 block(64);
   int cur = 0;
   uint32_t left = n;
   do {   // n = 1 still takes one level: the last partial is always a folded one
@@ -77,6 +73,16 @@ int verify_agg_enqueue(void* stream, const PreparedKey* vk, const uint32_t* proo
     left = groups;
   } while (left > 1);
   return cur;
+}
+
+int verify_agg_enqueue(void* stream, const PreparedKey* vk, const uint32_t* proofs, const uint32_t* vals,
+                       const uint32_t* scalars, const AggBuffers& b, uint32_t n, uint32_t n_values) {
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(div_up(n, 64)), block(64);
+  hipLaunchKernelGGL(k_verify_prepare_agg, grid, block, 0, st, vk, proofs, vals, scalars, b.prep, b.part[0], b.sums[0],
+                     b.rejected, n);
+  hipLaunchKernelGGL(k_verify_miller_agg, grid, block, 0, st, vk, b.prep, b.part[0], n);
+  return verify_agg_reduce_enqueue(stream, b, n, n_values);
 }
 
 }  // namespace rlnamd

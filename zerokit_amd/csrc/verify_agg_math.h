@@ -166,20 +166,13 @@ inline void fq12_words(const Fq12& f, uint8_t out[384]) {   // gt_words' order
   }
 }
 
-// The kernels of verify_agg.hip with their lanes in a loop: n proofs -> the last partial and its sums (levels of FOLD
-// until one partial is left), rejected[i] = 1 where the shared checks refuse proof i.  For the CPU suite.
-inline void host_aggregate_lanes(const PreparedKey* vk, size_t n, const uint32_t* proofs, const uint32_t* vals,
-                                 const uint32_t* scalars, uint8_t* rejected, Partial* last, std::vector<Fr>* last_sums) {
-  const uint32_t n1 = vk->n_values + 1;
-  std::vector<Partial> cur(n ? n : 1);
-  std::vector<Fr> sums((n ? n : 1) * n1, Fr::zero());
-  if (!n) partial_identity(&cur[0]);
-  for (size_t i = 0; i < n; i++) {
-    PrepAgg pa;
-    prepare_agg(vk, proofs + 32 * i, vals + (size_t)8 * vk->n_values * i, scalars + 4 * i, &pa, &cur[i].c, &sums[i * n1]);
-    miller_loop_pair(vk, &pa, &cur[i].f);
-    rejected[i] = (pa.flags & P_REJECT) ? 1 : 0;
-  }
+// The levels of k_verify_reduce with their lanes in a loop: cur (at least one partial) and its rows of n1 sums are
+// folded FOLD to 1 until one partial is left; both vectors are used up.  Shared by the lane and the team form
+// (verify_agg_team_math.h).
+inline void host_fold_levels(uint32_t n1, std::vector<Partial>* cur_in, std::vector<Fr>* sums_in, Partial* last,
+                             std::vector<Fr>* last_sums) {
+  std::vector<Partial>& cur = *cur_in;
+  std::vector<Fr>& sums = *sums_in;
   while (cur.size() > 1) {
     const size_t groups = (cur.size() + FOLD - 1) / FOLD;
     std::vector<Partial> next(groups);
@@ -201,6 +194,22 @@ inline void host_aggregate_lanes(const PreparedKey* vk, size_t n, const uint32_t
   }
   *last = cur[0];
   last_sums->assign(sums.begin(), sums.begin() + n1);
+}
+// The kernels of verify_agg.hip with their lanes in a loop: n proofs -> the last partial and its sums (levels of FOLD
+// until one partial is left), rejected[i] = 1 where the shared checks refuse proof i.  For the CPU suite.
+inline void host_aggregate_lanes(const PreparedKey* vk, size_t n, const uint32_t* proofs, const uint32_t* vals,
+                                 const uint32_t* scalars, uint8_t* rejected, Partial* last, std::vector<Fr>* last_sums) {
+  const uint32_t n1 = vk->n_values + 1;
+  std::vector<Partial> cur(n ? n : 1);
+  std::vector<Fr> sums((n ? n : 1) * n1, Fr::zero());
+  if (!n) partial_identity(&cur[0]);
+  for (size_t i = 0; i < n; i++) {
+    PrepAgg pa;
+    prepare_agg(vk, proofs + 32 * i, vals + (size_t)8 * vk->n_values * i, scalars + 4 * i, &pa, &cur[i].c, &sums[i * n1]);
+    miller_loop_pair(vk, &pa, &cur[i].f);
+    rejected[i] = (pa.flags & P_REJECT) ? 1 : 0;
+  }
+  host_fold_levels(n1, &cur, &sums, last, last_sums);
 }
 
 }  // namespace vm

@@ -15,41 +15,13 @@
 #include "verify.h"
 
 #include "common.h"
-#include "verify_team_math.h"
+#include "verify_team_lds.h"   // the device's exchange: LdsX, team_exchange, lds_bytes
 
 namespace rlnamd {
 
 using vm::F12;
 using vm::Prep;
 using vm::PreparedKey;
-
-extern __shared__ uint4 vt_lds_raw[];
-
-namespace {
-
-// The device's exchange (verify_team_math.h): this thread is one lane of one team, the team's memory is a slice of LDS
-struct LdsX {
-  static constexpr int NL = 1;
-  uint32_t base;  // the team's first Fq2 unit
-  int lane, n_slots;
-  __device__ __forceinline__ int lane_lo() const { return lane; }
-  __device__ __forceinline__ int lane_hi() const { return lane + 1; }
-  __device__ __forceinline__ int li(int) const { return 0; }
-  __device__ __forceinline__ Fq2* mem() const { return reinterpret_cast<Fq2*>(vt_lds_raw) + base; }
-  __device__ __forceinline__ Fq2& f(int slot, int i) const { return mem()[2 + 6 * slot + i]; }
-  __device__ __forceinline__ Fq2& s(int i) const { return mem()[2 + 6 * n_slots + i]; }
-  __device__ __forceinline__ uint32_t& w(int i) const { return reinterpret_cast<uint32_t*>(mem())[i]; }
-  __device__ __forceinline__ void sync() const { __syncthreads(); }
-};
-__device__ __forceinline__ LdsX team_exchange(int n_slots, int n_scratch) {
-  const uint32_t team = threadIdx.x / vt::TEAM;
-  return {team * (uint32_t)vt::team_units(n_slots, n_scratch), (int)(threadIdx.x % vt::TEAM), n_slots};
-}
-constexpr size_t lds_bytes(int n_slots, int n_scratch) {
-  return (size_t)vt::TEAMS_PER_WAVE * vt::team_units(n_slots, n_scratch) * sizeof(Fq2);
-}
-
-}  // namespace
 
 // proofs: n x 32 words, vals: n x nv x 8 words
 __global__ __launch_bounds__(64) void k_verify_prepare_team(const PreparedKey* __restrict__ vk, const uint32_t* __restrict__ proofs,

@@ -50,8 +50,11 @@ RLN_HD constexpr int team_units(int n_slots, int n_scratch) { return 2 + 6 * n_s
 constexpr int MILLER_SLOTS = 2, MILLER_SCRATCH = 30;
 constexpr int FINAL_SLOTS = 10, FINAL_SCRATCH = 0;
 constexpr int PREP_SLOTS = 0, PREP_SCRATCH = 32;
+// the optimistic form (verify_agg_team_math.h): no x_i IC_i places in its first stage; its Miller stage, without
+// alpha_beta and the lines of gamma and delta, is PAIR_SLOTS / PAIR_SCRATCH below
+constexpr int PREP_AGG_SCRATCH = 14;
 
-// The host's exchange: an array, the eight lanes run one after the other.  (verify_team.hip has the device's.)
+// The host's exchange: an array, the eight lanes run one after the other.  (verify_team_lds.h has the device's.)
 struct HostX {
   static constexpr int NL = TEAM;
   Fq2* mem;
@@ -318,12 +321,19 @@ enum {
   S_END
 };
 static_assert(S_END <= MILLER_SCRATCH, "scratch places of the Miller stage");
+// With one pair (KEY_LINES = false) the six places of the gamma and delta lines go: the added point moves down
+constexpr int PAIR_SLOTS = 1, PAIR_SCRATCH = S_END - (SQX - SGY);
+template <bool KEY_LINES>
+RLN_HD constexpr int sq_place(int i) { return KEY_LINES ? i : i - (SQX - SGY); }
+static_assert(sq_place<false>(SQY) + 1 <= PAIR_SCRATCH, "scratch places of the one-pair Miller stage");
 
 // Lanes 2..5 of a step's level 3 form the four places of its lines that need one product each: l0 y_A and l1 x_A of
 // the variable pair, -lam x of the gamma and of the delta line (an Fq factor as an Fq2, so that every lane of the level
 // runs one product program).  A pair that is absent (flags) gets the line 1: the same instructions, f unchanged.
-template <class X>
-RLN_HD void line_factor(const X& x, const PreparedKey* vk, const Prep* p, int k, int step, const Fq2& l0,
+// KEY_LINES = false is the one pair of the optimistic form: lanes 4 and 5 have no line, P is a record without icn / cn
+// (vm::PrepAgg) and the places of the gamma and delta lines are never touched.
+template <bool KEY_LINES, class X, class P>
+RLN_HD void line_factor(const X& x, const PreparedKey* vk, const P* p, int k, int step, const Fq2& l0,
                         const Fq2& l1, Fq2* a, Fq2* b) {
   if (k == 2) {
     *a = l0;
@@ -331,33 +341,37 @@ RLN_HD void line_factor(const X& x, const PreparedKey* vk, const Prep* p, int k,
   } else if (k == 3) {
     *a = l1;
     *b = fq_as_fq2(p->A.x);
-  } else if (k == 4) {
-    *a = vk->gamma[step].lam;
-    *b = fq_as_fq2(p->icn.x.neg());
-  } else if (k == 5) {
-    *a = vk->delta[step].lam;
-    *b = fq_as_fq2(p->cn.x.neg());
+  } else if constexpr (KEY_LINES) {
+    if (k == 4) {
+      *a = vk->gamma[step].lam;
+      *b = fq_as_fq2(p->icn.x.neg());
+    } else if (k == 5) {
+      *a = vk->delta[step].lam;
+      *b = fq_as_fq2(p->cn.x.neg());
+    }
   }
 }
-template <class X>
-RLN_HD void line_store(const X& x, const PreparedKey* vk, const Prep* p, int k, int step, const Fq2& v) {
-  const bool va = (p->flags & vm::P_VARYING) != 0, ga = (p->flags & vm::P_GAMMA) != 0,
-             de = (p->flags & vm::P_DELTA) != 0;
+template <bool KEY_LINES, class X, class P>
+RLN_HD void line_store(const X& x, const PreparedKey* vk, const P* p, int k, int step, const Fq2& v) {
+  const bool va = (p->flags & vm::P_VARYING) != 0;
   if (k == 2) {
     x.s(SA0) = sel(va, v, Fq2::one());
   } else if (k == 3) {
     x.s(SA1) = sel(va, v, Fq2::zero());
-  } else if (k == 4) {
-    x.s(SG1) = sel(ga, v, Fq2::zero());
-    x.s(SGC) = sel(ga, vk->gamma[step].c, Fq2::zero());
-  } else if (k == 5) {
-    x.s(SD1) = sel(de, v, Fq2::zero());
-    x.s(SDC) = sel(de, vk->delta[step].c, Fq2::zero());
+  } else if constexpr (KEY_LINES) {
+    const bool ga = (p->flags & vm::P_GAMMA) != 0, de = (p->flags & vm::P_DELTA) != 0;
+    if (k == 4) {
+      x.s(SG1) = sel(ga, v, Fq2::zero());
+      x.s(SGC) = sel(ga, vk->gamma[step].c, Fq2::zero());
+    } else if (k == 5) {
+      x.s(SD1) = sel(de, v, Fq2::zero());
+      x.s(SDC) = sel(de, vk->delta[step].c, Fq2::zero());
+    }
   }
 }
 // T <- 2 T and the lines of step `step` (vm::proj_double dealt to the lanes: three levels of products)
-template <class X>
-VT_FN void t_double_step(X x, const PreparedKey* vk, const Prep* p, int step) {
+template <bool KEY_LINES, class X, class P>
+VT_FN void t_double_step_t(X x, const PreparedKey* vk, const P* p, int step) {
   Fq2 r[X::NL];
   // level 1: Y^2, Z^2, Y Z, X^2, X Y on lanes 0..4
   VT_LANES(x, k) {
@@ -396,7 +410,7 @@ VT_FN void t_double_step(X x, const PreparedKey* vk, const Prep* p, int step) {
       d = E;
     } else {
       const Fq2 X2 = x.s(SX2);
-      line_factor(x, vk, p, k, step, x.s(SYZ).dbl().neg(), X2.dbl() + X2, &a, &b);
+      line_factor<KEY_LINES>(x, vk, p, k, step, x.s(SYZ).dbl().neg(), X2.dbl() + X2, &a, &b);
     }
     r[x.li(k)] = dot2(a, b, c, d);
   }
@@ -405,16 +419,17 @@ VT_FN void t_double_step(X x, const PreparedKey* vk, const Prep* p, int step) {
     if (k == 0) x.s(SX) = r[x.li(k)];
     if (k == 1) x.s(SY) = r[x.li(k)];
     if (k == 6) x.s(SA3) = sel((p->flags & vm::P_VARYING) != 0, x.s(SE) - x.s(SB), Fq2::zero());
-    line_store(x, vk, p, k, step, r[x.li(k)]);
+    line_store<KEY_LINES>(x, vk, p, k, step, r[x.li(k)]);
   }
   x.sync();
 }
 // T <- T + Q (Q in SQX, SQY) and the lines of step `step` (vm::proj_add: four levels)
-template <class X>
-VT_FN void t_add_step(X x, const PreparedKey* vk, const Prep* p, int step) {
+template <bool KEY_LINES, class X, class P>
+VT_FN void t_add_step_t(X x, const PreparedKey* vk, const P* p, int step) {
+  constexpr int QX = sq_place<KEY_LINES>(SQX), QY = sq_place<KEY_LINES>(SQY);
   Fq2 r[X::NL];
   // level 1: theta = Y - y_Q Z, lambda = X - x_Q Z
-  VT_LANES(x, k) r[x.li(k)] = x.s(k == 0 ? SY : SX) - x.s(k == 0 ? SQY : SQX) * x.s(SZ);
+  VT_LANES(x, k) r[x.li(k)] = x.s(k == 0 ? SY : SX) - x.s(k == 0 ? QY : QX) * x.s(SZ);
   x.sync();
   VT_LANES(x, k) {
     if (k < 2) x.s(STH + k) = r[x.li(k)];
@@ -425,7 +440,7 @@ VT_FN void t_add_step(X x, const PreparedKey* vk, const Prep* p, int step) {
     const Fq2 th = x.s(STH), la = x.s(SLA);
     const Fq2 a = sel(k == 1, la, th);
     const bool l3 = k == 2;
-    r[x.li(k)] = dot2(a, sel(l3, x.s(SQX), a), sel(l3, la.neg(), Fq2::zero()), x.s(SQY));
+    r[x.li(k)] = dot2(a, sel(l3, x.s(QX), a), sel(l3, la.neg(), Fq2::zero()), x.s(QY));
   }
   x.sync();
   VT_LANES(x, k) {
@@ -446,7 +461,7 @@ VT_FN void t_add_step(X x, const PreparedKey* vk, const Prep* p, int step) {
       a = x.s(SX);
       b = x.s(SDD);
     } else {
-      line_factor(x, vk, p, k, step, x.s(SLA), x.s(STH).neg(), &a, &b);
+      line_factor<KEY_LINES>(x, vk, p, k, step, x.s(SLA), x.s(STH).neg(), &a, &b);
     }
     r[x.li(k)] = a * b;
   }
@@ -455,7 +470,7 @@ VT_FN void t_add_step(X x, const PreparedKey* vk, const Prep* p, int step) {
     if (k == 0) x.s(SEE) = r[x.li(k)];
     if (k == 1) x.s(SFF) = r[x.li(k)];
     if (k == 6) x.s(SGG) = r[x.li(k)];
-    line_store(x, vk, p, k, step, r[x.li(k)]);
+    line_store<KEY_LINES>(x, vk, p, k, step, r[x.li(k)]);
   }
   x.sync();
   // level 4: X' = lambda H, Y' = theta (G - H) - E Y, Z' = Z E with H = E + F - 2 G
@@ -480,37 +495,44 @@ VT_FN void t_add_step(X x, const PreparedKey* vk, const Prep* p, int step) {
   }
   x.sync();
 }
-template <class X>
-RLN_HD void t_three_lines(const X& x) {
+template <bool KEY_LINES, class X>
+RLN_HD void t_step_lines(const X& x) {
   t_mul_line(x, 0, 0, SA0, SA1, SA3);
-  t_mul_line(x, 0, 0, SGY, SG1, SGC);
-  t_mul_line(x, 0, 0, SDY, SD1, SDC);
+  if constexpr (KEY_LINES) {
+    t_mul_line(x, 0, 0, SGY, SG1, SGC);
+    t_mul_line(x, 0, 0, SDY, SD1, SDC);
+  }
 }
-// vm::miller_loop times vk->alpha_beta: the value is left in slot 0
-template <class X>
-VT_FN void t_miller_loop(X x, const PreparedKey* vk, const Prep* p) {
+// The walk of the running point of (A, B) with the lines of each step folded into slot 0: all three pairs
+// (vm::miller_loop), or with KEY_LINES = false the variable pair alone (vm::miller_loop_pair: no line of gamma or
+// delta is formed or multiplied in, not even as the line 1)
+template <bool KEY_LINES, class X, class P>
+RLN_HD void t_miller_walk(const X& x, const PreparedKey* vk, const P* p) {
+  constexpr int QX = sq_place<KEY_LINES>(SQX), QY = sq_place<KEY_LINES>(SQY);
   VT_LANES(x, k) {
     if (k < 6) x.f(0, k) = k == 0 ? Fq2::one() : Fq2::zero();
     if (k == 0) {
-      x.s(SX) = x.s(SQX) = p->B.x;
-      x.s(SY) = x.s(SQY) = p->B.y;
+      x.s(SX) = x.s(QX) = p->B.x;
+      x.s(SY) = x.s(QY) = p->B.y;
       x.s(SZ) = Fq2::one();
     }
-    if (k == 1) {
-      x.s(SGY) = sel((p->flags & vm::P_GAMMA) != 0, fq_as_fq2(p->icn.y), Fq2::one());
-      x.s(SDY) = sel((p->flags & vm::P_DELTA) != 0, fq_as_fq2(p->cn.y), Fq2::one());
+    if constexpr (KEY_LINES) {
+      if (k == 1) {
+        x.s(SGY) = sel((p->flags & vm::P_GAMMA) != 0, fq_as_fq2(p->icn.y), Fq2::one());
+        x.s(SDY) = sel((p->flags & vm::P_DELTA) != 0, fq_as_fq2(p->cn.y), Fq2::one());
+      }
     }
   }
   x.sync();
   int step = 0;
   for (int i = ATE_LOOP_BITS - 2; i >= 0; i--) {
     t_sqr(x, 0, 0);
-    t_double_step(x, vk, p, step++);
-    t_three_lines(x);
+    t_double_step_t<KEY_LINES>(x, vk, p, step++);
+    t_step_lines<KEY_LINES>(x);
     const uint32_t word = i >= 32 ? ATE_LOOP[1] : ATE_LOOP[0];
     if ((word >> (i & 31)) & 1) {
-      t_add_step(x, vk, p, step++);
-      t_three_lines(x);
+      t_add_step_t<KEY_LINES>(x, vk, p, step++);
+      t_step_lines<KEY_LINES>(x);
     }
   }
   // pi(B) and -pi^2(B)
@@ -526,12 +548,17 @@ VT_FN void t_miller_loop(X x, const PreparedKey* vk, const Prep* p) {
     }
     x.sync();
     VT_LANES(x, k) {
-      if (k < 2) x.s(SQX + k) = r[x.li(k)];
+      if (k < 2) x.s(QX + k) = r[x.li(k)];
     }
     x.sync();
-    t_add_step(x, vk, p, step++);
-    t_three_lines(x);
+    t_add_step_t<KEY_LINES>(x, vk, p, step++);
+    t_step_lines<KEY_LINES>(x);
   }
+}
+// vm::miller_loop times vk->alpha_beta: the value is left in slot 0
+template <class X>
+VT_FN void t_miller_loop(X x, const PreparedKey* vk, const Prep* p) {
+  t_miller_walk<true>(x, vk, p);
   t_load(x, 1, &vk->alpha_beta);
   t_mul(x, 0, 0, 1);
 }
@@ -581,11 +608,14 @@ enum { WF = 0 /* + k: lanes 0..2 */, WCAND = 4 /* + k */, WOK = 8 /* + k: A, C, 
 enum : uint32_t { F_X = 1, F_ROOT = 2, F_INF = 4, F_SPECIAL = 8 };
 
 RLN_HD G1XYZZ ld_xyzz(const Fq2& a, const Fq2& b) { return {a.c0, a.c1, b.c0, b.c1}; }
-// vm::prepare with what is one program on different data run at once: the square-root chains of y_A, y_C and of the
-// norm of B's right-hand side (lanes 0..2), then both candidates of vm::fq2_sqrt (lanes 0, 1), then a lane per public
-// input for x_i IC_i, summed on lane 0.  The 128-step ladder of the subgroup test stays on lane 0.
+// The reject rules of the points, one text for both team forms (t_prepare below, verify_agg_team_math.h's
+// t_prepare_agg), as vm::checked_points is for the lane forms: the decompression phases and the subgroup test.  With
+// what is one program on different data run at once: the square-root chains of y_A, y_C and of the norm of B's
+// right-hand side (lanes 0..2), then both candidates of vm::fq2_sqrt (lanes 0, 1).  The 128-step ladder of the subgroup
+// test stays on lane 0.  Leaves A, C and B in PA, PC, PBX | PBY and the verdicts in WOK + 0..2 and WSUB; the bound on
+// the public inputs is the caller's (val_below_r).
 template <class X>
-VT_FN void t_prepare(X x, const PreparedKey* vk, const uint32_t* proof, const uint32_t* vals, Prep* out, bool live) {
+RLN_HD void t_checked_points(const X& x, const PreparedKey* vk, const uint32_t* proof) {
   // phase 1: read the three x coordinates, form the right-hand sides, one square root per lane
   {
     Fq in[X::NL], root[X::NL];
@@ -684,14 +714,35 @@ VT_FN void t_prepare(X x, const PreparedKey* vk, const uint32_t* proof, const ui
     }
   }
   x.sync();
-  // phase 4: the subgroup test on lane 0; a lane per public input, eight at a time
-  G1XYZZ total[X::NL];
+  // phase 4, first half: the subgroup test on lane 0
   VT_LANES(x, k) {
-    total[x.li(k)] = G1XYZZ::inf();
     if (k == 0) {
       const G2Affine B{x.s(PBX), x.s(PBY)};
       x.w(WSUB) = vm::g2_in_subgroup(vk, &B) ? 1 : 0;
     }
+  }
+}
+// a public input (8 canonical words) is below r
+RLN_HD bool val_below_r(const uint32_t* v) {
+  bool lt = false, decided = false;
+#pragma unroll
+  for (int j = 7; j >= 0; j--) {
+    const uint32_t c = v[j], m = FrParams::MOD[j];
+    if (!decided && c != m) {
+      lt = c < m;
+      decided = true;
+    }
+  }
+  return lt;
+}
+// vm::prepare: t_checked_points, then a lane per public input for x_i IC_i, summed on lane 0
+template <class X>
+VT_FN void t_prepare(X x, const PreparedKey* vk, const uint32_t* proof, const uint32_t* vals, Prep* out, bool live) {
+  t_checked_points(x, vk, proof);
+  // phase 4: a lane per public input, eight at a time
+  G1XYZZ total[X::NL];
+  VT_LANES(x, k) {
+    total[x.li(k)] = G1XYZZ::inf();
     x.w(WVAL + k) = 1;
   }
   const uint32_t nv = vk->n_values;
@@ -702,15 +753,7 @@ VT_FN void t_prepare(X x, const PreparedKey* vk, const uint32_t* proof, const ui
       const bool active = base + k < nv;
       const uint32_t i = active ? base + k : 0;
       const uint32_t* v = vals + 8 * i;
-      bool lt = false, decided = false;
-#pragma unroll
-      for (int j = 7; j >= 0; j--) {
-        const uint32_t c = v[j], m = FrParams::MOD[j];
-        if (!decided && c != m) {
-          lt = c < m;
-          decided = true;
-        }
-      }
+      const bool lt = val_below_r(v);
       if (active && !lt) x.w(WVAL + k) = 0;
       acc[l] = G1XYZZ::inf();
       for (int w = 63; w >= 0; w--) {

@@ -370,7 +370,7 @@ class RLN:
         if lib().rlnamd_ffi_verify_stats(self._h, out) != 0:
             raise RLNError("rlnamd_ffi_verify_stats failed")
         keys = ("combined", "accepted", "fell_back", "skipped_in_cooldown", "refused_proofs", "cooldown_left", "cooldown",
-                "reserved", "lane_passes", "team_passes")
+                "combined_team", "lane_passes", "team_passes")
         return dict(zip(keys, (int(v) for v in out)))
 
     def tree_store_info(self):
