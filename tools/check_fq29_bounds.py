@@ -4,6 +4,9 @@ every call site in fq29.h, walk29.h, poseidon.h and the NTT's mul_mont with ALL 
 representation class and the reduction digit at its maximum (2^32 - 1 in a wide round, 2^29 - 1 in a masked one), and
 asserts that no 64-bit column accumulator reaches 2^64.  Every term of a column is non-negative and monotone in each
 operand limb and in the digit, so the all-maximum replay bounds every real execution.  Run by tests/test_host_math.py.
+The second half (NttReplay) does the same for the big batches' quotient transforms, which run whole passes on these limbs
+with lazy sums: every level of every instantiated k_ntt_pass / k_ntt_turn and the reduction in front of their stores
+(tests/test_ntt29_host.py).
 
 Classes (limb vectors of 9 entries):
   N(B)      normalised value < B q: limbs 0..7 <= 2^29 - 1, limb 8 <= (B q) >> 232
@@ -150,6 +153,207 @@ def call_sites(name, f):
 FIELDS = (("Fq", Q), ("Fr", R))
 
 
+# ====================================================================================================================
+# The quotient transforms of a big batch on 29-bit limbs (prover_front.hip: k_ntt_pass / k_ntt_turn).  Every function
+# below restates one helper of the kernels, on MAXIMA: a value is (limb maxima, maximum of the integer).  The replay
+# walks every level of every instantiated pass and turn in both of a wave's modes (lo != 0: no butterfly is a unit one;
+# lo == 0: every butterfly with a compile-time zero twiddle index is) and asserts
+#   * no 32-bit limb sum and no normalisation carry reaches 2^32, no column of a product reaches 2^64,
+#   * every K - v has K[j] >= v[j] in every limb (so no limb borrows),
+#   * the quotient estimate of the pre-store reduction never exceeds x / r and leaves less than 2 r,
+#   * every stored integer is below 2^256 (below 2 r where the canonical store's conditional subtraction follows).
+# Kept apart from call_sites(): that table also drives the device's class-maximum operands (tests/field_ops_cases.py).
+NTT_RHO = (R >> 232) + 1                  # ceil(r / 2^232)
+NTT_MAGIC = (1 << 53) // NTT_RHO          # q = (v[8] * MAGIC) >> 53 = floor(v[8] / RHO), or one less on exact multiples
+NTT_NEGR = limbs((1 << 261) - R)          # x - q r = x + q (2^261 - r) mod 2^261
+
+
+def ntt_constants():
+    """name -> (limbs, integer): the minuend biases of the transforms' differences"""
+    lo1, lo2 = 1 << B29, 2 << B29
+    return {"K2": (biased(2 * R, lo1), 2 * R), "K6": (biased(6 * R, lo1), 6 * R), "K12": (biased(12 * R, lo1), 12 * R),
+            "K24": (biased(24 * R, lo1), 24 * R), "K12B2": (biased(12 * R, lo2), 12 * R), "K4B2": (biased(4 * R, lo2), 4 * R)}
+
+
+class NttReplay:
+    def __init__(self):
+        self.f = Field(R)
+        self.K = ntt_constants()
+        self.tw = ([M] * 8 + [(R - 1) >> 232], R - 1)      # table entries: canonical t 2^261 mod r
+        self.rows = {}                                     # label -> worst column
+        self.stored = 0
+        self.where = ""
+
+    # ---- the helpers of the kernels
+    def load(self):
+        return ([M] * 8 + [(1 << 24) - 1], (1 << 256) - 1)           # any integer below 2^256, re-sliced
+
+    def is_norm(self, a):
+        return all(x <= M for x in a[0][:8])
+
+    def add(self, a, b):
+        l = [x + y for x, y in zip(a[0], b[0])]
+        assert max(l) < 1 << 32, "%s: limb sum reaches 2^32" % self.where
+        return (l, a[1] + b[1])
+
+    def norm(self, a):
+        c = 0
+        for j in range(9):
+            x = a[0][j] + c
+            assert x < 1 << 32, "%s: normalisation carry reaches 2^32" % self.where
+            c = x >> 29
+        assert a[1] >> 232 < 1 << 29, "%s: value does not fit nine limbs" % self.where
+        return ([M] * 8 + [a[1] >> 232], a[1])
+
+    def sub(self, u, kname, v):
+        K, kval = self.K[kname]
+        assert all(K[j] >= v[0][j] for j in range(9)), "%s: %s does not dominate the subtrahend" % (self.where, kname)
+        assert kval >= v[1]
+        l = [x + y for x, y in zip(u[0], K)]
+        assert max(l) < 1 << 32, "%s: limb sum reaches 2^32" % self.where
+        return (l, u[1] + kval)
+
+    def mul(self, d, label):                                           # Fr29::mul: wide rounds at every call site
+        w = replay(self.f, [(d[0], self.tw[0])], True)
+        key = (label, True)
+        self.rows[key] = max(self.rows.get(key, 0), w)
+        val = R + ((d[1] * self.tw[1]) >> 261) + (R >> 25)            # digits < 2^261 + 2^236
+        return ([M] * 8 + [val >> 232], val)
+
+    def reduce(self, a):
+        assert self.is_norm(a)
+        v8max = a[0][8]
+        qmax = (v8max * NTT_MAGIC) >> 53
+        assert NTT_MAGIC < 1 << 32 and v8max < 1 << 29 and qmax < 1 << 8
+        worst = 0
+        for k in range(qmax + 1):
+            lo = -((-(k << 53)) // NTT_MAGIC)                          # smallest v[8] with estimate k
+            hi = min(v8max, -((-((k + 1) << 53)) // NTT_MAGIC) - 1)    # largest
+            assert (lo * NTT_MAGIC) >> 53 == k and (hi * NTT_MAGIC) >> 53 == k
+            assert (lo << 232) >= k * R, "%s: estimate above x / r" % self.where
+            worst = max(worst, min(((hi + 1) << 232) - 1, a[1]) - k * R)
+        assert worst < 2 * R and worst < 1 << 256, "%s: reduction leaves %.3f r" % (self.where, worst / R)
+        # columns of x + q NEGR: q NEGR[j] + v[j] + carry < 2^8 2^29 + 2^29 + 2^9
+        return ([M] * 8 + [worst >> 232], worst)
+
+    def store(self, a, canonical):
+        assert self.is_norm(a) and a[1] < (2 * R if canonical else 1 << 256), \
+            "%s: stored value reaches %.3f r" % (self.where, a[1] / R)
+        assert a[0][8] < 1 << 24
+        self.stored = max(self.stored, a[1])
+
+    # ---- the levels, as the kernels run them
+    @staticmethod
+    def dif_sums(K, m, t):
+        """how many of the DIF levels t - 1, t - 2, ... left element m on the sum side, consecutively"""
+        c = 0
+        for l in range(t - 1, -1, -1):
+            if m & ((1 << K) >> (l + 1)):
+                break
+            c += 1
+        return c
+
+    def dif_levels(self, e, K, lo0, tag):
+        for t in range(K):
+            half = (1 << K) >> (t + 1)
+            for m in range(1 << K):
+                if m & half:
+                    continue
+                self.where = "%s DIF level %d m %d" % (tag, t, m)
+                unit = lo0 and (m & (half - 1)) == 0
+                c = self.dif_sums(K, m + half, t)
+                assert c <= 2
+                u, v = e[m], e[m + half]
+                if c == 2:
+                    u, v = self.norm(u), self.norm(v)
+                kb = "K6" if t == 0 else "K2" if c == 0 else ("K12B2" if t == 1 else "K4B2") if c == 1 else "K24"
+                e[m] = self.add(u, v)
+                d = self.sub(u, kb, v)
+                e[m + half] = self.norm(d) if unit else self.mul(d, "ntt29 DIF (u + %s - v) tw" % kb)
+
+    def dit_levels(self, e, K, lo0, tag, unit_k=("K6", "K12", "K24")):
+        for t in range(K):
+            half = 1 << t
+            for m in range(1 << K):
+                if m & half:
+                    continue
+                self.where = "%s DIT level %d m %d" % (tag, t, m)
+                unit = lo0 and (m & (half - 1)) == 0
+                u, v = e[m], e[m + half]
+                if not unit:
+                    v = self.mul(v, "ntt29 DIT level %d v tw" % t)
+                    kb = "K2"
+                else:
+                    if t > 0:
+                        v = self.norm(v)
+                    assert self.is_norm(v)
+                    kb = unit_k[t]
+                e[m] = self.add(u, v)
+                e[m + half] = self.sub(u, kb, v)
+
+    def pass_dif(self, K, lo0):
+        tag = "k_ntt_pass<%d, DIF> lo %s 0" % (K, "==" if lo0 else "!=")
+        e = [self.load() for _ in range(1 << K)]
+        self.dif_levels(e, K, lo0, tag)
+        for m in range(1 << K):
+            self.where = "%s store m %d" % (tag, m)
+            x = e[m]
+            if self.dif_sums(K, m, K) > 0:
+                x = self.norm(x)
+            if m == 0 or lo0:
+                x = self.reduce(x)
+            self.store(x, False)
+
+    def pass_dit(self, K, lo0, last):
+        tag = "k_ntt_pass<%d, DIT%s> lo %s 0" % (K, ", last" if last else "", "==" if lo0 else "!=")
+        e = [self.load() for _ in range(1 << K)]
+        self.dit_levels(e, K, lo0, tag)
+        for m in range(1 << K):
+            self.where = "%s store m %d" % (tag, m)
+            self.store(self.reduce(self.norm(e[m])), last)
+
+    def turn(self, KT, last):
+        tag = "k_ntt_turn<%d%s>" % (KT, ", last" if last else "")
+        e = [self.load() for _ in range(1 << KT)]
+        self.dif_levels(e, KT, True, tag)
+        for m in range(1 << KT):
+            self.where = "%s scale m %d" % (tag, m)
+            e[m] = self.mul(e[m], "ntt29 turn scale")
+        self.dit_levels(e, KT, True, tag, ("K2", "K6", "K12"))      # from products, not from loads
+        for m in range(1 << KT):
+            self.where = "%s store m %d" % (tag, m)
+            x = self.norm(e[m])
+            if last or KT > 1:
+                x = self.reduce(x)
+            self.store(x, last)
+
+
+def ntt29_main(max_k=3):
+    """replays every instantiation; returns rows like main()'s and the largest stored integer in units of r"""
+    rp = NttReplay()
+    for lo0 in (False, True):
+        rp.pass_dif(max_k, lo0)
+        for last in (False, True):
+            rp.pass_dit(max_k, lo0, last)
+    for kt in range(1, max_k + 1):
+        for last in (False, True):
+            rp.turn(kt, last)
+    rows = [("Fr", label, "wide" if wide else "masked", w / 2**60) for (label, wide), w in sorted(rp.rows.items())]
+    return rows, rp.stored / R
+
+
+def ntt29_check_source(path):
+    """the constants in prover_front.hip are the ones the replay used"""
+    src = open(path).read()
+    want = {k: v[0] for k, v in ntt_constants().items() if k not in ("K2", "K6")}
+    want["NEGR"] = NTT_NEGR
+    for name, l in want.items():
+        assert ("%s[9] = {%s}" % (name, ", ".join("0x%08xu" % x for x in l))) in src, "prover_front.hip: %s differs" % name
+    assert ("MAGIC = 0x%08xu" % NTT_MAGIC) in src, "prover_front.hip: MAGIC differs"
+    f = Field(R)
+    assert ntt_constants()["K2"][0] == f.K2 and ntt_constants()["K6"][0] == f.K6      # Fr29C's own
+
+
 def main(verbose=True):
     rows = []
     for name, p in FIELDS:
@@ -157,6 +361,12 @@ def main(verbose=True):
         for label, prods, wide, addend, square in call_sites(name, f):
             w = replay(f, prods, wide, addend, square)
             rows.append((name, label, "wide" if wide else "masked", w / 2**60))
+    import os
+    ntt_rows, stored = ntt29_main()
+    rows += ntt_rows
+    ntt29_check_source(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "zerokit_amd", "csrc", "prover_front.hip"))
+    if verbose:
+        print("ntt29: largest integer stored between launches %.3f r (2^256 = %.3f r)" % (stored, (1 << 256) / R))
     if verbose:
         for r in rows:
             print("%-3s %-62s %-6s max column %6.3f x 2^60 (limit 16)" % r)

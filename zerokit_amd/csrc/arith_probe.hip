@@ -419,7 +419,10 @@ void probe_quotient_transform(int logn, int lds, uint32_t B, uint32_t nb, uint32
   const NttTables T = ntt_tables(logn);
   const std::vector<NttPass> passes = ntt_pass_list(logn);
   DevBuf<Fr> tw_i(T.tw_i.size()), tw_f(T.tw_f.size()), coset(T.coset.size()), data(rows * B);
-  DevBuf<uint32_t> din(rows * nb * 8), dout(rows * nb * 8);
+  DevBuf<uint32_t> din(rows * nb * 8), dout(rows * nb * 8), tw_i29, tw_f29, coset29;
+  tw_i29.assign(T.tw_i29, 0);
+  tw_f29.assign(T.tw_f29, 0);
+  coset29.assign(T.coset29, 0);
   RLN_HIP(hipMemcpy(tw_i.p, T.tw_i.data(), T.tw_i.size() * sizeof(Fr), hipMemcpyHostToDevice));
   RLN_HIP(hipMemcpy(tw_f.p, T.tw_f.data(), T.tw_f.size() * sizeof(Fr), hipMemcpyHostToDevice));
   RLN_HIP(hipMemcpy(coset.p, T.coset.data(), T.coset.size() * sizeof(Fr), hipMemcpyHostToDevice));
@@ -428,7 +431,8 @@ void probe_quotient_transform(int logn, int lds, uint32_t B, uint32_t nb, uint32
   const dim3 grid((uint32_t)div_up(rows * nb, 64));
   hipLaunchKernelGGL(k_probe_lanes_in, grid, dim3(64), 0, 0, (const uint32_t*)din.p, data.p, rows, B, nb);
   RLN_HIP(hipGetLastError());
-  launch_quotient_transform(lds != 0, passes, data.p, tw_i.p, tw_f.p, logn, coset.p, B, nb, vectors, 0);
+  launch_quotient_transform(lds != 0, passes, data.p, {tw_i.p, tw_f.p, coset.p, tw_i29.p, tw_f29.p, coset29.p}, logn, B, nb,
+                            vectors, 0);
   hipLaunchKernelGGL(k_probe_lanes_out, grid, dim3(64), 0, 0, (const Fr*)data.p, dout.p, rows, B, nb);
   RLN_HIP(hipGetLastError());
   RLN_HIP(hipMemcpy(out, dout.p, rows * nb * 32, hipMemcpyDeviceToHost));

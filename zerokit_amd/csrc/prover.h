@@ -49,8 +49,9 @@ struct ProverConfig {
 // whether it is alone on the device, the circuit and the partial-proof cache.  The one remaining shape switch that is
 // not a size overrides a detected condition (lone), so that the parity tests can pin each shape
 // (tests/test_gpu_parity.py: test_small_batch_shape_variants_give_the_golden_bytes).  Tuning constants whose alternative
-// lost every A/B (NTT through Fr29, the 8 x 32 walk, the plain 255-bit walk, copy-engine staging, one interpreter
-// stream, ...) are gone.
+// lost every A/B (twiddle products through Fr29::mul_mont one by one, the 8 x 32 walk, the plain 255-bit walk, copy-engine
+// staging, one interpreter stream, ...) are gone.  (The big batches' transforms do run on 29-bit limbs now, whole passes
+// at a time and without a switch: prover_front.hip, profiles/quotient_chain_29.md.)
 struct ProverTuning {
   // ---- sizes
   int window_bits = 120010;            // RLNAMD_WINDOW_BITS: comb schedule g1 + 10000 * g2, each c + 100 * wide;

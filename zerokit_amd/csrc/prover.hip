@@ -209,6 +209,7 @@ struct Prover::Impl {
   uint32_t n_mv_long = 0;
   DevBuf<Fr> a_coef, b_coef;
   DevBuf<Fr> tw_f, tw_i, coset;
+  DevBuf<uint32_t> tw_f29, tw_i29, coset29;   // the same tables for the passes of the big batches (NttTables)
   std::vector<NttPass> ntt_passes;   // the launches of the transforms with lanes = proofs (prover_plan.h)
   // MSM: the comb tables in the packed 9 x 29-bit form (one 64-byte line per G1 entry)
   DevBuf<G1Affine29> t1_29;
@@ -732,6 +733,9 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     D.tw_f.assign(T.tw_f, s);
     D.tw_i.assign(T.tw_i, s);
     D.coset.assign(T.coset, s);
+    D.tw_f29.assign(T.tw_f29, s);
+    D.tw_i29.assign(T.tw_i29, s);
+    D.coset29.assign(T.coset29, s);
     RLN_HIP(hipStreamSynchronize(s));
   }
 
@@ -968,24 +972,34 @@ void Prover::upload_witness(size_t n, const uint8_t* w_le) {
 }
 
 // iNTT (DIF) + g^i / n + NTT (DIT) over `vectors` vectors with lanes = proofs, by the pass list of prover_plan.h
-static void launch_ntt(const std::vector<NttPass>& passes, Fr* data, const Fr* tw_i, const Fr* tw_f, int logn, const Fr* scale,
-                       uint32_t B, uint32_t nb, uint32_t vectors, hipStream_t s) {
+// (the passes work on 29-bit limbs and leave loose representatives in the buffer between launches; the launch that ends
+// the transform stores the canonical values: prover_front.hip)
+static void launch_ntt(const std::vector<NttPass>& passes, Fr* data, const uint32_t* tw_i, const uint32_t* tw_f, int logn,
+                       const uint32_t* scale, uint32_t B, uint32_t nb, uint32_t vectors, hipStream_t s) {
   for (const NttPass& ps : passes) {
+    const bool last = &ps == &passes.back();
     // one wave per workgroup: a 4-wave workgroup needs four free wave slots on one CU at the same moment, which the
     // single-wave MSM workgroups streaming through the chip never leave (measured: mat-vec 0.6 -> 32 ms, NTT 5 -> 19 ms)
     const dim3 block(64, 1), grid(div_up(nb, 64), (1u << logn) >> ps.k, vectors);
     if (ps.kind == NTT_TURN) {
-      switch (ps.k) {
-        case 1: hipLaunchKernelGGL(k_ntt_turn<1>, grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
-        case 2: hipLaunchKernelGGL(k_ntt_turn<2>, grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
-        default: hipLaunchKernelGGL(k_ntt_turn<3>, grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+      switch (ps.k * 2 + (last ? 1 : 0)) {
+        case 2: hipLaunchKernelGGL((k_ntt_turn<1, false>), grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+        case 3: hipLaunchKernelGGL((k_ntt_turn<1, true>), grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+        case 4: hipLaunchKernelGGL((k_ntt_turn<2, false>), grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+        case 5: hipLaunchKernelGGL((k_ntt_turn<2, true>), grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+        case 6: hipLaunchKernelGGL((k_ntt_turn<3, false>), grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+        case 7: hipLaunchKernelGGL((k_ntt_turn<3, true>), grid, block, 0, s, data, tw_i, tw_f, logn, scale, B, nb); break;
+        default: throw Error("NTT pass list: the turn has one to three levels");
       }
     } else if (ps.k != NTT_MAX_K) {
       throw Error("NTT pass list: a pass that is not the turn has NTT_MAX_K levels");
     } else if (ps.kind == NTT_DIF) {
-      hipLaunchKernelGGL((k_ntt_pass<NTT_MAX_K, true>), grid, block, 0, s, data, tw_i, logn, (int)ps.s0, B, nb);
+      if (last) throw Error("NTT pass list: a transform ends with a forward pass or with the turn");
+      hipLaunchKernelGGL((k_ntt_pass<NTT_MAX_K, true, false>), grid, block, 0, s, data, tw_i, logn, (int)ps.s0, B, nb);
+    } else if (last) {
+      hipLaunchKernelGGL((k_ntt_pass<NTT_MAX_K, false, true>), grid, block, 0, s, data, tw_f, logn, (int)ps.s0, B, nb);
     } else {
-      hipLaunchKernelGGL((k_ntt_pass<NTT_MAX_K, false>), grid, block, 0, s, data, tw_f, logn, (int)ps.s0, B, nb);
+      hipLaunchKernelGGL((k_ntt_pass<NTT_MAX_K, false, false>), grid, block, 0, s, data, tw_f, logn, (int)ps.s0, B, nb);
     }
     RLN_HIP(hipGetLastError());
   }
@@ -993,12 +1007,13 @@ static void launch_ntt(const std::vector<NttPass>& passes, Fr* data, const Fr* t
 
 // The transforms of the quotient, either way the prover launches them (prover_kernels.h): Prover::enqueue and the probe
 // of arith_probe.hip (rlnamd_probe_quotient_transform) both come through here.
-void launch_quotient_transform(bool lds, const std::vector<NttPass>& passes, Fr* data, const Fr* tw_i, const Fr* tw_f,
-                               int logn, const Fr* coset, uint32_t B, uint32_t nb, uint32_t vectors, hipStream_t s) {
+void launch_quotient_transform(bool lds, const std::vector<NttPass>& passes, Fr* data, const NttDeviceTables& T, int logn,
+                               uint32_t B, uint32_t nb, uint32_t vectors, hipStream_t s) {
   if (!lds) {
-    launch_ntt(passes, data, tw_i, tw_f, logn, coset, B, nb, vectors, s);
+    launch_ntt(passes, data, T.tw_i29, T.tw_f29, logn, T.coset29, B, nb, vectors, s);
     return;
   }
+  const Fr *tw_i = T.tw_i, *tw_f = T.tw_f, *coset = T.coset;
   if (logn < 9 || logn > 18) throw Error("the LDS transforms take domains of 2^9 .. 2^18 points");
   // iNTT, coset scaling and NTT as edge / mid / edge: one butterfly per lane per level (prover_front.hip: k_ntt_mid)
   const dim3 grid(nb, (1u << logn) >> 9, vectors);
@@ -1687,7 +1702,8 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     // four free wave slots on one CU: the single-wave passes then finish earlier -- 128 proofs 13.3 -> 12.6 ms, 96 and
     // below no better or worse; RLNAMD_NTT_LG_MAX)
     // (the LDS kernels have one lane per butterfly and take the batch's size; the passes, lanes = proofs, its padded size)
-    launch_quotient_transform(sh.ntt_lds, D.ntt_passes, S.abc.p, D.tw_i.p, D.tw_f.p, D.logn, D.coset.p, B,
+    launch_quotient_transform(sh.ntt_lds, D.ntt_passes, S.abc.p,
+                              {D.tw_i.p, D.tw_f.p, D.coset.p, D.tw_i29.p, D.tw_f29.p, D.coset29.p}, D.logn, B,
                               sh.ntt_lds ? nb : nbp, 3, sA2);
     // (the recode below forms h = a o b - c itself)
   }

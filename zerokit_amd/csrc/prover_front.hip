@@ -327,16 +327,155 @@ __global__ void __launch_bounds__(256) k_consts_to29(const Fr* __restrict__ src,
 // proofs in the lanes like any batch.)
 // Which pass takes which levels: ntt_pass_list (prover_plan.h).  The lowest levels of both directions and the scaling
 // between them are k_ntt_turn's, so a pass here never has stride 1 and never scales.
-// A butterfly whose twiddle index j is 0 multiplies by tw[0], the Montgomery one (checked where the tables are built), and
-// the product would return its operand -- sums, differences and products of Fr are canonical -- so it is left out: 8 191
-// of a 2^13-point transform's 53 248 products, ~375 instructions each.  j = (m & (half - 1)) stride + lo: the first
-// term is known at compile time, lo is the same for the whole wave (a scalar branch).
-template <int K, bool DIF>
-__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0,
-                                                  uint32_t B, uint32_t nb) {
-  // (twiddle products through Fr29::mul_mont -- ~290 instead of ~375 instructions -- were measured neutral twice: beside the
-  // table walks the passes are bound by HBM and by waiting for SIMD slots; that variant is gone)
-  auto tmul = [&](const Fr& a, const Fr* __restrict__ tab, uint32_t idx) -> Fr { return a * tab[idx]; };
+//
+// ---- the arithmetic: 9 x 29 limbs, lazy, with NO change of radix
+// A canonical Fr word string is the integer X = x 2^256 mod r.  Cut into 29-bit limbs (Fr29::slice: no arithmetic) the same
+// integer is a valid Fr29 representative: of x 2^256 / 2^261 = x 2^-5 in the 2^261 radix.  The transform is linear, so a
+// constant factor on every input is the same factor on every output: nobody has to know about the 2^-5.  The twiddles and
+// the coset / (1/n) factors are held in Fr29's Montgomery form T = t 2^261 mod r (NttTables::tw_i29, tw_f29, coset29), and
+// Fr29::mul(D, T) = D T / 2^261 = D t mod r for ANY integer D: if D = X + k r then the product is X t + k' r.  Sums and
+// K r - v differences keep "X up to a multiple of r" as well, so from the first load to the last store the data integers
+// are the 8 x 32 Montgomery values up to a multiple of r, and the only conversions are the limb cuts at load (slice) and
+// store (ntt29_pack): no multiplication by a radix constant anywhere.
+// Inside a launch sums are nine 32-bit adds, differences u + K - v with a multiple K of r whose every limb dominates v's
+// (Fr29C::K2 / K6, Ntt29C below), products Fr29::mul with the table entry -- the same for all 64 lanes, so in SGPRs -- as the
+// normalised operand.  Which K, and where a normalize() is needed, follows from how an element got where it is, which the
+// unrolled loops know at compile time (ntt29_dif_sums); tools/check_fq29_bounds.py replays every level of every
+// instantiation with all limbs and values at their maxima (no limb sum reaches 2^32, no column 2^64, every K dominates).
+// Between launches the buffer holds ANY representative below 2^256, in place, 32 bytes as before: products are below
+// 1.5 r and are stored as they are; a sum that can exceed 2^256 first loses floor(top limb / ceil(r / 2^232)) times r
+// (ntt29_reduce: one v_mul_hi for the estimate, nine multiply-adds; leaves less than r + 2^240).  The last launch of a
+// transform (LAST) reduces every value that way and then subtracts r once more where needed (pack_reduced): the canonical
+// Fr, bit for bit what sums, differences and products of Fr gave.
+// A butterfly whose twiddle index j is 0 multiplies by the one and is left out as before (the tables' entry 0 is checked
+// against Fr29C::ONE where they are built): 8 191 of a 2^13-point transform's 53 248 products.  j = (m & (half - 1)) stride
+// + lo: the first term is known at compile time, lo is the same for the whole wave (a scalar branch).
+// (A variant that went through Fr29::mul_mont per PRODUCT -- both cuts around every product, canonical 8 x 32 sums -- was
+// measured neutral twice in earlier rounds and is gone.  This form, measured against the 8 x 32 passes on one box
+// (profiles/quotient_chain_29.md): 1.80 -> 1.43 G VALU wave-instructions per 1 024-proof batch, of which the 64-bit
+// multiply-adds are 0.61 -> 0.89 G; the nine launches alone 4.00 -> 3.81 ms; the 20-second rate +1.4 % in every run of
+// three, the 20-step headline rate unchanged within its spread -- by the condition set for it, not a speed-up.)
+struct Ntt29C {   // tools/check_fq29_bounds.py computes these and compares
+  static constexpr uint32_t K12[9] = {0x2000000cu, 0x34bc1779u, 0x2c51b3cau, 0x3dc6cb68u, 0x2245de25u, 0x22470907u, 0x27d28f0cu, 0x2c51ca6fu, 0x0244b3acu};  // 12 r, limbs >= 2^29
+  static constexpr uint32_t K24[9] = {0x20000018u, 0x29782ef3u, 0x38a36796u, 0x3b8d96d1u, 0x248bbc4cu, 0x248e120fu, 0x2fa51e19u, 0x38a394dfu, 0x04896759u};  // 24 r, limbs >= 2^29
+  static constexpr uint32_t K12B2[9] = {0x4000000cu, 0x54bc1778u, 0x4c51b3c9u, 0x5dc6cb67u, 0x4245de24u, 0x42470906u, 0x47d28f0bu, 0x4c51ca6eu, 0x0244b3abu};  // 12 r, limbs >= 2^30: a sum of two loads
+  static constexpr uint32_t K4B2[9] = {0x40000004u, 0x5c3eb27cu, 0x59709141u, 0x5f4243cbu, 0x56174a0au, 0x4b6d0300u, 0x429b8502u, 0x597098ceu, 0x00c19137u};  // 4 r, limbs >= 2^30: a sum of two products
+  static constexpr uint32_t NEGR[9] = {0x0fffffffu, 0x00f05360u, 0x11a3dbafu, 0x182f6f0cu, 0x0a7a2d7cu, 0x1d24bf3fu, 0x1f591ebeu, 0x11a3d9cbu, 0x1fcf9bb1u};  // 2^261 - r
+  static constexpr uint32_t MAGIC = 0xa948e6d7u;  // floor(2^53 / ceil(r / 2^232))
+};
+enum Ntt29K { NK_2, NK_6, NK_12, NK_24, NK_12B2, NK_4B2 };
+// how many of the DIF levels t - 1, t - 2, ... of a 2^K-point block left element m on the sum side, consecutively
+__host__ __device__ constexpr int ntt29_dif_sums(int K, int m, int t) {
+  int c = 0;
+  for (int l = t - 1; l >= 0; l--) {
+    if (m & ((1 << K) >> (l + 1))) break;
+    c++;
+  }
+  return c;
+}
+__device__ __forceinline__ Fr29 ntt29_add(const Fr29& a, const Fr29& b) {
+  Fr29 r;
+#pragma unroll
+  for (int j = 0; j < 9; j++) r.v[j] = a.v[j] + b.v[j];
+  return r;
+}
+__device__ __forceinline__ Fr29 ntt29_sub_k(const Fr29& u, const uint32_t (&K)[9], const Fr29& v) {
+  Fr29 r;
+#pragma unroll
+  for (int j = 0; j < 9; j++) r.v[j] = u.v[j] + K[j] - v.v[j];
+  return r;
+}
+// u + K - v, limbs left as they fall
+__device__ __forceinline__ Fr29 ntt29_sub(const Fr29& u, int k, const Fr29& v) {
+  switch (k) {
+    case NK_2: return ntt29_sub_k(u, Fr29C::K2, v);
+    case NK_6: return ntt29_sub_k(u, Fr29C::K6, v);
+    case NK_12: return ntt29_sub_k(u, Ntt29C::K12, v);
+    case NK_24: return ntt29_sub_k(u, Ntt29C::K24, v);
+    case NK_12B2: return ntt29_sub_k(u, Ntt29C::K12B2, v);
+    default: return ntt29_sub_k(u, Ntt29C::K4B2, v);
+  }
+}
+// a normalised x -> x - q r with q = floor(x[8] / ceil(r / 2^232)) (or one less): in [0, r + 2^240), normalised
+__device__ __forceinline__ void ntt29_reduce(Fr29& x) {
+  const uint32_t q = __umulhi(x.v[8], Ntt29C::MAGIC) >> 21;
+  uint64_t c = 0;
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    const uint64_t t = (uint64_t)q * Ntt29C::NEGR[j] + x.v[j] + c;   // x + q (2^261 - r): the 2^261 q leaves with the top limb's mask
+    x.v[j] = (uint32_t)t & Fr29::M;
+    c = t >> 29;
+  }
+}
+// a normalised integer below 2^256 as eight words (the inverse of Fr29::slice)
+__device__ __forceinline__ Fr ntt29_pack(const Fr29& x) {
+  const uint32_t r0 = x.v[0], r1 = x.v[1], r2 = x.v[2], r3 = x.v[3], r4 = x.v[4], r5 = x.v[5], r6 = x.v[6], r7 = x.v[7], r8 = x.v[8];
+  Fr o;
+  o.v[0] = r0 | (r1 << 29);
+  o.v[1] = (r1 >> 3) | (r2 << 26);
+  o.v[2] = (r2 >> 6) | (r3 << 23);
+  o.v[3] = (r3 >> 9) | (r4 << 20);
+  o.v[4] = (r4 >> 12) | (r5 << 17);
+  o.v[5] = (r5 >> 15) | (r6 << 14);
+  o.v[6] = (r6 >> 18) | (r7 << 11);
+  o.v[7] = (r7 >> 21) | (r8 << 8);
+  return o;
+}
+// DIF level t of a 2^K-point block.  Only differences are multiplied; the subtrahend v is never a unit butterfly's
+// difference (those land where all lower index bits are zero: the u side of every later level), so it is a load, a
+// product, or a sum of 2^c of either -- which picks K.  A sum of four is normalised before it is used again.
+template <int K, class UNIT, class TW>
+__device__ __forceinline__ void ntt29_dif_level(Fr29 (&e)[1 << K], int t, UNIT unit, TW twiddle) {
+  constexpr int R = 1 << K;
+  const int half = R >> (t + 1);
+#pragma unroll
+  for (int m = 0; m < R; m++) {
+    if (m & half) continue;
+    const int c = ntt29_dif_sums(K, m + half, t);
+    Fr29 u = e[m], v = e[m + half];
+    if (c == 2) {
+      u.normalize();
+      v.normalize();
+    }
+    const int k = t == 0 ? NK_6 : c == 0 ? NK_2 : c == 1 ? (t == 1 ? NK_12B2 : NK_4B2) : NK_24;
+    e[m] = ntt29_add(u, v);
+    Fr29 d = ntt29_sub(u, k, v);
+    if (unit(m & (half - 1))) d.normalize(); else d = Fr29::mul(d, twiddle(m & (half - 1), t));
+    e[m + half] = d;
+    // one butterfly at a time: with the products of neighbouring butterflies interleaved the eight-point turn takes 166
+    // registers instead of 139
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// DIT level t.  The product is below 1.2 r: K2.  A unit butterfly subtracts v itself: a load (FROM_LOADS) or a scaled
+// value at level 0, a sum of two / four of them above -- normalised first, K by the level.
+template <int K, bool FROM_LOADS, class UNIT, class TW>
+__device__ __forceinline__ void ntt29_dit_level(Fr29 (&e)[1 << K], int t, UNIT unit, TW twiddle) {
+  constexpr int R = 1 << K;
+  const int half = 1 << t;
+#pragma unroll
+  for (int m = 0; m < R; m++) {
+    if (m & half) continue;
+    Fr29 u = e[m], v = e[m + half];
+    if (unit(m & (half - 1))) {
+      if (t > 0) v.normalize();
+      const int k = FROM_LOADS ? (t == 0 ? NK_6 : t == 1 ? NK_12 : NK_24) : (t == 0 ? NK_2 : t == 1 ? NK_6 : NK_12);
+      e[m] = ntt29_add(u, v);
+      e[m + half] = ntt29_sub(u, k, v);
+    } else {
+      v = Fr29::mul(v, twiddle(m & (half - 1), t));
+      e[m] = ntt29_add(u, v);
+      e[m + half] = ntt29_sub(u, NK_2, v);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // (see ntt29_dif_level)
+  }
+}
+
+template <int K, bool DIF, bool LAST>
+__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict__ data, const uint32_t* __restrict__ tw29, int logn,
+                                                  int s0, uint32_t B, uint32_t nb) {
+  static_assert(K == 3, "the K / normalize() choices are replayed for three levels (tools/check_fq29_bounds.py)");
+  static_assert(!(DIF && LAST), "a transform ends with a DIT pass or with the turn");
   constexpr int R = 1 << K;
   const uint32_t n = 1u << logn;
   auto uni = [](uint32_t v) -> uint32_t { return __builtin_amdgcn_readfirstlane(v); };
@@ -356,37 +495,40 @@ __global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict_
     base = blk * (stride << K) + lo;
   }
   const uint32_t lo = g % stride;
-  Fr e[R];
+  const bool lo0 = lo == 0;   // wave-uniform
+  Fr29 e[R];
 #pragma unroll
-  for (int m = 0; m < R; m++) e[m] = x[(size_t)(base + m * stride) * B];
+  for (int m = 0; m < R; m++) e[m] = Fr29::slice(x[(size_t)(base + m * stride) * B]);
+  auto unit = [&](int jm) -> bool { return jm == 0 && lo0; };   // j == 0
+  // the twiddle index is the same for all 64 lanes (lanes = proofs): force the scalar path so the twiddle rides in SGPRs
+  // instead of VGPRs
+  auto twiddle = [&](int jm, int t) -> Fr29 {
+    const uint32_t j = (uint32_t)jm * stride + lo;
+    const uint32_t ti = DIF ? (j << (s0 + t)) : (j << (logn - 1 - (s0 + t)));
+    return load_fr29(tw29 + (size_t)uni(ti) * 9);
+  };
 #pragma unroll
   for (int t = 0; t < K; t++) {
-    const int half = DIF ? (R >> (t + 1)) : (1 << t);
+    if (DIF) ntt29_dif_level<K>(e, t, unit, twiddle); else ntt29_dit_level<K, true>(e, t, unit, twiddle);
+  }
+  // the eight store addresses are computed again from here: kept from the loads they are sixteen registers held through
+  // every level (DIF 169 -> 155 registers, the third wave per SIMD; DIT 140 -> 128)
+  asm volatile("" : "+s"(base));
 #pragma unroll
-    for (int m = 0; m < R; m++) {
-      if (m & half) continue;
-      const bool unit = (m & (half - 1)) == 0 && lo == 0;   // j == 0 (wave-uniform)
-      uint32_t j = (uint32_t)(m & (half - 1)) * stride + lo;
-      uint32_t ti = DIF ? (j << (s0 + t)) : (j << (logn - 1 - (s0 + t)));
-      // the twiddle index is the same for all 64 lanes (lanes = proofs): force the scalar path so the
-      // twiddle rides in SGPRs instead of VGPRs
-      const uint32_t tix = uni(ti);
-      if (DIF) {
-        Fr u = e[m], v = e[m + half];
-        e[m] = u + v;
-        Fr d = u - v;
-        if (!unit) d = tmul(d, tw, tix);
-        e[m + half] = d;
-      } else {
-        Fr u = e[m], v = e[m + half];
-        if (!unit) v = tmul(v, tw, tix);
-        e[m] = u + v;
-        e[m + half] = u - v;
-      }
+  for (int m = 0; m < R; m++) {
+    Fr29 y = e[m];
+    if (DIF) {
+      // products (and the normalised differences of unit butterflies) are normalised already; without a unit butterfly
+      // only the sum of all eight loads can reach 2^256, with them (lo == 0) anything can
+      if (ntt29_dif_sums(K, m, K) > 0) y.normalize();
+      if (m == 0 || lo0) ntt29_reduce(y);
+      x[(size_t)(base + m * stride) * B] = ntt29_pack(y);
+    } else {
+      y.normalize();
+      ntt29_reduce(y);
+      x[(size_t)(base + m * stride) * B] = LAST ? y.pack_reduced() : ntt29_pack(y);
     }
   }
-#pragma unroll
-  for (int m = 0; m < R; m++) x[(size_t)(base + m * stride) * B] = e[m];
 }
 
 // The turn: the lowest KT levels of the inverse transform (DIF levels logn - KT .. logn - 1), the coset / 1/n scaling and
@@ -394,11 +536,13 @@ __global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict_
 // bit-reversed order and DIT starts from it, so both close over the positions (g << KT) + m, as in k_ntt_mid.  One trip
 // through HBM where two one-level passes around the scaling made two.  Same butterflies, same twiddles, same products per
 // point as k_ntt_pass over those levels (stride 1, lo 0): j = m & (half - 1) is known at compile time and the products by
-// tw[0] are left out -- KT = 1 has no twiddle product at all.
-template <int KT>
-__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_turn(Fr* __restrict__ data, const Fr* __restrict__ tw_i,
-                                                  const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale,
-                                                  uint32_t B, uint32_t nb) {
+// the one are left out -- KT = 1 has no twiddle product at all, and what it stores (a sum or a K2 difference of two scaled
+// values, below 3.1 r) needs no reduction.  LAST: the turn is the whole transform (logn <= 3) and stores canonical values.
+template <int KT, bool LAST>
+__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_turn(Fr* __restrict__ data, const uint32_t* __restrict__ tw_i29,
+                                                  const uint32_t* __restrict__ tw_f29, int logn,
+                                                  const uint32_t* __restrict__ scale29, uint32_t B, uint32_t nb) {
+  static_assert(KT >= 1 && KT <= 3, "replayed for one to three levels (tools/check_fq29_bounds.py)");
   constexpr int R = 1 << KT;
   const uint32_t n = 1u << logn;
   uint32_t p = blockIdx.x * 64 + threadIdx.x;
@@ -407,40 +551,25 @@ __global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_turn(Fr* __restrict_
   if (p >= nb) return;
   const uint32_t base = g << KT;
   Fr* x = data + ((size_t)blockIdx.z * n + base) * B + p;
-  Fr e[R];
+  Fr29 e[R];
 #pragma unroll
-  for (int m = 0; m < R; m++) e[m] = x[(size_t)m * B];
+  for (int m = 0; m < R; m++) e[m] = Fr29::slice(x[(size_t)m * B]);
+  auto unit = [](int jm) -> bool { return jm == 0; };
+  auto tw_inv = [&](int jm, int t) -> Fr29 { return load_fr29(tw_i29 + ((size_t)jm << (logn - KT + t)) * 9); };   // inverse level logn - KT + t
+  auto tw_fwd = [&](int jm, int t) -> Fr29 { return load_fr29(tw_f29 + ((size_t)jm << (logn - 1 - t)) * 9); };    // forward level t
 #pragma unroll
-  for (int t = 0; t < KT; t++) {   // inverse level logn - KT + t
-    const int half = R >> (t + 1);
+  for (int t = 0; t < KT; t++) ntt29_dif_level<KT>(e, t, unit, tw_inv);
 #pragma unroll
-    for (int m = 0; m < R; m++) {
-      if (m & half) continue;
-      const uint32_t j = (uint32_t)(m & (half - 1));
-      Fr u = e[m], v = e[m + half];
-      e[m] = u + v;
-      Fr d = u - v;
-      if (j) d = d * tw_i[(size_t)j << (logn - KT + t)];
-      e[m + half] = d;
-    }
+  for (int m = 0; m < R; m++) e[m] = Fr29::mul(e[m], load_fr29(scale29 + (size_t)(base + m) * 9));   // (wave-uniform index: the factor rides in SGPRs)
+#pragma unroll
+  for (int t = 0; t < KT; t++) ntt29_dit_level<KT, false>(e, t, unit, tw_fwd);
+#pragma unroll
+  for (int m = 0; m < R; m++) {
+    Fr29 y = e[m];
+    y.normalize();
+    if (LAST || KT > 1) ntt29_reduce(y);
+    x[(size_t)m * B] = LAST ? y.pack_reduced() : ntt29_pack(y);
   }
-#pragma unroll
-  for (int m = 0; m < R; m++) e[m] = e[m] * scale[base + m];   // (wave-uniform index: the factor rides in SGPRs)
-#pragma unroll
-  for (int t = 0; t < KT; t++) {   // forward level t
-    const int half = 1 << t;
-#pragma unroll
-    for (int m = 0; m < R; m++) {
-      if (m & half) continue;
-      const uint32_t j = (uint32_t)(m & (half - 1));
-      Fr u = e[m], v = e[m + half];
-      if (j) v = v * tw_f[(size_t)j << (logn - 1 - t)];
-      e[m] = u + v;
-      e[m + half] = u - v;
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < R; m++) x[(size_t)m * B] = e[m];
 }
 
 // Small batches (lanes = groups), logn >= 9: the three transforms of the quotient in THREE kernels, one butterfly per lane
@@ -651,11 +780,14 @@ __global__ void __launch_bounds__(256) k_recode(const Fr* __restrict__ V, const 
 template __global__ void k_witness29<false>(const GNode29* __restrict__ nodes, uint32_t n_nodes, const uint32_t* __restrict__ consts29, uint32_t n_consts, const uint32_t* __restrict__ inputs, uint32_t n_inputs, uint4* __restrict__ V29, uint32_t* __restrict__ err, uint32_t B, uint32_t nb, unsigned long long* __restrict__ prof);
 template __global__ void k_matvec<true>(CsrView A, CsrView Bm, const Fr* __restrict__ V, const uint32_t* __restrict__ sig2node, uint32_t nc, uint32_t ni, uint32_t n, Fr* __restrict__ abc, uint32_t B, uint32_t nb, const uint32_t* __restrict__ long_rows, uint32_t nshort);
 template __global__ void k_matvec<false>(CsrView A, CsrView Bm, const Fr* __restrict__ V, const uint32_t* __restrict__ sig2node, uint32_t nc, uint32_t ni, uint32_t n, Fr* __restrict__ abc, uint32_t B, uint32_t nb, const uint32_t* __restrict__ long_rows, uint32_t nshort);
-template __global__ void k_ntt_pass<NTT_MAX_K, true>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, uint32_t B, uint32_t nb);
-template __global__ void k_ntt_pass<NTT_MAX_K, false>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0, uint32_t B, uint32_t nb);
-template __global__ void k_ntt_turn<1>(Fr* __restrict__ data, const Fr* __restrict__ tw_i, const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
-template __global__ void k_ntt_turn<2>(Fr* __restrict__ data, const Fr* __restrict__ tw_i, const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
-template __global__ void k_ntt_turn<3>(Fr* __restrict__ data, const Fr* __restrict__ tw_i, const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale, uint32_t B, uint32_t nb);
+template __global__ void k_ntt_pass<NTT_MAX_K, true, false>(Fr* __restrict__ data, const uint32_t* __restrict__ tw29, int logn, int s0, uint32_t B, uint32_t nb);
+template __global__ void k_ntt_pass<NTT_MAX_K, false, false>(Fr* __restrict__ data, const uint32_t* __restrict__ tw29, int logn, int s0, uint32_t B, uint32_t nb);
+template __global__ void k_ntt_pass<NTT_MAX_K, false, true>(Fr* __restrict__ data, const uint32_t* __restrict__ tw29, int logn, int s0, uint32_t B, uint32_t nb);
+#define RLN_NTT_TURN(KT, LAST)                                                                                                       \
+  template __global__ void k_ntt_turn<KT, LAST>(Fr* __restrict__ data, const uint32_t* __restrict__ tw_i29, const uint32_t* __restrict__ tw_f29, \
+                                                int logn, const uint32_t* __restrict__ scale29, uint32_t B, uint32_t nb);
+RLN_NTT_TURN(1, false) RLN_NTT_TURN(2, false) RLN_NTT_TURN(3, false) RLN_NTT_TURN(1, true) RLN_NTT_TURN(2, true) RLN_NTT_TURN(3, true)
+#undef RLN_NTT_TURN
 template __global__ void k_ntt_edge<true>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, uint32_t B, uint32_t nb);
 template __global__ void k_ntt_edge<false>(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, uint32_t B, uint32_t nb);
 

@@ -47,8 +47,13 @@ constexpr uint32_t SUM_TREE_LDS_G1 = SUM_TREE_LANES / 2 * 4 * 9 * 4, SUM_TREE_LD
 // ---- the quotient's transforms (prover.hip): iNTT, coset scaling, NTT over `vectors` vectors of 2^logn points in the
 // [index][B] layout, nb live lanes -- lds: k_ntt_edge / k_ntt_mid / k_ntt_edge (2^9 .. 2^18 points); otherwise the pass list
 // (ntt_pass_list(logn)) through k_ntt_pass / k_ntt_turn.  The one place either form is launched from.
-void launch_quotient_transform(bool lds, const std::vector<NttPass>& passes, Fr* data, const Fr* tw_i, const Fr* tw_f,
-                               int logn, const Fr* coset, uint32_t B, uint32_t nb, uint32_t vectors, hipStream_t s);
+// The tables of NttTables on the device: the LDS kernels read the 8 x 32 ones, the passes the 9 x 29 ones.
+struct NttDeviceTables {
+  const Fr *tw_i, *tw_f, *coset;
+  const uint32_t *tw_i29, *tw_f29, *coset29;
+};
+void launch_quotient_transform(bool lds, const std::vector<NttPass>& passes, Fr* data, const NttDeviceTables& T, int logn,
+                               uint32_t B, uint32_t nb, uint32_t vectors, hipStream_t s);
 
 // ---- kernels of prover_front.hip
 template <bool PROF>
@@ -66,13 +71,15 @@ __global__ void __launch_bounds__(256) k_matvec(CsrView A, CsrView Bm, const Fr*
                                                 uint32_t n, Fr* __restrict__ abc, uint32_t B, uint32_t nb,
                                                 const uint32_t* __restrict__ long_rows = nullptr, uint32_t nshort = 0);
 __global__ void __launch_bounds__(256) k_consts_to29(const Fr* __restrict__ src, uint32_t* __restrict__ dst, uint32_t n);
-template <int K, bool DIF>
-__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict__ data, const Fr* __restrict__ tw, int logn, int s0,
-                                                  uint32_t B, uint32_t nb);
-template <int KT>
-__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_turn(Fr* __restrict__ data, const Fr* __restrict__ tw_i,
-                                                  const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale,
-                                                  uint32_t B, uint32_t nb);
+// (tables in the 9 x 29 form, nine words an entry: NttTables::tw_i29 / tw_f29 / coset29.  LAST: the launch that ends a
+// transform and stores canonical values)
+template <int K, bool DIF, bool LAST>
+__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_pass(Fr* __restrict__ data, const uint32_t* __restrict__ tw29, int logn,
+                                                  int s0, uint32_t B, uint32_t nb);
+template <int KT, bool LAST>
+__global__ void __launch_bounds__(256, RLN_NTT_WAVES) k_ntt_turn(Fr* __restrict__ data, const uint32_t* __restrict__ tw_i29,
+                                                  const uint32_t* __restrict__ tw_f29, int logn,
+                                                  const uint32_t* __restrict__ scale29, uint32_t B, uint32_t nb);
 __global__ void __launch_bounds__(256) k_ntt_mid(Fr* __restrict__ data, const Fr* __restrict__ tw_i,
                                                  const Fr* __restrict__ tw_f, int logn, const Fr* __restrict__ scale,
                                                  uint32_t B, uint32_t nb);

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 
+#include "fq29_constants.h"
 #include "glv.h"
 #include "poseidon.h"
 #include "witness_sched.h"
@@ -617,6 +618,21 @@ static uint32_t bitrev(uint32_t x, int bits) {
   return r;
 }
 
+// t 2^256 (8 x 32 Montgomery) -> t 2^261 mod r, canonical, cut into nine 29-bit limbs: the Montgomery form of fq29.h
+static std::vector<uint32_t> table29(const std::vector<Fr>& t) {
+  const Fr k = Fr::from_u32(32);   // 2^261 / 2^256
+  std::vector<uint32_t> out(t.size() * 9);
+  for (size_t i = 0; i < t.size(); i++) {
+    const Fr x = t[i] * k;   // the words of (32 t) 2^256 = t 2^261
+    for (int j = 0; j < 9; j++) {
+      const int bit = 29 * j, w = bit >> 5, s = bit & 31;
+      const uint64_t two = (uint64_t)x.v[w] | (w + 1 < 8 ? (uint64_t)x.v[w + 1] << 32 : 0);
+      out[i * 9 + j] = (uint32_t)(two >> s) & (j < 8 ? (1u << 29) - 1 : 0xFFFFFFFFu);
+    }
+  }
+  return out;
+}
+
 NttTables ntt_tables(int logn) {
   if (logn < 1 || logn > 27) throw Error("NTT tables: domain size out of range");
   const uint32_t n = 1u << logn;
@@ -643,6 +659,11 @@ NttTables ntt_tables(int logn) {
     acc = acc * g;
   }
   for (uint32_t pos = 0; pos < n; pos++) T.coset[pos] = gp[bitrev(pos, logn)];
+  T.tw_f29 = table29(T.tw_f);
+  T.tw_i29 = table29(T.tw_i);
+  T.coset29 = table29(T.coset);
+  for (int j = 0; j < 9; j++)
+    if (T.tw_f29[j] != Fr29C::ONE[j] || T.tw_i29[j] != Fr29C::ONE[j]) throw Error("NTT tables: tw29[0] is not one");
   return T;
 }
 

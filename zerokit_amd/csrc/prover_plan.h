@@ -178,8 +178,12 @@ struct NttPass {
 // The tables of a 2^logn-point domain: tw_f[k] = w^k and tw_i[k] = w^-k for k < n / 2 (w = W^(2^(28 - logn))), and
 // coset[pos] = g^bitrev(pos) / n, g the root of the doubled domain -- the scaling between the transforms acts on
 // bit-reversed order.  Throws unless tw_f[0] and tw_i[0] are the Montgomery one: the kernels leave those products out.
+// tw_f29 / tw_i29 / coset29: the same entries for the passes of the big batches, which work on 9 x 29-bit limbs
+// (prover_front.hip): t 2^261 mod r, canonical, nine words an entry; entry 0 of both twiddle tables is checked against
+// Fr29C::ONE.
 struct NttTables {
   std::vector<Fr> tw_f, tw_i, coset;
+  std::vector<uint32_t> tw_f29, tw_i29, coset29;
 };
 NttTables ntt_tables(int logn);
 int ntt_turn_width(int logn);                  // kt; 0 for logn < 1
