@@ -136,6 +136,21 @@ CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t*
  * signals[i].ptr with length 0 is the empty message. */
 CBoolResult_t ffi_verify_rln_signals_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
                                            const Vec_uint8_t* signals, const Vec_CFr_t* roots, bool* ok);
+/* EXT: one step of a relay loop in one call: ffi_verify_rln_signals_batch and ffi_nullifier_log_observe(take = ok) over
+ * the same inputs, with the cause of a refusal kept.  verdict[i] is RLNAMD_RELAY_OK (0), or the first failing check in
+ * the order of ffi_verify_with_roots -- RLNAMD_RELAY_BAD_PROOF, _BAD_ROOT, _BAD_SIGNAL (rln_amd.h) -- so verdict[i] == 0
+ * exactly where ffi_verify_rln_signals_batch gives ok[i]; status, secrets (n contiguous CFr, or NULL) and first_tag (or
+ * NULL) are ffi_nullifier_log_observe's, RLNAMD_SHARE_SKIPPED for a refused message.  roots: NULL checks against the
+ * object's current root, an empty vector accepts any root.  From "relay_gpu_min" messages on (config JSON, default
+ * 1 024: the smallest measured n, at which this call wins by about 0.1 ms of 13, profiles/relay_step.md) the call is ONE rlnamd_relay_step on
+ * the device (rln_amd.h), over one relay per (object, log) made on first use with the process's hasher: the signals are
+ * hashed beside the pairing kernels and the shares never return to the host.  Then it asks the log for room for n *
+ * max_out shares before it starts.  Smaller calls, an object with "verify_optimistic": true (that setting keeps its
+ * meaning) and calls with more than RLNAMD_RELAY_ROOTS_MAX roots take the composition of the existing calls.  A log
+ * must not be freed while a step on it is running. */
+CBoolResult_t ffi_relay_step(FFI_RLN_t* const* rln, struct rlnamd_nullifier_log* log, FFI_RLNProof_t* const* proofs, size_t n,
+                             const Vec_uint8_t* signals, const Vec_CFr_t* roots /* NULL: the object's current root */,
+                             const uint64_t* tags, uint8_t* verdict, uint8_t* status, CFr_t* secrets, uint64_t* first_tag);
 
 /* EXT: n finishes in one call (single message-id): partials[i] is the partial proof witnesses[i] is finished from -- the
  * same pointer may repeat, one member's partial proof finished for n messages being what partial proofs are for
@@ -391,6 +406,7 @@ CResult_FFI_RLNV3ProofValues_ptr_Vec_uint8_t ffi_bytes_be_to_rln_v3_proof_values
 void ffi_rln_v3_proof_values_free(FFI_RLNV3ProofValues_t* pv); /* ffi_rln_v3.rs:1319 */
 CResult_CFr_ptr_Vec_uint8_t ffi_rln_v3_compute_id_secret(const CFr_t* share1_x, const CFr_t* share1_y, const CFr_t* share2_x, const CFr_t* share2_y); /* ffi_rln_v3.rs:1324 */
 CResult_CFr_ptr_Vec_uint8_t ffi_rln_v3_recover_id_secret(FFI_RLNV3ProofValues_t* const* pv1, FFI_RLNV3ProofValues_t* const* pv2); /* ffi_rln_v3.rs:1345 */
+CBoolResult_t ffi_rln_v3_relay_step(FFI_RLNV3_t* const* rln, struct rlnamd_nullifier_log* log, FFI_RLNV3Proof_t* const* proofs, size_t n, const Vec_uint8_t* signals, const Vec_CFr_t* roots, const uint64_t* tags, uint8_t* verdict, uint8_t* status, CFr_t* secrets, uint64_t* first_tag); /* EXT: ffi_relay_step over V3 proofs */
 CBoolResult_t ffi_rln_v3_nullifier_log_observe(struct rlnamd_nullifier_log* log, FFI_RLNV3ProofValues_t* const* values, size_t n, const bool* take, const uint64_t* tags, uint8_t* status, CFr_t* secrets, uint64_t* first_tag); /* EXT: ffi_nullifier_log_observe over V3 values */
 void ffi_rln_v3_merkle_proof_free(FFI_RLNV3MerkleProof_t* proof); /* ffi_rln_v3.rs:1371 */
 CBoolResult_t ffi_rln_v3_delete_leaf(FFI_RLNV3_t** rln, size_t index); /* ffi_rln_v3.rs:1376 */

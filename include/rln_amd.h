@@ -119,7 +119,7 @@ typedef struct rlnamd_nullifier_log rlnamd_nullifier_log;
 #define RLNAMD_SHARE_DUPLICATE 1
 #define RLNAMD_SHARE_SPAM 2
 #define RLNAMD_SHARE_FOREIGN 3
-#define RLNAMD_SHARE_SKIPPED 4   /* FFI layer only (rln.h: ffi_nullifier_log_observe): take[i] was false */
+#define RLNAMD_SHARE_SKIPPED 4   /* never from observe: rln.h's ffi_nullifier_log_observe (take[i] was false), rlnamd_relay_step */
 int rlnamd_nullifier_log_new(size_t capacity, uint64_t seed, rlnamd_nullifier_log** out);  /* 1 <= capacity <= 2^31; seed 0 = random */
 void rlnamd_nullifier_log_free(rlnamd_nullifier_log* l);
 int rlnamd_nullifier_log_observe(rlnamd_nullifier_log* l, size_t n, const uint8_t* shares_le /* n*128 */,
@@ -461,6 +461,53 @@ int rlnamd_parse_resources(const uint8_t* zkey, size_t zkey_len, const uint8_t* 
 /* ark-serialize point compression helpers (host): coords = A.x A.y B.x.c0 B.x.c1 B.y.c0 B.y.c1 C.x C.y */
 int rlnamd_proof_compress(const uint8_t coords_le[256], uint8_t proof[128]);
 int rlnamd_proof_decompress(const uint8_t proof[128], uint8_t coords_le[256]);
+
+/* ---- relay step on the device: hash, verify and log n messages in one call -------------------------------------
+ * The loop of a relay node over the three objects above -- rlnamd_hasher, the prover's device verifier and
+ * rlnamd_nullifier_log -- as one object and one call.  A step gives exactly the composition of the three calls over the
+ * same inputs: xs from rlnamd_hasher_hash_to_field (or xs_le as given), pass from rlnamd_verify_many_gpu_ex with the
+ * relay's lanes, verdict[i] the first failing check in the reference's order proof -> root -> signal
+ * (rln/src/public.rs:725-771), else RLNAMD_RELAY_OK; then the shares of the messages whose verdict is OK go through ONE
+ * observe in index order, by the rule of ffi_nullifier_log_observe (rln.h): a single-message proof (n_values == 5: y |
+ * root | nullifier | x | ext) gives one share, a multi-message proof (n_values == 3 k + 3, k the prover's max_out:
+ * ys[k] | root | nullifiers[k] | x | ext | selector_used[k]) one share per slot whose selector is 1, in slot order; all
+ * shares of a proof carry its x, its external nullifier and tags[i] (tags == NULL: each share's own sequence number).
+ * status[i] is RLNAMD_SHARE_SKIPPED for a verdict other than OK and for a proof without a used slot, otherwise the
+ * first of SPAM, FOREIGN, DUPLICATE, NEW that any of the proof's shares has; secrets_le[i] and first_tag[i] come from
+ * the lowest slot with that status and are zero for SKIPPED.  A call of n messages gives what any split into
+ * consecutive smaller calls gives.  The proofs' public values never return to the host between the stages, and
+ * hashing runs beside the pairing kernels, on the hasher's stream.
+ * The step refuses, each with its own text, before anything is enqueued and with the log, the hasher and the verifier
+ * untouched: null pointers with n > 0; both or neither of (signals, signals_len, offsets) and xs_le; signals given to a
+ * relay made without a hasher; what rlnamd_hasher_hash_to_field refuses (decreasing offsets, offsets[n] > signals_len);
+ * n_values not the key's; n_roots > RLNAMD_RELAY_ROOTS_MAX; n * max(1, max_out) larger than the room left in the log.
+ * The last is the one deliberate difference from the composition: how many shares a call records is known on the
+ * device only and a step is all-or-nothing for the log, so it asks for room for the worst case.  n == 0 succeeds and
+ * writes nothing.  rlnamd_relay_new borrows its three objects, which must outlive the relay, and refuses objects on
+ * different devices; h may be NULL, then every step must bring xs_le.  A step holds the relay's mutex, then the
+ * hasher's, the verifier's and the log's, in that order; between steps each borrowed object is usable on its own.
+ * The results of a step hold recovered identity secrets: the relay's device and pinned buffers are overwritten before
+ * the step returns, on every error path too.
+ * info: [0] steps, [1] verifier chunks, [2] messages, [3] messages with verdict OK, [4] shares recorded, [5] non-zero
+ * 16-byte words left in the relay's result buffers, device and pinned (0 expected), [6] messages hashed on the host
+ * route, [7] reserved 0.  The log's info[4] goes up by one per chunk that records a share, its info[6] stays 0. */
+typedef struct rlnamd_relay rlnamd_relay;
+#define RLNAMD_RELAY_OK 0
+#define RLNAMD_RELAY_BAD_PROOF 1    /* the verifier's ok == 0, or a selector element that is neither 0 nor 1 */
+#define RLNAMD_RELAY_BAD_ROOT 2
+#define RLNAMD_RELAY_BAD_SIGNAL 3
+#define RLNAMD_RELAY_ROOTS_MAX 64
+int rlnamd_relay_new(rlnamd_prover* p, rlnamd_nullifier_log* log, rlnamd_hasher* h /* or NULL */, int lanes /* 0 | 1 | 8 */,
+                     rlnamd_relay** out);
+void rlnamd_relay_free(rlnamd_relay* r);
+int rlnamd_relay_step(rlnamd_relay* r, size_t n, const uint8_t* proofs /* n*128 */,
+                      const uint8_t* values_le /* n*n_values*32, verifier order */, size_t n_values,
+                      const uint8_t* signals, size_t signals_len, const uint64_t* offsets /* n+1 */, /* either these three ... */
+                      const uint8_t* xs_le /* n*32 */,                                               /* ... or this, never both */
+                      const uint8_t* roots_le, size_t n_roots /* 0: any root, ffi_verify_with_roots' rule */,
+                      const uint64_t* tags /* n, or NULL */, uint8_t* verdict /* n */, uint8_t* status /* n */,
+                      uint8_t* secrets_le /* n*32 or NULL */, uint64_t* first_tag /* n or NULL */);
+int rlnamd_relay_info(rlnamd_relay* r, uint64_t out[8]);
 
 /* ---- variable-base MSM on G1 / G2 (BASELINE config 5; north_star: "windowed Pippenger MSM on G1/G2") ---------
  * Replaces VariableBaseMSM::msm_bigint (ark-ec 0.5.0; call sites rln/src/partial_proof.rs:98-104,255-256: generic

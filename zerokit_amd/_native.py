@@ -117,6 +117,12 @@ SIGNATURES = {
     "rlnamd_hasher_free": (None, [P]),
     "rlnamd_hasher_hash_to_field": (C.c_int, [P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_char_p]),
     "rlnamd_hasher_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "rlnamd_relay_new": (C.c_int, [P, P, P, C.c_int, PP]),
+    "rlnamd_relay_free": (None, [P]),
+    "rlnamd_relay_step": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
+                                    C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64),
+                                    C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "rlnamd_relay_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_tree_fill_sequential": (C.c_int, [P, C.c_size_t, C.c_size_t, C.c_uint64]),
     "rlnamd_tree_bench": (C.c_int, [P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_size_t)]),
     "rlnamd_prover_new": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, PP]),
@@ -302,6 +308,10 @@ SIGNATURES = {
     "ffi_generate_rln_proof_with_witness": (CResultPtr, [PP, C.POINTER(VecString), PP]),
     "ffi_compute_id_secret": (CResultPtr, [CFRP, CFRP, CFRP, CFRP]),
     "ffi_recover_id_secret": (CResultPtr, [PP, PP]),
+    "ffi_relay_step": (CBoolResult, [PP, P, PP, C.c_size_t, C.POINTER(VecU8), C.POINTER(VecCFr), C.POINTER(C.c_uint64),
+                                     C.c_char_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ffi_rln_v3_relay_step": (CBoolResult, [PP, P, PP, C.c_size_t, C.POINTER(VecU8), C.POINTER(VecCFr), C.POINTER(C.c_uint64),
+                                            C.c_char_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "ffi_nullifier_log_observe": (CBoolResult, [P, PP, C.c_size_t, C.POINTER(C.c_bool), C.POINTER(C.c_uint64), C.c_char_p,
                                                 CFRP, C.POINTER(C.c_uint64)]),
     "ffi_nullifier_log_retire": (CBoolResult, [P, CFRP, C.c_size_t, C.POINTER(C.c_size_t)]),

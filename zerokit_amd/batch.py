@@ -875,6 +875,72 @@ class Hasher:
         return dict(zip(self.INFO, (int(v) for v in out)))
 
 
+class Relay:
+    """One relay step on the device (rlnamd_relay_*): the signals of n messages hashed, their proofs verified and the
+    shares of the accepted ones run through the nullifier log in one call -- exactly what Hasher.hash_to_field,
+    BatchProver.verify_many_gpu and one NullifierLog.observe give over the same inputs, with the public values staying
+    on the device in between and the hashing running beside the pairing kernels.  It borrows the prover, the log and
+    the hasher (keep them alive); without a hasher every step brings xs."""
+    OK, BAD_PROOF, BAD_ROOT, BAD_SIGNAL = range(4)
+    ROOTS_MAX = 64
+    INFO = ("steps", "chunks", "messages", "accepted", "shares", "residue_words", "host_hashed", "reserved")
+
+    def __init__(self, prover: "BatchProver", log: "NullifierLog", hasher: "Hasher" = None, lanes=0):
+        self._h = C.c_void_p()
+        self._keep = (prover, log, hasher)
+        check(lib().rlnamd_relay_new(prover._h, log._h, hasher._h if hasher is not None else None, lanes, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rlnamd_relay_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step_raw(self, proofs: bytes, values: bytes, n_values, signals=None, offsets=None, xs=None, roots=b"", tags=None):
+        """n packed proofs (128 bytes each) and their values (n_values * 32 bytes each, canonical LE, verifier order);
+        either signals (bytes) with offsets (n + 1 ints) or xs (n * 32 bytes); roots: packed accepted roots, empty for
+        any root -> (verdict n bytes, status n bytes, secrets n * 32 bytes, first tags: list of n ints)"""
+        n = len(proofs) // 128
+        if len(proofs) != 128 * n or len(values) != 32 * n_values * n or (tags is not None and len(tags) != n) or \
+                len(roots) % 32 or (offsets is not None and len(offsets) != n + 1) or (xs is not None and len(xs) != 32 * n):
+            raise RLNError("Relay.step: the lengths of proofs, values, offsets, xs, roots and tags do not agree")
+        off = None if offsets is None else (C.c_uint64 * (n + 1))(*[int(o) for o in offsets])
+        tg = None if tags is None else (C.c_uint64 * max(n, 1))(*[int(t) for t in tags])
+        verdict, status = C.create_string_buffer(max(n, 1)), C.create_string_buffer(max(n, 1))
+        secrets = C.create_string_buffer(max(32 * n, 1))
+        first = (C.c_uint64 * max(n, 1))()
+        check(lib().rlnamd_relay_step(self._h, n, proofs, values, n_values, signals, len(signals) if signals is not None else 0,
+                                      off, xs, roots if roots else None, len(roots) // 32, tg, verdict, status, secrets, first))
+        return verdict.raw[:n], status.raw[:n], secrets.raw[:32 * n], list(first[:n])
+
+    def step(self, proofs, public_inputs, signals=None, xs=None, roots=(), tags=None):
+        """proofs: a list of 128-byte strings; public_inputs: their values as lists of ints; signals: a list of bytes,
+        or xs: a list of ints; roots: accepted roots as ints (none: any root) -> (verdict, status, secrets, first_tag),
+        four lists of ints"""
+        n = len(proofs)
+        nv = _check_verify_shapes(proofs, public_inputs) if n else 0
+        offsets = None
+        if signals is not None:
+            offsets = [0]
+            for m in signals:
+                offsets.append(offsets[-1] + len(m))
+        v, st, sec, first = self.step_raw(
+            b"".join(proofs), b"".join(_b(x) for pi in public_inputs for x in pi), nv,
+            None if signals is None else b"".join(signals), offsets,
+            None if xs is None else b"".join(_b(x) for x in xs), b"".join(_b(r) for r in roots), tags)
+        return list(v), list(st), [int.from_bytes(sec[32 * i:32 * i + 32], "little") for i in range(n)], first
+
+    def info(self):
+        out = (C.c_uint64 * 8)()
+        check(lib().rlnamd_relay_info(self._h, out))
+        return dict(zip(self.INFO, (int(v) for v in out)))
+
+
 class MsmG1:
     """Variable-base MSM (VariableBaseMSM::msm_bigint, ark-ec 0.5.0; BASELINE config 5) on G1; MsmG2 below is the same
     object on the twist: points are (x, y) ints for G1, ((x.c0, x.c1), (y.c0, y.c1)) for G2, None = infinity."""

@@ -22,6 +22,7 @@
 #include "pairing.h"
 #include "poseidon.h"
 #include "prover.h"
+#include "relay.h"
 #include "verify.h"
 #include "capi_util.h"
 
@@ -44,18 +45,17 @@ struct rlnamd_tree {
   DevBuf<uint8_t> bench_elems, bench_bits;
 };
 
-struct rlnamd_nullifier_log {
-  // one stream and one staging block per log: every call on a handle takes this
+struct rlnamd_relay {
+  // a step takes this, then the hasher's, the verifier's and the log handle's, in that order, and holds them for the
+  // call; between steps the borrowed objects are usable on their own
   std::mutex mu;
-  NullifierLogDev log;
-  rlnamd_nullifier_log(uint64_t capacity, uint64_t seed) : log(capacity, seed) {}
-};
-
-struct rlnamd_hasher {
-  // one stream and one pair of staging halves per hasher: every call on a handle takes this
-  std::mutex mu;
-  HasherDev hasher;
-  rlnamd_hasher(size_t stage_bytes, size_t lane_max_blocks) : hasher(stage_bytes, lane_max_blocks) {}
+  rlnamd_nullifier_log* log;
+  rlnamd_hasher* hasher;
+  GpuVerifier& verifier;
+  RelayDev relay;
+  rlnamd_relay(rlnamd_prover* p, rlnamd_nullifier_log* l, rlnamd_hasher* h, int lanes)
+      : log(l), hasher(h), verifier(p->p->gpu_verifier()),
+        relay(verifier, p->p->graph().max_out, l->log, h ? &h->hasher : nullptr, lanes) {}
 };
 
 static void verify_common(const Zkey& zk, const uint8_t proof[128], const uint8_t* values_le, int* ok, size_t nv = 5);
@@ -329,6 +329,43 @@ int rlnamd_hasher_info(rlnamd_hasher* h, uint64_t out[8]) {
   if (!h || !out) throw Error("rlnamd_hasher_info: null pointer");
   std::lock_guard<std::mutex> lk(h->mu);
   h->hasher.info(out);
+  RLN_CATCH
+}
+
+// -------------------------------------------------------------------------------------------- relay
+int rlnamd_relay_new(rlnamd_prover* p, rlnamd_nullifier_log* log, rlnamd_hasher* h, int lanes, rlnamd_relay** out) {
+  RLN_TRY
+  if (!p || !log || !out) throw Error("rlnamd_relay_new: null pointer");
+  if (lanes != 0 && lanes != 1 && lanes != 8) throw Error("rlnamd_relay_new: lanes must be 0, 1 or 8");
+  *out = new rlnamd_relay(p, log, h, lanes);
+  RLN_CATCH
+}
+void rlnamd_relay_free(rlnamd_relay* r) { delete r; }
+int rlnamd_relay_step(rlnamd_relay* r, size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t n_values,
+                      const uint8_t* signals, size_t signals_len, const uint64_t* offsets, const uint8_t* xs_le,
+                      const uint8_t* roots_le, size_t n_roots, const uint64_t* tags, uint8_t* verdict, uint8_t* status,
+                      uint8_t* secrets_le, uint64_t* first_tag) {
+  RLN_TRY
+  // what needs no object is checked before the handle is followed
+  if (const char* refused = relay::check_arguments(n, proofs, values_le, signals, offsets, xs_le, roots_le, n_roots, verdict, status))
+    throw Error(refused);
+  if (!r) throw Error("rlnamd_relay_step: null relay");
+  if (n == 0) return RLNAMD_OK;
+  std::lock_guard<std::mutex> lk(r->mu);
+  std::unique_lock<std::mutex> lk_hasher;
+  if (r->hasher) lk_hasher = std::unique_lock<std::mutex>(r->hasher->mu);
+  std::lock_guard<std::mutex> lk_verifier(r->verifier.relay_mutex());
+  std::lock_guard<std::mutex> lk_log(r->log->mu);
+  r->relay.step(n, proofs, values_le, n_values, signals, signals_len, offsets, xs_le, roots_le, n_roots, tags, verdict, status,
+                secrets_le, first_tag);
+  RLN_CATCH
+}
+int rlnamd_relay_info(rlnamd_relay* r, uint64_t out[8]) {
+  RLN_TRY
+  if (!r || !out) throw Error("rlnamd_relay_info: null pointer");
+  std::lock_guard<std::mutex> lk(r->mu);
+  std::lock_guard<std::mutex> lk_log(r->log->mu);   // the residue is read on the log's stream
+  r->relay.info(out);
   RLN_CATCH
 }
 

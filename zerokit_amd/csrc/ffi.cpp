@@ -16,12 +16,14 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <atomic>
 #include <fstream>
 #include <memory>
 #include <chrono>
 #include <thread>
 #include <condition_variable>
 #include <deque>
+#include <map>
 #include <mutex>
 #include <random>
 #include <string>
@@ -39,6 +41,7 @@
 #include "pairing.h"
 #include "poseidon.h"
 #include "prover.h"
+#include "relay.h"
 #include "verify.h"
 #include "gather.h"
 #include "ffi_wire.h"   // CFr, the FFI object structs, Cursor / V3Reader, every (de)serialiser and validation
@@ -283,6 +286,13 @@ static constexpr size_t VERIFY_GPU_MIN_DEFAULT = 512;
 // messages; the host takes 0.043 ms for 128 messages, against 0.045 ms, and 0.085 ms for 256, against 0.046 ms)
 static constexpr size_t HASH_GPU_MIN_DEFAULT = 256;
 
+// Smallest call that ffi_relay_step runs as one relay step on the device unless the config says otherwise
+// ("relay_gpu_min"); smaller calls take the composition of the three calls.  The smallest measured n at which the
+// step's median is below the composition's minimum (tools/relay_step_throughput.py --ffi, profiles/relay_step.md:
+// ffi_relay_step 12.91 ms against 12.98 for ffi_verify_rln_signals_batch + ffi_nullifier_log_observe at 1 024 messages,
+// 30.47 against 30.86 at 8 192; over packed rows 12.98 against 13.15; n below 1 024 not measured)
+static constexpr size_t RELAY_GPU_MIN_DEFAULT = 1024;
+
 // one hasher per device for the whole process, made on first use and never freed (it would outlive the HIP runtime's
 // own teardown otherwise); calls on one device take turns
 namespace {
@@ -327,6 +337,56 @@ void hash_signals(const Vec_uint8_t* signals, size_t n, size_t gpu_min, CFr* out
 }
 }  // namespace
 
+// the relays of one RLN object, by log id; every live registry is in all_relay_registries() so that a freed log can be
+// dropped from each (lock order: the list's mutex, then a registry's; a step takes a registry's alone)
+struct RelayEntry {
+  std::mutex mu;
+  std::unique_ptr<RelayDev> dev;
+};
+struct RelayRegistry;
+struct RelayRegistries {
+  std::mutex mu;
+  std::vector<RelayRegistry*> live;
+};
+static RelayRegistries& all_relay_registries() {
+  static RelayRegistries* all = new RelayRegistries;   // never freed: logs may be freed during the process's teardown
+  return *all;
+}
+struct RelayRegistry {
+  std::mutex mu;
+  std::map<uint64_t, std::shared_ptr<RelayEntry>> by_log;
+  RelayRegistry() {
+    RelayRegistries& all = all_relay_registries();
+    std::lock_guard<std::mutex> lk(all.mu);
+    all.live.push_back(this);
+  }
+  ~RelayRegistry() {
+    RelayRegistries& all = all_relay_registries();
+    std::lock_guard<std::mutex> lk(all.mu);
+    all.live.erase(std::remove(all.live.begin(), all.live.end(), this), all.live.end());
+  }
+  RelayRegistry(const RelayRegistry&) = delete;
+  RelayRegistry& operator=(const RelayRegistry&) = delete;
+};
+namespace rlnamd {
+uint64_t next_log_id() {
+  static std::atomic<uint64_t> next{1};
+  return next.fetch_add(1, std::memory_order_relaxed);
+}
+void relay_registry_drop_log(uint64_t log_id) {
+  std::vector<std::shared_ptr<RelayEntry>> dropped;   // freed behind the locks
+  RelayRegistries& all = all_relay_registries();
+  std::lock_guard<std::mutex> lk(all.mu);
+  for (RelayRegistry* reg : all.live) {
+    std::lock_guard<std::mutex> lk_reg(reg->mu);
+    auto it = reg->by_log.find(log_id);
+    if (it == reg->by_log.end()) continue;
+    dropped.push_back(std::move(it->second));
+    reg->by_log.erase(it);
+  }
+}
+}  // namespace rlnamd
+
 struct FFI_RLN {
   // generate / verify take &self in the reference and may be called from several threads (SURVEY section 8b,
   // "Threading"); the prover owns one set of device workspaces, so proving calls on one object take turns
@@ -350,6 +410,12 @@ struct FFI_RLN {
   size_t verify_gpu_min = VERIFY_GPU_MIN_DEFAULT;
   // ffi_verify_rln_signals_batch: calls of at least this many signals are hashed on the device ("hash_gpu_min")
   size_t hash_gpu_min = HASH_GPU_MIN_DEFAULT;
+  // ffi_relay_step: calls of at least this many messages run as one relay step on the device ("relay_gpu_min"), over
+  // one relay per log, made on the first such call with the process's hasher.  A relay borrows its log, so an entry
+  // dies with it: entries are named by the log's id (never issued twice, so a new log at an old address gets a relay
+  // of its own, device check included), and rlnamd_nullifier_log_free drops the freed log's entry from every object.
+  size_t relay_gpu_min = RELAY_GPU_MIN_DEFAULT;
+  RelayRegistry relays;
   int verify_lanes = 0;   // "verify_lanes": lanes per proof of those passes (0: the verifier chooses)
   bool verify_optimistic = false;        // "verify_optimistic": a combined check per chunk first (verify_agg.hip)
   bool verify_optimistic_teams = false;  // "verify_optimistic_teams": passes that take teams are checked combined too
@@ -438,6 +504,7 @@ struct FFI_RLN {
     auto_partial = tcfg.auto_partial > 0 ? (size_t)tcfg.auto_partial : 0;
     verify_gpu_min = tcfg.verify_gpu_min >= 0 ? (size_t)tcfg.verify_gpu_min : VERIFY_GPU_MIN_DEFAULT;
     hash_gpu_min = tcfg.hash_gpu_min >= 0 ? (size_t)tcfg.hash_gpu_min : HASH_GPU_MIN_DEFAULT;
+    relay_gpu_min = tcfg.relay_gpu_min >= 0 ? (size_t)tcfg.relay_gpu_min : RELAY_GPU_MIN_DEFAULT;
     verify_lanes = (int)tcfg.verify_lanes;
     verify_optimistic = tcfg.verify_optimistic;
     verify_optimistic_teams = tcfg.verify_optimistic_teams;
@@ -504,6 +571,10 @@ struct FFI_RLN {
   std::unique_ptr<tstore::TreeStore> st;
 
   ~FFI_RLN() {
+    {
+      std::lock_guard<std::mutex> lk(relays.mu);   // the relays go before the prover whose verifier they borrow
+      relays.by_log.clear();
+    }
     try {
       detach_store();  // sled flushes when the database is dropped
     } catch (...) {
@@ -1762,15 +1833,13 @@ CBoolResult_t ffi_verify_with_roots(FFI_RLN_t* const* rln, FFI_RLNProof_t* const
 // EXT: n proofs in one call; the public-input rows are verify_zk's (proof.rs:863-885), the pairing checks run on the
 // device from verify_gpu_min proofs on and on host threads below; with "verify_optimistic" the device passes that run a
 // lane per proof try one combined check per chunk first, and with "verify_optimistic_teams" the passes in team form too
-CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
-                                          const CFr_t* xs, const Vec_CFr_t* roots, bool* ok) {
-  return guard_bool([&]() {
-    if (!rln || !*rln) throw Error("Verification error: null RLN object");
-    if (n == 0) return true;
-    if (!proofs || !xs || !ok) throw Error("Verification error: null argument");
-    FFI_RLN& r = *(FFI_RLN*)*rln;
+}  // extern "C"
+// the proofs of a batch call as packed rows: bytes n x 128, rows n x nv x 32 in the verifier's order
+static size_t pack_proof_rows(FFI_RLN& r, FFI_RLNProof_t* const* proofs, size_t n, std::vector<uint8_t>& bytes,
+                              std::vector<uint8_t>& rows) {
     const size_t nv = r.prover->zkey().gamma_abc_g1.size() - 1;
-    std::vector<uint8_t> bytes(128 * n), rows;
+    bytes.assign(128 * n, 0);
+    rows.clear();
     rows.reserve(32 * nv * n);
     auto put = [&](const CFr& v) { rows.insert(rows.end(), v.le, v.le + 32); };
     for (size_t i = 0; i < n; i++) {
@@ -1792,6 +1861,13 @@ CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t*
         throw Error("Error producing proof: malformed verifying key (public input count does not match the circuit)");
       memcpy(&bytes[128 * i], pr.proof, 128);
     }
+    return nv;
+}
+// verdict[i]: RLNAMD_RELAY_OK, or the first failing check of proof i in the order proof, root, signal
+static void verify_batch_verdicts(FFI_RLN& r, FFI_RLNProof_t* const* proofs, size_t n, const CFr_t* xs, const Vec_CFr_t* roots,
+                                  uint8_t* verdict) {
+    std::vector<uint8_t> bytes, rows;
+    const size_t nv = pack_proof_rows(r, proofs, n, bytes, rows);
     std::vector<uint8_t> pass(n);
     if (n >= r.verify_gpu_min && r.verify_optimistic) {
       GpuVerifier& gv = r.prover->gpu_verifier();
@@ -1806,16 +1882,29 @@ CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t*
     if (!roots) r.tree.get_node_host(0, own.le);
     for (size_t i = 0; i < n; i++) {
       const FFI_RLNProofValues& v = ((const FFI_RLNProof*)proofs[i])->values;
-      bool good = pass[i] != 0;
+      bool root_ok = true;
       if (!roots) {
-        good = good && cfr_cmp(own, v.root) == 0;
+        root_ok = cfr_cmp(own, v.root) == 0;
       } else if (roots->len) {
         bool found = false;
         for (size_t k = 0; k < roots->len; k++) found |= cfr_cmp(((const CFr*)roots->ptr)[k], v.root) == 0;
-        good = good && found;
+        root_ok = found;
       }
-      ok[i] = good && cfr_cmp(((const CFr*)xs)[i], v.x) == 0;
+      verdict[i] = !pass[i] ? RLNAMD_RELAY_BAD_PROOF
+                   : !root_ok ? RLNAMD_RELAY_BAD_ROOT
+                   : cfr_cmp(((const CFr*)xs)[i], v.x) != 0 ? RLNAMD_RELAY_BAD_SIGNAL : RLNAMD_RELAY_OK;
     }
+}
+extern "C" {
+CBoolResult_t ffi_verify_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proofs, size_t n,
+                                          const CFr_t* xs, const Vec_CFr_t* roots, bool* ok) {
+  return guard_bool([&]() {
+    if (!rln || !*rln) throw Error("Verification error: null RLN object");
+    if (n == 0) return true;
+    if (!proofs || !xs || !ok) throw Error("Verification error: null argument");
+    std::vector<uint8_t> verdict(n);
+    verify_batch_verdicts(*(FFI_RLN*)*rln, proofs, n, xs, roots, verdict.data());
+    for (size_t i = 0; i < n; i++) ok[i] = verdict[i] == RLNAMD_RELAY_OK;
     return true;
   });
 }
@@ -2482,6 +2571,77 @@ CBoolResult_t ffi_nullifier_log_retire(struct rlnamd_nullifier_log* log, const C
       throw Error(rlnamd_last_error());
     if (removed) *removed = (size_t)gone;
     return true;
+  });
+}
+
+// EXT: one relay step over FFI objects (rln.h).  From relay_gpu_min messages on it is rlnamd_relay_step over packed rows,
+// on one relay per (object, log); below, for an object with "verify_optimistic", and for more roots than a step takes,
+// it is the composition: ffi_verify_rln_signals_batch's stages with the verdict's cause kept, then
+// ffi_nullifier_log_observe(take = verdict OK).  One function for V1 and V3 callers: the proofs are the same record.
+static bool relay_step_common(void* const* rln, rlnamd_nullifier_log* log, void* const* proofs, size_t n,
+                              const Vec_uint8_t* signals, const Vec_CFr_t* roots, const uint64_t* tags, uint8_t* verdict,
+                              uint8_t* status, CFr_t* secrets, uint64_t* first_tag) {
+  if (n == 0) return true;
+  if (!proofs || !signals || !verdict || !status) throw Error("relay step: null argument");
+  if (!rln || !*rln) throw Error("relay step: null RLN object");
+  if (!log) throw Error("relay step: null log");
+  FFI_RLN& r = *(FFI_RLN*)*rln;
+  for (size_t i = 0; i < n; i++) {
+    if (!proofs[i]) throw Error("relay step: null proof");
+    if (!signals[i].ptr && signals[i].len) throw Error("hash_to_field: signal " + std::to_string(i) + " is a null pointer with a length");
+  }
+  const size_t n_roots = roots ? roots->len : 1;
+  if (n < r.relay_gpu_min || r.verify_optimistic || n_roots > RLNAMD_RELAY_ROOTS_MAX) {
+    std::vector<CFr> xs(n);
+    hash_signals(signals, n, r.hash_gpu_min, xs.data());
+    verify_batch_verdicts(r, (FFI_RLNProof_t* const*)proofs, n, (const CFr_t*)xs.data(), roots, verdict);
+    std::vector<void*> values(n);
+    std::unique_ptr<bool[]> take(new bool[n]);
+    for (size_t i = 0; i < n; i++) {
+      values[i] = (void*)&((FFI_RLNProof*)proofs[i])->values;
+      take[i] = verdict[i] == RLNAMD_RELAY_OK;
+    }
+    return nullifier_log_observe_values(log, values.data(), n, take.get(), tags, status, secrets, first_tag);
+  }
+  std::vector<uint8_t> bytes, rows;
+  const size_t nv = pack_proof_rows(r, (FFI_RLNProof_t* const*)proofs, n, bytes, rows);
+  std::vector<uint64_t> offsets(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    if (signals[i].len > UINT64_MAX - offsets[i]) throw Error("hash_to_field: sizes overflow");
+    offsets[i + 1] = offsets[i] + signals[i].len;
+  }
+  std::vector<uint8_t> data((size_t)offsets[n] + 1);
+  for (size_t i = 0; i < n; i++)
+    if (signals[i].len) memcpy(&data[(size_t)offsets[i]], signals[i].ptr, signals[i].len);
+  CFr own;
+  if (!roots) r.tree.get_node_host(0, own.le);
+  const uint8_t* roots_le = !roots ? own.le : (const uint8_t*)roots->ptr;
+  SharedHasher& sh = shared_hasher();
+  std::shared_ptr<RelayEntry> entry;
+  {
+    std::lock_guard<std::mutex> lk(r.relays.mu);
+    std::shared_ptr<RelayEntry>& slot = r.relays.by_log[log->id];
+    if (!slot) slot = std::make_shared<RelayEntry>();
+    entry = slot;
+  }
+  GpuVerifier& gv = r.prover->gpu_verifier();
+  // rlnamd_relay_step's order: the relay, the hasher, the verifier, the log
+  std::lock_guard<std::mutex> lk_relay(entry->mu);
+  std::lock_guard<std::mutex> lk_hasher(sh.mu);
+  std::lock_guard<std::mutex> lk_verifier(gv.relay_mutex());
+  std::lock_guard<std::mutex> lk_log(log->mu);
+  if (!sh.h) sh.h.reset(new HasherDev(0, 0));
+  if (!entry->dev) entry->dev.reset(new RelayDev(gv, r.prover->graph().max_out, log->log, sh.h.get(), r.verify_lanes));
+  entry->dev->step(n, bytes.data(), rows.data(), nv, data.data(), (size_t)offsets[n], offsets.data(), nullptr, roots_le, n_roots,
+                   tags, verdict, status, (uint8_t*)secrets, first_tag);
+  return true;
+}
+CBoolResult_t ffi_relay_step(FFI_RLN_t* const* rln, struct rlnamd_nullifier_log* log, FFI_RLNProof_t* const* proofs, size_t n,
+                             const Vec_uint8_t* signals, const Vec_CFr_t* roots, const uint64_t* tags, uint8_t* verdict,
+                             uint8_t* status, CFr_t* secrets, uint64_t* first_tag) {
+  return guard_bool([&]() {
+    return relay_step_common((void* const*)rln, log, (void* const*)proofs, n, signals, roots, tags, verdict, status, secrets,
+                             first_tag);
   });
 }
 

@@ -429,6 +429,15 @@ CBoolResult_t ffi_rln_v3_nullifier_log_observe(struct rlnamd_nullifier_log* log,
       [&]() { return nullifier_log_observe_values(log, (void* const*)values, n, take, tags, status, secrets, first_tag); });
 }
 
+CBoolResult_t ffi_rln_v3_relay_step(FFI_RLNV3_t* const* rln, struct rlnamd_nullifier_log* log, FFI_RLNV3Proof_t* const* proofs,
+                                    size_t n, const Vec_uint8_t* signals, const Vec_CFr_t* roots, const uint64_t* tags,
+                                    uint8_t* verdict, uint8_t* status, CFr_t* secrets, uint64_t* first_tag) {   // EXT: the V3 proofs are the same record
+  return guard_bool([&]() {
+    return relay_step_common((void* const*)rln, log, (void* const*)proofs, n, signals, roots, tags, verdict, status, secrets,
+                             first_tag);
+  });
+}
+
 // ================================================================================ tree (:1363-1609)
 void ffi_rln_v3_merkle_proof_free(FFI_RLNV3MerkleProof_t* proof) { ffi_merkle_proof_free((FFI_MerkleProof_t*)proof); }
 CBoolResult_t ffi_rln_v3_delete_leaf(FFI_RLNV3_t** rln, size_t index) {

@@ -195,18 +195,24 @@ inline size_t chunk_bytes(const Chunk& c) { return header_bytes(c.count) + (size
 // room for any chunk of at most half_blocks blocks (and so at most half_blocks messages)
 inline size_t half_bytes(size_t half_blocks) { return header_bytes(half_blocks) + half_blocks * RATE; }
 
-// The plan of a call.  Returns null, or the text of the refusal; a refused call has written nothing but *p.
-// sorted = false keeps the lanes in index order (the measurement's other row).
-inline const char* plan_call(const uint8_t* data, uint64_t data_len, const uint64_t* offsets, uint64_t n,
-                             size_t half_blocks, size_t lane_max_blocks, bool sorted, Plan* p) {
-  *p = Plan();
-  if (n == 0) return nullptr;
+// what a call brings, checked: null, or the text of the refusal (n > 0)
+inline const char* check_call(const uint8_t* data, uint64_t data_len, const uint64_t* offsets, uint64_t n) {
   if (!offsets) return "hash_to_field: null offsets for n > 0 messages";
   if (n > MAX_MESSAGES) return "hash_to_field: sizes overflow, a call takes at most 2^32 - 1 messages";
   for (uint64_t i = 0; i < n; i++)
     if (offsets[i + 1] < offsets[i]) return "hash_to_field: offsets decrease";
   if (offsets[n] > data_len) return "hash_to_field: the last offset lies beyond data_len";
   if (!data && offsets[n] > offsets[0]) return "hash_to_field: null data for messages that are not empty";
+  return nullptr;
+}
+
+// The plan of a call.  Returns null, or the text of the refusal; a refused call has written nothing but *p.
+// sorted = false keeps the lanes in index order (the measurement's other row).
+inline const char* plan_call(const uint8_t* data, uint64_t data_len, const uint64_t* offsets, uint64_t n,
+                             size_t half_blocks, size_t lane_max_blocks, bool sorted, Plan* p) {
+  *p = Plan();
+  if (n == 0) return nullptr;
+  if (const char* refused = check_call(data, data_len, offsets, n)) return refused;
   if (half_blocks == 0 || lane_max_blocks == 0) return "hash_to_field: internal error, a hasher without staging";
 
   p->n = (size_t)n;
@@ -298,6 +304,16 @@ struct HasherDev {
   // the last call: messages on the device, on the host, chunks, blocks on the device, longest lane in blocks;
   // then staging blocks per half, lane_max_blocks, calls so far
   void info(uint64_t out[8]);
+
+  // ---- for the relay step (relay.hip): the same plan, packing and lanes, but the rows stay on the device, row i of
+  // rows_dev (n x 32 bytes of device memory) the element of message i: a lane writes row order[j], and the rows of the
+  // messages the plan gives to the host are hashed on the calling thread and copied into place.  Everything is
+  // enqueued on relay_stream() and NOT waited for: the caller waits for that stream before the hasher is used again
+  // (the pinned halves are packed anew by the next call).  Returns the number of messages hashed on the host.
+  // Refuses what hash_to_field refuses, before anything is enqueued.
+  size_t relay_hash(const uint8_t* data, size_t data_len, const uint64_t* offsets, size_t n, uint8_t* rows_dev);
+  void* relay_stream();   // a hipStream_t
+  int device() const;
 };
 
 }  // namespace rlnamd

@@ -37,6 +37,21 @@ __global__ void __launch_bounds__(HASH_LANES) k_hash_to_field(const uint32_t* __
   rows[2 * (size_t)j + 1] = make_uint4(v[4], v[5], v[6], v[7]);
 }
 
+// the same lane, its row put where its message is: row order[j] (the relay step keeps the rows on the device)
+__global__ void __launch_bounds__(HASH_LANES) k_hash_to_field_at(const uint32_t* __restrict__ first_block,
+                                                                 const uint64_t* __restrict__ blocks,
+                                                                 const uint32_t* __restrict__ order, uint32_t n,
+                                                                 uint32_t n_rows, uint4* __restrict__ rows) {
+  const uint32_t j = blockIdx.x * HASH_LANES + threadIdx.x;
+  if (j >= n) return;
+  uint32_t v[8];
+  kbatch::hash_blocks(blocks, first_block[j], first_block[j + 1], v);
+  const uint32_t i = order[j];
+  if (i >= n_rows) return;   // (not reached: order is a permutation of the call's messages)
+  rows[2 * (size_t)i] = make_uint4(v[0], v[1], v[2], v[3]);
+  rows[2 * (size_t)i + 1] = make_uint4(v[4], v[5], v[6], v[7]);
+}
+
 struct OnDevice {   // the hasher's device for the length of a call, the caller's afterwards
   int prev = 0, dev;
   explicit OnDevice(int dev_) : dev(dev_) {
@@ -64,6 +79,34 @@ struct HasherDev::Impl {
   DevBuf<uint8_t> rows_dev;
   uint64_t last[5] = {0, 0, 0, 0, 0}, calls = 0;
   kbatch::Plan plan;
+  // relay_hash: the lanes' part of order[], and the rows of the host's messages on their way to the device
+  size_t order_n = 0;
+  uint32_t* order_host = nullptr;
+  DevBuf<uint32_t> order_dev;
+  size_t host_rows_n = 0;
+  uint8_t* host_rows = nullptr;
+
+  void reserve_order(size_t n) {
+    if (n <= order_n) return;
+    RLN_HIP(hipStreamSynchronize(stream));
+    if (order_host) (void)hipHostFree(order_host);
+    order_host = nullptr;
+    order_n = 0;
+    order_dev.release();
+    RLN_HIP(hipHostMalloc((void**)&order_host, 4 * n, hipHostMallocDefault));
+    order_dev.alloc(n);
+    order_n = n;
+  }
+  void reserve_host_rows(size_t n) {
+    if (n <= host_rows_n) return;
+    RLN_HIP(hipStreamSynchronize(stream));
+    if (host_rows) (void)hipHostFree(host_rows);
+    host_rows = nullptr;
+    host_rows_n = 0;
+    const size_t m = n < 64 ? 64 : n;
+    RLN_HIP(hipHostMalloc((void**)&host_rows, 32 * m, hipHostMallocDefault));
+    host_rows_n = m;
+  }
 
   void reserve_rows(size_t n) {
     if (n <= rows_n) return;
@@ -83,6 +126,8 @@ struct HasherDev::Impl {
       if (half_host[h]) (void)hipHostFree(half_host[h]);
     }
     if (rows_host) (void)hipHostFree(rows_host);
+    if (order_host) (void)hipHostFree(order_host);
+    if (host_rows) (void)hipHostFree(host_rows);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -166,6 +211,57 @@ void HasherDev::hash_to_field(const uint8_t* data, size_t data_len, const uint64
   m.last[4] = P.longest_lane;
   m.calls++;
 }
+
+size_t HasherDev::relay_hash(const uint8_t* data, size_t data_len, const uint64_t* offsets, size_t n, uint8_t* rows_dev) {
+  Impl& m = *d;
+  if (n == 0) return 0;
+  if (!rows_dev) throw Error("hash_to_field: null output for n > 0 messages");
+  kbatch::Plan& P = m.plan;
+  if (const char* refused = kbatch::plan_call(data, data_len, offsets, n, m.half_blocks, m.lane_max_blocks, m.sorted, &P))
+    throw Error(refused);
+
+  OnDevice on(m.device);
+  const size_t n_dev = P.n - P.n_host;
+  m.reserve_order(n_dev);
+  m.reserve_host_rows(P.n_host);
+  if (n_dev) {
+    memcpy(m.order_host, P.order.data() + P.n_host, 4 * n_dev);
+    RLN_HIP(hipMemcpyAsync(m.order_dev.p, m.order_host, 4 * n_dev, hipMemcpyHostToDevice, m.stream));
+  }
+  // the host's messages behind the first chunk's launch, as hash_to_field has them; their rows go up one by one
+  auto host_share = [&]() {
+    for (size_t j = 0; j < P.n_host; j++) {
+      const uint32_t i = P.order[j];
+      kbatch::hash_message(data + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), m.host_rows + 32 * j);
+      RLN_HIP(hipMemcpyAsync(rows_dev + 32 * (size_t)i, m.host_rows + 32 * j, 32, hipMemcpyHostToDevice, m.stream));
+    }
+  };
+  for (size_t k = 0; k < P.chunks.size(); k++) {
+    const kbatch::Chunk& c = P.chunks[k];
+    const int h = (int)(k & 1);
+    if (k >= 2) RLN_HIP(hipEventSynchronize(m.copied[h]));   // the copy of chunk k - 2 has left this half
+    const size_t bytes = kbatch::pack_chunk(P, c, data, offsets, m.half_host[h]);
+    RLN_HIP(hipMemcpyAsync(m.half_dev[h].p, m.half_host[h], bytes, hipMemcpyHostToDevice, m.stream));
+    RLN_HIP(hipEventRecord(m.copied[h], m.stream));
+    hipLaunchKernelGGL(k_hash_to_field_at, dim3(div_up(c.count, HASH_LANES)), dim3(HASH_LANES), 0, m.stream,
+                       (const uint32_t*)m.half_dev[h].p, (const uint64_t*)(m.half_dev[h].p + kbatch::header_bytes(c.count)),
+                       (const uint32_t*)(m.order_dev.p + (c.first - P.n_host)), (uint32_t)c.count, (uint32_t)n,
+                       (uint4*)rows_dev);
+    RLN_HIP(hipGetLastError());
+    if (k == 0) host_share();
+  }
+  if (P.chunks.empty()) host_share();
+  m.last[0] = n_dev;
+  m.last[1] = P.n_host;
+  m.last[2] = P.chunks.size();
+  m.last[3] = P.device_blocks;
+  m.last[4] = P.longest_lane;
+  m.calls++;
+  return P.n_host;
+}
+
+void* HasherDev::relay_stream() { return (void*)d->stream; }
+int HasherDev::device() const { return d->device; }
 
 void HasherDev::info(uint64_t out[8]) {
   Impl& m = *d;

@@ -160,6 +160,22 @@ struct StdAtomics {
 };
 #endif
 
+#if defined(__HIPCC__)
+// the kernels' form (nullifier_log.hip, relay.hip): agent scope, the table is shared by all XCDs
+struct DevAtomics {
+  static __device__ __forceinline__ uint32_t cas(uint32_t* p, uint32_t expect, uint32_t v) {
+    __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return expect;   // on failure the exchange has put the entry found there
+  }
+  static __device__ __forceinline__ void min(uint32_t* p, uint32_t v) {
+    __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  static __device__ __forceinline__ uint32_t load(const uint32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+#endif
+
 // The probe loops below have two properties by construction:
 //   * Every loop's trip count is bounded by `slots`.  The table is at most half full (slots >= 2 * capacity, one slot
 //     per KEY, at most `capacity` records), so a walk reaches an EMPTY slot -- or its own key -- long before that.
@@ -341,6 +357,21 @@ struct NullifierLogDev {
   uint64_t home_slot(const uint8_t nullifier_le[32]) const;   // host only
   void info(uint64_t out[8]);
   void retire_info(uint64_t out[8]);   // include/rln_amd.h: rlnamd_nullifier_log_retire_info
+
+  // ---- for the relay step (relay.hip), whose kernels write a call's shares straight into rows [count, count + m) and
+  // then run the insert and judge passes over them on the log's stream.  The caller holds the handle's mutex from
+  // relay_rows() to relay_commit(); nothing of the log's host state changes in between.
+  struct RelayRows {
+    nlog::Records rows;   // seqs: null while the log is dense (row == sequence number)
+    nlog::View view;
+    uint64_t count, capacity, next_seq;
+    void* stream;         // a hipStream_t
+    int device;
+  };
+  RelayRows relay_rows();
+  int device() const;   // fixed when the log is made: needs no lock
+  // what observe() does on the host behind its passes: m rows taken, the call's longest walk, its NEW shares
+  void relay_commit(uint64_t m, uint32_t walk, uint64_t fresh);
 };
 
 // test support (rlnamd_probe_log_positions): the position pass of a retire on buffers of its own -- keep: n bytes,

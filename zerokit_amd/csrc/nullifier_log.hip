@@ -20,6 +20,7 @@
 // the scan reads what the kernel before it wrote, the move reads positions the last scan kernel wrote and writes rows
 // nobody reads before the insert pass.  A single-pass scan, in which a block looks back at its predecessors' sums,
 // would be fewer launches and is exactly what that rule forbids: it spins on other workgroups' stores across XCDs.
+// (The scan's kernels are in log_scan.h, which relay.hip shares.)
 #include "nullifier_log.h"
 
 #include <string.h>
@@ -30,30 +31,17 @@
 #include <vector>
 
 #include "common.h"
+#include "log_scan.h"
 
 namespace rlnamd {
 
+using nlog::DevAtomics;
 using nlog::Row32;
 using nlog::Records;
 using nlog::Row96;
 using nlog::View;
 
 namespace {
-
-struct DevAtomics {
-  static __device__ __forceinline__ uint32_t cas(uint32_t* p, uint32_t expect, uint32_t v) {
-    __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return expect;   // on failure the exchange has put the entry found there
-  }
-  static __device__ __forceinline__ void min(uint32_t* p, uint32_t v) {
-    __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  static __device__ __forceinline__ uint32_t load(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-};
-
-constexpr uint32_t LOG_LANES = 256;
 
 // one lane per share: record first_id + i takes its key's slot, or lowers the id that slot holds
 __global__ void __launch_bounds__(LOG_LANES) k_log_insert(View L, uint32_t first_id, uint32_t n) {
@@ -92,50 +80,6 @@ __global__ void __launch_bounds__(LOG_LANES) k_log_mark(const Row96* __restrict_
   __syncthreads();
   const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
   if (i < n) keep[i] = nlog::keeps(rest[i].ext, lds_set, k) ? 1 : 0;
-}
-
-// exclusive sum over the workgroup's LOG_LANES values, *total: their sum.  Every lane of the workgroup calls it.
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wave_sum[LOG_LANES / 64];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t below = __shfl_up(inc, d, 64);
-    if ((int)lane >= d) inc += below;
-  }
-  if (lane == 63) wave_sum[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < LOG_LANES / 64; w++) {
-    if (w < wave) base += wave_sum[w];
-    all += wave_sum[w];
-  }
-  *total = all;
-  return base + inc - v;
-}
-// an item of the scan's input: a keep mark counts as 0 or 1, a block sum as itself
-__device__ __forceinline__ uint32_t scan_item(uint8_t v) { return v != 0; }
-__device__ __forceinline__ uint32_t scan_item(uint32_t v) { return v; }
-
-// one level up: sums[b] = the sum of block b's items
-template <class T>
-__global__ void __launch_bounds__(LOG_LANES) k_scan_up(const T* __restrict__ in, size_t n, uint32_t* __restrict__ sums) {
-  const size_t i = (size_t)blockIdx.x * LOG_LANES + threadIdx.x;
-  uint32_t total;
-  block_scan(i < n ? scan_item(in[i]) : 0, &total);
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-// one level down: out[i] = the items before i, base[b] (the level above, already exclusive; null at the top: one block)
-// plus the items of block b before i.  in == out for the levels of block sums: a lane reads and writes its own word.
-template <class T>
-__global__ void __launch_bounds__(LOG_LANES) k_scan_down(const T* in, size_t n, const uint32_t* __restrict__ base,
-                                                         uint32_t* out) {
-  const size_t i = (size_t)blockIdx.x * LOG_LANES + threadIdx.x;
-  uint32_t total;
-  const uint32_t before = block_scan(i < n ? scan_item(in[i]) : 0, &total);
-  if (i < n) out[i] = (base ? base[blockIdx.x] : 0) + before;
 }
 
 // kept row i -> row pos[i] of the other set of record arrays.  dense: no sequence numbers are stored yet, row i is
@@ -191,37 +135,6 @@ __global__ void __launch_bounds__(LOG_LANES) k_log_number(uint64_t* __restrict__
 // get() after a retire, one lane: the row that carries `seq`, or `count`
 __global__ void k_log_find(const uint64_t* __restrict__ seqs, uint64_t count, uint64_t seq, uint32_t* __restrict__ row) {
   *row = (uint32_t)nlog::find_seq(seqs, count, seq);
-}
-
-// the levels of block sums above n items: level j + 1 has one entry per LOG_LANES entries of level j, the last has one
-struct ScanPlan {
-  std::vector<size_t> len, off;
-  size_t words = 0;
-  explicit ScanPlan(size_t n) {
-    do {
-      n = (n + LOG_LANES - 1) / LOG_LANES;
-      len.push_back(n);
-      off.push_back(words);
-      words += n;
-    } while (n > 1);
-  }
-};
-// keep[0 .. n) -> pos[0 .. n); sums: ScanPlan(n).words words.  Returns where the number of kept items is (on the device).
-const uint32_t* scan_positions(const uint8_t* keep, size_t n, uint32_t* pos, uint32_t* sums, hipStream_t stream) {
-  const ScanPlan P(n);
-  const size_t top = P.len.size();   // levels 1 .. top of block sums; level `top` is the one word with the total
-  auto level = [&](size_t j) { return sums + P.off[j - 1]; };
-  hipLaunchKernelGGL(k_scan_up<uint8_t>, dim3(P.len[0]), dim3(LOG_LANES), 0, stream, keep, n, level(1));
-  for (size_t j = 1; j < top; j++)
-    hipLaunchKernelGGL(k_scan_up<uint32_t>, dim3(P.len[j]), dim3(LOG_LANES), 0, stream, (const uint32_t*)level(j), P.len[j - 1],
-                       level(j + 1));
-  for (size_t j = top - 1; j >= 1; j--)
-    hipLaunchKernelGGL(k_scan_down<uint32_t>, dim3(P.len[j]), dim3(LOG_LANES), 0, stream, (const uint32_t*)level(j), P.len[j - 1],
-                       (const uint32_t*)(j + 1 < top ? level(j + 1) : nullptr), level(j));
-  hipLaunchKernelGGL(k_scan_down<uint8_t>, dim3(P.len[0]), dim3(LOG_LANES), 0, stream, keep, n,
-                     (const uint32_t*)(1 < top ? level(1) : nullptr), pos);
-  RLN_HIP(hipGetLastError());
-  return level(top);
 }
 
 // the stores go through a volatile pointer so that they cannot be elided as dead (ffi_wire.h: secure_zero)
@@ -594,6 +507,23 @@ void NullifierLogDev::retire_info(uint64_t out[8]) {
   out[4] = m.rebuild_longest;
   out[5] = m.spare ? 1 : 0;
   out[6] = out[7] = 0;
+}
+
+NullifierLogDev::RelayRows NullifierLogDev::relay_rows() {
+  Impl& m = *d;
+  return RelayRows{Records{m.nul.p, m.rest.p, m.tags.p, m.dense ? nullptr : m.seqs.p}, m.view(), m.count, m.capacity, m.next_seq,
+                   (void*)m.stream, m.device};
+}
+
+int NullifierLogDev::device() const { return d->device; }
+
+void NullifierLogDev::relay_commit(uint64_t n, uint32_t walk, uint64_t fresh) {
+  Impl& m = *d;
+  m.count += n;
+  m.next_seq += n;
+  m.calls++;
+  m.distinct += fresh;
+  if (walk > m.longest) m.longest = walk;
 }
 
 void probe_log_positions(const uint8_t* keep, size_t n, uint32_t* pos, uint64_t* kept) {

@@ -76,6 +76,9 @@ struct TreeConfig {
   // "hash_gpu_min": N -- ffi_verify_rln_signals_batch hashes its signals on the device when a call brings at least N of
   // them, one by one on the calling thread below.  -1 (default): HASH_GPU_MIN_DEFAULT; 0: always the device
   long hash_gpu_min = -1;
+  // "relay_gpu_min": N -- ffi_relay_step runs a call of at least N messages as one relay step on the device
+  // (relay.hip), smaller ones as the composition of the three calls.  -1 (default): RELAY_GPU_MIN_DEFAULT; 0: always the step
+  long relay_gpu_min = -1;
   // "verify_lanes": 1 | 8 | 0 -- lanes per proof of those device passes: a lane, a team of 8 (verify_team.hip), or by the
   // size of the call (0, the default: RLNAMD_VERIFY_LANES if set, else teams up to GpuVerifier::TEAM_MAX proofs)
   long verify_lanes = 0;
@@ -248,6 +251,10 @@ inline TreeConfig parse_tree_config(const std::string& js) {
       if (key == "hash_gpu_min") {
         if (num < 0 || num > 1000000000) throw Error("Configuration error: hash_gpu_min: expected 0 .. 1000000000 signals");
         c.hash_gpu_min = num;
+      }
+      if (key == "relay_gpu_min") {
+        if (num < 0 || num > 1000000000) throw Error("Configuration error: relay_gpu_min: expected 0 .. 1000000000 messages");
+        c.relay_gpu_min = num;
       }
       if (key == "verify_lanes") {
         if (num != 0 && num != 1 && num != 8) throw Error("Configuration error: verify_lanes: expected 0, 1 or 8");

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include <memory>
+#include <mutex>
 
 #include "zkey.h"
 
@@ -78,6 +79,22 @@ class GpuVerifier {
   // diagnosis: [0] nanoseconds the combined checks have spent in vm::finish_host (the host's three fixed pairs and the
   // one final exponentiation per chunk), [1] the number of those calls
   void finish_time(uint64_t out[2]);
+
+  // ---- for the relay step (relay.hip): one chunk of the exact pass enqueued and NOT waited for, its proofs, values and
+  // verdicts left on the device for the kernels the relay runs behind an event on relay_stream().  The caller holds
+  // relay_mutex() for the whole step, runs on device(), and waits (through that event) before the next chunk: the
+  // staging buffer and d_in are the ones verify() uses.
+  struct RelayChunk {
+    const uint32_t* proofs;   // n x 32 words
+    const uint32_t* vals;     // n x n_values x 8 words
+    const uint8_t* ok;        // n
+  };
+  std::mutex& relay_mutex();
+  int device() const;
+  size_t n_values() const;
+  void* relay_stream();                         // a hipStream_t
+  bool relay_team(size_t n, int lanes) const;   // verify()'s choice of shape for a call of n proofs
+  RelayChunk relay_enqueue(size_t n, const uint8_t* proofs, const uint8_t* values_le, bool team);   // n <= the shape's chunk
 
  private:
   struct Impl;

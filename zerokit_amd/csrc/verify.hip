@@ -183,25 +183,29 @@ struct GpuVerifier::Impl {
     }
     if (cur != dev) RLN_HIP(hipSetDevice(cur));
   }
-  void chunk(size_t n, const uint8_t* proofs, const uint8_t* values, uint8_t* ok, uint8_t* gt384, bool team) {
-    reserve(n, gt384 != nullptr);
+  // the copy in and the three kernels of one chunk, enqueued
+  void enqueue_chunk(size_t n, const uint8_t* proofs, const uint8_t* values, bool ok, bool gt, bool team) {
+    reserve(n, gt);
     memcpy(h_in, proofs, 128 * n);
     memcpy(h_in + 128 * n, values, 32 * nv * n);
     RLN_HIP(hipMemcpyAsync(d_in.p, h_in, n * (128 + 32 * nv), hipMemcpyHostToDevice, st));
     const uint32_t* d_proofs = d_in.p;
     const uint32_t* d_vals = d_in.p + 32 * n;
     if (team) {
-      verify_team_enqueue(st, key.p, d_proofs, d_vals, d_prep.p, d_f.p, ok ? d_ok.p : nullptr, gt384 ? d_gt.p : nullptr,
+      verify_team_enqueue(st, key.p, d_proofs, d_vals, d_prep.p, d_f.p, ok ? d_ok.p : nullptr, gt ? d_gt.p : nullptr,
                           (uint32_t)n);
     } else {
       const dim3 grid(div_up(n, 64)), block(64);
       hipLaunchKernelGGL(k_verify_prepare, grid, block, 0, st, key.p, d_proofs, d_vals, d_prep.p, (uint32_t)n);
       hipLaunchKernelGGL(k_verify_miller, grid, block, 0, st, key.p, d_prep.p, d_f.p, (uint32_t)n);
       hipLaunchKernelGGL(k_verify_final_exp, grid, block, 0, st, key.p, d_prep.p, d_f.p, ok ? d_ok.p : nullptr,
-                         gt384 ? d_gt.p : nullptr, (uint32_t)n);
+                         gt ? d_gt.p : nullptr, (uint32_t)n);
     }
     RLN_HIP(hipGetLastError());
     n_passes[team ? 1 : 0]++;
+  }
+  void chunk(size_t n, const uint8_t* proofs, const uint8_t* values, uint8_t* ok, uint8_t* gt384, bool team) {
+    enqueue_chunk(n, proofs, values, ok != nullptr, gt384 != nullptr, team);
     if (ok) RLN_HIP(hipMemcpyAsync(h_ok, d_ok.p, n, hipMemcpyDeviceToHost, st));
     if (gt384) RLN_HIP(hipMemcpyAsync(h_gt, d_gt.p, n * 384, hipMemcpyDeviceToHost, st));
     RLN_HIP(hipStreamSynchronize(st));
@@ -347,6 +351,21 @@ void GpuVerifier::finish_time(uint64_t out[2]) {
   std::lock_guard<std::mutex> lk(d_->mu);
   out[0] = d_->finish_ns;
   out[1] = d_->finish_calls;
+}
+
+std::mutex& GpuVerifier::relay_mutex() { return d_->mu; }
+int GpuVerifier::device() const { return d_->dev; }
+size_t GpuVerifier::n_values() const { return d_->nv; }
+void* GpuVerifier::relay_stream() { return (void*)d_->st; }
+bool GpuVerifier::relay_team(size_t n, int lanes) const {
+  if (lanes == 0) lanes = d_->forced_lanes ? d_->forced_lanes : (n <= TEAM_MAX ? 8 : 1);
+  return lanes == 8;
+}
+GpuVerifier::RelayChunk GpuVerifier::relay_enqueue(size_t n, const uint8_t* proofs, const uint8_t* values_le, bool team) {
+  Impl& D = *d_;
+  if (n == 0 || n > (team ? TEAM_CHUNK : CHUNK)) throw Error("verify: internal error, a relay chunk of the wrong size");
+  D.enqueue_chunk(n, proofs, values_le, true, false, team);
+  return RelayChunk{D.d_in.p, D.d_in.p + 32 * n, D.d_ok.p};
 }
 
 void GpuVerifier::passes(size_t out[2]) {

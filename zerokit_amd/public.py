@@ -585,6 +585,35 @@ class RLN:
         _ok_bool(lib().ffi_verify_rln_signals_batch(C.byref(self._h), hs, n, vecs, rp, ok))
         return [bool(b) for b in ok]
 
+    def relay_step(self, log, proofs, signals, roots=None, tags=None):
+        """EXT: one step of a relay loop (ffi_relay_step): verify_rln_signals_batch and observe_proof_values(take=ok) in
+        one call, on the device as one relay step when n is at least the object's "relay_gpu_min".  log: a
+        batch.NullifierLog.  Returns (verdict, status, secrets, first_tag), one entry per message: verdict 0, or 1 / 2 / 3
+        for a bad proof, root or signal; the rest as observe_proof_values returns it."""
+        return _relay_step(lib().ffi_relay_step, self, log, proofs, signals, roots, tags)
+
+
+def _relay_step(fn, rln, log, proofs, signals, roots, tags):
+    n = len(proofs)
+    if len(signals) != n or (tags is not None and len(tags) != n):
+        raise RLNError("relay_step: %d proofs, but signals or tags of another length" % n)
+    if n == 0:
+        return [], [], [], []
+    hs = (C.c_void_p * n)(*[p._h.value for p in proofs])
+    keep = [_vec_u8(s) for s in signals]
+    vecs = (VecU8 * n)(*[v if len(s) else VecU8(None, 0, 0) for (v, _k), s in zip(keep, signals)])
+    rp = None
+    if roots is not None:
+        v, _k2 = _vec_cfr(list(roots))
+        rp = C.byref(v)
+    tg = None if tags is None else (C.c_uint64 * n)(*[int(t) for t in tags])
+    verdict, status = C.create_string_buffer(n), C.create_string_buffer(n)
+    secrets = (CFr * n)()
+    first = (C.c_uint64 * n)()
+    _ok_bool(fn(C.byref(rln._h), log._h, hs, n, vecs, rp, tg, verdict, status, secrets, first))
+    return (list(verdict.raw[:n]), list(status.raw[:n]),
+            [int.from_bytes(bytes(secrets[i].le), "little") for i in range(n)], list(first[:n]))
+
 
 def compute_id_secret(share1, share2) -> int:
     """protocol/slashing.rs:12-36: shares are (x, y) pairs"""

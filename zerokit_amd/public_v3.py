@@ -4,7 +4,7 @@ Field elements are Python ints; errors are RLNError with the text the ABI return
 import ctypes as C
 
 from ._native import CFr, RLNError, VecSize, lib
-from .public import (_cfr, _err, _observe_proof_values, _ok_bool, _ok_ptr, _take_bytes, _take_cfr, _take_vec_bool,
+from .public import (_cfr, _err, _observe_proof_values, _ok_bool, _relay_step, _ok_ptr, _take_bytes, _take_cfr, _take_vec_bool,
                      _take_vec_cfr, _vec_bool, _vec_cfr, _vec_u8)
 
 
@@ -229,8 +229,9 @@ class RLNV3(_Handle):
         return cls(_ok_ptr(lib().ffi_rln_v3_new_stateless(C.byref(z), C.byref(g))))
 
     @classmethod
-    def stateful(cls, tree_depth=20, zkey: bytes = None, graph: bytes = None, tree="full"):
-        """tree: "full" | "optimal" | "pm" (one device tree behind all three)"""
+    def stateful(cls, tree_depth=20, zkey: bytes = None, graph: bytes = None, tree="full", config_path: str = None):
+        """tree: "full" | "optimal" | "pm" (one device tree behind all three); config_path: the JSON config file of the
+        "pm" constructor with explicit resources (the PmTreeConfig keys and this backend's own)"""
         L = lib()
         if zkey is None:
             h = {"full": L.ffi_rln_v3_new_with_full_merkle_tree_default,
@@ -242,7 +243,8 @@ class RLNV3(_Handle):
         z, _k1 = _vec_u8(zkey)
         g, _k2 = _vec_u8(graph)
         if tree == "pm":
-            return cls(_ok_ptr(L.ffi_rln_v3_new_with_pm_tree(tree_depth, C.byref(z), C.byref(g), b"")))
+            return cls(_ok_ptr(L.ffi_rln_v3_new_with_pm_tree(tree_depth, C.byref(z), C.byref(g),
+                                                             (config_path or "").encode())))
         fn = L.ffi_rln_v3_new_with_full_merkle_tree if tree == "full" else L.ffi_rln_v3_new_with_optimal_merkle_tree
         return cls(_ok_ptr(fn(tree_depth, C.byref(z), C.byref(g))))
 
@@ -280,6 +282,10 @@ class RLNV3(_Handle):
     def set_leaves_from(self, index, leaves):
         v, _k = _vec_cfr(list(leaves))
         _ok_bool(lib().ffi_rln_v3_set_leaves_from(self._ref(), index, C.byref(v)))
+
+    def relay_step(self, log, proofs, signals, roots=None, tags=None):
+        """EXT: public.RLN.relay_step over RLNProofV3 (ffi_rln_v3_relay_step)"""
+        return _relay_step(lib().ffi_rln_v3_relay_step, self, log, proofs, signals, roots, tags)
 
     def init_tree_with_leaves(self, leaves):
         v, _k = _vec_cfr(list(leaves))
