@@ -299,6 +299,13 @@ int rlnamd_prover_fetch_h(rlnamd_prover* p, size_t index, uint8_t* out_le);
  * by member (device and pinned copy) + the witness given with rlnamd_prover_upload_witness.  All zero behind a collect
  * that wipes, and behind rlnamd_prover_wipe after a resident run. */
 int rlnamd_prover_residue(rlnamd_prover* p, uint64_t out[6]);
+/* the same tap for workspace slot `slot` (0 <= slot < rlnamd_prover_slots; anything else is an error), whichever batch
+ * used it last, with the buffers rlnamd_prover_residue does not look at: [0] .. [5] as above for that slot, [6] the inputs
+ * and (r, s) regions of the slot's pinned staging buffer, [7] the slot's pinned hints (rlnamd_prover_submit_hinted; the
+ * first hint of a proof with the proof's public share gives the identity secret), [8] the witness interpreter's stored
+ * values, [9] reserved, 0.  Whole buffers; the partial points staged behind (r, s) are handed out like a proof and not
+ * counted.  Drains the pipeline as rlnamd_prover_residue does.  All zero behind a collect that wipes. */
+int rlnamd_prover_residue_slot(rlnamd_prover* p, int slot, uint64_t out[10]);
 /* ---- partial proofs (generate_partial_zk_proof / finish_zk_proof_with_rs, protocol/proof.rs:783-849;
  * Groth16Partial, partial_proof.rs:108-274).  mode: 0 full proof, 1 partial (inputs hold only identitySecret,
  * userMessageLimit, pathElements, identityPathIndex; other slots zero), 2 finish (full inputs + r, s + the
@@ -331,7 +338,9 @@ int rlnamd_prover_hint_stats(rlnamd_prover* p, uint64_t out[7]);
  * call, safe beside a running batch), rlnamd_prover_submit_hinted() is rlnamd_prover_submit (full proofs) for a batch of
  * at most 64 proofs whose hints (n x hint_words) are at hand: nothing is hashed inside the call and the batch takes the
  * segments whatever its members' chains would have cost.  The device checks every hint as always: hints that do not
- * belong to the inputs cost a run over the whole graph, never a wrong proof. */
+ * belong to the inputs cost a run over the whole graph, never a wrong proof: the run takes the batch's own workspace
+ * slot and ticket, however many other batches are pending and in whatever order they are collected.  The slot's pinned
+ * copy of the hints is overwritten with the batch's inputs (a1 is a hint: see rlnamd_prover_residue_slot). */
 uint32_t rlnamd_prover_hint_words(rlnamd_prover* p);
 int rlnamd_prover_hints_for(rlnamd_prover* p, const uint8_t* inputs_le, uint32_t* hints);
 int rlnamd_prover_submit_hinted(rlnamd_prover* p, size_t n, const uint8_t* inputs_le, const uint8_t* rs_le,

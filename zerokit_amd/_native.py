@@ -146,6 +146,7 @@ SIGNATURES = {
     "rlnamd_prover_fetch_witness": (C.c_int, [P, C.c_size_t, C.c_char_p]),
     "rlnamd_prover_fetch_h": (C.c_int, [P, C.c_size_t, C.c_char_p]),
     "rlnamd_prover_residue": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "rlnamd_prover_residue_slot": (C.c_int, [P, C.c_int, C.POINTER(C.c_uint64)]),
     "rlnamd_prover_collect_partial_cached": (C.c_int, [P, C.c_uint64, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint64),
                                                        C.POINTER(C.c_uint32)]),
     "rlnamd_prover_submit_finish": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64),

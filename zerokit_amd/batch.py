@@ -425,6 +425,16 @@ class BatchProver:
         check(lib().rlnamd_prover_residue(self._h, out))
         return dict(zip(("digits_g1", "digits_g2", "abc", "partial_g1", "partial_g2", "inputs"), (int(v) for v in out)))
 
+    RESIDUE_SLOT = ("digits_g1", "digits_g2", "abc", "partial_g1", "partial_g2", "inputs", "staging", "hints", "v29",
+                    "reserved")
+
+    def residue_slot(self, k):
+        """the same tap for workspace slot k (rlnamd_prover_residue_slot), with the pinned staging buffer, the pinned
+        hints and the interpreter's stored values; an error for k >= n_slots()"""
+        out = (C.c_uint64 * len(self.RESIDUE_SLOT))()
+        check(lib().rlnamd_prover_residue_slot(self._h, k, out))
+        return dict(zip(self.RESIDUE_SLOT, (int(v) for v in out)))
+
     def verify_many(self, proofs, public_inputs, threads=0):
         """n independent verifications on host threads (rlnamd_verify_many); returns a list of bools"""
         n = len(proofs)

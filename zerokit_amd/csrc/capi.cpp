@@ -631,6 +631,12 @@ int rlnamd_prover_residue(rlnamd_prover* p, uint64_t out[6]) {
   p->p->residue(out);
   RLN_CATCH
 }
+int rlnamd_prover_residue_slot(rlnamd_prover* p, int slot, uint64_t out[10]) {
+  RLN_TRY
+  static_assert(Prover::RESIDUE_SLOT_FIELDS == 10, "rln_amd.h states ten counters");
+  p->p->residue_slot(slot, out);
+  RLN_CATCH
+}
 
 int rlnamd_verify(rlnamd_prover* p, const uint8_t proof[128], const uint8_t values_le[160], int* ok) {
   RLN_TRY

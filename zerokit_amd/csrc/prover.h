@@ -258,6 +258,11 @@ class Prover {
   // batch submitted by member (device and pinned copy)]
   static constexpr int RESIDUE_FIELDS = 6;
   void residue(uint64_t out[RESIDUE_FIELDS]);
+  // the same tap for workspace slot `slot` (< slots()), and what residue() does not look at: [0 .. 5] as above, [6] the
+  // inputs | (r, s) regions of the slot's pinned staging buffer, [7] its pinned hints, [8] the interpreter's stored values
+  // on 29-bit limbs, [9] reserved (0).  Whole buffers.  Drains the pipeline, the wipes' stream included.
+  static constexpr int RESIDUE_SLOT_FIELDS = 10;
+  void residue_slot(int slot, uint64_t out[RESIDUE_SLOT_FIELDS]);
   // the device Groth16 verifier of this prover's key (verify.h), made on first use; independent of the proving pipeline
   GpuVerifier& gpu_verifier();
 
@@ -268,6 +273,7 @@ class Prover {
                    const MemberGather* members = nullptr);
   void check_members(const MemberTree& tree, size_t n, const uint64_t* leaf_indices) const;
   void fetch_public_slot(void* slot, size_t n, std::vector<uint8_t>* out_le);
+  void residue_of(void* slot, uint64_t out[RESIDUE_SLOT_FIELDS]);
   struct Impl;
   std::unique_ptr<Impl> d_;
   Zkey zk_;

@@ -30,6 +30,7 @@
 #include "witness_sched.h"
 #include "fin29.h"
 #include "merkle.h"
+#include "ffi_wire.h"   // secure_zero
 
 namespace rlnamd {
 
@@ -42,6 +43,21 @@ const char* const kProverStageNames[PROVER_STAGES] = {"witness", "matvec", "ntt"
 // Everything one in-flight batch owns.  Two slots let batch k+1 run its latency-bound front end (witness
 // interpreter, NTT) and batch k-1 its back end (reduction, finalize) on their own streams while batch k
 // keeps the chip busy with the MSM.
+//
+// What wipe_slot overwrites and Prover::residue_slot counts (field), and what neither touches (why):
+//   digits / digits2                      counted [0] / [1]
+//   abc                                   counted [2]
+//   part1 grp1 sums1 prod tbl affA affB1  counted [3]
+//   part2 grp2 sums2 affB2                counted [4]
+//   inputs rs idx h_idx                   counted [5]  (with Impl::wgiven, the witness of upload_witness)
+//   h_in: inputs | (r, s)                 counted [6]
+//   h_hints                               counted [7]  (a1 = Poseidon(secret, external nullifier, message id) is a hint:
+//                                                       with the proof's public (x, y), y - x a1 is the identity secret)
+//   V29                                   counted [8]
+//   V                                     wiped; tapped column by column through fetch_witness
+//   err coords values comp h_comp h_values h_err   exempt: the results the caller receives
+//   pp_in pp_out h_pp pp_pow, h_in: points         exempt: partial points (and powers of them), handed to the caller like a proof
+//   h_cone                                exempt: entry numbers of the partial-proof cache
 struct Slot {
   DevBuf<uint32_t> err, coords, values;
   DevBuf<uint8_t> comp;
@@ -62,6 +78,7 @@ struct Slot {
   uint32_t* h_cone = nullptr;   // pinned: partial-cache entry of every proof of the batch (read by k_cone_save / _restore)
   uint32_t* h_hints = nullptr;  // pinned: the hints of a batch interpreted as segments (HINT_PROOFS x n_hints x 8 words)
   bool hinted = false;          // ... and this batch was; cleared once its hints have checked (Prover::collect)
+  bool hints_staged = false;    // h_hints holds a batch's hints: until wipe_slot clears them
   hipEvent_t evU = nullptr;     // H2D of this slot's inputs done
   hipEvent_t evE = nullptr;     // small batches: the walk of the h-independent G1 rows done
   uint64_t ticket = 0;          // submit() ticket of the batch the slot holds (0: resident-input run)
@@ -268,6 +285,7 @@ struct Prover::Impl {
   uint32_t n_cut = 0, n_hints = 0;
   uint64_t hinted_batches = 0, hint_fallbacks = 0;
   bool no_hints_now = false;     // set around the re-run of a batch whose hints did not check
+  int rerun_slot = -1;           // ... with the slot the batch has: the re-run takes it again, not the next of the ring
   HintChains hints;              // their hashing on the host, with the cache of remembered chains (prover_plan.h)
   // ---- the partial-proof cache and the cone program (prover.h: collect_partial_cached / submit_finish)
   WitLanes cone;                 // the unknown cone of evaluate_partial, scheduled like the full graph (witness_sched.h: wl_cone)
@@ -353,6 +371,11 @@ struct Prover::Impl {
       memset(S.h_in, 0, n * (size_t)NI * 32);
       memset(S.h_in + B * (size_t)NI * 32, 0, n * 64);
       __asm__ __volatile__("" : : "r"(S.h_in) : "memory");
+      if (S.hints_staged) {   // the values between the chained hashes: the first of them gives the secret away (see Slot)
+        memset(S.h_hints, 0, (size_t)HINT_PROOFS * 64 * 32);
+        __asm__ __volatile__("" : : "r"(S.h_hints) : "memory");
+        S.hints_staged = false;
+      }
       zero(S.inputs.p, n * (size_t)NI * 32);
       zero(S.rs.p, n * 64);
       if (S.members) {   // the leaf indices of a batch submitted by member
@@ -363,9 +386,10 @@ struct Prover::Impl {
       }
     }
     const uint32_t pg = div_up(n, 64);
+    const size_t np = std::min<size_t>(B, (n + 63) / 64 * 64);   // the padding lanes of the last wave wrote their columns too
     hipLaunchKernelGGL(k_wipe_cols, dim3(pg, nstore29), dim3(64), 0, sW, S.V.p, slot2node.p, nstore29, (uint32_t)B, (uint32_t)n);
-    hipLaunchKernelGGL(k_wipe_v29, dim3(div_up(3 * n, 64), nstore29 + 1), dim3(64), 0, sW, S.V29.p, nstore29 + 1, (uint32_t)B,
-                       (uint32_t)n);
+    hipLaunchKernelGGL(k_wipe_v29, dim3(div_up(3 * np, 64), nstore29 + 1), dim3(64), 0, sW, S.V29.p, nstore29 + 1, (uint32_t)B,
+                       (uint32_t)np);
     // an externally supplied witness (upload_witness) was stored at the signal rows
     hipLaunchKernelGGL(k_wipe_cols, dim3(pg, NS), dim3(64), 0, sW, S.V.p, sig2node.p, NS, (uint32_t)B, (uint32_t)n);
     // The signed window digits are a lossless re-encoding of every witness scalar (the identity secret among them) and
@@ -377,7 +401,6 @@ struct Prover::Impl {
                          (uint32_t)stride16, (uint32_t)std::min(n16, stride16));
     };
     const size_t dB = S.dB ? S.dB : B;
-    const size_t np = std::min<size_t>(B, (n + 63) / 64 * 64);   // the padding lanes of the last wave wrote their columns too
     for (DevBuf<int16_t>* d : {&S.digits, &S.digits2}) {
       if (!d->p) continue;
       const size_t drows = d->n / B;
@@ -869,6 +892,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     RLN_HIP(hipMemsetAsync(S.rs.p, 0, S.rs.bytes(), s));
     RLN_HIP(hipMemsetAsync(S.pp_in.p, 0, S.pp_in.bytes(), s));
     RLN_HIP(hipHostMalloc((void**)&S.h_in, B * ((size_t)D.NI * 32 + 64 + 320), hipHostMallocDefault));
+    memset(S.h_in, 0, B * ((size_t)D.NI * 32 + 64 + 320));   // (residue_slot reads whole buffers)
     RLN_HIP(hipHostMalloc((void**)&S.h_cone, B * 4, hipHostMallocDefault));
     static_assert(sizeof(uint64_t) == 8, "two leaf indices per 16-byte word");
     if (B % 2) throw Error("internal: the workspace capacity is a multiple of 64");   // idx / h_idx are staged and counted in 16-byte words
@@ -879,6 +903,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     RLN_HIP(hipEventCreateWithFlags(&S.evT, hipEventDisableTiming));
     RLN_HIP(hipEventCreateWithFlags(&S.evG, hipEventDisableTiming));
     RLN_HIP(hipHostMalloc((void**)&S.h_hints, (size_t)HINT_PROOFS * 64 * 32, hipHostMallocDefault));
+    memset(S.h_hints, 0, (size_t)HINT_PROOFS * 64 * 32);
     RLN_HIP(hipEventCreateWithFlags(&S.evU, hipEventDisableTiming));
     RLN_HIP(hipEventCreateWithFlags(&S.evE, hipEventDisableTiming));
     RLN_HIP(hipHostMalloc((void**)&S.h_pp, B * 320, hipHostMallocDefault));
@@ -899,6 +924,11 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     for (auto& e : S.t) RLN_HIP(hipEventCreate(&e));
     RLN_HIP(hipMemsetAsync(S.digits.p, 0, S.digits.bytes(), s));
     RLN_HIP(hipMemsetAsync(S.digits2.p, 0, S.digits2.bytes(), s));
+    // residue_slot counts whole buffers, and hipMalloc may hand out memory that an earlier prover of the process freed:
+    // whatever it counts starts at zero
+    auto clear = [&](auto& buf) { if (buf.p) RLN_HIP(hipMemsetAsync(buf.p, 0, buf.bytes(), s)); };
+    clear(S.V29); clear(S.abc); clear(S.part1); clear(S.part2); clear(S.grp1); clear(S.grp2); clear(S.sums1); clear(S.sums2);
+    clear(S.prod); clear(S.tbl); clear(S.affA); clear(S.affB1); clear(S.affB2);
   }
   RLN_HIP(hipStreamSynchronize(s));
   g_init_ms[3] = ms_since(t_ctor) - g_init_ms[0] - g_init_ms[1] - g_init_ms[2];
@@ -930,7 +960,10 @@ Prover::~Prover() {
     if (S.h_idx) (void)hipHostFree(S.h_idx);
     if (S.evT) (void)hipEventDestroy(S.evT);
     if (S.evG) (void)hipEventDestroy(S.evG);
-    if (S.h_hints) (void)hipHostFree(S.h_hints);
+    if (S.h_hints) {   // (a slot whose batch was never collected, or whose wipe threw above)
+      secure_zero(S.h_hints, (size_t)HINT_PROOFS * 64 * 32);
+      (void)hipHostFree(S.h_hints);
+    }
     if (S.evU) (void)hipEventDestroy(S.evU);
     if (S.evE) (void)hipEventDestroy(S.evE);
     if (S.h_comp) (void)hipHostFree(S.h_comp);
@@ -1116,6 +1149,7 @@ void Prover::hints_for(const uint8_t* inputs, uint32_t* hints) const {
   Fr hv[64];
   D.hints.hints(inputs, hv);
   for (uint32_t j = 0; j < D.n_hints; j++) hv[j].to_canonical(hints + (size_t)j * 8);
+  secure_zero(hv, sizeof hv);
 }
 
 uint64_t Prover::submit_hinted(size_t n, const uint8_t* inputs, const uint8_t* rs, const uint32_t* hints) {
@@ -1240,17 +1274,32 @@ uint64_t Prover::settle_hints(uint64_t ticket) {
   for (size_t i = 0; i < S.n; i++) bad = bad || (S.h_err[i] & WERR_HINT) != 0;
   if (!bad) return ticket;
   D.hint_fallbacks++;
+  // The re-run takes the batch's OWN slot: the next slot of the ring may hold another ticket's results (with slots() batches
+  // pending it always does).  Its inputs, (r, s) and points leave the slot's staging buffer for a host copy first, so that
+  // the failed run can be wiped as any other batch -- staging, hints and, by the strides IT used, everything on the device
+  // -- before the re-run stages them again; enqueue waits for that wipe (free_event) as a slot's next user does.  What the
+  // re-run leaves is wiped by its own collect.  The ticket stays the caller's.
+  const size_t n = S.n, in_bytes = n * (size_t)D.NI * 32;
+  const int mode = S.mode;
+  const bool finish = mode == PROVE_FINISH;
+  std::vector<uint8_t> keep(in_bytes + n * 64 + (finish ? n * 320 : 0));
+  struct ZeroOnExit wipe_keep{keep};
+  memcpy(keep.data(), S.h_in, in_bytes);
+  memcpy(keep.data() + in_bytes, S.h_in + B_ * (size_t)D.NI * 32, n * 64);
+  if (finish) memcpy(keep.data() + in_bytes + n * 64, S.h_in + B_ * ((size_t)D.NI * 32 + 64), n * 320);
+  if (!S.wiped) D.wipe_slot(S, false);
   D.no_hints_now = true;
+  D.rerun_slot = (int)(Sp - D.slot);
   uint64_t again = 0;
   try {
-    const uint8_t* in = S.h_in;
-    again = enqueue(S.n, S.mode, in, in + B_ * (size_t)D.NI * 32, S.mode == PROVE_FINISH ? in + B_ * ((size_t)D.NI * 32 + 64) : nullptr, nullptr);
+    again = enqueue(n, mode, keep.data(), keep.data() + in_bytes, finish ? keep.data() + in_bytes + n * 64 : nullptr, nullptr);
   } catch (...) {
     D.no_hints_now = false;
+    D.rerun_slot = -1;
     throw;
   }
   D.no_hints_now = false;
-  if (!S.wiped) D.wipe_slot(S, false);
+  D.rerun_slot = -1;
   return again;
 }
 
@@ -1307,7 +1356,7 @@ void Prover::wipe(uint64_t ticket) {
 
 void Prover::collect_public(uint64_t ticket, size_t n, std::vector<uint8_t>* out_le) {
   Impl& D = *d_;
-  if (ticket != settle_hints(ticket)) throw Error("collect_public: the batch was run again (collect it first)");
+  ticket = settle_hints(ticket);
   for (int k = 0; k < D.nslot; k++)
     if (D.slot[k].used && D.slot[k].ticket == ticket && ticket != 0) {
       if (n > D.slot[k].n) throw Error("collect: more proofs requested than the batch holds");
@@ -1460,7 +1509,9 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
              fused = sh.fused, tiny = sh.tiny, tiny_partial = sh.tiny_partial, walk_lp = sh.walk_lp;
   const Impl::Plan &P1 = D.plan1[sh.plan1][mode], &P2 = D.plan2[sh.plan2][mode];
   const uint32_t PB = sh.PB, dB = sh.dB;
-  Slot& S = D.slot[D.cur];
+  // the next slot of the ring -- or, for the re-run of a batch whose hints did not check, the slot the batch has (settle_hints)
+  const bool in_place = D.rerun_slot >= 0;
+  Slot& S = D.slot[in_place ? D.rerun_slot : D.cur];
   S.dB = dB;
   S.PB = PB;
   S.nch1 = P1.nchunks;
@@ -1482,8 +1533,8 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   const uint32_t* rs_p = streamed ? S.rs.p : D.rs.p;
   const uint32_t* pp_p = (streamed && h_pp320) ? S.pp_in.p : D.pp_in.p;
   S.mode = mode;
-  S.ticket = streamed ? ++D.tickets : 0;
-  D.cur = (D.cur + 1) % D.nslot;
+  if (!in_place) S.ticket = streamed ? ++D.tickets : 0;   // (a re-run answers to the ticket its caller holds)
+  if (!in_place) D.cur = (D.cur + 1) % D.nslot;
   // Front end in two pipeline stages on their own streams: A1 = graph interpreter (16 latency-bound waves per 1024
   // proofs, ~28 ms), A2 = mat-vec + NTTs + quotient (throughput kernels squeezed in beside the MSM, ~25 ms contended).
   // Chained on one stream they were the critical path (54 ms against 49 ms of MSM).
@@ -1583,6 +1634,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   if (cone) memcpy(S.h_cone, cone_entries.data(), n * sizeof(uint32_t));   // (the slot's previous batch has finished: see `streamed` above)
   S.hinted = hinted;
   if (hinted) {
+    S.hints_staged = true;
     // a proof's hints: one dependent chain of depth + 2 hashes; the chains of the batch's proofs are independent of each
     // other: the calling thread and up to hint_threads - 1 helpers take them in turn
     if (pre_hints)
@@ -1592,6 +1644,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
         Fr hv[64];
         D.hints.hints(h_inputs + i * (size_t)D.NI * 32, hv, probes.empty() ? nullptr : &probes[i]);
         for (uint32_t j = 0; j < D.n_hints; j++) hv[j].to_canonical(S.h_hints + (i * D.n_hints + j) * 8);
+        secure_zero(hv, sizeof hv);
       });
     if (T.hint_fault > 0 && (uint32_t)T.hint_fault <= D.n_hints) S.h_hints[(size_t)(T.hint_fault - 1) * 8] ^= 1u;   // test hook
     D.hinted_batches++;
@@ -2091,8 +2144,24 @@ void Prover::residue(uint64_t out[RESIDUE_FIELDS]) {
   Impl& D = *d_;
   sync();
   if (!D.last) throw Error("no run to read from");
-  Slot& S = *D.last;
-  DevBuf<unsigned long long> cnt(RESIDUE_FIELDS);
+  uint64_t all[RESIDUE_SLOT_FIELDS];
+  residue_of(D.last, all);
+  for (int k = 0; k < RESIDUE_FIELDS; k++) out[k] = all[k];
+}
+
+void Prover::residue_slot(int slot, uint64_t out[RESIDUE_SLOT_FIELDS]) {
+  Impl& D = *d_;
+  if (slot < 0 || slot >= D.nslot) throw Error("residue_slot: no such workspace slot");
+  sync();
+  residue_of(&D.slot[slot], out);
+}
+
+// the pipeline has been drained (sync): the wipes' stream too
+void Prover::residue_of(void* slot, uint64_t out[RESIDUE_SLOT_FIELDS]) {
+  Impl& D = *d_;
+  Slot& S = *(Slot*)slot;
+  constexpr int NDEV = RESIDUE_SLOT_FIELDS;
+  DevBuf<unsigned long long> cnt(NDEV);
   RLN_HIP(hipMemsetAsync(cnt.p, 0, cnt.bytes(), D.sC));
   auto count = [&](int k, const void* p, size_t bytes) {
     if (p && bytes >= 16)
@@ -2112,12 +2181,24 @@ void Prover::residue(uint64_t out[RESIDUE_FIELDS]) {
   count(5, S.rs.p, S.rs.bytes());
   count(5, D.wgiven.p, D.wgiven.bytes());   // a supplied witness (upload_witness): wiped with the resident inputs
   count(5, S.idx.p, S.idx.bytes());   // the leaf indices of a batch submitted by member, device and (below) pinned copy
+  count(8, S.V29.p, S.V29.bytes());
   RLN_HIP(hipGetLastError());
-  unsigned long long h[RESIDUE_FIELDS];
+  unsigned long long h[NDEV];
   RLN_HIP(hipMemcpyAsync(h, cnt.p, sizeof h, hipMemcpyDeviceToHost, D.sC));
   RLN_HIP(hipStreamSynchronize(D.sC));
-  for (int k = 0; k < RESIDUE_FIELDS; k++) out[k] = h[k];
+  for (int k = 0; k < NDEV; k++) out[k] = h[k];
   for (size_t i = 0; i + 1 < B_; i += 2) out[5] += (S.h_idx[i] | S.h_idx[i + 1]) ? 1 : 0;
+  // the pinned buffers, read by the host: the inputs | (r, s) regions of the staging (not the partial points behind them)
+  // and the hints, whole
+  auto host16 = [](const void* p, size_t bytes) {
+    const uint64_t* w = (const uint64_t*)p;
+    uint64_t nz = 0;
+    for (size_t i = 0; i + 1 < bytes / 8; i += 2) nz += (w[i] | w[i + 1]) ? 1 : 0;
+    return nz;
+  };
+  out[6] = host16(S.h_in, B_ * ((size_t)D.NI * 32 + 64));
+  out[7] = host16(S.h_hints, (size_t)HINT_PROOFS * 64 * 32);
+  out[9] = 0;
 }
 
 }  // namespace rlnamd
