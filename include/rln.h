@@ -145,8 +145,10 @@ CBoolResult_t ffi_verify_rln_signals_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t
  * 1 024: the smallest measured n, at which this call wins by about 0.1 ms of 13, profiles/relay_step.md) the call is ONE rlnamd_relay_step on
  * the device (rln_amd.h), over one relay per (object, log) made on first use with the process's hasher: the signals are
  * hashed beside the pairing kernels and the shares never return to the host.  Then it asks the log for room for n *
- * max_out shares before it starts.  Smaller calls, an object with "verify_optimistic": true (that setting keeps its
- * meaning) and calls with more than RLNAMD_RELAY_ROOTS_MAX roots take the composition of the existing calls.  A log
+ * max_out shares before it starts.  An object with "verify_optimistic": true makes those relays with
+ * RLNAMD_RELAY_OPTIMISTIC (and RLNAMD_RELAY_OPTIMISTIC_TEAMS for "verify_optimistic_teams"; rln_amd.h:
+ * rlnamd_relay_new_ex), under its "verify_optimistic_cooldown".  Smaller calls and calls with more than
+ * RLNAMD_RELAY_ROOTS_MAX roots take the composition of the existing calls.  A log
  * must not be freed while a step on it is running. */
 CBoolResult_t ffi_relay_step(FFI_RLN_t* const* rln, struct rlnamd_nullifier_log* log, FFI_RLNProof_t* const* proofs, size_t n,
                              const Vec_uint8_t* signals, const Vec_CFr_t* roots /* NULL: the object's current root */,

@@ -452,6 +452,22 @@ int rlnamd_verify_gpu_aggregate(rlnamd_prover* p, size_t n, const uint8_t* proof
 int rlnamd_verify_gpu_aggregate_ex(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
                                    size_t n_values, const uint8_t* scalars16, int lanes, uint8_t gt384[384],
                                    uint8_t* rejected);
+/* EXT: the scalars of a combined check derived from one 32-byte seed per chunk, as the relay step's combined check
+ * derives them on the device (csrc/verify_agg_scalars.h, one permutation per 8 proofs).  Host only; out16 = n x 16
+ * bytes.  Scalar i of chunk `chunk` is bytes [16 j, 16 j + 16) of S, little-endian, with g = i / 8, j = i % 8 and
+ *   S = Keccak-f[1600]( seed[0..32) | "RLNAMD-AGG-SCAL1" (16 ASCII bytes) | chunk as 8 bytes LE | g as 8 bytes LE
+ *                       | 0x01 | 70 zero bytes | 0x80 | 64 zero bytes )
+ * that is, the 200-byte state is the one rate block (136 bytes) of the 64-byte message under the original Keccak pad
+ * (the pad of hash_to_field) over a zero capacity, permuted ONCE; the state's bytes are its 25 lanes in order, each
+ * little-endian.  A scalar that comes out 0 is replaced by 1.  Only bytes [0, 128) of S are used. */
+int rlnamd_verify_agg_scalars(const uint8_t seed[32], uint64_t chunk, size_t n, uint8_t* out16);
+/* test / diagnosis: rlnamd_verify_gpu_aggregate_ex, except that the scalars of chunk c of the call (c = 0, 1, ...; chunks
+ * of 65 536 proofs for lanes = 1, of 8 192 for lanes = 8) are derived ON THE DEVICE from (seed32, c): the value equals
+ * rlnamd_verify_gpu_aggregate_ex over rlnamd_verify_agg_scalars' output for each chunk.  A seed known to the sender of
+ * the proofs voids the bound, as supplied scalars do. */
+int rlnamd_verify_gpu_aggregate_seeded(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                       size_t n_values, const uint8_t seed32[32], int lanes, uint8_t gt384[384],
+                                       uint8_t* rejected);
 /* its host-only twin from pairing.h alone (no GPU, none of the device form's folding): the product of the exact
  * per-proof pairing products raised to the scalars.  scalars16 must be given.  The value the device is judged by. */
 int rlnamd_verify_aggregate_with_zkey(const uint8_t* zkey, size_t zkey_len, size_t n, const uint8_t* proofs,
@@ -499,7 +515,31 @@ int rlnamd_proof_decompress(const uint8_t proof[128], uint8_t coords_le[256]);
  * the step returns, on every error path too.
  * info: [0] steps, [1] verifier chunks, [2] messages, [3] messages with verdict OK, [4] shares recorded, [5] non-zero
  * 16-byte words left in the relay's result buffers, device and pinned (0 expected), [6] messages hashed on the host
- * route, [7] reserved 0.  The log's info[4] goes up by one per chunk that records a share, its info[6] stays 0. */
+ * route, [7] reserved 0.  The log's info[4] goes up by one per chunk that records a share, its info[6] stays 0.
+ *
+ * rlnamd_relay_new_ex: the same relay with flags; rlnamd_relay_new is flags = 0.
+ *   RLNAMD_RELAY_OPTIMISTIC        every chunk that would run a lane per proof (more than 1 024 messages, or lanes = 1)
+ *                                  takes the combined check of rlnamd_verify_many_gpu_optimistic instead of the exact
+ *                                  pass: the per-proof checks, then ONE pairing check for the chunk
+ *   RLNAMD_RELAY_OPTIMISTIC_TEAMS  the chunks in team form too (the rule of rlnamd_verify_many_gpu_optimistic_ex);
+ *                                  alone it is an error, and so is any other bit
+ * The flags are judged before the pointers, each refusal with its own text.  A step of such a relay returns what the
+ * exact relay returns for the same inputs and log, byte for byte -- verdicts, statuses, secrets, first tags and the
+ * log's records -- except that a chunk holding an invalid proof is accepted whole with probability about 2^-128.
+ * The scalars are not drawn on the host: per chunk the step draws ONE seed of 32 bytes (getrandom) after the chunk's
+ * proofs and values are in its staging buffer, sends it up with them, and a kernel derives the n scalars on the device
+ * (rlnamd_verify_agg_scalars states the derivation; the chunk counter is the verifier's count of seeds drawn).  The
+ * seed is uniform and unknown to the sender when the proofs are fixed, and each scalar is 128 bits of a keyed sponge's
+ * output, so the bound holds up to the advantage of telling that output from uniform.
+ * A chunk the combined check accepts runs no exact pass.  One it rejects runs the exact kernels of the same shape over
+ * the proofs and values already on the device (no second copy in), which names the bad proofs, and starts the
+ * verifier's cool-down: the next `cooldown` chunks of optimistic relays and calls (one setting and one set of
+ * counters per prover: rlnamd_verify_gpu_set_cooldown, rlnamd_verify_gpu_optimistic_stats, rlnamd_verify_gpu_passes)
+ * take the exact pass as a flags = 0 relay does.  A combined chunk waits twice on the host -- for the verifier's
+ * stream before the host's share of the pairing check, then for the log's stream -- where an exact chunk waits once;
+ * the hashing and the log's copy in run under the first wait.  rlnamd_relay_info is unchanged ([7] stays 0). */
+#define RLNAMD_RELAY_OPTIMISTIC 1
+#define RLNAMD_RELAY_OPTIMISTIC_TEAMS 2
 typedef struct rlnamd_relay rlnamd_relay;
 #define RLNAMD_RELAY_OK 0
 #define RLNAMD_RELAY_BAD_PROOF 1    /* the verifier's ok == 0, or a selector element that is neither 0 nor 1 */
@@ -508,6 +548,8 @@ typedef struct rlnamd_relay rlnamd_relay;
 #define RLNAMD_RELAY_ROOTS_MAX 64
 int rlnamd_relay_new(rlnamd_prover* p, rlnamd_nullifier_log* log, rlnamd_hasher* h /* or NULL */, int lanes /* 0 | 1 | 8 */,
                      rlnamd_relay** out);
+int rlnamd_relay_new_ex(rlnamd_prover* p, rlnamd_nullifier_log* log, rlnamd_hasher* h /* or NULL */, int lanes /* 0 | 1 | 8 */,
+                        int flags /* RLNAMD_RELAY_OPTIMISTIC [| RLNAMD_RELAY_OPTIMISTIC_TEAMS] */, rlnamd_relay** out);
 void rlnamd_relay_free(rlnamd_relay* r);
 int rlnamd_relay_step(rlnamd_relay* r, size_t n, const uint8_t* proofs /* n*128 */,
                       const uint8_t* values_le /* n*n_values*32, verifier order */, size_t n_values,

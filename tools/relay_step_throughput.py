@@ -23,6 +23,11 @@ prints ONE JSON line.  Torch-free (ctypes and numpy).
             proof, which a caller of the three-call loop pays on every call) are made outside the timed region
             (sizes up to 8 192: every proof object is parsed and subgroup-checked on the host when it is made)
 
+  --optimistic   another measurement instead (optimistic_main): the exact relay against the relay made with
+            RLNAMD_RELAY_OPTIMISTIC | RLNAMD_RELAY_OPTIMISTIC_TEAMS, alternated, all-valid and with one forged proof per
+            call under cool-down 0; with --ffi the drop-in entry of an optimistic object on its two routes; and the
+            seeded aggregate against the one that draws its scalars on the host (profiles/relay_step_optimistic.md)
+
 "relay_gpu_min" is the smallest measured n at which the step's median is below the composition's minimum, for both
 signal lengths (the rule profiles/verify_gpu_lanes.md used for verify_team_max); null if there is none.
 """
@@ -155,14 +160,164 @@ def ffi_rows(lib, sizes, calls, proofs, values, signals, signal_len, tmp):
     return rows
 
 
+def summary(t):
+    return dict(median=round(statistics.median(t), 4), min=round(min(t), 4), max=round(max(t), 4))
+
+
+def optimistic_ffi_rows(lib, sizes, calls, proofs, values, signals, signal_len, tmp):
+    """ffi_relay_step of an object with "verify_optimistic" (and "verify_optimistic_teams", cool-down 0) on the device
+    route against the same call on an object whose "relay_gpu_min" keeps it on the composition, which is what such an
+    object ran at every n before its relays could take the combined check"""
+    from zerokit_amd._native import CFr, VecCFr, VecU8
+    from zerokit_amd.batch import NullifierLog
+    from zerokit_amd.public import RLN, RLNProof, _err
+    objs = []
+    for name, gpu_min in (("device", 0), ("composition", 1000000000)):
+        cfg = os.path.join(tmp, "relay_opt_%s.json" % name)
+        with open(cfg, "w") as f:
+            f.write(json.dumps({"verify_optimistic": True, "verify_optimistic_teams": True, "verify_optimistic_cooldown": 0,
+                                "relay_gpu_min": gpu_min}))
+        objs.append(RLN(20, tree_config=cfg))
+    logs = NullifierLog(CAPACITY, SEED), NullifierLog(CAPACITY, SEED)
+    n_max = max(sizes)
+    v = np.frombuffer(values, dtype=np.uint8).reshape(-1, 5, 32)
+    pobjs = [RLNProof.from_bytes_le(b"\0" + proofs[128 * i:128 * i + 128] + b"\0" + v[i, (1, 4, 3, 0, 2), :].tobytes())
+             for i in range(n_max)]
+    sig = np.frombuffer(signals, dtype=np.uint8).reshape(-1, signal_len)
+    sig_bufs = [(C.c_uint8 * signal_len).from_buffer_copy(sig[i].tobytes()) for i in range(n_max)]
+    rows = []
+    for n in sizes:
+        hs = (C.c_void_p * n)(*[p._h.value for p in pobjs[:n]])
+        vecs = (VecU8 * n)(*[VecU8(C.cast(b, C.POINTER(C.c_uint8)), signal_len, signal_len) for b in sig_bufs[:n]])
+        any_root = VecCFr(None, 0, 0)
+        tags = (C.c_uint64 * n)(*range(n))
+        out = [(C.create_string_buffer(n), C.create_string_buffer(n), (CFr * n)(), (C.c_uint64 * n)()) for _ in range(2)]
+        ms = ([], [])
+        for k in range(WARMUP + calls):
+            for log in logs:
+                log.clear()
+            for j in (0, 1):
+                t0 = time.perf_counter()
+                res = lib.ffi_relay_step(C.byref(objs[j]._h), logs[j]._h, hs, n, vecs, C.byref(any_root), tags, *out[j])
+                t1 = time.perf_counter()
+                if not res.ok:
+                    raise SystemExit("ffi_relay_step failed: " + _err(res.err))
+                if k >= WARMUP:
+                    ms[j].append((t1 - t0) * 1e3)
+            if any(bytes(x) != bytes(y) for x, y in zip(out[0][:3], out[1][:3])) or list(out[0][3]) != list(out[1][3]):
+                raise SystemExit("the two routes of ffi_relay_step differ: n %d, call %d" % (n, k))
+        rows.append(dict(n=n, device_ms=summary(ms[0]), composition_ms=summary(ms[1]),
+                         device_stats=objs[0].verify_stats(), composition_stats=objs[1].verify_stats()))
+    for log in logs:
+        log.close()
+    return rows
+
+
+def optimistic_main(a):
+    """--optimistic: the exact relay (flags 0) and the optimistic relay (both flags) take the same call alternately, each
+    on a log of its own, emptied before every call; all-valid rows, then the same rows with ONE forged proof (row 1's
+    points under row 0's values, in the middle of the call) under cool-down 0, so that every call of the optimistic
+    relay pays a combined check AND the exact pass.  Then the drop-in entry (--ffi), and the seeded aggregate against
+    the one that draws n scalars on the host, at the largest size."""
+    from zerokit_amd import lib as load
+    from zerokit_amd._native import check
+    from zerokit_amd.batch import BatchProver, Hasher, NullifierLog, Relay
+    lib = load()
+    sizes = [int(s) for s in a.sizes.split(",")]
+    signal_len = 32
+    prover = BatchProver(max_batch=PROVE_CHUNK)
+    prover.verify_set_cooldown(0)
+    hasher = Hasher()
+    logs = NullifierLog(CAPACITY, SEED), NullifierLog(CAPACITY, SEED)
+    relays = Relay(prover, logs[0], hasher, 0), Relay(prover, logs[1], hasher, 0, optimistic=True, team_checks=True)
+    rnd = np.random.default_rng(20261020)
+    proofs, values, signals, offsets = make_rows(prover, hasher, max(sizes), signal_len, rnd)
+    rows = []
+    for forged in (False, True):
+        for n in sizes:
+            pr, va, sg = bytearray(proofs[:128 * n]), values[:160 * n], signals[:signal_len * n]
+            if forged:
+                at = n // 2
+                pr[128 * at:128 * at + 128] = proofs[128:256]
+                va = va[:160 * at] + values[:160] + va[160 * at + 160:]
+                sg = sg[:signal_len * at] + signals[:signal_len] + sg[signal_len * at + signal_len:]
+            pr = bytes(pr)
+            off_c = np.ascontiguousarray(offsets[:n + 1]).ctypes.data_as(U64P)
+            tags = np.arange(n, dtype=np.uint64)
+            outs = [(C.create_string_buffer(n), C.create_string_buffer(n), C.create_string_buffer(32 * n), np.zeros(n, dtype=np.uint64))
+                    for _ in range(2)]
+            ms = ([], [])
+            s0, p0 = prover.verify_optimistic_stats(), prover.verify_gpu_passes()
+            for call in range(WARMUP + a.calls):
+                for log in logs:
+                    log.clear()
+                for j in (0, 1):
+                    o = outs[j]
+                    t0 = time.perf_counter()
+                    check(lib.rlnamd_relay_step(relays[j]._h, n, pr, va, 5, sg, len(sg), off_c, None, None, 0,
+                                                tags.ctypes.data_as(U64P), o[0], o[1], o[2], o[3].ctypes.data_as(U64P)))
+                    t1 = time.perf_counter()
+                    if call >= WARMUP:
+                        ms[j].append((t1 - t0) * 1e3)
+                if any(x.raw != y.raw for x, y in zip(outs[0][:3], outs[1][:3])) or not np.array_equal(outs[0][3], outs[1][3]):
+                    raise SystemExit("the exact and the optimistic step differ: n %d, call %d" % (n, call))
+                if logs[0].info()[1] != logs[1].info()[1] or logs[0].info()[3] != logs[1].info()[3]:
+                    raise SystemExit("the two logs differ: n %d, call %d" % (n, call))
+            s1, p1 = prover.verify_optimistic_stats(), prover.verify_gpu_passes()
+            rows.append(dict(n=n, forged=int(forged), bad_proofs=int(outs[0][0].raw.count(b"\1")), exact_ms=summary(ms[0]),
+                             optimistic_ms=summary(ms[1]),
+                             stats={k: s1[k] - s0[k] for k in ("combined", "accepted", "fell_back", "combined_team")},
+                             passes=[p1[0] - p0[0], p1[1] - p0[1]]))
+            print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+    out = dict(tool="relay_step_throughput --optimistic", calls=a.calls, warmup=WARMUP, capacity=CAPACITY, rows=rows)
+    # the scalars: derived on the device from a seed, against n x 16 bytes drawn on the calling thread and copied in
+    n = max(sizes)
+    gt, rej = C.create_string_buffer(384), C.create_string_buffer(n)
+    seed = bytes(range(32))
+    ms = dict(seeded=[], drawn=[], getrandom=[])
+    for call in range(WARMUP + a.calls):
+        t0 = time.perf_counter()
+        check(lib.rlnamd_verify_gpu_aggregate_seeded(prover._h, n, proofs[:128 * n], values[:160 * n], 5, seed, 1, gt, rej))
+        t1 = time.perf_counter()
+        check(lib.rlnamd_verify_gpu_aggregate_ex(prover._h, n, proofs[:128 * n], values[:160 * n], 5, None, 1, gt, rej))
+        t2 = time.perf_counter()
+        os.getrandom(16 * n)
+        t3 = time.perf_counter()
+        if call >= WARMUP:
+            ms["seeded"].append((t1 - t0) * 1e3)
+            ms["drawn"].append((t2 - t1) * 1e3)
+            ms["getrandom"].append((t3 - t2) * 1e3)
+    out["scalars"] = dict(n=n, aggregate_seeded_ms=summary(ms["seeded"]), aggregate_drawn_ms=summary(ms["drawn"]),
+                          getrandom_16n_bytes_ms=summary(ms["getrandom"]))
+    for r in relays:
+        r.close()
+    if a.ffi:
+        import tempfile
+        with tempfile.TemporaryDirectory() as tmp:
+            out["ffi_rows"] = optimistic_ffi_rows(lib, [n for n in sizes if n <= 8192], a.calls, proofs, values, signals,
+                                                  signal_len, tmp)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    for log in logs:
+        log.close()
+    hasher.close()
+    prover.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=9)
     ap.add_argument("--sizes", default="1024,8192,65536")
     ap.add_argument("--signal-bytes", default="32,1024")
     ap.add_argument("--ffi", action="store_true")
+    ap.add_argument("--optimistic", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.optimistic:
+        return optimistic_main(a)
     from zerokit_amd import lib as load
     from zerokit_amd._native import check
     from zerokit_amd.batch import BatchProver, Hasher, NullifierLog, Relay

@@ -118,6 +118,7 @@ SIGNATURES = {
     "rlnamd_hasher_hash_to_field": (C.c_int, [P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_char_p]),
     "rlnamd_hasher_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_relay_new": (C.c_int, [P, P, P, C.c_int, PP]),
+    "rlnamd_relay_new_ex": (C.c_int, [P, P, P, C.c_int, C.c_int, PP]),
     "rlnamd_relay_free": (None, [P]),
     "rlnamd_relay_step": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                                     C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64),
@@ -182,6 +183,9 @@ SIGNATURES = {
                                               C.c_char_p]),
     "rlnamd_verify_gpu_aggregate_ex": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_int,
                                                  C.c_char_p, C.c_char_p]),
+    "rlnamd_verify_agg_scalars": (C.c_int, [C.c_char_p, C.c_uint64, C.c_size_t, C.c_char_p]),
+    "rlnamd_verify_gpu_aggregate_seeded": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p,
+                                                     C.c_int, C.c_char_p, C.c_char_p]),
     "rlnamd_verify_aggregate_with_zkey": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p,
                                                     C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rlnamd_verify_many_with_zkey": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t,

@@ -511,6 +511,19 @@ class BatchProver:
 
     verify_gpu_aggregate = verify_aggregate
 
+    def verify_aggregate_seeded(self, proofs, public_inputs, seed: bytes, lanes=1):
+        """test / diagnosis (rlnamd_verify_gpu_aggregate_seeded): verify_aggregate with the scalars of chunk c derived on
+        the device from (seed, c), seed = 32 bytes; equals verify_aggregate over agg_scalars(seed, c, ...) per chunk"""
+        n = len(proofs)
+        if len(seed) != 32:
+            raise RLNError("verify_aggregate_seeded: the seed is 32 bytes")
+        nv = _check_verify_shapes(proofs, public_inputs) if n else self.num_public
+        gt, rej = C.create_string_buffer(384), C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_verify_gpu_aggregate_seeded(self._h, n, b"".join(proofs),
+                                                       b"".join(_b(v) for pi in public_inputs for v in pi), nv, seed,
+                                                       int(lanes), gt, rej))
+        return gt.raw, [bool(x) for x in rej.raw[:n]]
+
     def verify_optimistic_stats(self):
         """rlnamd_verify_gpu_optimistic_stats as a dict"""
         out = (C.c_uint64 * 8)()
@@ -527,6 +540,16 @@ class BatchProver:
         ok = C.c_int()
         check(lib().rlnamd_verify(self._h, proof, b"".join(_b(v) for v in public_inputs), C.byref(ok)))
         return bool(ok.value)
+
+
+def agg_scalars(seed: bytes, chunk: int, n: int):
+    """the n scalars a combined check derives for chunk `chunk` from a 32-byte seed (rlnamd_verify_agg_scalars, host
+    only; include/rln_amd.h states the layout) -> a list of n ints in [1, 2^128)"""
+    if len(seed) != 32:
+        raise RLNError("agg_scalars: the seed is 32 bytes")
+    out = C.create_string_buffer(max(16 * n, 1))
+    check(lib().rlnamd_verify_agg_scalars(seed, chunk, n, out))
+    return [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(n)]
 
 
 def verify_many_with_zkey(zkey: bytes, proofs, public_inputs, threads=0):
@@ -890,15 +913,24 @@ class Relay:
     shares of the accepted ones run through the nullifier log in one call -- exactly what Hasher.hash_to_field,
     BatchProver.verify_many_gpu and one NullifierLog.observe give over the same inputs, with the public values staying
     on the device in between and the hashing running beside the pairing kernels.  It borrows the prover, the log and
-    the hasher (keep them alive); without a hasher every step brings xs."""
+    the hasher (keep them alive); without a hasher every step brings xs.
+
+    optimistic: the chunks that would run a lane per proof take one combined pairing check (verify_many_gpu_optimistic's,
+    the scalars derived on the device from one seed per chunk) and the exact pass only when it rejects; team_checks: the
+    chunks in team form too (needs optimistic).  The same results, up to about 2^-128 per accepted chunk; progress is
+    read from BatchProver.verify_optimistic_stats and verify_gpu_passes."""
     OK, BAD_PROOF, BAD_ROOT, BAD_SIGNAL = range(4)
     ROOTS_MAX = 64
+    OPTIMISTIC, OPTIMISTIC_TEAMS = 1, 2
     INFO = ("steps", "chunks", "messages", "accepted", "shares", "residue_words", "host_hashed", "reserved")
 
-    def __init__(self, prover: "BatchProver", log: "NullifierLog", hasher: "Hasher" = None, lanes=0):
+    def __init__(self, prover: "BatchProver", log: "NullifierLog", hasher: "Hasher" = None, lanes=0, optimistic=False,
+                 team_checks=False):
         self._h = C.c_void_p()
         self._keep = (prover, log, hasher)
-        check(lib().rlnamd_relay_new(prover._h, log._h, hasher._h if hasher is not None else None, lanes, C.byref(self._h)))
+        flags = (self.OPTIMISTIC if optimistic else 0) | (self.OPTIMISTIC_TEAMS if team_checks else 0)
+        check(lib().rlnamd_relay_new_ex(prover._h, log._h, hasher._h if hasher is not None else None, lanes, flags,
+                                        C.byref(self._h)))
 
     def close(self):
         if self._h:

@@ -24,6 +24,7 @@
 #include "prover.h"
 #include "relay.h"
 #include "verify.h"
+#include "verify_agg_scalars.h"
 #include "capi_util.h"
 
 using namespace rlnamd;
@@ -53,9 +54,9 @@ struct rlnamd_relay {
   rlnamd_hasher* hasher;
   GpuVerifier& verifier;
   RelayDev relay;
-  rlnamd_relay(rlnamd_prover* p, rlnamd_nullifier_log* l, rlnamd_hasher* h, int lanes)
+  rlnamd_relay(rlnamd_prover* p, rlnamd_nullifier_log* l, rlnamd_hasher* h, int lanes, int flags)
       : log(l), hasher(h), verifier(p->p->gpu_verifier()),
-        relay(verifier, p->p->graph().max_out, l->log, h ? &h->hasher : nullptr, lanes) {}
+        relay(verifier, p->p->graph().max_out, l->log, h ? &h->hasher : nullptr, lanes, flags) {}
 };
 
 static void verify_common(const Zkey& zk, const uint8_t proof[128], const uint8_t* values_le, int* ok, size_t nv = 5);
@@ -333,11 +334,24 @@ int rlnamd_hasher_info(rlnamd_hasher* h, uint64_t out[8]) {
 }
 
 // -------------------------------------------------------------------------------------------- relay
+static_assert(RLNAMD_RELAY_OPTIMISTIC == RelayDev::OPTIMISTIC && RLNAMD_RELAY_OPTIMISTIC_TEAMS == RelayDev::OPTIMISTIC_TEAMS,
+              "the relay's flags");
 int rlnamd_relay_new(rlnamd_prover* p, rlnamd_nullifier_log* log, rlnamd_hasher* h, int lanes, rlnamd_relay** out) {
   RLN_TRY
   if (!p || !log || !out) throw Error("rlnamd_relay_new: null pointer");
   if (lanes != 0 && lanes != 1 && lanes != 8) throw Error("rlnamd_relay_new: lanes must be 0, 1 or 8");
-  *out = new rlnamd_relay(p, log, h, lanes);
+  *out = new rlnamd_relay(p, log, h, lanes, 0);
+  RLN_CATCH
+}
+int rlnamd_relay_new_ex(rlnamd_prover* p, rlnamd_nullifier_log* log, rlnamd_hasher* h, int lanes, int flags, rlnamd_relay** out) {
+  RLN_TRY
+  // the flags need no object and no device: they are judged first
+  if (const int unknown = flags & ~(RLNAMD_RELAY_OPTIMISTIC | RLNAMD_RELAY_OPTIMISTIC_TEAMS))
+    throw Error("rlnamd_relay_new_ex: unknown flag bits " + std::to_string(unknown) + " in flags " + std::to_string(flags));
+  if (const char* refused = RelayDev::check_flags(flags)) throw Error(std::string("rlnamd_relay_new_ex: ") + refused);
+  if (!p || !log || !out) throw Error("rlnamd_relay_new_ex: null pointer");
+  if (lanes != 0 && lanes != 1 && lanes != 8) throw Error("rlnamd_relay_new_ex: lanes must be 0, 1 or 8");
+  *out = new rlnamd_relay(p, log, h, lanes, flags);
   RLN_CATCH
 }
 void rlnamd_relay_free(rlnamd_relay* r) { delete r; }
@@ -902,6 +916,23 @@ int rlnamd_verify_gpu_aggregate(rlnamd_prover* p, size_t n, const uint8_t* proof
   if (n_values + 1 != p->p->zkey().gamma_abc_g1.size())
     throw Error("MalformedVerifyingKey: rlnamd_verify_gpu_aggregate: n_values is not the key's input count");
   p->p->gpu_verifier().aggregate(n, proofs, values_le, n_values, scalars16, gt384, rejected);
+  RLN_CATCH
+}
+int rlnamd_verify_agg_scalars(const uint8_t seed[32], uint64_t chunk, size_t n, uint8_t* out16) {
+  RLN_TRY
+  if (!seed || (n && !out16)) throw Error("rlnamd_verify_agg_scalars: null argument");
+  aggsc::scalars_host(seed, chunk, n, out16);
+  RLN_CATCH
+}
+int rlnamd_verify_gpu_aggregate_seeded(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,
+                                       size_t n_values, const uint8_t seed32[32], int lanes, uint8_t gt384[384],
+                                       uint8_t* rejected) {
+  RLN_TRY
+  if (lanes != 1 && lanes != 8) throw Error("rlnamd_verify_gpu_aggregate_seeded: lanes must be 1 or 8");
+  if (!seed32) throw Error("rlnamd_verify_gpu_aggregate_seeded: null seed");
+  if (n_values + 1 != p->p->zkey().gamma_abc_g1.size())
+    throw Error("MalformedVerifyingKey: rlnamd_verify_gpu_aggregate_seeded: n_values is not the key's input count");
+  p->p->gpu_verifier().aggregate_seeded(n, proofs, values_le, n_values, seed32, gt384, rejected, lanes);
   RLN_CATCH
 }
 int rlnamd_verify_gpu_aggregate_ex(rlnamd_prover* p, size_t n, const uint8_t* proofs, const uint8_t* values_le,

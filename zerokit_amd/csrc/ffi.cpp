@@ -2575,8 +2575,8 @@ CBoolResult_t ffi_nullifier_log_retire(struct rlnamd_nullifier_log* log, const C
 }
 
 // EXT: one relay step over FFI objects (rln.h).  From relay_gpu_min messages on it is rlnamd_relay_step over packed rows,
-// on one relay per (object, log); below, for an object with "verify_optimistic", and for more roots than a step takes,
-// it is the composition: ffi_verify_rln_signals_batch's stages with the verdict's cause kept, then
+// on one relay per (object, log), which takes the combined check for an object with "verify_optimistic"
+// (rlnamd_relay_new_ex's flags); below, and for more roots than a step takes, it is the composition: ffi_verify_rln_signals_batch's stages with the verdict's cause kept, then
 // ffi_nullifier_log_observe(take = verdict OK).  One function for V1 and V3 callers: the proofs are the same record.
 static bool relay_step_common(void* const* rln, rlnamd_nullifier_log* log, void* const* proofs, size_t n,
                               const Vec_uint8_t* signals, const Vec_CFr_t* roots, const uint64_t* tags, uint8_t* verdict,
@@ -2591,7 +2591,7 @@ static bool relay_step_common(void* const* rln, rlnamd_nullifier_log* log, void*
     if (!signals[i].ptr && signals[i].len) throw Error("hash_to_field: signal " + std::to_string(i) + " is a null pointer with a length");
   }
   const size_t n_roots = roots ? roots->len : 1;
-  if (n < r.relay_gpu_min || r.verify_optimistic || n_roots > RLNAMD_RELAY_ROOTS_MAX) {
+  if (n < r.relay_gpu_min || n_roots > RLNAMD_RELAY_ROOTS_MAX) {
     std::vector<CFr> xs(n);
     hash_signals(signals, n, r.hash_gpu_min, xs.data());
     verify_batch_verdicts(r, (FFI_RLNProof_t* const*)proofs, n, (const CFr_t*)xs.data(), roots, verdict);
@@ -2625,13 +2625,17 @@ static bool relay_step_common(void* const* rln, rlnamd_nullifier_log* log, void*
     entry = slot;
   }
   GpuVerifier& gv = r.prover->gpu_verifier();
+  // "verify_optimistic": the object's relays take the combined check (RelayDev's flags), under the object's cool-down
+  const int flags = !r.verify_optimistic ? 0
+                                         : RelayDev::OPTIMISTIC | (r.verify_optimistic_teams ? RelayDev::OPTIMISTIC_TEAMS : 0);
+  if (flags && r.verify_optimistic_cooldown >= 0) gv.set_cooldown((size_t)r.verify_optimistic_cooldown);
   // rlnamd_relay_step's order: the relay, the hasher, the verifier, the log
   std::lock_guard<std::mutex> lk_relay(entry->mu);
   std::lock_guard<std::mutex> lk_hasher(sh.mu);
   std::lock_guard<std::mutex> lk_verifier(gv.relay_mutex());
   std::lock_guard<std::mutex> lk_log(log->mu);
   if (!sh.h) sh.h.reset(new HasherDev(0, 0));
-  if (!entry->dev) entry->dev.reset(new RelayDev(gv, r.prover->graph().max_out, log->log, sh.h.get(), r.verify_lanes));
+  if (!entry->dev) entry->dev.reset(new RelayDev(gv, r.prover->graph().max_out, log->log, sh.h.get(), r.verify_lanes, flags));
   entry->dev->step(n, bytes.data(), rows.data(), nv, data.data(), (size_t)offsets[n], offsets.data(), nullptr, roots_le, n_roots,
                    tags, verdict, status, (uint8_t*)secrets, first_tag);
   return true;

@@ -193,7 +193,17 @@ struct RelayDev {
   Impl* d = nullptr;
   // lanes: 0 | 1 | 8 as GpuVerifier::verify.  Refuses objects on different devices and a circuit whose public values are
   // neither of the two layouts above.
-  RelayDev(GpuVerifier& verifier, uint64_t max_out, NullifierLogDev& log, HasherDev* hasher, int lanes);
+  // flags: OPTIMISTIC -- a chunk that would run a lane per proof takes the verifier's combined check
+  // (GpuVerifier::relay_enqueue_combined / relay_settle) unless a cool-down lasts; OPTIMISTIC_TEAMS with it -- the team
+  // chunks too, the rule of GpuVerifier::verify_optimistic(team_checks).  Every other chunk is the exact pass.
+  static constexpr int OPTIMISTIC = 1, OPTIMISTIC_TEAMS = 2;
+  // null, or why `flags` is refused (include/rln_amd.h: rlnamd_relay_new_ex)
+  static const char* check_flags(int flags) {
+    if (flags & ~(OPTIMISTIC | OPTIMISTIC_TEAMS)) return "unknown flag bits";
+    if ((flags & OPTIMISTIC_TEAMS) && !(flags & OPTIMISTIC)) return "RLNAMD_RELAY_OPTIMISTIC_TEAMS needs RLNAMD_RELAY_OPTIMISTIC";
+    return nullptr;
+  }
+  RelayDev(GpuVerifier& verifier, uint64_t max_out, NullifierLogDev& log, HasherDev* hasher, int lanes, int flags = 0);
   ~RelayDev();
   RelayDev(const RelayDev&) = delete;
   RelayDev& operator=(const RelayDev&) = delete;

@@ -20,6 +20,13 @@
 // words lanes share are the table entries (agent-scope atomics, as in nullifier_log.hip) and three counters, each
 // written with one atomic a workgroup.
 //
+// A relay made with RelayDev::OPTIMISTIC runs the verifier's combined check instead of its three kernels for the chunks
+// the flags name (relay.h): the chunk is enqueued (GpuVerifier::relay_enqueue_combined), the hasher's and the log's
+// stream get their work, THEN the verifier's stream is waited for and the host finishes the pairing check
+// (relay_settle); a rejected chunk's exact kernels run behind that, over the inputs already resident.  Such a chunk has
+// two stream waits.  An accepted chunk leaves reject flags where the exact pass leaves verdicts, and k_relay_gate is
+// told which it reads.
+//
 // The chunks of a call run one after the other: the wait at the end of a chunk is also what lets the verifier's and the
 // hasher's staging be packed again.  Within a chunk hashing runs beside the pairing kernels.
 //
@@ -53,13 +60,16 @@ namespace {
 __global__ void __launch_bounds__(LOG_LANES) k_relay_gate(Layout L, const uint32_t* __restrict__ vals,
                                                           const uint8_t* __restrict__ ok, const Row32* __restrict__ xs,
                                                           const Row32* __restrict__ roots, uint32_t n_roots, uint32_t n,
-                                                          uint8_t* __restrict__ verdict, ShareCount* __restrict__ counts) {
+                                                          uint32_t ok_is_rejected, uint8_t* __restrict__ verdict,
+                                                          ShareCount* __restrict__ counts) {
   __shared__ Row32 lds_roots[relay::ROOTS_MAX];
   for (uint32_t j = threadIdx.x; j < n_roots * 8; j += LOG_LANES) lds_roots[j >> 3].w[j & 7] = roots[j >> 3].w[j & 7];
   __syncthreads();
   const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
   if (i >= n) return;
-  const relay::Gate g = relay::gate(L, vals + (size_t)8 * L.n_values * i, ok[i], xs[i], lds_roots, n_roots);
+  // behind an accepted combined check ok[] holds the reject flags, and every proof without one is valid
+  const uint8_t valid = ok_is_rejected ? (ok[i] ? 0 : 1) : ok[i];
+  const relay::Gate g = relay::gate(L, vals + (size_t)8 * L.n_values * i, valid, xs[i], lds_roots, n_roots);
   verdict[i] = g.verdict;
   counts[i].v = g.count;
 }
@@ -159,7 +169,7 @@ struct RelayDev::Impl {
   GpuVerifier& V;
   NullifierLogDev& log;
   HasherDev* hasher;
-  int lanes, device = 0;
+  int lanes, flags, device = 0;
   Layout L;
   hipEvent_t ev_verified = nullptr, ev_hashed = nullptr;
   uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -177,7 +187,8 @@ struct RelayDev::Impl {
   DevBuf<ShareCount> counts;
   DevBuf<uint32_t> pos, sums;
 
-  Impl(GpuVerifier& v, NullifierLogDev& l, HasherDev* h, int lanes_) : V(v), log(l), hasher(h), lanes(lanes_) {}
+  Impl(GpuVerifier& v, NullifierLogDev& l, HasherDev* h, int lanes_, int flags_)
+      : V(v), log(l), hasher(h), lanes(lanes_), flags(flags_) {}
 
   static size_t in_bytes(size_t n) { return 32 * relay::ROOTS_MAX + pad16(8 * n) + 32 * n; }
   static size_t result_bytes(size_t n) { return 16 + pad16(42 * n); }
@@ -228,8 +239,9 @@ struct RelayDev::Impl {
              uint8_t* verdict, uint8_t* status, uint8_t* secrets_le, uint64_t* first_tag);
 };
 
-RelayDev::RelayDev(GpuVerifier& verifier, uint64_t max_out, NullifierLogDev& log, HasherDev* hasher, int lanes) {
+RelayDev::RelayDev(GpuVerifier& verifier, uint64_t max_out, NullifierLogDev& log, HasherDev* hasher, int lanes, int flags) {
   if (lanes != 0 && lanes != 1 && lanes != 8) throw Error("relay: lanes must be 0 (choose), 1 or 8");
+  if (const char* refused = check_flags(flags)) throw Error(std::string("relay: ") + refused);
   Layout L;
   if (!relay::layout_for(verifier.n_values(), max_out, &L))
     throw Error("relay: a circuit of " + std::to_string(verifier.n_values()) + " public values and " + std::to_string(max_out) +
@@ -237,7 +249,7 @@ RelayDev::RelayDev(GpuVerifier& verifier, uint64_t max_out, NullifierLogDev& log
   const int dev = verifier.device();
   if (log.device() != dev || (hasher && hasher->device() != dev))
     throw Error("relay: the prover, the log and the hasher are not on one device");
-  Impl* m = new Impl(verifier, log, hasher, lanes);
+  Impl* m = new Impl(verifier, log, hasher, lanes, flags);
   try {
     m->L = L;
     m->device = dev;
@@ -328,9 +340,16 @@ void RelayDev::Impl::chunk(size_t n, bool team, const uint8_t* proofs, const uin
     }
   } wipe{*this, n, ls, vs, hs};
 
-  // 1. the verifier's pass
-  const GpuVerifier::RelayChunk vc = V.relay_enqueue(n, proofs, values_le, team);
-  RLN_HIP(hipEventRecord(ev_verified, vs));
+  // 1. the verifier's pass: exact, or (flags, and no cool-down) the combined check, which is settled in step 3
+  const bool combined = (flags & RelayDev::OPTIMISTIC) && (!team || (flags & RelayDev::OPTIMISTIC_TEAMS)) &&
+                        !V.relay_cooldown_skip();
+  GpuVerifier::RelayChunk vc{nullptr, nullptr, nullptr};
+  if (combined) {
+    V.relay_enqueue_combined(n, proofs, values_le, team);
+  } else {
+    vc = V.relay_enqueue(n, proofs, values_le, team);
+    RLN_HIP(hipEventRecord(ev_verified, vs));
+  }
   // 2. the signals beside it (offsets are the call's: the chunk's messages lie at offsets[0 .. n])
   if (offsets) {
     stats[6] += hasher->relay_hash(signals, signals_len, offsets, n, d_xs);
@@ -345,11 +364,17 @@ void RelayDev::Impl::chunk(size_t n, bool team, const uint8_t* proofs, const uin
     in_len += 32 * n;
   }
   RLN_HIP(hipMemcpyAsync(in_dev.p, in_host, in_len, hipMemcpyHostToDevice, ls));
+  if (combined) {
+    // the first of this chunk's two waits: the hashing and the copy above run under the combined kernels and the
+    // host's finish.  An accepted chunk has nothing left on the verifier's stream; a rejected one its exact kernels.
+    vc = V.relay_settle();
+    RLN_HIP(hipEventRecord(ev_verified, vs));
+  }
   RLN_HIP(hipStreamWaitEvent(ls, ev_verified, 0));
   if (offsets) RLN_HIP(hipStreamWaitEvent(ls, ev_hashed, 0));
   const dim3 per_message(div_up(n, LOG_LANES)), per_share(div_up(room, LOG_LANES)), block(LOG_LANES);
   hipLaunchKernelGGL(k_relay_gate, per_message, block, 0, ls, L, vc.vals, vc.ok, (const Row32*)d_xs, (const Row32*)d_roots,
-                     (uint32_t)n_roots, n32, d_verdict, counts.p);
+                     (uint32_t)n_roots, n32, vc.ok_is_rejected ? 1u : 0u, d_verdict, counts.p);
   const uint32_t* d_m = scan_positions((const ShareCount*)counts.p, n, pos.p, sums.p, ls);
   hipLaunchKernelGGL(k_relay_emit, per_message, block, 0, ls, L, vc.vals, (const ShareCount*)counts.p, (const uint32_t*)pos.p, d_m,
                      (const uint64_t*)(tags ? d_tags : nullptr), n32, at.rows, at.count, at.next_seq, at.capacity, d_hdr);

@@ -67,6 +67,9 @@ class GpuVerifier {
   // lanes: 1 a lane per proof (chunks of CHUNK), 8 a team per proof (chunks of TEAM_CHUNK); anything else throws.
   void aggregate(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv, const uint8_t* scalars16,
                  uint8_t gt384[384], uint8_t* rejected, int lanes = 1);
+  // the same with the scalars of chunk c of the call derived on the device from (seed32, c): verify_agg_scalars.h
+  void aggregate_seeded(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv, const uint8_t seed32[32],
+                        uint8_t gt384[384], uint8_t* rejected, int lanes = 1);
   // Chunks after a fallback that go straight to the exact pass.  A sender of one bad proof per chunk then costs at
   // most one wasted combined check per cooldown + 1 chunks.  16 is a policy bound on that overhead, not a measured
   // optimum; 0 means no cool-down.
@@ -88,6 +91,7 @@ class GpuVerifier {
     const uint32_t* proofs;   // n x 32 words
     const uint32_t* vals;     // n x n_values x 8 words
     const uint8_t* ok;        // n
+    bool ok_is_rejected = false;   // ok[i] = 1 where the reject rules refuse proof i, and every other proof is valid
   };
   std::mutex& relay_mutex();
   int device() const;
@@ -95,6 +99,19 @@ class GpuVerifier {
   void* relay_stream();                         // a hipStream_t
   bool relay_team(size_t n, int lanes) const;   // verify()'s choice of shape for a call of n proofs
   RelayChunk relay_enqueue(size_t n, const uint8_t* proofs, const uint8_t* values_le, bool team);   // n <= the shape's chunk
+  // The same chunk under the combined check of verify_optimistic, in two calls so that the caller can enqueue other
+  // streams' work between them.  relay_enqueue_combined stages the chunk, draws ONE 32-byte seed (getrandom, after the
+  // proofs and values are in the staging buffer), copies both in, and enqueues the scalar kernel
+  // (verify_agg_scalars.h), the combined kernels of the shape and the copy back of the last partial, its sums and the n
+  // reject flags; it does not wait.  relay_settle waits for the stream, finishes on the host (vm::finish_host) and
+  // counts as verify_optimistic counts (optimistic_stats [0] [1] [2] [4] [7], finish_time).  Accepted: the chunk, with
+  // ok_is_rejected set.  Rejected: the cool-down is set and the exact kernels of the same shape are enqueued over the
+  // proofs and values already resident, with no second copy in; passes() goes up and ok is the exact verdict.
+  // relay_cooldown_skip: true while a cool-down lasts (one chunk of it is used up, [3] goes up): the caller then takes
+  // relay_enqueue.  The cool-down and the counters are the ones verify_optimistic uses.
+  bool relay_cooldown_skip();
+  void relay_enqueue_combined(size_t n, const uint8_t* proofs, const uint8_t* values_le, bool team);
+  RelayChunk relay_settle();
 
  private:
   struct Impl;
@@ -117,6 +134,9 @@ struct AggBuffers {
 };
 int verify_agg_enqueue(void* stream, const vm::PreparedKey* vk, const uint32_t* proofs, const uint32_t* vals,
                        const uint32_t* scalars, const AggBuffers& b, uint32_t n, uint32_t n_values);
+// verify_agg.hip: n scalars of 16 bytes from the 8 seed words at `seed` and the chunk counter (verify_agg_scalars.h),
+// enqueued on `stream`.  scalars is 16-byte aligned and does not overlap the seed.
+void verify_agg_scalars_enqueue(void* stream, const uint32_t* seed, uint64_t chunk, uint32_t* scalars, uint32_t n);
 // verify_agg.hip: the levels of the fold alone, over the n partials in part[0] / sums[0]; the same return value
 int verify_agg_reduce_enqueue(void* stream, const AggBuffers& b, uint32_t n, uint32_t n_values);
 // verify_agg_team.hip: the same combined check with a team of 8 lanes per proof, n <= TEAM_CHUNK: its two kernels, then

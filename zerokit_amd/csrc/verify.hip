@@ -88,16 +88,23 @@ struct GpuVerifier::Impl {
   uint64_t stats[6] = {0, 0, 0, 0, 0, 0};   // [5]: the chunks of [0] checked in team form
   size_t cooldown = COOLDOWN_DEFAULT, cooldown_left = 0;
   uint64_t finish_ns = 0, finish_calls = 0;   // the host's share of the combined checks: time inside vm::finish_host
+  // the relay's combined chunk between relay_enqueue_combined and relay_settle
+  struct Pending {
+    size_t n = 0;
+    bool team = false;
+  } pending;
+  uint64_t seeds_drawn = 0;   // the chunk counter of the seeds drawn here: a seed is used once whatever it is
 
   void reserve(size_t n, bool want_gt) {
     if (n > cap) {
       release_host();
-      d_in.alloc(n * (32 + 8 * nv + 4));   // + 4 words: a proof's scalar in the optimistic form
+      // + 4 words: a proof's scalar in the optimistic form; + 8: the seed they are derived from, in front of them
+      d_in.alloc(n * (32 + 8 * nv + 4) + 8);
       d_prep.alloc(n);
       d_f.alloc(n);
       d_ok.alloc(n);
       d_gt.release();
-      RLN_HIP(hipHostMalloc((void**)&h_in, n * (128 + 32 * nv + 16), hipHostMallocDefault));
+      RLN_HIP(hipHostMalloc((void**)&h_in, n * (128 + 32 * nv + 16) + 32, hipHostMallocDefault));
       RLN_HIP(hipHostMalloc((void**)&h_ok, n, hipHostMallocDefault));
       cap = n;
     }
@@ -154,11 +161,19 @@ struct GpuVerifier::Impl {
                                                                          d_in.p + (32 + 8 * nv) * n, b, (uint32_t)n,
                                                                          (uint32_t)nv);
     RLN_HIP(hipGetLastError());
+    agg_copy_back(n, at);
+    RLN_HIP(hipStreamSynchronize(st));
+    memcpy(rejected, h_ok, n);
+    return agg_finish();
+  }
+  // the copies back of a combined check, enqueued: the last partial, its sums and the n reject flags
+  void agg_copy_back(size_t n, int at) {
     RLN_HIP(hipMemcpyAsync(h_last, d_part[at].p, sizeof(vm::Partial), hipMemcpyDeviceToHost, st));
     RLN_HIP(hipMemcpyAsync(h_last + sizeof(vm::Partial), d_sums[at].p, (nv + 1) * sizeof(Fr), hipMemcpyDeviceToHost, st));
     RLN_HIP(hipMemcpyAsync(h_ok, d_ok.p, n, hipMemcpyDeviceToHost, st));
-    RLN_HIP(hipStreamSynchronize(st));
-    memcpy(rejected, h_ok, n);
+  }
+  // the host's finish over what agg_copy_back brought, once the stream has been waited for
+  Fq12 agg_finish() {
     vm::Partial last;
     std::vector<Fr> sums(nv + 1);
     memcpy(&last, h_last, sizeof(last));
@@ -168,6 +183,36 @@ struct GpuVerifier::Impl {
     finish_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
     finish_calls++;
     return value;
+  }
+  // agg_chunk's front with the scalars derived on the device (verify_agg_scalars.h), enqueued and not waited for.  The
+  // staging buffer holds proofs | values | seed and goes up in one copy; on the device the scalars lie 8 words behind
+  // the values, behind the seed, because every lane of the scalar kernel reads the seed.  seed32: null (drawn here,
+  // after the proofs were copied into the staging buffer) or given, then `chunk` is the caller's counter.
+  void agg_enqueue_seeded(size_t n, const uint8_t* proofs, const uint8_t* values, const uint8_t* seed32, uint64_t chunk,
+                          bool team) {
+    reserve_agg(n);
+    memcpy(h_in, proofs, 128 * n);
+    memcpy(h_in + 128 * n, values, 32 * nv * n);
+    uint8_t* sd = h_in + (128 + 32 * nv) * n;
+    if (seed32) {
+      memcpy(sd, seed32, 32);
+    } else {
+      for (size_t off = 0; off < 32;) {
+        const ssize_t got = getrandom(sd + off, 32 - off, 0);
+        if (got < 0) throw Error("verify_optimistic: getrandom failed");
+        off += (size_t)got;
+      }
+      chunk = seeds_drawn++;
+    }
+    RLN_HIP(hipMemcpyAsync(d_in.p, h_in, n * (128 + 32 * nv) + 32, hipMemcpyHostToDevice, st));
+    uint32_t* d_seed = d_in.p + (32 + 8 * nv) * n;
+    uint32_t* d_scalars = d_seed + 8;
+    verify_agg_scalars_enqueue(st, d_seed, chunk, d_scalars, (uint32_t)n);
+    const AggBuffers b{d_pa.p, {d_part[0].p, d_part[1].p}, {d_sums[0].p, d_sums[1].p}, d_ok.p};
+    const int at = (team ? verify_agg_team_enqueue : verify_agg_enqueue)(st, key.p, d_in.p, d_in.p + 32 * n, d_scalars, b,
+                                                                         (uint32_t)n, (uint32_t)nv);
+    RLN_HIP(hipGetLastError());
+    agg_copy_back(n, at);
   }
   // runs f with the verifier's device current
   template <class F>
@@ -189,6 +234,10 @@ struct GpuVerifier::Impl {
     memcpy(h_in, proofs, 128 * n);
     memcpy(h_in + 128 * n, values, 32 * nv * n);
     RLN_HIP(hipMemcpyAsync(d_in.p, h_in, n * (128 + 32 * nv), hipMemcpyHostToDevice, st));
+    enqueue_exact(n, ok, gt, team);
+  }
+  // the three kernels of one chunk over the n proofs and values resident in d_in, enqueued
+  void enqueue_exact(size_t n, bool ok, bool gt, bool team) {
     const uint32_t* d_proofs = d_in.p;
     const uint32_t* d_vals = d_in.p + 32 * n;
     if (team) {
@@ -333,6 +382,27 @@ void GpuVerifier::aggregate(size_t n, const uint8_t* proofs, const uint8_t* valu
   vm::fq12_words(all, gt384);
 }
 
+void GpuVerifier::aggregate_seeded(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t nv,
+                                   const uint8_t seed32[32], uint8_t gt384[384], uint8_t* rejected, int lanes) {
+  Impl& D = *d_;
+  if (lanes != 1 && lanes != 8) throw Error("verify_aggregate: lanes must be 1 or 8");
+  if (nv != D.nv) throw Error("MalformedVerifyingKey");
+  if (!gt384 || !seed32 || (n && (!proofs || !values_le || !rejected))) throw Error("verify_aggregate: null argument");
+  Fq12 all = Fq12::one();
+  std::lock_guard<std::mutex> lk(D.mu);
+  D.on_device([&]() {
+    const size_t step = lanes == 8 ? TEAM_CHUNK : CHUNK;
+    for (size_t off = 0, c = 0; off < n; off += step, c++) {
+      const size_t m = n - off < step ? n - off : step;
+      D.agg_enqueue_seeded(m, proofs + 128 * off, values_le + 32 * nv * off, seed32, (uint64_t)c, lanes == 8);
+      RLN_HIP(hipStreamSynchronize(D.st));
+      memcpy(rejected + off, D.h_ok, m);
+      all = f12_mul(all, D.agg_finish());
+    }
+  });
+  vm::fq12_words(all, gt384);
+}
+
 void GpuVerifier::set_cooldown(size_t chunks) {
   std::lock_guard<std::mutex> lk(d_->mu);
   d_->cooldown = chunks;
@@ -366,6 +436,44 @@ GpuVerifier::RelayChunk GpuVerifier::relay_enqueue(size_t n, const uint8_t* proo
   if (n == 0 || n > (team ? TEAM_CHUNK : CHUNK)) throw Error("verify: internal error, a relay chunk of the wrong size");
   D.enqueue_chunk(n, proofs, values_le, true, false, team);
   return RelayChunk{D.d_in.p, D.d_in.p + 32 * n, D.d_ok.p};
+}
+bool GpuVerifier::relay_cooldown_skip() {
+  Impl& D = *d_;
+  if (!D.cooldown_left) return false;
+  D.cooldown_left--;
+  D.stats[3]++;
+  return true;
+}
+void GpuVerifier::relay_enqueue_combined(size_t n, const uint8_t* proofs, const uint8_t* values_le, bool team) {
+  Impl& D = *d_;
+  if (n == 0 || n > (team ? TEAM_CHUNK : CHUNK)) throw Error("verify: internal error, a relay chunk of the wrong size");
+  D.pending = Impl::Pending();
+  D.agg_enqueue_seeded(n, proofs, values_le, nullptr, 0, team);
+  D.stats[0]++;
+  if (team) D.stats[5]++;
+  D.pending.n = n;
+  D.pending.team = team;
+}
+GpuVerifier::RelayChunk GpuVerifier::relay_settle() {
+  Impl& D = *d_;
+  const size_t n = D.pending.n;
+  const bool team = D.pending.team;
+  if (n == 0) throw Error("verify: internal error, no combined relay chunk is in flight");
+  D.pending = Impl::Pending();
+  RLN_HIP(hipStreamSynchronize(D.st));
+  size_t refused = 0;
+  for (size_t i = 0; i < n; i++) refused += D.h_ok[i];
+  const bool accept = D.agg_finish().is_one();
+  D.stats[4] += refused;
+  RelayChunk out{D.d_in.p, D.d_in.p + 32 * n, D.d_ok.p, accept};
+  if (accept) {
+    D.stats[1]++;
+  } else {
+    D.stats[2]++;
+    D.cooldown_left = D.cooldown;
+    D.enqueue_exact(n, true, false, team);   // over the inputs the combined kernels read: nothing is copied in again
+  }
+  return out;
 }
 
 void GpuVerifier::passes(size_t out[2]) {

@@ -1,7 +1,8 @@
 // The optimistic form of the device verifier (verify_agg_math.h): a lane per proof computes its part of one combined
 // pairing check -- the shared reject rules, r A, r C and the r x_j, then the Miller loop of the one pair (r A, B) --
 // and the parts are folded 64 to 1 per launch until one is left.  GpuVerifier (verify.hip) draws the scalars, copies
-// the last partial and the reject flags back and decides with vm::finish_host.
+// the last partial and the reject flags back and decides with vm::finish_host.  For the relay step it draws one seed
+// per chunk instead, and k_verify_agg_scalars derives the scalars here (verify_agg_scalars.h).
 //
 // The levels of the fold are separate launches of k_verify_reduce, ordered by the stream.  A workgroup reads what
 // workgroups of the launch before wrote; it never waits for a workgroup of its own launch and no flag is passed
@@ -13,6 +14,7 @@
 #include "common.h"
 #include "verify.h"
 #include "verify_agg_math.h"
+#include "verify_agg_scalars.h"
 
 namespace rlnamd {
 
@@ -58,6 +60,32 @@ __global__ __launch_bounds__(64) void k_verify_reduce(const Partial* __restrict_
   const uint32_t count = n_in - first < (uint32_t)vm::FOLD ? n_in - first : (uint32_t)vm::FOLD;
   for (uint32_t j = lane; j < n1; j += vm::FOLD)
     out_sums[(size_t)blockIdx.x * n1 + j] = vm::sum_column(in_sums + (size_t)first * n1, count, n1, j);
+}
+
+// The scalars of a chunk from its seed (verify_agg_scalars.h): a lane derives the scalars of 8 consecutive proofs with
+// one permutation and stores those below n, 16 bytes each.  seed: 8 words; scalars: n x 4 words, 16-byte aligned, and
+// not the seed's own words -- every lane reads the seed, so it lies where no lane writes.
+__global__ __launch_bounds__(64) void k_verify_agg_scalars(const uint32_t* __restrict__ seed, uint64_t chunk,
+                                                           uint32_t* __restrict__ scalars, uint32_t n) {
+  const uint32_t g = blockIdx.x * 64 + threadIdx.x;
+  if ((uint64_t)g * aggsc::GROUP >= n) return;
+  uint64_t s[4], out[16];
+#pragma unroll
+  for (int k = 0; k < 4; k++) s[k] = (uint64_t)seed[2 * k] | ((uint64_t)seed[2 * k + 1] << 32);
+  aggsc::derive_group(s, chunk, g, out);
+  uint4* dst = (uint4*)scalars + (size_t)g * aggsc::GROUP;
+  const uint32_t left = n - g * aggsc::GROUP;
+#pragma unroll
+  for (uint32_t j = 0; j < aggsc::GROUP; j++)
+    if (j < left)
+      dst[j] = make_uint4((uint32_t)out[2 * j], (uint32_t)(out[2 * j] >> 32), (uint32_t)out[2 * j + 1],
+                          (uint32_t)(out[2 * j + 1] >> 32));
+}
+
+void verify_agg_scalars_enqueue(void* stream, const uint32_t* seed, uint64_t chunk, uint32_t* scalars, uint32_t n) {
+  const uint32_t groups = div_up(n, aggsc::GROUP);
+  hipLaunchKernelGGL(k_verify_agg_scalars, dim3(div_up(groups, 64u)), dim3(64), 0, (hipStream_t)stream, seed, chunk,
+                     scalars, n);
 }
 
 int verify_agg_reduce_enqueue(void* stream, const AggBuffers& b, uint32_t n, uint32_t n_values) {
