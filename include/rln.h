@@ -111,6 +111,12 @@ CBoolResult_t ffi_nullifier_log_observe(struct rlnamd_nullifier_log* log, FFI_RL
  * the semantics and the refusals are described).  One function for V1 and V3 callers: shares do not know which variant
  * they came from. */
 CBoolResult_t ffi_nullifier_log_retire(struct rlnamd_nullifier_log* log, const CFr_t* external_nullifiers, size_t k, size_t* removed); /* EXT */
+/* EXT: the other side of the same removal: every record under an external nullifier that is NOT among the k given
+ * (1 .. RLNAMD_LOG_RETIRE_MAX of them) goes, however many strangers there are; what a three-call loop does when its
+ * clock moves, and after a gap in it.  Everything else is ffi_nullifier_log_retire's contract (rln_amd.h:
+ * rlnamd_nullifier_log_retain, where the refusals are listed: a null pointer, k == 0, k too large, an element >= r).
+ * One function for V1 and V3 callers. */
+CBoolResult_t ffi_nullifier_log_retain(struct rlnamd_nullifier_log* log, const CFr_t* external_nullifiers, size_t k, size_t* removed); /* EXT */
 /* EXT: generate_zk_proof_with_rs (protocol/proof.rs:753-777) -- explicit blinding scalars r, s */
 CResult_FFI_RLNProof_ptr_Vec_uint8_t ffi_generate_rln_proof_with_rs(FFI_RLN_t* const* rln,
                                                                     FFI_RLNWitnessInput_t* const* witness,
@@ -138,8 +144,9 @@ CBoolResult_t ffi_verify_rln_signals_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t
                                            const Vec_uint8_t* signals, const Vec_CFr_t* roots, bool* ok);
 /* EXT: one step of a relay loop in one call: ffi_verify_rln_signals_batch and ffi_nullifier_log_observe(take = ok) over
  * the same inputs, with the cause of a refusal kept.  verdict[i] is RLNAMD_RELAY_OK (0), or the first failing check in
- * the order of ffi_verify_with_roots -- RLNAMD_RELAY_BAD_PROOF, _BAD_ROOT, _BAD_SIGNAL (rln_amd.h) -- so verdict[i] == 0
- * exactly where ffi_verify_rln_signals_batch gives ok[i]; status, secrets (n contiguous CFr, or NULL) and first_tag (or
+ * the order of ffi_verify_with_roots -- RLNAMD_RELAY_BAD_PROOF, _BAD_ROOT, _BAD_SIGNAL (rln_amd.h) -- so, for a pair
+ * without an epoch window (ffi_relay_set_epochs, below), verdict[i] == 0 exactly where ffi_verify_rln_signals_batch
+ * gives ok[i]; status, secrets (n contiguous CFr, or NULL) and first_tag (or
  * NULL) are ffi_nullifier_log_observe's, RLNAMD_SHARE_SKIPPED for a refused message.  roots: NULL checks against the
  * object's current root, an empty vector accepts any root.  From "relay_gpu_min" messages on (config JSON, default
  * 1 024: the smallest measured n, at which this call wins by about 0.1 ms of 13, profiles/relay_step.md) the call is ONE rlnamd_relay_step on
@@ -153,6 +160,19 @@ CBoolResult_t ffi_verify_rln_signals_batch(FFI_RLN_t* const* rln, FFI_RLNProof_t
 CBoolResult_t ffi_relay_step(FFI_RLN_t* const* rln, struct rlnamd_nullifier_log* log, FFI_RLNProof_t* const* proofs, size_t n,
                              const Vec_uint8_t* signals, const Vec_CFr_t* roots /* NULL: the object's current root */,
                              const uint64_t* tags, uint8_t* verdict, uint8_t* status, CFr_t* secrets, uint64_t* first_tag);
+/* EXT: the epoch window of ffi_relay_step for the pair (object, log): the k external nullifiers (0 .. RLNAMD_RELAY_
+ * EPOCHS_MAX) the relay follows.  With k >= 1 the log retains the set (ffi_nullifier_log_retain; *removed, may be NULL,
+ * is what that removed), whether or not a device relay exists for the pair yet, and only then is the set the window.
+ * From then on a message that ffi_relay_step would give RLNAMD_RELAY_OK and whose external nullifier is not in the
+ * window gets RLNAMD_RELAY_BAD_EPOCH, status RLNAMD_SHARE_SKIPPED, and never reaches the log; no other verdict changes
+ * (rln_amd.h: rlnamd_relay_set_epochs).  The window lives with the pair's relay entry, which is made on first use as a
+ * step makes it: it is pushed into the device relay when that exists, applied when the device relay is made later, and
+ * judged on the host for the calls that take the composition, so ffi_relay_step gives the same answers on either side
+ * of "relay_gpu_min".  k == 0 switches the window off and removes nothing.  Refused with the window and the log as
+ * they were: what rlnamd_relay_set_epochs refuses, a null object, a null log.  The window goes with the log: a freed
+ * log's entry is dropped. */
+CBoolResult_t ffi_relay_set_epochs(FFI_RLN_t* const* rln, struct rlnamd_nullifier_log* log, const CFr_t* external_nullifiers,
+                                   size_t k, size_t* removed); /* EXT */
 
 /* EXT: n finishes in one call (single message-id): partials[i] is the partial proof witnesses[i] is finished from -- the
  * same pointer may repeat, one member's partial proof finished for n messages being what partial proofs are for
@@ -409,6 +429,7 @@ void ffi_rln_v3_proof_values_free(FFI_RLNV3ProofValues_t* pv); /* ffi_rln_v3.rs:
 CResult_CFr_ptr_Vec_uint8_t ffi_rln_v3_compute_id_secret(const CFr_t* share1_x, const CFr_t* share1_y, const CFr_t* share2_x, const CFr_t* share2_y); /* ffi_rln_v3.rs:1324 */
 CResult_CFr_ptr_Vec_uint8_t ffi_rln_v3_recover_id_secret(FFI_RLNV3ProofValues_t* const* pv1, FFI_RLNV3ProofValues_t* const* pv2); /* ffi_rln_v3.rs:1345 */
 CBoolResult_t ffi_rln_v3_relay_step(FFI_RLNV3_t* const* rln, struct rlnamd_nullifier_log* log, FFI_RLNV3Proof_t* const* proofs, size_t n, const Vec_uint8_t* signals, const Vec_CFr_t* roots, const uint64_t* tags, uint8_t* verdict, uint8_t* status, CFr_t* secrets, uint64_t* first_tag); /* EXT: ffi_relay_step over V3 proofs */
+CBoolResult_t ffi_rln_v3_relay_set_epochs(FFI_RLNV3_t* const* rln, struct rlnamd_nullifier_log* log, const CFr_t* external_nullifiers, size_t k, size_t* removed); /* EXT: ffi_relay_set_epochs for a V3 object */
 CBoolResult_t ffi_rln_v3_nullifier_log_observe(struct rlnamd_nullifier_log* log, FFI_RLNV3ProofValues_t* const* values, size_t n, const bool* take, const uint64_t* tags, uint8_t* status, CFr_t* secrets, uint64_t* first_tag); /* EXT: ffi_nullifier_log_observe over V3 values */
 void ffi_rln_v3_merkle_proof_free(FFI_RLNV3MerkleProof_t* proof); /* ffi_rln_v3.rs:1371 */
 CBoolResult_t ffi_rln_v3_delete_leaf(FFI_RLNV3_t** rln, size_t index); /* ffi_rln_v3.rs:1376 */

@@ -112,7 +112,19 @@ int rlnamd_tree_bench(rlnamd_tree* t, size_t n_leaves, uint64_t first_value, int
  * A failed allocation during a retire leaves the log as it was.  From a log's first retire on its record memory doubles
  * (the survivors are moved into a spare set of record arrays, which then becomes the live one); a log that never
  * retires pays nothing.
- * retire_info: [0] retire calls, [1] records removed over the life of the handle, [2] next default tag, [3] records
+ *
+ * Retaining.  retain(W), W a set of 1 .. RLNAMD_LOG_RETIRE_MAX external nullifiers, removes every record whose external
+ * nullifier is NOT in W, however many different ones the removed records carry: what a relay needs when its window
+ * moves, and after a gap or a restart of its clock, when it can name the epochs it follows and not the strangers.
+ * Everything else is retire's contract, word for word: the survivors keep their order, their tags and their sequence
+ * numbers; afterwards every observe answers as a fresh log with the same seed would, had it been fed only the
+ * survivors; sequence numbers are not reused; the spare record arrays appear with the first removal; a failed
+ * allocation leaves the log as it was; retire_info [0] and [1] count a retain as a retire.  The two calls run the same
+ * passes and differ in the sense of the mark alone.  retain refuses, each with its own text, before anything is
+ * enqueued and with the log unchanged: a null pointer with k > 0; k == 0 (it would remove everything: use clear);
+ * k > RLNAMD_LOG_RETIRE_MAX; an external nullifier >= r (the text names the first such one).  These are judged before
+ * the handle is followed.  A duplicate in W is not an error.  A set every record matches: removed = 0, nothing moves.
+ * retire_info: [0] retire and retain calls, [1] records removed over the life of the handle, [2] next default tag, [3] records
  * held, [4] longest probe walk of the last rebuild, [5] 1 once the spare arrays exist, [6..7] reserved 0. */
 typedef struct rlnamd_nullifier_log rlnamd_nullifier_log;
 #define RLNAMD_SHARE_NEW 0
@@ -128,6 +140,8 @@ int rlnamd_nullifier_log_observe(rlnamd_nullifier_log* l, size_t n, const uint8_
 int rlnamd_nullifier_log_clear(rlnamd_nullifier_log* l);      /* everything goes: empty table, count 0, same seed */
 #define RLNAMD_LOG_RETIRE_MAX 64
 int rlnamd_nullifier_log_retire(rlnamd_nullifier_log* l, const uint8_t* external_nullifiers_le /* k*32 */, size_t k,
+                                uint64_t* removed /* or NULL */);
+int rlnamd_nullifier_log_retain(rlnamd_nullifier_log* l, const uint8_t* external_nullifiers_le /* k*32 */, size_t k,
                                 uint64_t* removed /* or NULL */);
 int rlnamd_nullifier_log_retire_info(rlnamd_nullifier_log* l, uint64_t out[8]);
 int rlnamd_nullifier_log_get(rlnamd_nullifier_log* l, uint64_t seq, uint8_t share_le[128], uint64_t* tag);
@@ -515,7 +529,25 @@ int rlnamd_proof_decompress(const uint8_t proof[128], uint8_t coords_le[256]);
  * the step returns, on every error path too.
  * info: [0] steps, [1] verifier chunks, [2] messages, [3] messages with verdict OK, [4] shares recorded, [5] non-zero
  * 16-byte words left in the relay's result buffers, device and pinned (0 expected), [6] messages hashed on the host
- * route, [7] reserved 0.  The log's info[4] goes up by one per chunk that records a share, its info[6] stays 0.
+ * route, [7] messages refused RLNAMD_RELAY_BAD_EPOCH (0 for a relay that never sets a window).  The log's info[4] goes
+ * up by one per chunk that records a share, its info[6] stays 0.
+ *
+ * The epoch window.  A member's quota is per external nullifier, so a relay must also decide WHICH external nullifiers
+ * it relays for: a sender who proves under a fresh one for every message is otherwise never rate-limited, and a late
+ * message of a retired epoch is recorded again and never removed.  The window W is the relay's state: k external
+ * nullifiers, 0 <= k <= RLNAMD_RELAY_EPOCHS_MAX, kept on the device beside the roots; k = 0 (as made) is no window.
+ * With a window a step is the windowless step with one change: a message whose verdict would be RLNAMD_RELAY_OK and
+ * whose external nullifier is not in W gets RLNAMD_RELAY_BAD_EPOCH -- the check comes after proof, root and signal, so
+ * no other verdict changes -- and status, secrets, first_tag and the log's records are what follows from those messages
+ * never reaching the log.  The exact and the combined relay share the check and stay byte for byte equal.
+ * rlnamd_relay_set_epochs with k >= 1 takes the relay's mutex and the log's, runs rlnamd_nullifier_log_retain on the
+ * borrowed log with the new set, and only when that has succeeded installs the set; *removed is what the retain
+ * removed.  So: everything the relay records lies in its window, and after every set_epochs the log holds only the
+ * window.  A caller may still observe into the borrowed log directly; the next set_epochs sweeps what that brought in.
+ * With k == 0 it switches the window off and removes nothing (*removed = 0).  It refuses what retain refuses for
+ * k >= 1, and k > RLNAMD_RELAY_EPOCHS_MAX with a text of its own, before the handle is followed; a refused call and a
+ * retain that fails leave both the window and the log as they were.  rlnamd_relay_epochs copies the window out, in the
+ * order it was given (duplicates included): *k elements into out_le, which has room for RLNAMD_RELAY_EPOCHS_MAX.
  *
  * rlnamd_relay_new_ex: the same relay with flags; rlnamd_relay_new is flags = 0.
  *   RLNAMD_RELAY_OPTIMISTIC        every chunk that would run a lane per proof (more than 1 024 messages, or lanes = 1)
@@ -537,7 +569,7 @@ int rlnamd_proof_decompress(const uint8_t proof[128], uint8_t coords_le[256]);
  * counters per prover: rlnamd_verify_gpu_set_cooldown, rlnamd_verify_gpu_optimistic_stats, rlnamd_verify_gpu_passes)
  * take the exact pass as a flags = 0 relay does.  A combined chunk waits twice on the host -- for the verifier's
  * stream before the host's share of the pairing check, then for the log's stream -- where an exact chunk waits once;
- * the hashing and the log's copy in run under the first wait.  rlnamd_relay_info is unchanged ([7] stays 0). */
+ * the hashing and the log's copy in run under the first wait.  rlnamd_relay_info is unchanged. */
 #define RLNAMD_RELAY_OPTIMISTIC 1
 #define RLNAMD_RELAY_OPTIMISTIC_TEAMS 2
 typedef struct rlnamd_relay rlnamd_relay;
@@ -545,7 +577,9 @@ typedef struct rlnamd_relay rlnamd_relay;
 #define RLNAMD_RELAY_BAD_PROOF 1    /* the verifier's ok == 0, or a selector element that is neither 0 nor 1 */
 #define RLNAMD_RELAY_BAD_ROOT 2
 #define RLNAMD_RELAY_BAD_SIGNAL 3
+#define RLNAMD_RELAY_BAD_EPOCH 4     /* would be OK, but its external nullifier is not in the relay's window */
 #define RLNAMD_RELAY_ROOTS_MAX 64
+#define RLNAMD_RELAY_EPOCHS_MAX 64   /* = RLNAMD_LOG_RETIRE_MAX */
 int rlnamd_relay_new(rlnamd_prover* p, rlnamd_nullifier_log* log, rlnamd_hasher* h /* or NULL */, int lanes /* 0 | 1 | 8 */,
                      rlnamd_relay** out);
 int rlnamd_relay_new_ex(rlnamd_prover* p, rlnamd_nullifier_log* log, rlnamd_hasher* h /* or NULL */, int lanes /* 0 | 1 | 8 */,
@@ -558,6 +592,9 @@ int rlnamd_relay_step(rlnamd_relay* r, size_t n, const uint8_t* proofs /* n*128 
                       const uint8_t* roots_le, size_t n_roots /* 0: any root, ffi_verify_with_roots' rule */,
                       const uint64_t* tags /* n, or NULL */, uint8_t* verdict /* n */, uint8_t* status /* n */,
                       uint8_t* secrets_le /* n*32 or NULL */, uint64_t* first_tag /* n or NULL */);
+int rlnamd_relay_set_epochs(rlnamd_relay* r, const uint8_t* external_nullifiers_le /* k*32 */, size_t k /* 0: no window */,
+                            uint64_t* removed /* or NULL */);
+int rlnamd_relay_epochs(rlnamd_relay* r, uint8_t* out_le /* RLNAMD_RELAY_EPOCHS_MAX*32 */, size_t* k);
 int rlnamd_relay_info(rlnamd_relay* r, uint64_t out[8]);
 
 /* ---- variable-base MSM on G1 / G2 (BASELINE config 5; north_star: "windowed Pippenger MSM on G1/G2") ---------

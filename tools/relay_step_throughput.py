@@ -28,6 +28,12 @@ prints ONE JSON line.  Torch-free (ctypes and numpy).
             call under cool-down 0; with --ffi the drop-in entry of an optimistic object on its two routes; and the
             seeded aggregate against the one that draws its scalars on the host (profiles/relay_step_optimistic.md)
 
+  --window  another measurement instead (window_main): the same step on three relays that take the call alternately, each
+            on a log of its own -- no epoch window, a window of 3 external nullifiers, a window of 64 whose matching
+            ones come last -- over rows under three external nullifiers, all of them in the window, so that the three
+            do the same work but for the compares; then rlnamd_relay_set_epochs that drops one epoch of three from a
+            log of 2^20 records against rlnamd_nullifier_log_retire of that epoch on a twin (profiles/relay_window.md)
+
 "relay_gpu_min" is the smallest measured n at which the step's median is below the composition's minimum, for both
 signal lengths (the rule profiles/verify_gpu_lanes.md used for verify_team_max); null if there is none.
 """
@@ -51,8 +57,9 @@ PROVE_CHUNK = 1024
 U64P = C.POINTER(C.c_uint64)
 
 
-def make_rows(prover, hasher, n, signal_len, rnd):
-    """-> (proofs n x 128, values n x 160, signals, offsets)"""
+def make_rows(prover, hasher, n, signal_len, rnd, epochs=None):
+    """-> (proofs n x 128, values n x 160, signals, offsets); epochs: row i proves under external nullifier
+    epochs[i % len(epochs)] instead of the workload's own"""
     from zerokit_amd import workload
     signals = rnd.integers(0, 256, size=(n, signal_len), dtype=np.uint8)
     offsets = np.arange(n + 1, dtype=np.uint64) * signal_len
@@ -64,6 +71,10 @@ def make_rows(prover, hasher, n, signal_len, rnd):
         inp, rsb = workload.config2_packed(prover.slots, prover.inputs_size, first, c)
         buf = np.frombuffer(inp, dtype=np.uint8).reshape(c, prover.inputs_size, 32).copy()
         buf[:, off_x, :] = xs[first:first + c]
+        if epochs:
+            off_e = prover.slots["externalNullifier"][0]
+            for i in range(c):
+                buf[i, off_e, :] = np.frombuffer(int(epochs[(first + i) % len(epochs)]).to_bytes(32, "little"), dtype=np.uint8)
         t, got = prover.submit(buf.tobytes(), rsb)
         pr, va, errs = prover.collect_raw(t, got)
         assert not any(errs)
@@ -307,6 +318,97 @@ def optimistic_main(a):
     prover.close()
 
 
+def window_main(a):
+    """--window: see the module's text"""
+    from zerokit_amd import lib as load
+    from zerokit_amd._native import check
+    from zerokit_amd.batch import BatchProver, Hasher, NullifierLog, Relay
+    lib = load()
+    sizes = [int(s) for s in a.sizes.split(",")]
+    signal_len = 32
+    epochs = [900001, 900002, 900003]
+    windows = dict(none=[], window_3=epochs, window_64=[800000 + j for j in range(61)] + epochs)
+    prover = BatchProver(max_batch=PROVE_CHUNK)
+    hasher = Hasher()
+    logs = [NullifierLog(CAPACITY, SEED) for _ in windows]
+    relays = [Relay(prover, log, hasher, 0) for log in logs]
+    for relay, w in zip(relays, windows.values()):
+        relay.set_epochs(w)
+    rnd = np.random.default_rng(20261021)
+    proofs, values, signals, offsets = make_rows(prover, hasher, max(sizes), signal_len, rnd, epochs)
+    rows = []
+    for n in sizes:
+        pr, va, sg = proofs[:128 * n], values[:160 * n], signals[:signal_len * n]
+        off_c = np.ascontiguousarray(offsets[:n + 1]).ctypes.data_as(U64P)
+        tags = np.arange(n, dtype=np.uint64)
+        outs = [(C.create_string_buffer(n), C.create_string_buffer(n), C.create_string_buffer(32 * n), np.zeros(n, dtype=np.uint64))
+                for _ in relays]
+        ms = [[] for _ in relays]
+        for call in range(WARMUP + a.calls):
+            for log in logs:
+                log.clear()
+            for j, relay in enumerate(relays):
+                o = outs[j]
+                t0 = time.perf_counter()
+                check(lib.rlnamd_relay_step(relay._h, n, pr, va, 5, sg, len(sg), off_c, None, None, 0, tags.ctypes.data_as(U64P),
+                                            o[0], o[1], o[2], o[3].ctypes.data_as(U64P)))
+                t1 = time.perf_counter()
+                if call >= WARMUP:
+                    ms[j].append((t1 - t0) * 1e3)
+            for o in outs[1:]:
+                if any(x.raw != y.raw for x, y in zip(outs[0][:3], o[:3])) or not np.array_equal(outs[0][3], o[3]):
+                    raise SystemExit("the steps with and without a window differ: n %d, call %d" % (n, call))
+        row = dict(n=n, accepted=int(outs[0][0].raw.count(b"\0")), bad_epoch=[r.info()["bad_epoch"] for r in relays])
+        for name, t in zip(windows, ms):
+            row[name + "_ms"] = summary(t)
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    for r in relays:
+        r.close()
+    for log in logs:
+        log.close()
+    # moving the window on a log of 2^20 records under three epochs in equal parts: set_epochs keeps two, retire drops one
+    m = 1 << 20
+    raw = np.zeros((m, 4, 32), dtype=np.uint8)
+    raw[:, :3, :24] = rnd.integers(0, 256, size=(m, 3, 24), dtype=np.uint8)   # nullifier, x, y: random, below r
+    for i, e in enumerate(epochs):
+        raw[i::3, 3, :] = np.frombuffer(int(e).to_bytes(32, "little"), dtype=np.uint8)
+    shares = raw.tobytes()
+    pair = NullifierLog(m, SEED), NullifierLog(m, SEED)
+    relay = Relay(prover, pair[0], None, 0)
+    status = C.create_string_buffer(m)
+    ms = dict(set_epochs=[], retire=[])
+    removed = []
+    for call in range(WARMUP + a.calls):
+        relay.set_epochs([])
+        for log in pair:
+            log.clear()
+            check(lib.rlnamd_nullifier_log_observe(log._h, m, shares, None, status, None, None))
+        t0 = time.perf_counter()
+        gone = relay.set_epochs(epochs[1:])
+        t1 = time.perf_counter()
+        other = pair[1].retire(epochs[:1])
+        t2 = time.perf_counter()
+        if gone != other or pair[0].info()[:4] != pair[1].info()[:4]:
+            raise SystemExit("set_epochs and the retire of the complement differ")
+        removed.append(gone)
+        if call >= WARMUP:
+            ms["set_epochs"].append((t1 - t0) * 1e3)
+            ms["retire"].append((t2 - t1) * 1e3)
+    out = dict(tool="relay_step_throughput --window", calls=a.calls, warmup=WARMUP, capacity=CAPACITY, rows=rows,
+               move=dict(records=m, removed=removed[-1], set_epochs_ms=summary(ms["set_epochs"]), retire_ms=summary(ms["retire"])))
+    relay.close()
+    for log in pair:
+        log.close()
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    hasher.close()
+    prover.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=9)
@@ -314,10 +416,13 @@ def main():
     ap.add_argument("--signal-bytes", default="32,1024")
     ap.add_argument("--ffi", action="store_true")
     ap.add_argument("--optimistic", action="store_true")
+    ap.add_argument("--window", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.optimistic:
         return optimistic_main(a)
+    if a.window:
+        return window_main(a)
     from zerokit_amd import lib as load
     from zerokit_amd._native import check
     from zerokit_amd.batch import BatchProver, Hasher, NullifierLog, Relay

@@ -109,6 +109,7 @@ SIGNATURES = {
                                               C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_clear": (C.c_int, [P]),
     "rlnamd_nullifier_log_retire": (C.c_int, [P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "rlnamd_nullifier_log_retain": (C.c_int, [P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_retire_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_get": (C.c_int, [P, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_home_slot": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_uint64)]),
@@ -123,6 +124,8 @@ SIGNATURES = {
     "rlnamd_relay_step": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                                     C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64),
                                     C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "rlnamd_relay_set_epochs": (C.c_int, [P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "rlnamd_relay_epochs": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_size_t)]),
     "rlnamd_relay_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_tree_fill_sequential": (C.c_int, [P, C.c_size_t, C.c_size_t, C.c_uint64]),
     "rlnamd_tree_bench": (C.c_int, [P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_size_t)]),
@@ -320,6 +323,9 @@ SIGNATURES = {
     "ffi_nullifier_log_observe": (CBoolResult, [P, PP, C.c_size_t, C.POINTER(C.c_bool), C.POINTER(C.c_uint64), C.c_char_p,
                                                 CFRP, C.POINTER(C.c_uint64)]),
     "ffi_nullifier_log_retire": (CBoolResult, [P, CFRP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ffi_nullifier_log_retain": (CBoolResult, [P, CFRP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ffi_relay_set_epochs": (CBoolResult, [PP, P, CFRP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ffi_rln_v3_relay_set_epochs": (CBoolResult, [PP, P, CFRP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ffi_seeded_key_gen": (VecCFr, [C.POINTER(VecU8)]),
     "ffi_extended_key_gen": (VecCFr, []),
     "ffi_seeded_extended_key_gen": (VecCFr, [C.POINTER(VecU8)]),

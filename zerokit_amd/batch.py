@@ -833,8 +833,16 @@ class NullifierLog:
         check(lib().rlnamd_nullifier_log_retire(self._h, b"".join(_b(e) for e in external_nullifiers), k, C.byref(removed)))
         return int(removed.value)
 
+    def retain(self, external_nullifiers):
+        """1 .. 64 external nullifiers (ints): every record under NONE of them is removed, however many others there
+        are -> how many.  Everything else as retire(); an empty list is refused (that is clear())."""
+        k = len(external_nullifiers)
+        removed = C.c_uint64()
+        check(lib().rlnamd_nullifier_log_retain(self._h, b"".join(_b(e) for e in external_nullifiers), k, C.byref(removed)))
+        return int(removed.value)
+
     def retire_info(self):
-        """[retire calls, records removed so far, next default tag, records held, longest probe walk of the last
+        """[retire and retain calls, records removed so far, next default tag, records held, longest probe walk of the last
         rebuild, 1 once the spare record arrays exist, 0, 0]"""
         out = (C.c_uint64 * 8)()
         check(lib().rlnamd_nullifier_log_retire_info(self._h, out))
@@ -918,11 +926,16 @@ class Relay:
     optimistic: the chunks that would run a lane per proof take one combined pairing check (verify_many_gpu_optimistic's,
     the scalars derived on the device from one seed per chunk) and the exact pass only when it rejects; team_checks: the
     chunks in team form too (needs optimistic).  The same results, up to about 2^-128 per accepted chunk; progress is
-    read from BatchProver.verify_optimistic_stats and verify_gpu_passes."""
-    OK, BAD_PROOF, BAD_ROOT, BAD_SIGNAL = range(4)
+    read from BatchProver.verify_optimistic_stats and verify_gpu_passes.
+
+    The epoch window: set_epochs(W) names the external nullifiers the relay follows.  The log retains them
+    (NullifierLog.retain), and from then on a message that would be OK under an external nullifier outside W is
+    BAD_EPOCH and never reaches the log.  No window (as made, or set_epochs([])): any external nullifier."""
+    OK, BAD_PROOF, BAD_ROOT, BAD_SIGNAL, BAD_EPOCH = range(5)
     ROOTS_MAX = 64
+    EPOCHS_MAX = 64
     OPTIMISTIC, OPTIMISTIC_TEAMS = 1, 2
-    INFO = ("steps", "chunks", "messages", "accepted", "shares", "residue_words", "host_hashed", "reserved")
+    INFO = ("steps", "chunks", "messages", "accepted", "shares", "residue_words", "host_hashed", "bad_epoch")
 
     def __init__(self, prover: "BatchProver", log: "NullifierLog", hasher: "Hasher" = None, lanes=0, optimistic=False,
                  team_checks=False):
@@ -977,10 +990,27 @@ class Relay:
             None if xs is None else b"".join(_b(x) for x in xs), b"".join(_b(r) for r in roots), tags)
         return list(v), list(st), [int.from_bytes(sec[32 * i:32 * i + 32], "little") for i in range(n)], first
 
+    def set_epochs(self, external_nullifiers):
+        """0 .. 64 external nullifiers (ints).  One or more: the log drops every record outside them, then they are the
+        window -> how many records went.  None: the window is switched off, nothing is removed -> 0."""
+        k = len(external_nullifiers)
+        removed = C.c_uint64()
+        check(lib().rlnamd_relay_set_epochs(self._h, b"".join(_b(e) for e in external_nullifiers), k, C.byref(removed)))
+        return int(removed.value)
+
+    def epochs(self):
+        """the window, as it was given: a list of ints, empty for none"""
+        out = C.create_string_buffer(32 * self.EPOCHS_MAX)
+        k = C.c_size_t()
+        check(lib().rlnamd_relay_epochs(self._h, out, C.byref(k)))
+        return [int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(k.value)]
+
     def info(self):
         out = (C.c_uint64 * 8)()
         check(lib().rlnamd_relay_info(self._h, out))
-        return dict(zip(self.INFO, (int(v) for v in out)))
+        d = dict(zip(self.INFO, (int(v) for v in out)))
+        d["reserved"] = 0   # the name [7] had before it counted BAD_EPOCH
+        return d
 
 
 class MsmG1:

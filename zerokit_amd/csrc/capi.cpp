@@ -281,6 +281,17 @@ int rlnamd_nullifier_log_retire(rlnamd_nullifier_log* l, const uint8_t* external
   if (removed) *removed = gone;
   RLN_CATCH
 }
+int rlnamd_nullifier_log_retain(rlnamd_nullifier_log* l, const uint8_t* external_nullifiers_le, size_t k, uint64_t* removed) {
+  RLN_TRY
+  // what needs no object is checked before the handle is followed
+  const std::string refused = nlog::retain_refusal(external_nullifiers_le, k);
+  if (!refused.empty()) throw Error(refused);
+  if (!l) throw Error("rlnamd_nullifier_log_retain: null log");
+  std::lock_guard<std::mutex> lk(l->mu);
+  const uint64_t gone = l->log.retain(k, external_nullifiers_le);
+  if (removed) *removed = gone;
+  RLN_CATCH
+}
 int rlnamd_nullifier_log_retire_info(rlnamd_nullifier_log* l, uint64_t out[8]) {
   RLN_TRY
   if (!l || !out) throw Error("rlnamd_nullifier_log_retire_info: null pointer");
@@ -372,6 +383,28 @@ int rlnamd_relay_step(rlnamd_relay* r, size_t n, const uint8_t* proofs, const ui
   std::lock_guard<std::mutex> lk_log(r->log->mu);
   r->relay.step(n, proofs, values_le, n_values, signals, signals_len, offsets, xs_le, roots_le, n_roots, tags, verdict, status,
                 secrets_le, first_tag);
+  RLN_CATCH
+}
+static_assert(RLNAMD_RELAY_EPOCHS_MAX == relay::EPOCHS_MAX && RLNAMD_RELAY_EPOCHS_MAX == RLNAMD_LOG_RETIRE_MAX &&
+                  RLNAMD_RELAY_BAD_EPOCH == relay::BAD_EPOCH,
+              "the relay's window");
+int rlnamd_relay_set_epochs(rlnamd_relay* r, const uint8_t* external_nullifiers_le, size_t k, uint64_t* removed) {
+  RLN_TRY
+  // what needs no object is checked before the handle is followed
+  const std::string refused = relay::epochs_refusal(external_nullifiers_le, k);
+  if (!refused.empty()) throw Error(refused);
+  if (!r) throw Error("rlnamd_relay_set_epochs: null relay");
+  std::lock_guard<std::mutex> lk(r->mu);
+  std::lock_guard<std::mutex> lk_log(r->log->mu);   // the step's order: the relay's, then the log's
+  const uint64_t gone = r->relay.set_epochs(k, external_nullifiers_le);
+  if (removed) *removed = gone;
+  RLN_CATCH
+}
+int rlnamd_relay_epochs(rlnamd_relay* r, uint8_t* out_le, size_t* k) {
+  RLN_TRY
+  if (!r || !out_le || !k) throw Error("rlnamd_relay_epochs: null pointer");
+  std::lock_guard<std::mutex> lk(r->mu);
+  *k = r->relay.epochs(out_le);
   RLN_CATCH
 }
 int rlnamd_relay_info(rlnamd_relay* r, uint64_t out[8]) {

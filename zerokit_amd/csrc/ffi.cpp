@@ -342,6 +342,9 @@ void hash_signals(const Vec_uint8_t* signals, size_t n, size_t gpu_min, CFr* out
 struct RelayEntry {
   std::mutex mu;
   std::unique_ptr<RelayDev> dev;
+  // the epoch window of the (object, log) pair (rln.h: ffi_relay_set_epochs), empty for none: the host route judges it
+  // here, and the device relay gets it when it is made and whenever it is set
+  std::vector<CFr> window;
 };
 struct RelayRegistry;
 struct RelayRegistries {
@@ -2574,10 +2577,52 @@ CBoolResult_t ffi_nullifier_log_retire(struct rlnamd_nullifier_log* log, const C
   });
 }
 
+// the entry of the (object, log) pair, made on first use
+static std::shared_ptr<RelayEntry> relay_entry(FFI_RLN& r, rlnamd_nullifier_log* log) {
+  std::lock_guard<std::mutex> lk(r.relays.mu);
+  std::shared_ptr<RelayEntry>& slot = r.relays.by_log[log->id];
+  if (!slot) slot = std::make_shared<RelayEntry>();
+  return slot;
+}
+// EXT: the epoch window of the (object, log) pair (rln.h).  The log retains the set whether or not a device relay exists
+// yet; only then is the set the window.  One function for V1 and V3 callers.
+static bool relay_set_epochs_common(void* const* rln, rlnamd_nullifier_log* log, const CFr_t* ext, size_t k, size_t* removed) {
+  const std::string refused = relay::epochs_refusal((const uint8_t*)ext, k);
+  if (!refused.empty()) throw Error(refused);
+  if (!rln || !*rln) throw Error("relay set_epochs: null RLN object");
+  if (!log) throw Error("relay set_epochs: null log");
+  FFI_RLN& r = *(FFI_RLN*)*rln;
+  std::shared_ptr<RelayEntry> entry = relay_entry(r, log);
+  // rlnamd_relay_set_epochs' order: the relay, the log
+  std::lock_guard<std::mutex> lk_relay(entry->mu);
+  std::lock_guard<std::mutex> lk_log(log->mu);
+  uint64_t gone = 0;
+  if (entry->dev) gone = entry->dev->set_epochs(k, (const uint8_t*)ext);
+  else if (k) gone = log->log.retain(k, (const uint8_t*)ext);
+  entry->window.assign((const CFr*)ext, (const CFr*)ext + k);
+  if (removed) *removed = (size_t)gone;
+  return true;
+}
+CBoolResult_t ffi_nullifier_log_retain(struct rlnamd_nullifier_log* log, const CFr_t* external_nullifiers, size_t k,
+                                       size_t* removed) {
+  return guard_bool([&]() {
+    uint64_t gone = 0;
+    if (rlnamd_nullifier_log_retain(log, (const uint8_t*)external_nullifiers, k, &gone) != RLNAMD_OK)
+      throw Error(rlnamd_last_error());
+    if (removed) *removed = (size_t)gone;
+    return true;
+  });
+}
+CBoolResult_t ffi_relay_set_epochs(FFI_RLN_t* const* rln, struct rlnamd_nullifier_log* log, const CFr_t* external_nullifiers,
+                                   size_t k, size_t* removed) {
+  return guard_bool([&]() { return relay_set_epochs_common((void* const*)rln, log, external_nullifiers, k, removed); });
+}
+
 // EXT: one relay step over FFI objects (rln.h).  From relay_gpu_min messages on it is rlnamd_relay_step over packed rows,
 // on one relay per (object, log), which takes the combined check for an object with "verify_optimistic"
 // (rlnamd_relay_new_ex's flags); below, and for more roots than a step takes, it is the composition: ffi_verify_rln_signals_batch's stages with the verdict's cause kept, then
-// ffi_nullifier_log_observe(take = verdict OK).  One function for V1 and V3 callers: the proofs are the same record.
+// ffi_nullifier_log_observe(take = verdict OK).  The pair's epoch window is judged on either route: on the host one a message
+// that would be OK and whose external nullifier is not in it gets BAD_EPOCH and is not taken.  One function for V1 and V3 callers: the proofs are the same record.
 static bool relay_step_common(void* const* rln, rlnamd_nullifier_log* log, void* const* proofs, size_t n,
                               const Vec_uint8_t* signals, const Vec_CFr_t* roots, const uint64_t* tags, uint8_t* verdict,
                               uint8_t* status, CFr_t* secrets, uint64_t* first_tag) {
@@ -2591,14 +2636,25 @@ static bool relay_step_common(void* const* rln, rlnamd_nullifier_log* log, void*
     if (!signals[i].ptr && signals[i].len) throw Error("hash_to_field: signal " + std::to_string(i) + " is a null pointer with a length");
   }
   const size_t n_roots = roots ? roots->len : 1;
+  std::shared_ptr<RelayEntry> entry = relay_entry(r, log);
   if (n < r.relay_gpu_min || n_roots > RLNAMD_RELAY_ROOTS_MAX) {
+    // the entry's lock for the whole route, as on the device route (and before the hasher's, the verifier's and the
+    // log's, which the calls below take): a window that moves meanwhile must not let a message of the old one in
+    std::lock_guard<std::mutex> lk_relay(entry->mu);
     std::vector<CFr> xs(n);
+    const std::vector<CFr>& window = entry->window;
     hash_signals(signals, n, r.hash_gpu_min, xs.data());
     verify_batch_verdicts(r, (FFI_RLNProof_t* const*)proofs, n, (const CFr_t*)xs.data(), roots, verdict);
     std::vector<void*> values(n);
     std::unique_ptr<bool[]> take(new bool[n]);
     for (size_t i = 0; i < n; i++) {
-      values[i] = (void*)&((FFI_RLNProof*)proofs[i])->values;
+      const FFI_RLNProofValues& v = ((FFI_RLNProof*)proofs[i])->values;
+      values[i] = (void*)&v;
+      if (verdict[i] == RLNAMD_RELAY_OK && !window.empty()) {
+        bool in_window = false;
+        for (const CFr& e : window) in_window |= cfr_cmp(e, v.external_nullifier) == 0;
+        if (!in_window) verdict[i] = RLNAMD_RELAY_BAD_EPOCH;
+      }
       take[i] = verdict[i] == RLNAMD_RELAY_OK;
     }
     return nullifier_log_observe_values(log, values.data(), n, take.get(), tags, status, secrets, first_tag);
@@ -2617,13 +2673,6 @@ static bool relay_step_common(void* const* rln, rlnamd_nullifier_log* log, void*
   if (!roots) r.tree.get_node_host(0, own.le);
   const uint8_t* roots_le = !roots ? own.le : (const uint8_t*)roots->ptr;
   SharedHasher& sh = shared_hasher();
-  std::shared_ptr<RelayEntry> entry;
-  {
-    std::lock_guard<std::mutex> lk(r.relays.mu);
-    std::shared_ptr<RelayEntry>& slot = r.relays.by_log[log->id];
-    if (!slot) slot = std::make_shared<RelayEntry>();
-    entry = slot;
-  }
   GpuVerifier& gv = r.prover->gpu_verifier();
   // "verify_optimistic": the object's relays take the combined check (RelayDev's flags), under the object's cool-down
   const int flags = !r.verify_optimistic ? 0
@@ -2635,7 +2684,11 @@ static bool relay_step_common(void* const* rln, rlnamd_nullifier_log* log, void*
   std::lock_guard<std::mutex> lk_verifier(gv.relay_mutex());
   std::lock_guard<std::mutex> lk_log(log->mu);
   if (!sh.h) sh.h.reset(new HasherDev(0, 0));
-  if (!entry->dev) entry->dev.reset(new RelayDev(gv, r.prover->graph().max_out, log->log, sh.h.get(), r.verify_lanes, flags));
+  if (!entry->dev) {
+    entry->dev.reset(new RelayDev(gv, r.prover->graph().max_out, log->log, sh.h.get(), r.verify_lanes, flags));
+    // a window set before the device relay existed: the log retained it then, the relay only has to learn it
+    if (!entry->window.empty()) entry->dev->set_epochs(entry->window.size(), (const uint8_t*)entry->window.data(), false);
+  }
   entry->dev->step(n, bytes.data(), rows.data(), nv, data.data(), (size_t)offsets[n], offsets.data(), nullptr, roots_le, n_roots,
                    tags, verdict, status, (uint8_t*)secrets, first_tag);
   return true;

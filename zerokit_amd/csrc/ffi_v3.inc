@@ -437,6 +437,10 @@ CBoolResult_t ffi_rln_v3_relay_step(FFI_RLNV3_t* const* rln, struct rlnamd_nulli
                              first_tag);
   });
 }
+CBoolResult_t ffi_rln_v3_relay_set_epochs(FFI_RLNV3_t* const* rln, struct rlnamd_nullifier_log* log,
+                                          const CFr_t* external_nullifiers, size_t k, size_t* removed) {   // EXT: the same entry
+  return guard_bool([&]() { return relay_set_epochs_common((void* const*)rln, log, external_nullifiers, k, removed); });
+}
 
 // ================================================================================ tree (:1363-1609)
 void ffi_rln_v3_merkle_proof_free(FFI_RLNV3MerkleProof_t* proof) { ffi_merkle_proof_free((FFI_MerkleProof_t*)proof); }

@@ -30,6 +30,11 @@
 // nullifiers survives under the one that was not retired, and that record becomes the first.  `capacity` counts
 // records held, so a retire hands back the room of what it removed.
 //
+// Retaining.  retain(W), W a set of 1 .. 64 external nullifiers, is the same removal with the sense of the set turned
+// round: every record whose external nullifier is NOT in W goes, however many different ones those carry -- what a relay
+// asks for when its window moves or its clock has jumped (relay.h: the epoch window).  Everything said of a retire holds
+// for it word for word; the two share every pass and differ in nlog::keeps alone, which is told the sense.
+//
 // Rows and sequence numbers.  A record's sequence number is its arrival index since the last clear; it never changes
 // and is not issued again before the next clear, and a share observed without a tag is tagged with it (a retire does
 // not lower that counter).  The table holds ROWS.  Until the first retire that removes something, row == sequence
@@ -48,7 +53,10 @@
 // nullifier_log.hip passes device atomics of agent scope (the table is shared by all XCDs); SeqAtomics is the one-thread
 // form (the host baseline and the model of the tests), StdAtomics is std::atomic for the threaded CPU test.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+
+#include <string>
 
 #include "field.h"
 
@@ -251,17 +259,22 @@ RLN_HD Verdict judge(const View& L, uint32_t id) {
 
 // ---- retiring
 constexpr uint32_t RETIRE_MAX = 64;
-struct RetireSet {   // the external nullifiers of one retire call, canonical; duplicates do no harm
+struct RetireSet {   // the external nullifiers of one retire or retain call, canonical; duplicates do no harm
   Row32 e[RETIRE_MAX];
   uint32_t k;
+  uint32_t retain = 0;   // the sense of the set: 0, a retire, the records under e[] go; 1, a retain, only they stay
 };
 
-// the keep predicate: the record stays unless its external nullifier is one of set[0 .. k)
-RLN_HD bool keeps(const Row32& ext, const Row32* set, uint32_t k) {
+// is ext one of set[0 .. k)?  (the roots check of relay::gate and its window check are the same compare)
+RLN_HD bool among(const Row32& ext, const Row32* set, uint32_t k) {
   bool hit = false;
   for (uint32_t j = 0; j < k; j++) hit |= same(ext, set[j]);
-  return !hit;
+  return hit;
 }
+
+// the keep predicate.  A retire (retain false): the record stays unless its external nullifier is one of set[0 .. k).
+// A retain: it stays only if it is one of them.
+RLN_HD bool keeps(const Row32& ext, const Row32* set, uint32_t k, bool retain = false) { return among(ext, set, k) == retain; }
 
 // sequence number -> row: binary search over the ascending seqs[0 .. count); `count` if no record carries it
 RLN_HD uint64_t find_seq(const uint64_t* seqs, uint64_t count, uint64_t seq) {
@@ -286,12 +299,13 @@ struct Records {
 // ascending order the move is in place here; the device, one lane per record, moves into a spare set.  Then the table
 // is emptied and the survivors are inserted again, which leaves the lowest surviving row of each key in the key's
 // slot.  Returns the number of survivors; *distinct: taken slots, *longest: the longest walk of the rebuild.
+// With E.retain set this is the sequential retain: the same passes over the other side of the set.
 template <class A>
 inline uint64_t retire(const Records& R, uint32_t* table, uint64_t slots, uint64_t seed, uint64_t count, const RetireSet& E,
                        uint64_t* distinct, uint32_t* longest) {
   uint64_t kept = 0;
   for (uint64_t i = 0; i < count; i++) {
-    if (!keeps(R.rest[i].ext, E.e, E.k)) continue;
+    if (!keeps(R.rest[i].ext, E.e, E.k, E.retain != 0)) continue;
     if (kept != i) {
       R.nul[kept] = R.nul[i];
       R.rest[kept] = R.rest[i];
@@ -328,6 +342,18 @@ inline bool share_is_canonical(const uint8_t share_le[128]) {
   return true;
 }
 
+// The checks of a retain, which need no log and no device.  Returns the empty string, or the text of the refusal.
+inline std::string retain_refusal(const uint8_t* external_nullifiers_le, size_t k) {
+  if (k > 0 && !external_nullifiers_le) return "nullifier log: retain was given a null pointer for k > 0 external nullifiers";
+  if (k == 0) return "nullifier log: a retain of no external nullifiers would remove every record: use clear";
+  if (k > RETIRE_MAX)
+    return "nullifier log: retain takes at most " + std::to_string(RETIRE_MAX) + " external nullifiers a call, not " + std::to_string(k);
+  for (size_t j = 0; j < k; j++)
+    if (!element_is_canonical(external_nullifiers_le + 32 * j))
+      return "nullifier log: external nullifier " + std::to_string(j) + " of the retain is not canonical (>= r)";
+  return std::string();
+}
+
 }  // namespace nlog
 
 // The log as a device-resident object (nullifier_log.hip): records and table in HBM, a non-blocking stream of its own and
@@ -352,6 +378,10 @@ struct NullifierLogDev {
   // pointer with k > 0, k > RETIRE_MAX, an element >= r.  k = 0 and a set no record matches return 0 and move nothing.
   // A failed allocation leaves the log as it was.
   uint64_t retire(size_t k, const uint8_t* external_nullifiers_le);
+  // k external nullifiers of 32 bytes, 1 <= k <= RETIRE_MAX: every record under none of them goes; returns how many.
+  // The passes, the spare arrays, the counters of retire_info() and the behaviour on a failed allocation are retire's.
+  // Refused before anything is enqueued (nlog::retain_refusal), the log left as it was.
+  uint64_t retain(size_t k, const uint8_t* external_nullifiers_le);
   // by sequence number; one that was retired and one that was never issued are two different errors
   void get(uint64_t seq, uint8_t share_le[128], uint64_t* tag);
   uint64_t home_slot(const uint8_t nullifier_le[32]) const;   // host only

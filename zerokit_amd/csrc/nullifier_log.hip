@@ -8,7 +8,8 @@
 // not coherent with each other).
 //
 // One retire() call: a host check, then on the log's stream
-//   k_log_mark                keep[i] = the record's external nullifier is not in the set (the set in LDS)
+//   k_log_mark                keep[i] = the record's external nullifier is not in the set (the set in LDS); a retain()
+//                             call is a retire() whose mark keeps what IS in the set, and nothing else differs
 //   k_scan_up / k_scan_down   pos[i] = kept records below i: block sums of block sums, one kernel per level up and one
 //                             per level down, as many levels as the count asks for (256 items a block: 4 for 2^24 + 1)
 //   k_log_move                kept row i -> row pos[i] of the spare record arrays, which then become the live ones
@@ -70,16 +71,16 @@ __global__ void __launch_bounds__(LOG_LANES) k_log_judge(View L, uint32_t first_
 }
 
 // ---------------------------------------------------------------------------------------------------- retire
-// keep[i]: record i stays.  The set goes to LDS once per workgroup; a lane reads the 32 bytes of its row's external
-// nullifier and nothing else of the 96.
+// keep[i]: record i stays (retain: the sense of the set, nlog::keeps).  The set goes to LDS once per workgroup; a lane
+// reads the 32 bytes of its row's external nullifier and nothing else of the 96.
 __global__ void __launch_bounds__(LOG_LANES) k_log_mark(const Row96* __restrict__ rest, uint32_t n,
-                                                        const Row32* __restrict__ set, uint32_t k,
+                                                        const Row32* __restrict__ set, uint32_t k, uint32_t retain,
                                                         uint8_t* __restrict__ keep) {
   __shared__ Row32 lds_set[nlog::RETIRE_MAX];
   for (uint32_t j = threadIdx.x; j < k * 8; j += LOG_LANES) lds_set[j >> 3].w[j & 7] = set[j >> 3].w[j & 7];
   __syncthreads();
   const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
-  if (i < n) keep[i] = nlog::keeps(rest[i].ext, lds_set, k) ? 1 : 0;
+  if (i < n) keep[i] = nlog::keeps(rest[i].ext, lds_set, k, retain != 0) ? 1 : 0;
 }
 
 // kept row i -> row pos[i] of the other set of record arrays.  dense: no sequence numbers are stored yet, row i is
@@ -203,6 +204,8 @@ struct NullifierLogDev::Impl {
   static size_t in_bytes(size_t n) { return n * 136; }
   static size_t out_bytes(size_t n) { return 16 + (n * 41 + 15) / 16 * 16; }
   View view() const { return View{nul.p, rest.p, tags.p, table.p, slots, seed}; }
+  // the passes of retire() and retain() behind their host checks: 1 <= k <= RETIRE_MAX canonical elements
+  uint64_t remove(size_t k, const uint8_t* external_nullifiers_le, bool retain);
 
   void reserve_retire() {
     if (spare) return;
@@ -400,15 +403,33 @@ uint64_t NullifierLogDev::retire(size_t k, const uint8_t* external_nullifiers_le
     m.retires++;
     return 0;
   }
+  return m.remove(k, external_nullifiers_le, false);
+}
+
+uint64_t NullifierLogDev::retain(size_t k, const uint8_t* external_nullifiers_le) {
+  Impl& m = *d;
+  // the host check: nothing is enqueued and nothing of the log changes before it has passed
+  const std::string refused = nlog::retain_refusal(external_nullifiers_le, k);
+  if (!refused.empty()) throw Error(refused);
+  if (m.count == 0) {
+    m.retires++;
+    return 0;
+  }
+  return m.remove(k, external_nullifiers_le, true);
+}
+
+uint64_t NullifierLogDev::Impl::remove(size_t k, const uint8_t* external_nullifiers_le, bool retain) {
+  Impl& m = *this;
   OnDevice on(m.device);
   m.reserve_retire();
   m.retires++;
   memcpy(m.set_host.e, external_nullifiers_le, 32 * k);
   m.set_host.k = (uint32_t)k;
+  m.set_host.retain = retain ? 1 : 0;
   const uint32_t n32 = (uint32_t)m.count;
   RLN_HIP(hipMemcpyAsync(m.set_dev.p, m.set_host.e, 32 * k, hipMemcpyHostToDevice, m.stream));
   hipLaunchKernelGGL(k_log_mark, dim3(div_up(m.count, LOG_LANES)), dim3(LOG_LANES), 0, m.stream, (const Row96*)m.rest.p, n32,
-                     (const Row32*)m.set_dev.p, m.set_host.k, m.keep.p);
+                     (const Row32*)m.set_dev.p, m.set_host.k, m.set_host.retain, m.keep.p);
   const uint32_t* d_kept = scan_positions(m.keep.p, m.count, m.pos.p, m.sums.p, m.stream);
   uint32_t kept = 0;
   RLN_HIP(hipMemcpyAsync(&kept, d_kept, 4, hipMemcpyDeviceToHost, m.stream));

@@ -5,11 +5,19 @@
 // A message is its proof's public values, in the verifier's order (n_values rows of 8 canonical little-endian words):
 //   single (n_values == 5)                        y | root | nullifier | x | external_nullifier
 //   multi  (n_values == 3 k + 3, k = max_out)     ys[k] | root | nullifiers[k] | x | external_nullifier | selector_used[k]
+//
+// The epoch window.  A relay may hold a window W of 1 .. 64 external nullifiers, the epochs it relays for.  A message
+// that passes the three checks and whose external nullifier is not in W gets BAD_EPOCH and no share: a member's quota
+// is per external nullifier, so a sender who proves under one the relay does not follow would otherwise never be
+// rate-limited, and its records would never be retired.  Setting the window retains it in the log
+// (NullifierLogDev::retain), so: everything a relay records lies in its window, and after every set_epochs the log
+// holds only the window.  No window (k = 0): any external nullifier, the step as it was.
+//
 // Three passes, each one lane per message and each a kernel of its own, so that none reads what a lane of the same
 // kernel writes:
-//   gate   the verdict -- the first failing check in the order proof, root, signal (rln/src/public.rs:725-771) -- and
-//          the message's share count: 1 for an accepted single proof, the number of selectors equal to 1 for an
-//          accepted multi proof, 0 otherwise
+//   gate   the verdict -- the first failing check in the order proof, root, signal (rln/src/public.rs:725-771), then
+//          the epoch window -- and the message's share count: 1 for an accepted single proof, the number of selectors
+//          equal to 1 for an accepted multi proof, 0 otherwise
 //   emit   behind an exclusive sum of the counts (log_scan.h): the shares into rows [first, first + count) of the log's
 //          record arrays, nullifier | x | y | external_nullifier as nullifier_log.h lays a record out, in slot order
 //   fold   behind the log's insert and judge passes over the new rows: of the message's shares the first status in the
@@ -27,9 +35,10 @@ using nlog::Records;
 using nlog::Row32;
 using nlog::Row96;
 
-constexpr uint8_t OK = 0, BAD_PROOF = 1, BAD_ROOT = 2, BAD_SIGNAL = 3;
+constexpr uint8_t OK = 0, BAD_PROOF = 1, BAD_ROOT = 2, BAD_SIGNAL = 3, BAD_EPOCH = 4;
 constexpr uint8_t SKIPPED = 4;   // RLNAMD_SHARE_SKIPPED: no share of this message was recorded
 constexpr uint32_t ROOTS_MAX = 64;
+constexpr uint32_t EPOCHS_MAX = nlog::RETIRE_MAX;   // a window is what one retain call takes
 constexpr uint32_t SLOTS_MAX = 255;   // a share count is a byte
 
 // where the values of a message are
@@ -77,8 +86,9 @@ struct Gate {
   uint8_t verdict, count;
 };
 // vals: the message's values; ok: the verifier's verdict; x: hash_to_field of its signal; roots: n_roots accepted roots
-// (0: any root, ffi_verify_with_roots' rule)
-RLN_HD Gate gate(const Layout& L, const uint32_t* vals, uint8_t ok, const Row32& x, const Row32* roots, uint32_t n_roots) {
+// (0: any root, ffi_verify_with_roots' rule); window: n_window external nullifiers (0: no window, any of them)
+RLN_HD Gate gate(const Layout& L, const uint32_t* vals, uint8_t ok, const Row32& x, const Row32* roots, uint32_t n_roots,
+                 const Row32* window = nullptr, uint32_t n_window = 0) {
   Gate g{OK, 0};
   uint32_t used = 0;
   bool selectors = true;
@@ -106,6 +116,10 @@ RLN_HD Gate gate(const Layout& L, const uint32_t* vals, uint8_t ok, const Row32&
   }
   if (!nlog::same(value(vals, L.x()), x)) {
     g.verdict = BAD_SIGNAL;
+    return g;
+  }
+  if (n_window && !nlog::among(value(vals, L.ext()), window, n_window)) {
+    g.verdict = BAD_EPOCH;
     return g;
   }
   g.count = (uint8_t)used;
@@ -179,6 +193,16 @@ inline const char* check_arguments(size_t n, const void* proofs, const void* val
   return nullptr;
 }
 
+// The checks of set_epochs, which need no object and no device: k = 0 switches the window off and looks at nothing,
+// anything else is what a retain of the set would refuse.  Returns the empty string, or the text of the refusal.
+inline std::string epochs_refusal(const uint8_t* external_nullifiers_le, size_t k) {
+  if (k == 0) return std::string();
+  if (external_nullifiers_le && k > EPOCHS_MAX)
+    return "relay: a window holds at most " + std::to_string(EPOCHS_MAX) + " external nullifiers (RLNAMD_RELAY_EPOCHS_MAX), not " +
+           std::to_string(k);
+  return nlog::retain_refusal(external_nullifiers_le, k);
+}
+
 }  // namespace relay
 
 class GpuVerifier;
@@ -212,6 +236,13 @@ struct RelayDev {
   void step(size_t n, const uint8_t* proofs, const uint8_t* values_le, size_t n_values, const uint8_t* signals,
             size_t signals_len, const uint64_t* offsets, const uint8_t* xs_le, const uint8_t* roots_le, size_t n_roots,
             const uint64_t* tags, uint8_t* verdict, uint8_t* status, uint8_t* secrets_le, uint64_t* first_tag);
+  // include/rln_amd.h: rlnamd_relay_set_epochs.  k >= 1: the log retains the set, and only then is it the window;
+  // returns what the retain removed.  k = 0: no window from now on, nothing removed.  A refused call (relay::
+  // epochs_refusal) and a retain that throws leave the window and the log as they were.  The caller holds the log's lock.
+  // retain = false installs the set alone: for a caller that has run the log's retain itself (ffi.cpp, whose window
+  // may be older than its device relay).
+  uint64_t set_epochs(size_t k, const uint8_t* external_nullifiers_le, bool retain = true);
+  size_t epochs(uint8_t out_le[32 * relay::EPOCHS_MAX]) const;   // the window, in the order it was given; returns k
   void info(uint64_t out[8]);
 };
 

@@ -6,8 +6,8 @@
 //   hasher's stream     at the same time: the chunk's signals packed and hashed, the rows left in message order
 //                       (k_hash_to_field_at; the host's share of the plan is hashed on the calling thread and copied
 //                       into place); with xs_le the rows come with the step's one small copy in instead
-//   log's stream        the copy in of tags and roots, then behind an event from each of the other two:
-//     k_relay_gate                verdict[i] and the message's share count (the roots in LDS)
+//   log's stream        the copy in of roots, window and tags, then behind an event from each of the other two:
+//     k_relay_gate                verdict[i] and the message's share count (the roots and the epoch window in LDS)
 //     k_scan_up / k_scan_down     pos[i] = shares of the messages below i (log_scan.h)
 //     k_relay_emit                the shares into rows [count + pos[i], ...) of the log's record arrays
 //     k_relay_insert, k_relay_judge   nlog::insert and nlog::judge over the m new rows; m is known on the device only, so
@@ -59,17 +59,20 @@ namespace {
 
 __global__ void __launch_bounds__(LOG_LANES) k_relay_gate(Layout L, const uint32_t* __restrict__ vals,
                                                           const uint8_t* __restrict__ ok, const Row32* __restrict__ xs,
-                                                          const Row32* __restrict__ roots, uint32_t n_roots, uint32_t n,
+                                                          const Row32* __restrict__ roots, uint32_t n_roots,
+                                                          const Row32* __restrict__ window, uint32_t n_window, uint32_t n,
                                                           uint32_t ok_is_rejected, uint8_t* __restrict__ verdict,
                                                           ShareCount* __restrict__ counts) {
   __shared__ Row32 lds_roots[relay::ROOTS_MAX];
+  __shared__ Row32 lds_window[relay::EPOCHS_MAX];
   for (uint32_t j = threadIdx.x; j < n_roots * 8; j += LOG_LANES) lds_roots[j >> 3].w[j & 7] = roots[j >> 3].w[j & 7];
+  for (uint32_t j = threadIdx.x; j < n_window * 8; j += LOG_LANES) lds_window[j >> 3].w[j & 7] = window[j >> 3].w[j & 7];
   __syncthreads();
   const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
   if (i >= n) return;
   // behind an accepted combined check ok[] holds the reject flags, and every proof without one is valid
   const uint8_t valid = ok_is_rejected ? (ok[i] ? 0 : 1) : ok[i];
-  const relay::Gate g = relay::gate(L, vals + (size_t)8 * L.n_values * i, valid, xs[i], lds_roots, n_roots);
+  const relay::Gate g = relay::gate(L, vals + (size_t)8 * L.n_values * i, valid, xs[i], lds_roots, n_roots, lds_window, n_window);
   verdict[i] = g.verdict;
   counts[i].v = g.count;
 }
@@ -173,8 +176,11 @@ struct RelayDev::Impl {
   Layout L;
   hipEvent_t ev_verified = nullptr, ev_hashed = nullptr;
   uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // the epoch window: n_window external nullifiers, 0 for none; copied in beside the roots with every chunk
+  Row32 window[relay::EPOCHS_MAX];
+  uint32_t n_window = 0;
   // buffers for a chunk of up to cap messages, K = L.k shares each at the most
-  //   in  (pinned + device):  [roots 32 x 64][tags 8 n, padded to 16][xs 32 n]   (xs: copied with xs_le, written by the
+  //   in  (pinned + device):  [roots 32 x 64][window 32 x 64][tags 8 n, padded to 16][xs 32 n]   (xs: copied with xs_le, written by the
   //                           hasher else)
   //   out (device):           [hdr 16][secrets 32 n][first tags 8 n][verdicts n][statuses n] = result(n), copied back,
   //                           then per share [secrets 32 nK][first tags 8 nK][statuses nK]
@@ -190,7 +196,8 @@ struct RelayDev::Impl {
   Impl(GpuVerifier& v, NullifierLogDev& l, HasherDev* h, int lanes_, int flags_)
       : V(v), log(l), hasher(h), lanes(lanes_), flags(flags_) {}
 
-  static size_t in_bytes(size_t n) { return 32 * relay::ROOTS_MAX + pad16(8 * n) + 32 * n; }
+  static constexpr size_t IN_HEAD = 32 * (relay::ROOTS_MAX + relay::EPOCHS_MAX);   // roots and window
+  static size_t in_bytes(size_t n) { return IN_HEAD + pad16(8 * n) + 32 * n; }
   static size_t result_bytes(size_t n) { return 16 + pad16(42 * n); }
   size_t out_bytes(size_t n) const { return result_bytes(n) + pad16(41 * n * L.k); }
 
@@ -313,7 +320,8 @@ void RelayDev::Impl::chunk(size_t n, bool team, const uint8_t* proofs, const uin
   const uint32_t n32 = (uint32_t)n, room = (uint32_t)(n * L.k);   // n <= 65 536, k <= 255
 
   uint8_t* d_roots = in_dev.p;
-  uint8_t* d_tags = d_roots + 32 * relay::ROOTS_MAX;
+  uint8_t* d_window = d_roots + 32 * relay::ROOTS_MAX;
+  uint8_t* d_tags = in_dev.p + IN_HEAD;
   uint8_t* d_xs = d_tags + pad16(8 * n);
   uint32_t* d_hdr = (uint32_t*)out_dev.p;
   uint8_t* d_secrets = out_dev.p + 16;
@@ -356,9 +364,10 @@ void RelayDev::Impl::chunk(size_t n, bool team, const uint8_t* proofs, const uin
     RLN_HIP(hipEventRecord(ev_hashed, hs));
   }
   // 3. the log's stream
-  size_t in_len = 32 * relay::ROOTS_MAX + pad16(8 * n);
+  size_t in_len = IN_HEAD + pad16(8 * n);
   if (n_roots) memcpy(in_host, roots_le, 32 * n_roots);
-  if (tags) memcpy(in_host + 32 * relay::ROOTS_MAX, tags, 8 * n);
+  if (n_window) memcpy(in_host + 32 * relay::ROOTS_MAX, window, 32 * n_window);
+  if (tags) memcpy(in_host + IN_HEAD, tags, 8 * n);
   if (xs_le) {
     memcpy(in_host + in_len, xs_le, 32 * n);
     in_len += 32 * n;
@@ -374,7 +383,7 @@ void RelayDev::Impl::chunk(size_t n, bool team, const uint8_t* proofs, const uin
   if (offsets) RLN_HIP(hipStreamWaitEvent(ls, ev_hashed, 0));
   const dim3 per_message(div_up(n, LOG_LANES)), per_share(div_up(room, LOG_LANES)), block(LOG_LANES);
   hipLaunchKernelGGL(k_relay_gate, per_message, block, 0, ls, L, vc.vals, vc.ok, (const Row32*)d_xs, (const Row32*)d_roots,
-                     (uint32_t)n_roots, n32, vc.ok_is_rejected ? 1u : 0u, d_verdict, counts.p);
+                     (uint32_t)n_roots, (const Row32*)d_window, n_window, n32, vc.ok_is_rejected ? 1u : 0u, d_verdict, counts.p);
   const uint32_t* d_m = scan_positions((const ShareCount*)counts.p, n, pos.p, sums.p, ls);
   hipLaunchKernelGGL(k_relay_emit, per_message, block, 0, ls, L, vc.vals, (const ShareCount*)counts.p, (const uint32_t*)pos.p, d_m,
                      (const uint64_t*)(tags ? d_tags : nullptr), n32, at.rows, at.count, at.next_seq, at.capacity, d_hdr);
@@ -405,25 +414,44 @@ void RelayDev::Impl::chunk(size_t n, bool team, const uint8_t* proofs, const uin
   const uint8_t* h_first = h_secrets + 32 * n;
   const uint8_t* h_verdict = h_first + 8 * n;
   const uint8_t* h_status = h_verdict + n;
-  size_t accepted = 0;
+  size_t accepted = 0, bad_epoch = 0;
   for (size_t i = 0; i < n; i++) {
     if (h_status[i] > relay::SKIPPED) throw Error("nullifier log: internal error, a share's key is not in the table");
     accepted += h_verdict[i] == relay::OK;
+    bad_epoch += h_verdict[i] == relay::BAD_EPOCH;
   }
   stats[1]++;
   stats[2] += n;
   stats[3] += accepted;
   stats[4] += hdr[0];
+  stats[7] += bad_epoch;
   memcpy(verdict, h_verdict, n);
   memcpy(status, h_status, n);
   if (secrets_le) memcpy(secrets_le, h_secrets, 32 * n);
   if (first_tag) memcpy(first_tag, h_first, 8 * n);
 }
 
+uint64_t RelayDev::set_epochs(size_t k, const uint8_t* external_nullifiers_le, bool retain) {
+  Impl& m = *d;
+  const std::string refused = relay::epochs_refusal(external_nullifiers_le, k);
+  if (!refused.empty()) throw Error(refused);
+  // the log first: a retain that throws leaves the log as it was, and the window with it
+  const uint64_t gone = k && retain ? m.log.retain(k, external_nullifiers_le) : 0;
+  if (k) memcpy(m.window, external_nullifiers_le, 32 * k);
+  m.n_window = (uint32_t)k;
+  return gone;
+}
+
+size_t RelayDev::epochs(uint8_t out_le[32 * relay::EPOCHS_MAX]) const {
+  const Impl& m = *d;
+  if (m.n_window) memcpy(out_le, m.window, 32 * (size_t)m.n_window);
+  return m.n_window;
+}
+
 void RelayDev::info(uint64_t out[8]) {
   Impl& m = *d;
   for (int k = 0; k < 8; k++) out[k] = m.stats[k];
-  out[5] = out[7] = 0;
+  out[5] = 0;
   if (m.cap) {
     OnDevice on(m.device);
     hipStream_t ls = (hipStream_t)m.log.relay_rows().stream;

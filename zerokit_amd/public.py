@@ -592,6 +592,13 @@ class RLN:
         for a bad proof, root or signal; the rest as observe_proof_values returns it."""
         return _relay_step(lib().ffi_relay_step, self, log, proofs, signals, roots, tags)
 
+    def relay_set_epochs(self, log, external_nullifiers) -> int:
+        """EXT: the epoch window of relay_step for this object and `log` (ffi_relay_set_epochs): the log drops every
+        record outside the 1 .. 64 external nullifiers, and from then on relay_step gives verdict 4 (BAD_EPOCH) to a
+        message that would be accepted under any other, on either side of "relay_gpu_min".  An empty list switches
+        the window off and removes nothing.  Returns the number of records removed."""
+        return _relay_set_epochs(lib().ffi_relay_set_epochs, self, log, external_nullifiers)
+
 
 def _relay_step(fn, rln, log, proofs, signals, roots, tags):
     n = len(proofs)
@@ -613,6 +620,14 @@ def _relay_step(fn, rln, log, proofs, signals, roots, tags):
     _ok_bool(fn(C.byref(rln._h), log._h, hs, n, vecs, rp, tg, verdict, status, secrets, first))
     return (list(verdict.raw[:n]), list(status.raw[:n]),
             [int.from_bytes(bytes(secrets[i].le), "little") for i in range(n)], list(first[:n]))
+
+
+def _relay_set_epochs(fn, rln, log, external_nullifiers):
+    k = len(external_nullifiers)
+    ext = (CFr * max(k, 1))(*[_cfr(e) for e in external_nullifiers])
+    removed = C.c_size_t()
+    _ok_bool(fn(C.byref(rln._h), log._h, ext, k, C.byref(removed)))
+    return int(removed.value)
 
 
 def compute_id_secret(share1, share2) -> int:
@@ -659,6 +674,17 @@ def retire_external_nullifiers(log, external_nullifiers) -> int:
     ext = (CFr * max(k, 1))(*[_cfr(e) for e in external_nullifiers])
     removed = C.c_size_t()
     _ok_bool(lib().ffi_nullifier_log_retire(log._h, ext, k, C.byref(removed)))
+    return int(removed.value)
+
+
+def retain_external_nullifiers(log, external_nullifiers) -> int:
+    """EXT: only the epochs of the window stay in a batch.NullifierLog (ffi_nullifier_log_retain): every record under
+    none of the 1 .. 64 external nullifiers is removed, however many others there are.  Serves V1 and V3 proof values
+    alike.  Returns the number of records removed, which is the room handed back."""
+    k = len(external_nullifiers)
+    ext = (CFr * max(k, 1))(*[_cfr(e) for e in external_nullifiers])
+    removed = C.c_size_t()
+    _ok_bool(lib().ffi_nullifier_log_retain(log._h, ext, k, C.byref(removed)))
     return int(removed.value)
 
 

@@ -4,7 +4,7 @@ Field elements are Python ints; errors are RLNError with the text the ABI return
 import ctypes as C
 
 from ._native import CFr, RLNError, VecSize, lib
-from .public import (_cfr, _err, _observe_proof_values, _ok_bool, _relay_step, _ok_ptr, _take_bytes, _take_cfr, _take_vec_bool,
+from .public import (_cfr, _err, _observe_proof_values, _ok_bool, _relay_set_epochs, _relay_step, _ok_ptr, _take_bytes, _take_cfr, _take_vec_bool,
                      _take_vec_cfr, _vec_bool, _vec_cfr, _vec_u8)
 
 
@@ -286,6 +286,10 @@ class RLNV3(_Handle):
     def relay_step(self, log, proofs, signals, roots=None, tags=None):
         """EXT: public.RLN.relay_step over RLNProofV3 (ffi_rln_v3_relay_step)"""
         return _relay_step(lib().ffi_rln_v3_relay_step, self, log, proofs, signals, roots, tags)
+
+    def relay_set_epochs(self, log, external_nullifiers) -> int:
+        """EXT: public.RLN.relay_set_epochs for this object (ffi_rln_v3_relay_set_epochs)"""
+        return _relay_set_epochs(lib().ffi_rln_v3_relay_set_epochs, self, log, external_nullifiers)
 
     def init_tree_with_leaves(self, leaves):
         v, _k = _vec_cfr(list(leaves))
