@@ -195,6 +195,22 @@ CBoolResult_t ffi_generate_rln_proofs_for_members(FFI_RLN_t* const* rln, const s
                                                   const CFr_t* identity_secrets, const CFr_t* user_message_limits,
                                                   const CFr_t* message_ids, const CFr_t* xs,
                                                   const CFr_t* external_nullifiers, const CFr_t* rs, FFI_RLNProof_t** out);
+/* EXT: ffi_generate_rln_proofs_for_members with the message ids drawn on the device from a quota ledger (rln_amd.h:
+ * rlnamd_quota_new makes it, rlnamd_quota_set_epochs opens the external nullifiers signed under; the RLNAMD_QUOTA_* codes
+ * and the meaning of a draw are described there).  The caller brings secret, limit, x and external nullifier; request i
+ * is (leaf_indices[i], external_nullifiers[i], user_message_limits[i]), ONE draw covers the call, status[i] (n bytes) is
+ * its answer, and out[i] is a proof with the id drawn where status[i] is RLNAMD_QUOTA_OK and NULL where no proof was
+ * made -- a member past its quota, an external nullifier outside the ledger's window.  No two proofs made through one
+ * ledger carry the same (external nullifier, member, message id), so a relay's nullifier log never reports them as spam.
+ * Locks: the object's prover, its tree, then the ledger.  Errors before anything is drawn: what
+ * ffi_generate_rln_proofs_for_members refuses (a multi-message-id object among it), a null ledger, a ledger whose depth
+ * is not the tree's or that lives on another device, a limit of 2^32 or more.  n = 0 succeeds. */
+struct rlnamd_quota;
+CBoolResult_t ffi_generate_rln_proofs_for_members_drawn(FFI_RLN_t* const* rln, struct rlnamd_quota* quota,
+                                                        const size_t* leaf_indices, size_t n, const CFr_t* identity_secrets,
+                                                        const CFr_t* user_message_limits, const CFr_t* xs,
+                                                        const CFr_t* external_nullifiers, const CFr_t* rs, uint8_t* status,
+                                                        FFI_RLNProof_t** out);
 
 FFI_RLNProofValues_t* ffi_rln_proof_get_values(FFI_RLNProof_t* const* proof);                 /* ffi_rln.rs:158 */
 uint8_t ffi_rln_proof_get_version_byte(FFI_RLNProof_t* const* proof);                         /* ffi_rln.rs:165 */

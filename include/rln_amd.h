@@ -597,6 +597,90 @@ int rlnamd_relay_set_epochs(rlnamd_relay* r, const uint8_t* external_nullifiers_
 int rlnamd_relay_epochs(rlnamd_relay* r, uint8_t* out_le /* RLNAMD_RELAY_EPOCHS_MAX*32 */, size_t* k);
 int rlnamd_relay_info(rlnamd_relay* r, uint64_t out[8]);
 
+/* ---- quota ledger: message ids drawn on the device, per member and external nullifier -----------------------------
+ * The signer's counterpart of the relay's epoch window.  A second proof under one (external nullifier, member, message
+ * id) is two shares on one line and gives the member's identity secret to every relay; a service that signs for many
+ * members by leaf index (rlnamd_prover_submit_members) keeps that from happening by drawing each proof's message id
+ * from a ledger.  The reference has no such state (zerokit leaves message ids to the caller); the meaning below is the
+ * sequential text of zerokit_amd/csrc/quota_ledger.h.
+ * rlnamd_quota_new: max_epochs x 2^depth 32-bit counters in device memory, zeroed, on the current device; 1 <= depth <=
+ * 24, 1 <= max_epochs <= RLNAMD_RELAY_EPOCHS_MAX, anything else is refused with a text of its own.  used[slot][leaf]
+ * is the next message id of member `leaf` under the external nullifier that holds `slot` of the window.  A ledger has a
+ * mutex and a stream of its own; every call on a handle takes the mutex.
+ * rlnamd_quota_set_epochs: the external nullifiers signed under from now on, 0 <= k <= max_epochs.  One that stays
+ * keeps its slot and its counters; one that leaves has its slot zeroed on the device and freed; a new one gets a zeroed
+ * slot; k = 0 empties the window; a duplicate in the list counts once and is no error.  Refused before anything is
+ * enqueued, the ledger unchanged: a null pointer with k > 0, k > max_epochs, an element >= r.  (A device error behind
+ * those checks is not a refusal and does change the ledger: the external nullifiers that leave are out of the window
+ * before their slots are zeroed, the new ones are not in it; no id can repeat.)  rlnamd_quota_epochs copies
+ * the window out in the order it was given, duplicates once: *k elements into out_le, which has room for
+ * RLNAMD_RELAY_EPOCHS_MAX.
+ *   AN EXTERNAL NULLIFIER THAT HAS LEFT THE WINDOW MUST NOT COME BACK: its counters are gone, and the ids drawn after
+ *   its return repeat the ids drawn before it left.
+ *   THE LEDGER IS NOT PERSISTED: a process that is restarted must not sign under an external nullifier that was open
+ *   before the restart.
+ * rlnamd_quota_draw: n requests (leaf_indices[i], ext_le[i], limits[i]) -> ids_out[i], status[i].
+ *   RLNAMD_QUOTA_NO_EPOCH  ext[i] is not in the window; the request touches nothing
+ *   otherwise              rank_i = the number of requests j < i of this call with the same (external nullifier, leaf),
+ *                          whatever their outcome; id_i = used + rank_i with `used` as it was before the call;
+ *                          RLNAMD_QUOTA_OK iff id_i < limits[i], else RLNAMD_QUOTA_OVER
+ *   afterwards             the counter is one more than the highest id issued for it in this call, and unchanged if none was
+ * ids_out[i] is id_i for OK and limits[i] otherwise (never a valid message id: the circuit's range check fails for it).  The protocol
+ * means one limit per member; with that this is drawing one by one in index order -- OVER consumes nothing, and a call
+ * gives what any split of it into consecutive calls gives.  With differing limits for one member an id can be skipped
+ * but none is issued twice.  Refused before anything is enqueued, the ledger unchanged: null pointers with n > 0, a
+ * leaf index >= 2^depth, n >= 2^32.  n == 0 succeeds.  The time of a draw does not depend on how often members repeat:
+ * n requests of one member and n requests of n members run the same passes (a stable radix sort by key, two running
+ * maxima, one pass that issues, one that advances the counters).
+ * Who signs how often is as secret as who proves: the staged leaf indices, the sort's keys and every other per-call word,
+ * in device and in pinned memory, are overwritten before draw returns, on error paths too, and rlnamd_quota_free zeroes
+ * the counters.
+ * rlnamd_quota_used: the counters of n (leaf, external nullifier) pairs, for diagnostics and tests; in_window[i] = 0 and
+ * used_out[i] = 0 for an external nullifier outside the window.
+ * info: [0] external nullifiers in the window, [1] draws, [2] ids issued, [3] requests refused OVER, [4] requests
+ * refused NO_EPOCH, [5] non-zero 16-byte words left in the ledger's per-call buffers, device and pinned (0 expected),
+ * [6] depth, [7] max_epochs.
+ * rlnamd_quota_plan (host only): the passes of a draw of n requests on a ledger of `depth` -- [0] sort passes, [1]
+ * workgroups a pass, [2] scan levels over a pass's bins, [3] scan levels over the requests. */
+typedef struct rlnamd_quota rlnamd_quota;
+#define RLNAMD_QUOTA_OK 0
+#define RLNAMD_QUOTA_OVER 1
+#define RLNAMD_QUOTA_NO_EPOCH 2
+int rlnamd_quota_new(size_t depth, size_t max_epochs, rlnamd_quota** out);
+void rlnamd_quota_free(rlnamd_quota* q);
+int rlnamd_quota_set_epochs(rlnamd_quota* q, const uint8_t* external_nullifiers_le /* k*32 */, size_t k /* 0: empty */);
+int rlnamd_quota_epochs(rlnamd_quota* q, uint8_t* out_le /* RLNAMD_RELAY_EPOCHS_MAX*32 */, size_t* k);
+int rlnamd_quota_draw(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le /* n*32 */,
+                      const uint32_t* limits /* n */, uint32_t* ids_out /* n */, uint8_t* status /* n */);
+int rlnamd_quota_used(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le /* n*32 */,
+                      uint32_t* used_out /* n */, uint8_t* in_window /* n */);
+int rlnamd_quota_info(rlnamd_quota* q, uint64_t out[8]);
+int rlnamd_quota_plan(size_t n, size_t depth, uint64_t out[4]);
+
+/* ---- proving with drawn message ids.  rlnamd_prover_submit_members_drawn is rlnamd_prover_submit_members (full proofs
+ * only) with the messageId slot of inputs_le ignored: each proof's limit and external nullifier are read from its own
+ * input row (userMessageLimit, externalNullifier), ONE rlnamd_quota_draw covers the call, and status[i] is its answer.
+ * A batch so needs only secret, limit, x and external nullifier from the caller.  A request that is not
+ * RLNAMD_QUOTA_OK yields no proof: its messageId slot is filled with 0xFF bytes, which is no field element, so the
+ * witness interpreter refuses the row as it refuses any input >= r, and collect gives errors[i] != 0, 128 zero proof
+ * bytes and 160 zero value bytes for it (collect zeroes them, behind its copies, for every row of such a batch that has an error: every refused row is
+ * evaluated with one and the same message id, and the y values of two of them would be two shares on one line).  Its
+ * limit would not do: the interpreter evaluates the circuit's range check without asserting it.  On the device
+ * route (rlnamd_prover_submit_members' rule) the ids never visit the host: one kernel behind the staging writes them
+ * into the staged rows, ordered against the ledger's stream by events; the host route copies the batch's ids back once.
+ * The staged bytes are the same.  The draw's block is overwritten before the call returns (rlnamd_quota_info[5] is 0).
+ * Locks: the tree's, then the ledger's, both held for the call.  Refused before anything is drawn or enqueued, each with
+ * a text of its own: what submit_members refuses; a graph without a single messageId input (the multi-message-id
+ * circuit); a ledger whose depth is not the tree's; objects on different devices; a limit >= 2^32.
+ * rlnamd_prover_prove_stream_members_drawn: the chunked form.  All n ids are drawn first and every chunk reads its
+ * slice, so a call keeps the one-by-one meaning across chunks. */
+int rlnamd_prover_submit_members_drawn(rlnamd_prover* p, rlnamd_tree* t, rlnamd_quota* q, size_t n, const uint64_t* leaf_indices,
+                                       const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* status /* n */, uint64_t* ticket);
+int rlnamd_prover_prove_stream_members_drawn(rlnamd_prover* p, rlnamd_tree* t, rlnamd_quota* q, size_t n,
+                                             const uint64_t* leaf_indices, const uint8_t* inputs_le, const uint8_t* rs_le,
+                                             uint8_t* status /* n */, uint8_t* proofs /* n*128 */, uint8_t* values /* n*160 */,
+                                             uint32_t* errors /* n */);
+
 /* ---- variable-base MSM on G1 / G2 (BASELINE config 5; north_star: "windowed Pippenger MSM on G1/G2") ---------
  * Replaces VariableBaseMSM::msm_bigint (ark-ec 0.5.0; call sites rln/src/partial_proof.rs:98-104,255-256: generic
  * over the group) for large n with bases that are not fixed.  Multi-GPU: every rank runs rlnamd_msm_run on its slice of

@@ -1,0 +1,172 @@
+#!/usr/bin/env python3
+"""Quota-ledger throughput: rlnamd_quota_draw by itself, and proving with drawn ids against proving with ids the host
+supplies.
+
+    python tools/quota_draw_throughput.py [--calls 9] [--out FILE]
+
+prints ONE JSON line.  Torch-free (ctypes).  Each of the two steps runs in a child process of its own under a time
+limit; a step that fails or runs out of time ends the run there.
+
+  draw    a draw of 1 024, 8 192 and 65 536 requests on a depth-20 ledger with two open external nullifiers, in two
+          shapes: every request a member of its own, and every request the SAME member.  The limit is 2^32 - 1, so every
+          request is granted and the counters rise from call to call.  Leaf indices, external nullifiers and limits in,
+          ids and statuses out, the copies inside the timed region.  The two shapes take turns in one process; median
+          and min-max of `calls` calls after 2 warm-up calls each.  "one_member_over_distinct" is the ratio of the
+          medians: the draw's passes do not depend on how often members repeat, so it is expected near 1.
+  prove   rlnamd_prover_prove_stream_members_drawn against rlnamd_prover_prove_stream_members with the ids in the
+          inputs, 1 024 and 8 192 proofs for distinct members through a prover of capacity 1 024; the two take turns in
+          one process, median of `calls` calls after 1 warm-up call each.  "draw_share_1024" is the median of a
+          1 024-request draw (step draw, distinct) over the median of the drawn 1 024-proof call.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import random
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DRAW_SIZES = (1024, 8192, 65536)
+PROVE_SIZES = (1024, 8192)
+DEPTH = 20
+R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+EA, EB = 1001, 1002
+STEP_LIMIT_S = {"draw": 120, "prove": 420}
+
+
+def row(n, ts):
+    med = statistics.median(ts)
+    return {"n": n, "calls": len(ts), "median_ms": round(med * 1e3, 3), "min_ms": round(min(ts) * 1e3, 3),
+            "max_ms": round(max(ts) * 1e3, 3), "per_s": round(n / med, 1)}
+
+
+def need_device():
+    from zerokit_amd import lib
+    if lib().rlnamd_device_count() < 1:
+        raise SystemExit("quota_draw_throughput: no HIP device (there is no CPU fallback)")
+
+
+def step_draw(calls):
+    from zerokit_amd import lib
+    from zerokit_amd._native import check
+    from zerokit_amd.batch import QuotaLedger
+    need_device()
+    q = QuotaLedger(DEPTH, 4)
+    q.set_epochs([EA, EB])
+    rnd = random.Random(20261020)
+    rows = []
+    for n in DRAW_SIZES:
+        ext = b"".join((EA if i & 1 else EB).to_bytes(32, "little") for i in range(n))
+        limits = (C.c_uint32 * n)(*([0xFFFFFFFF] * n))
+        ids, status = (C.c_uint32 * n)(), C.create_string_buffer(n)
+        shapes = {"distinct": (C.c_uint64 * n)(*rnd.sample(range(1 << DEPTH), n)), "one_member": (C.c_uint64 * n)(*([12345] * n))}
+        ts = {k: [] for k in shapes}
+        for c in range(2 + calls):
+            for name, leaf in shapes.items():
+                t0 = time.perf_counter()
+                check(lib().rlnamd_quota_draw(q._h, n, leaf, ext, limits, ids, status))
+                t1 = time.perf_counter()
+                assert status.raw == b"\0" * n
+                if c >= 2:
+                    ts[name].append(t1 - t0)
+        r = {name: row(n, t) for name, t in ts.items()}
+        r["one_member_over_distinct"] = round(r["one_member"]["median_ms"] / r["distinct"]["median_ms"], 3)
+        r["plan"] = list(QuotaLedger.plan(n, DEPTH))
+        rows.append(r)
+    info = q.info()
+    q.close()
+    return {"depth": DEPTH, "rows": rows, "residue": info["residue"]}
+
+
+def step_prove(calls):
+    from zerokit_amd import lib
+    from zerokit_amd._native import check
+    from zerokit_amd.batch import BatchProver, PoseidonTree, QuotaLedger
+    need_device()
+    p = BatchProver(max_batch=1024)
+    tree = PoseidonTree(DEPTH)
+    tree.fill_sequential(0, max(PROVE_SIZES), 1)
+    q = QuotaLedger(DEPTH, 4)
+    q.set_epochs([EA, EB])
+    rnd = random.Random(7)
+    rows = []
+    for n in PROVE_SIZES:
+        ws = [dict(identity_secret=rnd.randrange(1, R), user_message_limit=1 << 20, message_id=i % 1000, x=rnd.randrange(R),
+                   external_nullifier=EA if i & 1 else EB) for i in range(n)]
+        inputs = p.pack_member_inputs(ws)
+        rsb = p.pack_rs([(rnd.randrange(1, R), rnd.randrange(1, R)) for _ in range(n)])
+        idx = (C.c_uint64 * n)(*range(n))
+        proofs, values = C.create_string_buffer(128 * n), C.create_string_buffer(160 * n)
+        errs, status = (C.c_uint32 * n)(), C.create_string_buffer(n)
+
+        def host_ids():
+            check(lib().rlnamd_prover_prove_stream_members(p._h, tree._h, n, idx, inputs, rsb, proofs, values, errs))
+
+        def drawn():
+            check(lib().rlnamd_prover_prove_stream_members_drawn(p._h, tree._h, q._h, n, idx, inputs, rsb, status, proofs, values, errs))
+        ts = {"host_ids": [], "drawn": []}
+        for c in range(1 + calls):
+            for name, fn in (("host_ids", host_ids), ("drawn", drawn)):
+                t0 = time.perf_counter()
+                fn()
+                t1 = time.perf_counter()
+                assert not any(errs)
+                if c >= 1:
+                    ts[name].append(t1 - t0)
+        assert status.raw == b"\0" * n
+        r = {name: row(n, t) for name, t in ts.items()}
+        r["drawn_over_host_ids"] = round(r["drawn"]["median_ms"] / r["host_ids"]["median_ms"], 4)
+        rows.append(r)
+    out = {"capacity": 1024, "rows": rows, "ledger_residue": q.info()["residue"]}
+    q.close()
+    tree.close()
+    p.close()
+    return out
+
+
+STEPS = {"draw": step_draw, "prove": step_prove}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=9)
+    ap.add_argument("--out")
+    ap.add_argument("--step", choices=sorted(STEPS))
+    a = ap.parse_args()
+    if a.calls < 5:
+        ap.error("--calls: at least 5")
+    if a.step:
+        print(json.dumps(STEPS[a.step](a.calls)))
+        return 0
+    out = {"tool": "quota_draw_throughput", "calls": a.calls}
+    for name in ("draw", "prove"):
+        try:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--calls", str(a.calls)],
+                               stdout=subprocess.PIPE, timeout=STEP_LIMIT_S[name])
+        except subprocess.TimeoutExpired:
+            out[name] = {"error": "time limit of %d s" % STEP_LIMIT_S[name]}
+            break
+        if r.returncode != 0:
+            out[name] = {"error": "exit status %d" % r.returncode}
+            break   # nothing more is started on the device after a failed step
+        out[name] = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    good = all("error" not in out.get(k, {"error": 1}) for k in STEPS)
+    if good:
+        draw_1024 = next(r["distinct"]["median_ms"] for r in out["draw"]["rows"] if r["distinct"]["n"] == 1024)
+        batch_1024 = next(r["drawn"]["median_ms"] for r in out["prove"]["rows"] if r["drawn"]["n"] == 1024)
+        out["draw_share_1024"] = round(draw_1024 / batch_1024, 4)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if good else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -103,6 +103,10 @@ SIGNATURES = {
                                                C.POINTER(C.c_uint64)]),
     "rlnamd_prover_prove_stream_members": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
                                                      C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
+    "rlnamd_prover_submit_members_drawn": (C.c_int, [P, P, P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
+                                                     C.c_char_p, C.POINTER(C.c_uint64)]),
+    "rlnamd_prover_prove_stream_members_drawn": (C.c_int, [P, P, P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
+                                                           C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
     "rlnamd_nullifier_log_new": (C.c_int, [C.c_size_t, C.c_uint64, PP]),
     "rlnamd_nullifier_log_free": (None, [P]),
     "rlnamd_nullifier_log_observe": (C.c_int, [P, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
@@ -127,6 +131,15 @@ SIGNATURES = {
     "rlnamd_relay_set_epochs": (C.c_int, [P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "rlnamd_relay_epochs": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_size_t)]),
     "rlnamd_relay_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "rlnamd_quota_new": (C.c_int, [C.c_size_t, C.c_size_t, PP]),
+    "rlnamd_quota_free": (None, [P]),
+    "rlnamd_quota_set_epochs": (C.c_int, [P, C.c_char_p, C.c_size_t]),
+    "rlnamd_quota_epochs": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_size_t)]),
+    "rlnamd_quota_draw": (C.c_int, [P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint32), C.c_char_p]),
+    "rlnamd_quota_used": (C.c_int, [P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p]),
+    "rlnamd_quota_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "rlnamd_quota_plan": (C.c_int, [C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]),
     "rlnamd_tree_fill_sequential": (C.c_int, [P, C.c_size_t, C.c_size_t, C.c_uint64]),
     "rlnamd_tree_bench": (C.c_int, [P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_size_t)]),
     "rlnamd_prover_new": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, PP]),
@@ -269,6 +282,8 @@ SIGNATURES = {
     "ffi_finish_rln_proofs_batch": (CBoolResult, [PP, PP, PP, C.c_size_t, CFRP, PP]),
     "ffi_generate_rln_proofs_for_members": (CBoolResult, [PP, C.POINTER(C.c_size_t), C.c_size_t, CFRP, CFRP, CFRP, CFRP,
                                                           CFRP, CFRP, PP]),
+    "ffi_generate_rln_proofs_for_members_drawn": (CBoolResult, [PP, P, C.POINTER(C.c_size_t), C.c_size_t, CFRP, CFRP, CFRP, CFRP,
+                                                                CFRP, C.c_char_p, PP]),
     "ffi_verify_rln_proof": (CBoolResult, [PP, PP, CFRP]),
     "ffi_verify_rln_proofs_batch": (CBoolResult, [PP, PP, C.c_size_t, CFRP, C.POINTER(VecCFr), C.POINTER(C.c_bool)]),
     "ffi_verify_rln_signals_batch": (CBoolResult, [PP, PP, C.c_size_t, C.POINTER(VecU8), C.POINTER(VecCFr),

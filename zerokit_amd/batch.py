@@ -221,6 +221,42 @@ class BatchProver:
         return _unpack_results(*self.prove_members_raw(tree, leaf_indices, self.pack_member_inputs(witnesses),
                                                        self.pack_rs(rs)))
 
+    def submit_members_drawn(self, tree: "PoseidonTree", quota: "QuotaLedger", leaf_indices, inputs: bytes, rsb: bytes):
+        """submit_members (full proofs) with the message ids drawn from `quota` on the device: the messageId slot of
+        `inputs` is ignored, each row's own limit and external nullifier make its request, one draw covers the call
+        (rlnamd_prover_submit_members_drawn).  Returns (ticket, n, statuses); a request that is not QuotaLedger.OK
+        collects with a non-zero error and no proof."""
+        n = len(inputs) // (self.inputs_size * 32)
+        if len(inputs) != n * self.inputs_size * 32 or len(rsb) != 64 * n or len(leaf_indices) != n:
+            raise RLNError("submit_members_drawn: leaf indices / inputs / rs sizes do not match")
+        idx = (C.c_uint64 * max(n, 1))(*[int(i) for i in leaf_indices])
+        t = C.c_uint64()
+        status = C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_prover_submit_members_drawn(self._h, tree._h, quota._h, n, idx, inputs, rsb, status, C.byref(t)))
+        return int(t.value), n, list(status.raw[:n])
+
+    def prove_members_drawn_raw(self, tree: "PoseidonTree", quota: "QuotaLedger", leaf_indices, inputs: bytes, rsb: bytes):
+        """any n members through rlnamd_prover_prove_stream_members_drawn: one draw for all n, chunks of `capacity`
+        -> (proofs, values, errors, statuses)"""
+        n = len(inputs) // (self.inputs_size * 32)
+        if len(inputs) != n * self.inputs_size * 32 or len(rsb) != 64 * n or len(leaf_indices) != n:
+            raise RLNError("prove_members_drawn: leaf indices / inputs / rs sizes do not match")
+        idx = (C.c_uint64 * max(n, 1))(*[int(i) for i in leaf_indices])
+        proofs = C.create_string_buffer(128 * n)
+        values = C.create_string_buffer(160 * n)
+        errs = (C.c_uint32 * max(n, 1))()
+        status = C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_prover_prove_stream_members_drawn(self._h, tree._h, quota._h, n, idx, inputs, rsb, status, proofs,
+                                                             values, errs))
+        return proofs.raw, values.raw, list(errs)[:n], list(status.raw[:n])
+
+    def prove_members_drawn(self, tree: "PoseidonTree", quota: "QuotaLedger", leaf_indices, witnesses, rs):
+        """witnesses: dicts with identity_secret, user_message_limit, x and external_nullifier, one per leaf index; a
+        message_id, if given, is ignored -> (results as prove_members gives them, statuses)"""
+        ws = [dict(w, message_id=0) for w in witnesses]
+        p, v, e, st = self.prove_members_drawn_raw(tree, quota, leaf_indices, self.pack_member_inputs(ws), self.pack_rs(rs))
+        return _unpack_results(p, v, e), st
+
     def hints_for(self, inputs: bytes):
         """the hints of the proofs packed in `inputs`, one proof at a time on this thread (rlnamd_prover_hints_for): a list
         of ctypes arrays, or None when the circuit has no segments form"""
@@ -865,6 +901,80 @@ class NullifierLog:
         out = (C.c_uint64 * 8)()
         check(lib().rlnamd_nullifier_log_info(self._h, out))
         return [int(v) for v in out]
+
+
+class QuotaLedger:
+    """Device-resident ledger of the message ids a signer has handed out (rlnamd_quota_*): max_epochs x 2^depth counters,
+    the next message id of each member under each external nullifier of the window, and draw(), which hands out the
+    next ids of a batch of requests.  A request past its member's limit gets no id, so no proof, and no two proofs under
+    one (external nullifier, member) ever carry the same id -- the NullifierLog of a relay never says SPAM.
+
+    An external nullifier that has left the window must not come back (its counters are gone), and the ledger is not
+    persisted: a restarted process must not sign under an external nullifier that was open before the restart."""
+    OK, OVER, NO_EPOCH = range(3)
+    EPOCHS_MAX = 64
+    INFO = ("window", "draws", "issued", "over", "no_epoch", "residue", "depth", "max_epochs")
+
+    def __init__(self, depth, max_epochs):
+        self._h = C.c_void_p()
+        check(lib().rlnamd_quota_new(depth, max_epochs, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rlnamd_quota_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_epochs(self, external_nullifiers):
+        """0 .. max_epochs external nullifiers (ints): one that stays keeps its counters, one that leaves loses them,
+        a new one starts at zero; an empty list empties the window"""
+        check(lib().rlnamd_quota_set_epochs(self._h, b"".join(_b(e) for e in external_nullifiers), len(external_nullifiers)))
+
+    def epochs(self):
+        """the window in the order it was given, duplicates once: a list of ints"""
+        out = C.create_string_buffer(32 * self.EPOCHS_MAX)
+        k = C.c_size_t()
+        check(lib().rlnamd_quota_epochs(self._h, out, C.byref(k)))
+        return [int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(k.value)]
+
+    def draw(self, leaf_indices, external_nullifiers, limits):
+        """n requests -> (ids, statuses), two lists of ints; ids[i] is limits[i] where statuses[i] is not OK"""
+        n = len(leaf_indices)
+        if len(external_nullifiers) != n or len(limits) != n:
+            raise RLNError("QuotaLedger.draw: %d leaf indices, %d external nullifiers, %d limits" % (n, len(external_nullifiers), len(limits)))
+        ids, status = (C.c_uint32 * max(n, 1))(), C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_quota_draw(self._h, n, (C.c_uint64 * max(n, 1))(*[int(v) for v in leaf_indices]),
+                                      b"".join(_b(e) for e in external_nullifiers) or b"\0",
+                                      (C.c_uint32 * max(n, 1))(*[int(v) for v in limits]), ids, status))
+        return list(ids[:n]), list(status.raw[:n])
+
+    def used(self, leaf_indices, external_nullifiers):
+        """the counters of n (leaf, external nullifier) pairs -> [next id, or None outside the window]"""
+        n = len(leaf_indices)
+        if len(external_nullifiers) != n:
+            raise RLNError("QuotaLedger.used: %d leaf indices, %d external nullifiers" % (n, len(external_nullifiers)))
+        out, inside = (C.c_uint32 * max(n, 1))(), C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_quota_used(self._h, n, (C.c_uint64 * max(n, 1))(*[int(v) for v in leaf_indices]),
+                                      b"".join(_b(e) for e in external_nullifiers) or b"\0", out, inside))
+        return [int(out[i]) if inside.raw[i] else None for i in range(n)]
+
+    def info(self):
+        out = (C.c_uint64 * 8)()
+        check(lib().rlnamd_quota_info(self._h, out))
+        return dict(zip(self.INFO, (int(v) for v in out)))
+
+    @staticmethod
+    def plan(n, depth):
+        """the passes of a draw of n requests: (sort passes, workgroups a pass, scan levels over a pass's bins, scan
+        levels over the requests); no device needed"""
+        out = (C.c_uint64 * 4)()
+        check(lib().rlnamd_quota_plan(n, depth, out))
+        return tuple(int(v) for v in out)
 
 
 class Hasher:

@@ -416,6 +416,77 @@ int rlnamd_relay_info(rlnamd_relay* r, uint64_t out[8]) {
   RLN_CATCH
 }
 
+// ------------------------------------------------------------------------------------- quota ledger
+static_assert(RLNAMD_QUOTA_OK == quota::OK && RLNAMD_QUOTA_OVER == quota::OVER && RLNAMD_QUOTA_NO_EPOCH == quota::NO_EPOCH &&
+                  RLNAMD_RELAY_EPOCHS_MAX == quota::EPOCHS_MAX,
+              "the ledger's statuses and window");
+int rlnamd_quota_new(size_t depth, size_t max_epochs, rlnamd_quota** out) {
+  RLN_TRY
+  // what needs no device is checked before one is asked for
+  const std::string refused = quota::new_refusal(depth, max_epochs);
+  if (!refused.empty()) throw Error(refused);
+  if (!out) throw Error("rlnamd_quota_new: null pointer");
+  *out = new rlnamd_quota(depth, max_epochs);
+  RLN_CATCH
+}
+void rlnamd_quota_free(rlnamd_quota* q) { delete q; }
+int rlnamd_quota_set_epochs(rlnamd_quota* q, const uint8_t* external_nullifiers_le, size_t k) {
+  RLN_TRY
+  // what needs no object is judged without one (the ledger judges the same with its own max_epochs, before it enqueues)
+  if (!q) {
+    const std::string refused = quota::epochs_refusal(external_nullifiers_le, k, quota::EPOCHS_MAX);
+    throw Error(refused.empty() ? "rlnamd_quota_set_epochs: null ledger" : refused);
+  }
+  std::lock_guard<std::mutex> lk(q->mu);
+  q->ledger.set_epochs(k, external_nullifiers_le);
+  RLN_CATCH
+}
+int rlnamd_quota_epochs(rlnamd_quota* q, uint8_t* out_le, size_t* k) {
+  RLN_TRY
+  if (!q || !out_le || !k) throw Error("rlnamd_quota_epochs: null pointer");
+  std::lock_guard<std::mutex> lk(q->mu);
+  *k = q->ledger.epochs(out_le);
+  RLN_CATCH
+}
+int rlnamd_quota_draw(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
+                      uint32_t* ids_out, uint8_t* status) {
+  RLN_TRY
+  // what needs no object is judged without one (the ledger judges the same with its own depth, before it enqueues)
+  if (!q) {
+    const std::string refused = quota::draw_refusal(n, leaf_indices, ext_le, limits, ids_out, status, quota::DEPTH_MAX);
+    throw Error(refused.empty() ? "rlnamd_quota_draw: null ledger" : refused);
+  }
+  std::lock_guard<std::mutex> lk(q->mu);
+  q->ledger.draw(n, leaf_indices, ext_le, limits, ids_out, status);
+  RLN_CATCH
+}
+int rlnamd_quota_used(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, uint32_t* used_out,
+                      uint8_t* in_window) {
+  RLN_TRY
+  if (!q) throw Error("rlnamd_quota_used: null ledger");
+  std::lock_guard<std::mutex> lk(q->mu);
+  q->ledger.used(n, leaf_indices, ext_le, used_out, in_window);
+  RLN_CATCH
+}
+int rlnamd_quota_info(rlnamd_quota* q, uint64_t out[8]) {
+  RLN_TRY
+  if (!q || !out) throw Error("rlnamd_quota_info: null pointer");
+  std::lock_guard<std::mutex> lk(q->mu);
+  q->ledger.info(out);
+  RLN_CATCH
+}
+int rlnamd_quota_plan(size_t n, size_t depth, uint64_t out[4]) {
+  RLN_TRY
+  if (!out) throw Error("rlnamd_quota_plan: null pointer");
+  if (depth < 1 || depth > quota::DEPTH_MAX) throw Error(quota::new_refusal(depth, 1));
+  const quota::DrawPlan P = quota::plan_for(n, (uint32_t)depth);
+  out[0] = P.passes;
+  out[1] = P.blocks;
+  out[2] = P.bin_levels;
+  out[3] = P.rank_levels;
+  RLN_CATCH
+}
+
 // -------------------------------------------------------------------------------------------- prover
 int rlnamd_prover_new(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_t graph_len, size_t max_batch,
                       int window_bits, rlnamd_prover** out) {
@@ -581,6 +652,26 @@ int rlnamd_prover_prove_stream_members(rlnamd_prover* p, rlnamd_tree* t, size_t 
   if (!p || !t) throw Error("rlnamd_prover_prove_stream_members: null pointer");
   std::lock_guard<std::mutex> tree_lk(t->mu);
   p->p->prove_stream_members(member_tree(t), n, leaf_indices, inputs_le, rs_le, proofs, values, errors);
+  RLN_CATCH
+}
+// (lock order: the tree's, then the ledger's; both are held from the draw to the wipe of its block)
+int rlnamd_prover_submit_members_drawn(rlnamd_prover* p, rlnamd_tree* t, rlnamd_quota* q, size_t n, const uint64_t* leaf_indices,
+                                       const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* status, uint64_t* ticket) {
+  RLN_TRY
+  if (!p || !t || !q || !ticket) throw Error("rlnamd_prover_submit_members_drawn: null pointer");
+  std::lock_guard<std::mutex> tree_lk(t->mu);
+  std::lock_guard<std::mutex> quota_lk(q->mu);
+  *ticket = p->p->submit_members_drawn(member_tree(t), q->ledger, n, leaf_indices, inputs_le, rs_le, status);
+  RLN_CATCH
+}
+int rlnamd_prover_prove_stream_members_drawn(rlnamd_prover* p, rlnamd_tree* t, rlnamd_quota* q, size_t n, const uint64_t* leaf_indices,
+                                             const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* status, uint8_t* proofs,
+                                             uint8_t* values, uint32_t* errors) {
+  RLN_TRY
+  if (!p || !t || !q) throw Error("rlnamd_prover_prove_stream_members_drawn: null pointer");
+  std::lock_guard<std::mutex> tree_lk(t->mu);
+  std::lock_guard<std::mutex> quota_lk(q->mu);
+  p->p->prove_stream_members_drawn(member_tree(t), q->ledger, n, leaf_indices, inputs_le, rs_le, status, proofs, values, errors);
   RLN_CATCH
 }
 int rlnamd_prover_run_mode(rlnamd_prover* p, size_t n, int mode) {

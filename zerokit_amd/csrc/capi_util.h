@@ -11,6 +11,7 @@
 #include "msm.h"
 #include "nullifier_log.h"
 #include "prover.h"
+#include "quota_ledger.h"
 
 namespace rlnamd {
 extern thread_local std::string g_last_error;
@@ -53,6 +54,12 @@ struct rlnamd_hasher {
   std::mutex mu;
   rlnamd::HasherDev hasher;
   rlnamd_hasher(size_t stage_bytes, size_t lane_max_blocks) : hasher(stage_bytes, lane_max_blocks) {}
+};
+struct rlnamd_quota {
+  // one stream and one per-call block per ledger: every call on a handle takes this
+  std::mutex mu;
+  rlnamd::QuotaLedgerDev ledger;
+  rlnamd_quota(size_t depth, size_t max_epochs) : ledger(depth, max_epochs) {}
 };
 struct rlnamd_msm {   // one of the two (rlnamd_msm_new / rlnamd_msm_new_g2)
   std::unique_ptr<rlnamd::MsmG1> m;

@@ -1733,77 +1733,114 @@ CBoolResult_t ffi_generate_rln_proofs_batch(FFI_RLN_t* const* rln, FFI_RLNWitnes
 // EXT: n proofs for members of the object's OWN tree, named by leaf index -- no Merkle path crosses the boundary.  The paths
 // are read from the tree on the device into the batch's staged inputs (Prover::submit_members); replica 0 proves, with
 // the tree locked for the whole call, so all n proofs are at one root.
+// quota: null, or the ledger the message ids are drawn from (ffi_generate_rln_proofs_for_members_drawn: message_ids is
+// null then, status takes the draw's answers, and out[i] is null where no proof was made)
+static bool proofs_for_members(const char* who, FFI_RLN_t* const* rln, rlnamd_quota* quota, const size_t* leaf_indices, size_t n,
+                               const CFr_t* identity_secrets, const CFr_t* user_message_limits, const CFr_t* message_ids,
+                               const CFr_t* xs, const CFr_t* external_nullifiers, const CFr_t* rs, uint8_t* status,
+                               FFI_RLNProof_t** out) {
+  if (n == 0) return true;
+  const std::string name(who);
+  if (!rln || !*rln) throw Error(name + ": null RLN object");
+  if (!leaf_indices || !identity_secrets || !user_message_limits || (!quota && !message_ids) || !xs || !external_nullifiers || !out)
+    throw Error(name + ": null argument");
+  FFI_RLN& r = *(FFI_RLN*)*rln;
+  if (r.stateless) throw Error(name + ": the object has no tree");
+  std::lock_guard<std::mutex> guard(*r.prove_mu);
+  Prover& P = *r.prover;
+  if (P.graph().max_out != 1 || P.graph().input_mapping.count("selectorUsed"))
+    throw Error(name + ": single message-id circuits only");
+  if (r.auto_partial) r.memo_adopt_pending();
+  const size_t cap = P.capacity(), ni = P.inputs_per_proof(), d = P.graph().tree_depth;
+  std::vector<uint8_t> inputs(n * ni * 32), rsb(n * 64), idx8(n * 8);
+  ZeroOnExit z1{inputs}, z2{rsb}, z3{idx8};   // (who proves is a secret as well)
+  uint64_t* idx = reinterpret_cast<uint64_t*>(idx8.data());
+  {
+    FFI_RLNWitnessInput w;   // the witness constructor's checks and texts (validate_witness), the path left to the device
+    w.path_elements.assign(d, cfr_from_u64(0));
+    w.identity_path_index.assign(d, 0);
+    for (size_t i = 0; i < n; i++) {
+      w.identity_secret = R(&identity_secrets[i]);
+      w.user_message_limit = R(&user_message_limits[i]);
+      w.message_id = quota ? cfr_from_u64(0) : R(&message_ids[i]);   // (drawn: the slot is overwritten with the id drawn)
+      w.x = R(&xs[i]);
+      w.external_nullifier = R(&external_nullifiers[i]);
+      validate_witness(w);
+      fill_inputs(P, w, inputs.data() + i * ni * 32);
+      const CFr rr = rs ? R(&rs[2 * i]) : random_fr(), ss = rs ? R(&rs[2 * i + 1]) : random_fr();
+      memcpy(rsb.data() + i * 64, rr.le, 32);
+      memcpy(rsb.data() + i * 64 + 32, ss.le, 32);
+      idx[i] = leaf_indices[i];
+    }
+  }
+  std::vector<uint8_t> proofs(n * 128), values(n * 160);
+  std::vector<uint32_t> errs(n);
+  {
+    // the tree's lock, from the flush of its pending writes to the event that orders later writes behind the gather
+    std::lock_guard<std::mutex> tree_lk(r.tree.pend->mu);
+    r.tree.flush_pending_locked();
+    MemberTree mt;
+    mt.dense = r.tree.sparse ? nullptr : &r.tree.dense;
+    mt.depth = r.tree.depth;
+    mt.proofs_at = [&](const uint64_t* ix, size_t k, uint8_t* e, uint8_t* b) { r.tree.proofs_at_locked(ix, k, e, b); };
+    if (quota) {   // the order of the locks: prover, tree, ledger
+      std::lock_guard<std::mutex> quota_lk(quota->mu);
+      if (n <= cap) {
+        const uint64_t ticket = P.submit_members_drawn(mt, quota->ledger, n, idx, inputs.data(), rsb.data(), status);
+        P.collect(ticket, n, proofs.data(), values.data(), errs.data());
+      } else {
+        P.prove_stream_members_drawn(mt, quota->ledger, n, idx, inputs.data(), rsb.data(), status, proofs.data(), values.data(),
+                                     errs.data());
+      }
+    } else if (n <= cap) {
+      const uint64_t ticket = P.submit_members(mt, n, idx, inputs.data(), rsb.data(), PROVE_FULL);
+      P.collect(ticket, n, proofs.data(), values.data(), errs.data());
+    } else {   // streamed on this prover: the replicas of a pool hold no tree
+      P.prove_stream_members(mt, n, idx, inputs.data(), rsb.data(), proofs.data(), values.data(), errs.data());
+    }
+  }
+  for (size_t i = 0; i < n; i++)
+    if (errs[i] && !(quota && status[i] != quota::OK))
+      throw Error("Error calculating witness: graph evaluation failed (code " + std::to_string(errs[i]) + ")");
+  std::vector<std::unique_ptr<FFI_RLNProof>> made;
+  for (size_t i = 0; i < n; i++) {
+    if (quota && status[i] != quota::OK) {
+      made.push_back(nullptr);
+      continue;
+    }
+    std::unique_ptr<FFI_RLNProof> pr(new FFI_RLNProof);
+    memcpy(pr->proof, proofs.data() + 128 * i, 128);
+    const uint8_t* v = values.data() + 160 * i;
+    memcpy(pr->values.y.le, v, 32);
+    memcpy(pr->values.root.le, v + 32, 32);
+    memcpy(pr->values.nullifier.le, v + 64, 32);
+    memcpy(pr->values.x.le, v + 96, 32);
+    memcpy(pr->values.external_nullifier.le, v + 128, 32);
+    made.push_back(std::move(pr));
+  }
+  for (size_t i = 0; i < n; i++) out[i] = (FFI_RLNProof_t*)made[i].release();
+  return true;
+}
 CBoolResult_t ffi_generate_rln_proofs_for_members(FFI_RLN_t* const* rln, const size_t* leaf_indices, size_t n,
                                                   const CFr_t* identity_secrets, const CFr_t* user_message_limits,
                                                   const CFr_t* message_ids, const CFr_t* xs,
                                                   const CFr_t* external_nullifiers, const CFr_t* rs, FFI_RLNProof_t** out) {
   return guard_bool([&]() {
+    return proofs_for_members("ffi_generate_rln_proofs_for_members", rln, nullptr, leaf_indices, n, identity_secrets,
+                              user_message_limits, message_ids, xs, external_nullifiers, rs, nullptr, out);
+  });
+}
+// EXT: the same with the message ids drawn from a quota ledger on the device (Prover::submit_members_drawn)
+CBoolResult_t ffi_generate_rln_proofs_for_members_drawn(FFI_RLN_t* const* rln, struct rlnamd_quota* quota, const size_t* leaf_indices,
+                                                        size_t n, const CFr_t* identity_secrets, const CFr_t* user_message_limits,
+                                                        const CFr_t* xs, const CFr_t* external_nullifiers, const CFr_t* rs,
+                                                        uint8_t* status, FFI_RLNProof_t** out) {
+  return guard_bool([&]() {
     if (n == 0) return true;
-    if (!rln || !*rln) throw Error("ffi_generate_rln_proofs_for_members: null RLN object");
-    if (!leaf_indices || !identity_secrets || !user_message_limits || !message_ids || !xs || !external_nullifiers || !out)
-      throw Error("ffi_generate_rln_proofs_for_members: null argument");
-    FFI_RLN& r = *(FFI_RLN*)*rln;
-    if (r.stateless) throw Error("ffi_generate_rln_proofs_for_members: the object has no tree");
-    std::lock_guard<std::mutex> guard(*r.prove_mu);
-    Prover& P = *r.prover;
-    if (P.graph().max_out != 1 || P.graph().input_mapping.count("selectorUsed"))
-      throw Error("ffi_generate_rln_proofs_for_members: single message-id circuits only");
-    if (r.auto_partial) r.memo_adopt_pending();
-    const size_t cap = P.capacity(), ni = P.inputs_per_proof(), d = P.graph().tree_depth;
-    std::vector<uint8_t> inputs(n * ni * 32), rsb(n * 64), idx8(n * 8);
-    ZeroOnExit z1{inputs}, z2{rsb}, z3{idx8};   // (who proves is a secret as well)
-    uint64_t* idx = reinterpret_cast<uint64_t*>(idx8.data());
-    {
-      FFI_RLNWitnessInput w;   // the witness constructor's checks and texts (validate_witness), the path left to the device
-      w.path_elements.assign(d, cfr_from_u64(0));
-      w.identity_path_index.assign(d, 0);
-      for (size_t i = 0; i < n; i++) {
-        w.identity_secret = R(&identity_secrets[i]);
-        w.user_message_limit = R(&user_message_limits[i]);
-        w.message_id = R(&message_ids[i]);
-        w.x = R(&xs[i]);
-        w.external_nullifier = R(&external_nullifiers[i]);
-        validate_witness(w);
-        fill_inputs(P, w, inputs.data() + i * ni * 32);
-        const CFr rr = rs ? R(&rs[2 * i]) : random_fr(), ss = rs ? R(&rs[2 * i + 1]) : random_fr();
-        memcpy(rsb.data() + i * 64, rr.le, 32);
-        memcpy(rsb.data() + i * 64 + 32, ss.le, 32);
-        idx[i] = leaf_indices[i];
-      }
-    }
-    std::vector<uint8_t> proofs(n * 128), values(n * 160);
-    std::vector<uint32_t> errs(n);
-    {
-      // the tree's lock, from the flush of its pending writes to the event that orders later writes behind the gather
-      std::lock_guard<std::mutex> tree_lk(r.tree.pend->mu);
-      r.tree.flush_pending_locked();
-      MemberTree mt;
-      mt.dense = r.tree.sparse ? nullptr : &r.tree.dense;
-      mt.depth = r.tree.depth;
-      mt.proofs_at = [&](const uint64_t* ix, size_t k, uint8_t* e, uint8_t* b) { r.tree.proofs_at_locked(ix, k, e, b); };
-      if (n <= cap) {
-        const uint64_t ticket = P.submit_members(mt, n, idx, inputs.data(), rsb.data(), PROVE_FULL);
-        P.collect(ticket, n, proofs.data(), values.data(), errs.data());
-      } else {   // streamed on this prover: the replicas of a pool hold no tree
-        P.prove_stream_members(mt, n, idx, inputs.data(), rsb.data(), proofs.data(), values.data(), errs.data());
-      }
-    }
-    for (size_t i = 0; i < n; i++)
-      if (errs[i]) throw Error("Error calculating witness: graph evaluation failed (code " + std::to_string(errs[i]) + ")");
-    std::vector<std::unique_ptr<FFI_RLNProof>> made;
-    for (size_t i = 0; i < n; i++) {
-      std::unique_ptr<FFI_RLNProof> pr(new FFI_RLNProof);
-      memcpy(pr->proof, proofs.data() + 128 * i, 128);
-      const uint8_t* v = values.data() + 160 * i;
-      memcpy(pr->values.y.le, v, 32);
-      memcpy(pr->values.root.le, v + 32, 32);
-      memcpy(pr->values.nullifier.le, v + 64, 32);
-      memcpy(pr->values.x.le, v + 96, 32);
-      memcpy(pr->values.external_nullifier.le, v + 128, 32);
-      made.push_back(std::move(pr));
-    }
-    for (size_t i = 0; i < n; i++) out[i] = (FFI_RLNProof_t*)made[i].release();
-    return true;
+    if (!quota) throw Error("ffi_generate_rln_proofs_for_members_drawn: null ledger");
+    if (!status) throw Error("ffi_generate_rln_proofs_for_members_drawn: null argument");
+    return proofs_for_members("ffi_generate_rln_proofs_for_members_drawn", rln, quota, leaf_indices, n, identity_secrets,
+                              user_message_limits, nullptr, xs, external_nullifiers, rs, status, out);
   });
 }
 CBoolResult_t ffi_verify_rln_proof(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proof, const CFr_t* x) {

@@ -109,7 +109,14 @@ struct MemberTree {
 struct MemberGather {   // enqueue's view of a device-route members batch
   MerkleTreeDev* tree;
   const uint64_t* leaf;
+  // message ids drawn from a quota ledger (submit_members_drawn): the batch's ids on the device and the ledger's stream
+  // (a hipStream_t), which has written them; null: the message ids are the caller's
+  const uint32_t* ids = nullptr;
+  const uint8_t* ids_status = nullptr;   // ... and the draw's statuses beside them: a refused request gets no field element
+  void* ids_stream = nullptr;
 };
+struct QuotaLedgerDev;
+struct DrawnIds;   // prover.hip: a held draw and where a chunk's ids start in it
 
 class Prover {
  public:
@@ -172,6 +179,22 @@ class Prover {
                           const uint8_t* rs, int mode = PROVE_FULL);
   void prove_stream_members(const MemberTree& tree, size_t n, const uint64_t* leaf_indices, const uint8_t* inputs,
                             const uint8_t* rs, uint8_t* proofs, uint8_t* values, uint32_t* errors);
+  // submit_members(PROVE_FULL) with the message ids drawn from a quota ledger (quota_ledger.h): the messageId slot of
+  // `inputs` is ignored, each proof's limit and external nullifier are read from its own input row, ONE draw covers the
+  // call, and status[i] is the draw's answer.  A request that is not OK gets a messageId that is no field element, which
+  // the witness interpreter refuses: errors[i] != 0, and collect hands out 128 zero proof bytes for every row of such a
+  // batch that has an error.  On the device route the ids never visit
+  // the host: a kernel behind the staging writes them into the staged rows, ordered against the ledger's stream by
+  // events; the host route (submit_members) copies the batch's ids back once.  The staged bytes are the same.  Refused
+  // before anything is enqueued or drawn, each with its own text: what submit_members refuses, a graph without a single
+  // messageId input (the multi-message-id circuit), a ledger of another depth or on another device, a limit >= 2^32.
+  // The caller holds the tree's lock and the ledger's, taken in that order.  prove_stream_members_drawn: the chunked
+  // form; all n ids are drawn first and every chunk reads its slice, so the call keeps the one-by-one meaning across chunks.
+  uint64_t submit_members_drawn(const MemberTree& tree, QuotaLedgerDev& quota, size_t n, const uint64_t* leaf_indices,
+                                const uint8_t* inputs, const uint8_t* rs, uint8_t* status);
+  void prove_stream_members_drawn(const MemberTree& tree, QuotaLedgerDev& quota, size_t n, const uint64_t* leaf_indices,
+                                  const uint8_t* inputs, const uint8_t* rs, uint8_t* status, uint8_t* proofs, uint8_t* values,
+                                  uint32_t* errors);
   // The hints of a lone small batch (the values between the circuit's chained hashes: prover_plan.h, HintChains) may be
   // computed ahead of the call, by any thread, one proof at a time: hint_words() 32-bit words per proof (0: this circuit
   // has no such form), hints_for() fills them from one proof's packed inputs.  submit_hinted() is submit() for a full
@@ -198,7 +221,7 @@ class Prover {
   typedef std::function<bool(size_t* off, size_t* cnt)> ChunkSource;
   void prove_stream_from(const ChunkSource& next, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs, uint8_t* values,
                          uint32_t* errors, int max_in_flight = 0, const MemberTree* tree = nullptr,
-                         const uint64_t* leaf_indices = nullptr);
+                         const uint64_t* leaf_indices = nullptr, const DrawnIds* drawn = nullptr);
   void prove_stream(size_t n, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs, uint8_t* values,
                     uint32_t* errors);
   // Partial proofs.  PROVE_PARTIAL: inputs carry only the partial witness (unknown slots zero); the result is
@@ -272,6 +295,11 @@ class Prover {
                    const uint64_t* cone_handles = nullptr, const uint32_t* pre_hints = nullptr,
                    const MemberGather* members = nullptr);
   void check_members(const MemberTree& tree, size_t n, const uint64_t* leaf_indices) const;
+  uint64_t submit_members_by(const MemberTree& tree, size_t n, const uint64_t* leaf_indices, const uint8_t* inputs,
+                             const uint8_t* rs, int mode, const DrawnIds* drawn);
+  // the checks of a drawn batch behind check_members; fills the draw's limits and external nullifiers from the rows
+  void check_drawn(const MemberTree& tree, const QuotaLedgerDev& quota, size_t n, const uint8_t* inputs,
+                   std::vector<uint32_t>* limits, std::vector<uint8_t>* ext_le) const;
   void fetch_public_slot(void* slot, size_t n, std::vector<uint8_t>* out_le);
   void residue_of(void* slot, uint64_t out[RESIDUE_SLOT_FIELDS]);
   struct Impl;

@@ -30,6 +30,7 @@
 #include "witness_sched.h"
 #include "fin29.h"
 #include "merkle.h"
+#include "quota_ledger.h"
 #include "ffi_wire.h"   // secure_zero
 
 namespace rlnamd {
@@ -103,7 +104,9 @@ struct Slot {
   DevBuf<uint64_t> idx;
   uint64_t* h_idx = nullptr;
   hipEvent_t evT = nullptr, evG = nullptr;   // the tree's stream up to the gather; the gather done
+  hipEvent_t evQ = nullptr;                  // a quota ledger's stream up to the write of the batch's drawn message ids
   bool members = false;
+  bool drawn = false;           // ... with message ids drawn from a quota ledger: collect hands out no proof bytes for a refused row
   uint32_t seq = 0;             // the batch's sequence number (Impl::seq) and whether it took the big-batch streams
   bool big = false;             // (prover_plan.h: stream_plan): which stream its wipe goes to
 };
@@ -317,6 +320,8 @@ struct Prover::Impl {
   InputSlots slots{};
   bool have_path_slots = false;           // the graph names pathElements and identityPathIndex (submit_members)
   uint32_t path_off = 0, path_idx_off = 0;
+  bool have_drawn_slots = false;          // ... and userMessageLimit, externalNullifier and ONE messageId (submit_members_drawn)
+  uint32_t drawn_msg_off = 0;
   bool have_values_kernel = false;
   // resident inputs (shared by both slots; upload() drains the pipeline first)
   DevBuf<uint32_t> inputs, rs;
@@ -333,6 +338,10 @@ struct Prover::Impl {
   // its (r, s) and the witness values, on the back-end stream behind the batch's last reader; evC is recorded again, so
   // whoever reuses the slot -- or reads the resident inputs next -- waits for the wipe as well.
   size_t batch_cap = 0;   // = Prover::B_
+  void mark_drawn(uint64_t ticket) {   // the batch behind `ticket` carries message ids drawn from a quota ledger
+    for (int k = 0; k < nslot; k++)
+      if (slot[k].used && slot[k].ticket == ticket && ticket != 0) slot[k].drawn = true;
+  }
   void wipe_slot(Slot& S, bool resident) {
     const size_t n = S.n ? S.n : batch_cap;
     const size_t B = batch_cap;
@@ -655,6 +664,8 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
   D.have_path_slots = named.have_path_slots;
   D.path_off = named.path_off;
   D.path_idx_off = named.path_idx_off;
+  D.have_drawn_slots = named.have_drawn_slots;
+  D.drawn_msg_off = named.drawn_msg_off;
   D.hints.configure(named, D.tune.hint_chains);
   // ---- where the graph can be cut (segments behind hints; find_hint_cuts): a circuit on which a hint matches no node
   //      keeps the whole-graph interpreter
@@ -902,6 +913,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     memset(S.h_idx, 0, B * 8);
     RLN_HIP(hipEventCreateWithFlags(&S.evT, hipEventDisableTiming));
     RLN_HIP(hipEventCreateWithFlags(&S.evG, hipEventDisableTiming));
+    RLN_HIP(hipEventCreateWithFlags(&S.evQ, hipEventDisableTiming));
     RLN_HIP(hipHostMalloc((void**)&S.h_hints, (size_t)HINT_PROOFS * 64 * 32, hipHostMallocDefault));
     memset(S.h_hints, 0, (size_t)HINT_PROOFS * 64 * 32);
     RLN_HIP(hipEventCreateWithFlags(&S.evU, hipEventDisableTiming));
@@ -960,6 +972,7 @@ Prover::~Prover() {
     if (S.h_idx) (void)hipHostFree(S.h_idx);
     if (S.evT) (void)hipEventDestroy(S.evT);
     if (S.evG) (void)hipEventDestroy(S.evG);
+    if (S.evQ) (void)hipEventDestroy(S.evQ);
     if (S.h_hints) {   // (a slot whose batch was never collected, or whose wipe threw above)
       secure_zero(S.h_hints, (size_t)HINT_PROOFS * 64 * 32);
       (void)hipHostFree(S.h_hints);
@@ -1097,8 +1110,94 @@ void Prover::check_members(const MemberTree& t, size_t n, const uint64_t* leaf) 
       throw Error("submit_members: leaf index " + std::to_string(leaf[i]) + " is outside a tree of depth " + std::to_string(t.depth));
 }
 
+// a held draw of a quota ledger (QuotaLedgerDev::draw_hold) and where the ids of the batch at hand start in it
+struct DrawnIds {
+  QuotaLedgerDev* quota;
+  QuotaLedgerDev::Held held;
+  const uint8_t* status;   // the draw's statuses on the host (the caller's array), from request 0
+  size_t first;
+};
+
 uint64_t Prover::submit_members(const MemberTree& t, size_t n, const uint64_t* leaf, const uint8_t* inputs, const uint8_t* rs,
                                 int mode) {
+  return submit_members_by(t, n, leaf, inputs, rs, mode, nullptr);
+}
+
+// Message ids drawn from a quota ledger.  The draw runs first, on the ledger's stream, and only its statuses come back;
+// the ids stay in the draw's block on the device until the batch's kernel has copied them into the staged rows (enqueue)
+// -- or, on the host route, until one copy has brought them back -- and the block is overwritten before the call returns.
+void Prover::check_drawn(const MemberTree& t, const QuotaLedgerDev& q, size_t n, const uint8_t* inputs, std::vector<uint32_t>* limits,
+                         std::vector<uint8_t>* ext_le) const {
+  const Impl& D = *d_;
+  if (!D.have_drawn_slots)
+    throw Error("submit_members_drawn: the witness graph names no single messageId input beside userMessageLimit and "
+                "externalNullifier (the multi-message-id circuit takes several ids a proof)");
+  if (q.depth() != t.depth)
+    throw Error("submit_members_drawn: the ledger's depth (" + std::to_string(q.depth()) + ") is not the tree's (" +
+                std::to_string(t.depth) + ")");
+  if (q.device() != D.device.dev) throw Error("submit_members_drawn: the ledger and the prover are on different devices");
+  const size_t NIB = (size_t)D.NI * 32;
+  limits->resize(n);
+  ext_le->resize(32 * n);
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t* limit = inputs + i * NIB + (size_t)D.slots.limit * 32;
+    uint8_t high = 0;
+    for (int b = 4; b < 32; b++) high |= limit[b];
+    if (high) throw Error("submit_members_drawn: the message limit of proof " + std::to_string(i) + " is 2^32 or more");
+    memcpy(&(*limits)[i], limit, 4);
+    memcpy(ext_le->data() + 32 * i, inputs + i * NIB + (size_t)D.slots.ext * 32, 32);
+  }
+}
+
+namespace {
+struct ReleaseDraw {   // success or error: the draw's block is overwritten when the call returns
+  QuotaLedgerDev& q;
+  ~ReleaseDraw() {
+    try {
+      q.release();
+    } catch (...) {
+    }
+  }
+};
+}  // namespace
+
+uint64_t Prover::submit_members_drawn(const MemberTree& t, QuotaLedgerDev& q, size_t n, const uint64_t* leaf, const uint8_t* inputs,
+                                      const uint8_t* rs, uint8_t* status) {
+  if (n == 0) throw Error("empty batch");
+  if (!leaf || !inputs || !rs || !status) throw Error("submit_members_drawn: leaf indices, inputs, rs and status are required");
+  if (n > B_) throw Error("batch larger than the prover workspace (max_batch)");
+  check_members(t, n, leaf);
+  std::vector<uint32_t> limits;
+  std::vector<uint8_t> ext;
+  check_drawn(t, q, n, inputs, &limits, &ext);
+  ReleaseDraw release{q};
+  const DrawnIds drawn{&q, q.draw_hold(n, leaf, ext.data(), limits.data(), status), status, 0};
+  return submit_members_by(t, n, leaf, inputs, rs, PROVE_FULL, &drawn);
+}
+
+void Prover::prove_stream_members_drawn(const MemberTree& t, QuotaLedgerDev& q, size_t n, const uint64_t* leaf, const uint8_t* inputs,
+                                        const uint8_t* rs, uint8_t* status, uint8_t* proofs, uint8_t* values, uint32_t* errors) {
+  if (n && (!leaf || !inputs || !rs || !status))
+    throw Error("prove_stream_members_drawn: leaf indices, inputs, rs and status are required");
+  check_members(t, n, leaf);   // all of it before anything is drawn or enqueued
+  std::vector<uint32_t> limits;
+  std::vector<uint8_t> ext;
+  check_drawn(t, q, n, inputs, &limits, &ext);
+  if (n == 0) return;
+  ReleaseDraw release{q};
+  const DrawnIds drawn{&q, q.draw_hold(n, leaf, ext.data(), limits.data(), status), status, 0};   // ONE draw: the chunks read their slices
+  size_t at = 0;
+  prove_stream_from([&](size_t* off, size_t* cnt) {
+    if (at >= n) return false;
+    *off = at;
+    *cnt = std::min(B_, n - at);
+    at += *cnt;
+    return true;
+  }, inputs, rs, proofs, values, errors, 0, &t, leaf, &drawn);
+}
+
+uint64_t Prover::submit_members_by(const MemberTree& t, size_t n, const uint64_t* leaf, const uint8_t* inputs, const uint8_t* rs,
+                                   int mode, const DrawnIds* drawn) {
   if (n == 0) throw Error("empty batch");
   if (!leaf || !inputs || !rs) throw Error("submit_members: leaf indices, inputs and rs are required");
   if (mode != PROVE_FULL && mode != PROVE_PARTIAL)
@@ -1109,13 +1208,20 @@ uint64_t Prover::submit_members(const MemberTree& t, size_t n, const uint64_t* l
   bool host = !t.dense;
   if (!host && n <= D.tune.hint_max) host = batch_shape(D.query(n, mode, true), D.tune).hinted;
   if (!host) {
-    const MemberGather g{t.dense, leaf};
-    return enqueue(n, mode, inputs, rs, nullptr, nullptr, nullptr, &g);
+    MemberGather g{t.dense, leaf};
+    if (drawn) {
+      g.ids = drawn->held.ids + drawn->first;
+      g.ids_status = drawn->held.status + drawn->first;
+      g.ids_stream = drawn->held.stream;
+    }
+    const uint64_t ticket = enqueue(n, mode, inputs, rs, nullptr, nullptr, nullptr, &g);
+    if (drawn) D.mark_drawn(ticket);
+    return ticket;
   }
   const size_t d = (size_t)t.depth, NIB = (size_t)D.NI * 32;
-  std::vector<uint8_t> elems(n * d * 32), bits(n * d), in(inputs, inputs + n * NIB);
+  std::vector<uint8_t> elems(n * d * 32), bits(n * d), in(inputs, inputs + n * NIB), ids(drawn ? n * 4 : 0);
   auto scrub = [&]() {   // the copy holds what the caller's inputs hold: the identity secret among it
-    for (std::vector<uint8_t>* v : {&in, &elems, &bits}) {   // (the path bits are the member's leaf index)
+    for (std::vector<uint8_t>* v : {&in, &elems, &bits, &ids}) {   // (the path bits are the member's leaf index)
       memset(v->data(), 0, v->size());
       __asm__ __volatile__("" : : "r"(v->data()) : "memory");
     }
@@ -1123,13 +1229,20 @@ uint64_t Prover::submit_members(const MemberTree& t, size_t n, const uint64_t* l
   try {
     if (t.proofs_at) t.proofs_at(leaf, n, elems.data(), bits.data());
     else t.dense->proofs_at_host(leaf, n, elems.data(), bits.data());
+    if (drawn) drawn->quota->held_ids(drawn->first, n, (uint32_t*)ids.data());   // the one copy back of this route
     for (size_t i = 0; i < n; i++) {
       uint8_t* row = in.data() + i * NIB;
       memcpy(row + (size_t)D.path_off * 32, elems.data() + i * d * 32, d * 32);
       memset(row + (size_t)D.path_idx_off * 32, 0, d * 32);
       for (size_t l = 0; l < d; l++) row[((size_t)D.path_idx_off + l) * 32] = bits[i * d + l];
+      if (drawn) {   // the bytes k_quota_fill writes on the device route
+        const bool granted = drawn->status[drawn->first + i] == quota::OK;
+        memset(row + (size_t)D.drawn_msg_off * 32, granted ? 0 : 0xFF, 32);
+        if (granted) memcpy(row + (size_t)D.drawn_msg_off * 32, ids.data() + 4 * i, 4);
+      }
     }
     const uint64_t ticket = enqueue(n, mode, in.data(), rs, nullptr);
+    if (drawn) D.mark_drawn(ticket);
     scrub();
     return ticket;
   } catch (...) {
@@ -1321,6 +1434,13 @@ void Prover::collect(uint64_t ticket, size_t n, uint8_t* proofs, uint8_t* values
     if (partial320) memcpy(partial320, S.h_pp, n * 320);
   } else {
     if (proofs) memcpy(proofs, S.h_comp, n * 128);
+    // a batch with drawn message ids: a refused row yields no proof bytes -- at once, and once more with the value bytes
+    // and the coordinates behind the copies below, which write over whatever is cleared here
+    for (size_t i = 0; i < n && S.drawn; i++)
+      if (S.h_err[i]) {
+        if (proofs) memset(proofs + 128 * i, 0, 128);
+        if (values) memset(values + 160 * i, 0, 160);
+      }
     if (values) {
       if (D.have_values_kernel)
         memcpy(values, S.h_values, n * 160);
@@ -1332,6 +1452,16 @@ void Prover::collect(uint64_t ticket, size_t n, uint8_t* proofs, uint8_t* values
         memset(values, 0, n * 160);
     }
     if (coords) RLN_HIP(hipMemcpy(coords, S.coords.p, n * 256, hipMemcpyDeviceToHost));
+    // A batch with drawn message ids: a row the interpreter refused -- a request past its quota among them -- yields
+    // nothing, behind every copy above.  The kernels do run for such a row, and every refused row reads the same
+    // messageId (the reduction of its 0xFF bytes): the y values of two refused requests of one member under one external
+    // nullifier would be two shares on one line, which is what the ledger exists to prevent.
+    for (size_t i = 0; i < n && S.drawn; i++)
+      if (S.h_err[i]) {
+        if (proofs) memset(proofs + 128 * i, 0, 128);
+        if (values) memset(values + 160 * i, 0, 160);
+        if (coords) memset(coords + 256 * i, 0, 256);
+      }
   }
   if (errors) memcpy(errors, S.h_err, n * 4);
   if (wipe_after && !S.wiped) D.wipe_slot(S, false);
@@ -1363,6 +1493,9 @@ void Prover::collect_public(uint64_t ticket, size_t n, std::vector<uint8_t>* out
       if (D.slot[k].wiped) throw Error("collect_public: the batch has been wiped (collect it with wipe_after = false first)");
       RLN_HIP(hipEventSynchronize(D.slot[k].evC));
       fetch_public_slot(&D.slot[k], n, out_le);
+      const size_t row = num_public() * 32;   // (a refused row of a drawn batch yields nothing: collect)
+      for (size_t i = 0; i < n && D.slot[k].drawn && out_le->size() >= n * row; i++)
+        if (D.slot[k].h_err[i]) memset(out_le->data() + i * row, 0, row);
       return;
     }
   throw Error("collect: unknown or expired ticket (its workspace slot has been reused)");
@@ -1401,7 +1534,7 @@ void Prover::prove_stream_members(const MemberTree& tree, size_t n, const uint64
 
 void Prover::prove_stream_from(const ChunkSource& next, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs,
                                uint8_t* values, uint32_t* errors, int max_in_flight, const MemberTree* tree,
-                               const uint64_t* leaf) {
+                               const uint64_t* leaf, const DrawnIds* drawn) {
   Impl& D = *d_;
   struct Pending { uint64_t ticket; size_t off, cnt; };
   std::deque<Pending> q;
@@ -1420,7 +1553,9 @@ void Prover::prove_stream_from(const ChunkSource& next, const uint8_t* inputs, c
       if (!next(&off, &cnt)) break;         // (asked only when a slot is free: a shared cursor hands out no chunk early)
       if (cnt == 0) continue;
       if (cnt > B_) throw Error("prove_stream: a chunk larger than the prover workspace (max_batch)");
-      q.push_back({tree ? submit_members(*tree, cnt, leaf + off, inputs + off * NIB, rs + off * 64, PROVE_FULL)
+      DrawnIds slice{};
+      if (drawn) slice = DrawnIds{drawn->quota, drawn->held, drawn->status, drawn->first + off};
+      q.push_back({tree ? submit_members_by(*tree, cnt, leaf + off, inputs + off * NIB, rs + off * 64, PROVE_FULL, drawn ? &slice : nullptr)
                         : submit(cnt, inputs + off * NIB, rs + off * 64),
                    off, cnt});
     }
@@ -1534,6 +1669,7 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
   const uint32_t* pp_p = (streamed && h_pp320) ? S.pp_in.p : D.pp_in.p;
   S.mode = mode;
   if (!in_place) S.ticket = streamed ? ++D.tickets : 0;   // (a re-run answers to the ticket its caller holds)
+  if (!in_place) S.drawn = false;                          // (submit_members_by marks the batch behind this call)
   if (!in_place) D.cur = (D.cur + 1) % D.nslot;
   // Front end in two pipeline stages on their own streams: A1 = graph interpreter (16 latency-bound waves per 1024
   // proofs, ~28 ms), A2 = mat-vec + NTTs + quotient (throughput kernels squeezed in beside the MSM, ~25 ms contended).
@@ -1616,8 +1752,18 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
       const uint64_t NIB = (uint64_t)D.NI * 32;
       const PathDest dest{in8 + (size_t)D.path_off * 32, in8 + (size_t)D.path_idx_off * 32, NIB, 32, NIB, 32, 1};
       tree.proofs_at_device(S.idx.p, n, dest, sA);
+      if (members->ids) {
+        // Drawn message ids, beside the paths and by the same rule: the write waits for whatever the ledger's stream holds
+        // so far (the draw), and the ledger's stream waits for the write (evG below), so the wipe of the draw's block that
+        // follows this call finds the ids read.  The caller holds the ledger's lock across both.
+        hipStream_t sQ = (hipStream_t)members->ids_stream;
+        RLN_HIP(hipEventRecord(S.evQ, sQ));
+        RLN_HIP(hipStreamWaitEvent(sA, S.evQ, 0));
+        QuotaLedgerDev::fill_rows(members->ids, members->ids_status, n, S.inputs.p, (size_t)D.NI * 8, D.drawn_msg_off, (void*)sA);
+      }
       RLN_HIP(hipEventRecord(S.evG, sA));
       RLN_HIP(hipStreamWaitEvent(tree.stream, S.evG, 0));
+      if (members->ids) RLN_HIP(hipStreamWaitEvent((hipStream_t)members->ids_stream, S.evG, 0));
     }
     RLN_HIP(hipGetLastError());
     RLN_HIP(hipEventRecord(S.evU, sA));

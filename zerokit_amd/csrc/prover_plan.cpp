@@ -56,6 +56,8 @@ NamedInputs find_named_inputs(const Graph& graph, uint32_t ni) {
   // the proof-values kernel: the same names on a single message-id circuit with six instance variables
   R.have_values_kernel = R.have_hint_slots && graph.max_out == 1 && ni == 6;
   if (R.have_values_kernel) sl.msg_id = R.hint_msg_off;
+  R.have_drawn_slots = find("userMessageLimit", 1, &sl.limit) && find("externalNullifier", 1, &sl.ext) &&
+                       find("messageId", 1, &R.drawn_msg_off);
   return R;
 }
 

@@ -30,6 +30,10 @@ struct NamedInputs {
   // the Merkle path by itself (Prover::submit_members writes it on the device): both names, tree_depth elements each
   bool have_path_slots = false;
   uint32_t path_off = 0, path_idx_off = 0;
+  // what a batch with drawn message ids reads and writes (Prover::submit_members_drawn): slots.limit and slots.ext of
+  // each input row, and ONE messageId slot -- the multi-message-id circuit, which has max_out of them, is refused
+  bool have_drawn_slots = false;
+  uint32_t drawn_msg_off = 0;
 };
 NamedInputs find_named_inputs(const Graph& graph, uint32_t ni);
 

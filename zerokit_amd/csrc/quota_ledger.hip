@@ -1,0 +1,517 @@
+// The quota ledger on the device: the kernels over quota_ledger.h and the QuotaLedgerDev object.
+//
+// One draw() call: a host check, the requests (leaf, limit, external nullifier) copied into the call's block, then on the
+// ledger's stream
+//   k_quota_key                 key[i] = slot << 24 | leaf, the slot looked up in the window (in LDS, as k_relay_gate
+//                               holds its roots); a request outside the window gets the slot above all others
+//   per sort pass (DrawPlan: one 8-bit digit of the leaf's bits or the slot's, least significant first)
+//     k_quota_count             bins[digit][block] = the block's requests with that digit
+//     k_scan_up / k_scan_down   where each (digit, block) starts in the output (log_scan.h)
+//     k_quota_scatter           (key, i) to that start plus the request's place among the block's requests of the same
+//                               digit, in lane order: the pass is stable
+//   k_quota_heads               mark[j] = j where sorted position j starts a group of equal keys
+//   k_max_up / k_max_down       start[j] = the running maximum of the marks: where j's group starts; rank = j - start[j]
+//   k_quota_issue               id and status by quota::issue, written to the request's own index; ok[j] = j + 1 if granted
+//   k_max_up / k_max_down       last[j] = the running maximum of ok: the last granted position at or below j
+//   k_quota_advance             the last lane of each group stores the group's counter (quota::advance)
+// then one copy back of ids and statuses, one memset over the whole block and one stream wait.
+// The rule of nullifier_log.hip holds: passes are ordered by kernel boundaries only, and no lane waits for, or reads,
+// what another lane of the same kernel writes.  The issue pass reads the counters, the advance pass behind it writes
+// them, one lane per key.  Nothing walks a chain per duplicate: n requests of one member and n requests of n members run
+// the same kernels over the same n words (profiles/quota_ledger.md).
+//
+// Proving with drawn ids (Prover::submit_members_drawn): draw_hold() is the same call that copies back the statuses alone
+// and leaves the block where it is until release(); in between, k_quota_fill -- launched by the prover on its own stream,
+// ordered against the ledger's by events -- copies each batch's ids into the messageId slot of its staged input rows.
+#include "quota_ledger.h"
+
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "log_scan.h"
+
+namespace rlnamd {
+
+using nlog::Row32;
+
+static_assert(quota::BLOCK == LOG_LANES, "a draw's workgroup is the scan's");
+static_assert(quota::DIGITS == LOG_LANES, "k_quota_count writes one bin a lane");
+
+namespace {
+
+__global__ void __launch_bounds__(LOG_LANES) k_quota_key(const Row32* __restrict__ window, uint64_t live, uint32_t slots,
+                                                         const uint32_t* __restrict__ leaf, const Row32* __restrict__ ext, uint32_t n,
+                                                         uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
+  __shared__ Row32 lds_window[quota::EPOCHS_MAX];
+  for (uint32_t j = threadIdx.x; j < slots * 8; j += LOG_LANES) lds_window[j >> 3].w[j & 7] = window[j >> 3].w[j & 7];
+  __syncthreads();
+  const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (i >= n) return;
+  key[i] = quota::pack_key(quota::slot_of(lds_window, live, slots, ext[i]), leaf[i]);
+  val[i] = i;
+}
+
+__device__ __forceinline__ uint32_t digit_of(uint32_t key, uint32_t shift) { return (key >> shift) & (quota::DIGITS - 1); }
+
+// bins[digit * blocks + block]: the LDS counts are the only words lanes share, and only their totals are read
+__global__ void __launch_bounds__(LOG_LANES) k_quota_count(const uint32_t* __restrict__ key, uint32_t n, uint32_t shift,
+                                                           uint32_t* __restrict__ bins) {
+  __shared__ uint32_t count[quota::DIGITS];
+  count[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (i < n) atomicAdd(&count[digit_of(key[i], shift)], 1u);
+  __syncthreads();
+  bins[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = count[threadIdx.x];
+}
+
+// A request's place among its block's requests with the same digit, in lane order: the lanes of its wave below it (a
+// ballot per digit bit leaves the mask of the wave's lanes with the same digit), plus the counts of the waves below.
+__global__ void __launch_bounds__(LOG_LANES) k_quota_scatter(const uint32_t* __restrict__ key, const uint32_t* __restrict__ val,
+                                                             uint32_t n, uint32_t shift, const uint32_t* __restrict__ bin_start,
+                                                             uint32_t* __restrict__ key_out, uint32_t* __restrict__ val_out) {
+  __shared__ uint32_t wave_count[LOG_LANES / 64][quota::DIGITS];
+#pragma unroll
+  for (uint32_t w = 0; w < LOG_LANES / 64; w++) wave_count[w][threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool live = i < n;
+  const uint32_t k = live ? key[i] : 0, v = live ? val[i] : 0, d = digit_of(k, shift);
+  uint64_t peers = __ballot(live);
+#pragma unroll
+  for (uint32_t b = 0; b < quota::DIGIT_BITS; b++) {
+    const bool bit = (d >> b) & 1;
+    const uint64_t with = __ballot(bit);
+    peers &= bit ? with : ~with;
+  }
+  const uint32_t below = __popcll(peers & (((uint64_t)1 << lane) - 1));
+  if (live && below == 0) wave_count[wave][d] = __popcll(peers);   // the lowest lane with the digit speaks for it
+  __syncthreads();
+  if (!live) return;
+  uint32_t place = below;
+  for (uint32_t w = 0; w < wave; w++) place += wave_count[w][d];
+  const uint32_t to = bin_start[(size_t)d * gridDim.x + blockIdx.x] + place;
+  if (to >= n) return;   // (not reached; a write past the arrays is not an answer to a wrong position)
+  key_out[to] = k;
+  val_out[to] = v;
+}
+
+__global__ void __launch_bounds__(LOG_LANES) k_quota_heads(const uint32_t* __restrict__ key, uint32_t n, uint32_t* __restrict__ mark) {
+  const uint32_t j = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (j < n) mark[j] = (j > 0 && key[j] != key[j - 1]) ? j : 0;
+}
+
+__device__ __forceinline__ bool counted(uint32_t key, uint32_t slots, uint32_t depth) {
+  return quota::key_slot(key) < slots && (quota::key_leaf(key) >> depth) == 0;   // NO_SLOT is above every real slot
+}
+
+__global__ void __launch_bounds__(LOG_LANES) k_quota_issue(const uint32_t* __restrict__ key, const uint32_t* __restrict__ val,
+                                                           const uint32_t* __restrict__ start, const uint32_t* __restrict__ limits,
+                                                           const uint32_t* __restrict__ counters, uint32_t depth, uint32_t slots,
+                                                           uint32_t n, uint32_t* __restrict__ ids, uint8_t* __restrict__ status,
+                                                           uint32_t* __restrict__ ok) {
+  const uint32_t j = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t k = key[j], i = val[j];
+  ok[j] = 0;
+  if (i >= n) return;   // (not reached)
+  const uint32_t limit = limits[i];
+  if (!counted(k, slots, depth)) {
+    ids[i] = limit;
+    status[i] = quota::NO_EPOCH;
+    return;
+  }
+  const quota::Issue r = quota::issue(counters[quota::counter_of(k, depth)], j - start[j], limit);
+  ids[i] = r.id;
+  status[i] = r.status;
+  if (r.status == quota::OK) ok[j] = j + 1;
+}
+
+__global__ void __launch_bounds__(LOG_LANES) k_quota_advance(const uint32_t* __restrict__ key, const uint32_t* __restrict__ start,
+                                                             const uint32_t* __restrict__ last, uint32_t* __restrict__ counters,
+                                                             uint32_t depth, uint32_t slots, uint32_t n) {
+  const uint32_t j = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t k = key[j];
+  if (j + 1 < n && key[j + 1] == k) return;   // the group's last lane alone
+  if (!counted(k, slots, depth)) return;
+  uint32_t* counter = counters + quota::counter_of(k, depth);
+  const uint32_t used = *counter, next = quota::advance(used, start[j], last[j]);
+  if (next != used) __hip_atomic_store(counter, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Proving with drawn ids (Prover::enqueue): a lane per staged input row, behind the row's staging on the same stream
+__global__ void __launch_bounds__(LOG_LANES) k_quota_fill(const uint32_t* __restrict__ ids, const uint8_t* __restrict__ status,
+                                                          uint32_t n, uint32_t* __restrict__ rows, size_t row_words, uint32_t slot) {
+  const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (i >= n) return;
+  uint32_t* to = rows + (size_t)i * row_words + (size_t)slot * 8;
+  const bool granted = status[i] == quota::OK;   // refused: no field element, the interpreter refuses the row
+  to[0] = granted ? ids[i] : QuotaLedgerDev::REFUSED_WORD;
+#pragma unroll
+  for (int w = 1; w < 8; w++) to[w] = granted ? 0 : QuotaLedgerDev::REFUSED_WORD;
+}
+
+void wipe_host(void* p, size_t n) {   // through a volatile pointer: not elided as dead (ffi_wire.h: secure_zero)
+  volatile uint8_t* v = (volatile uint8_t*)p;
+  for (size_t i = 0; i < n; i++) v[i] = 0;
+}
+
+size_t nonzero_words16(const uint8_t* p, size_t bytes) {
+  size_t c = 0;
+  for (size_t o = 0; o + 16 <= bytes; o += 16) {
+    uint8_t any = 0;
+    for (int k = 0; k < 16; k++) any |= p[o + k];
+    c += any != 0;
+  }
+  return c;
+}
+
+struct OnDevice {   // the ledger's device for the length of a call, the caller's afterwards
+  int prev = 0, dev;
+  explicit OnDevice(int dev_) : dev(dev_) {
+    RLN_HIP(hipGetDevice(&prev));
+    if (prev != dev) RLN_HIP(hipSetDevice(dev));
+  }
+  ~OnDevice() {
+    if (prev != dev) (void)hipSetDevice(prev);
+  }
+};
+
+// The block of one call of n requests, in bytes from its start; every array starts 16-byte aligned.
+//   in  (pinned -> device, one copy):  leaf 4 n | limits 4 n | ext 32 n
+//   out (device -> pinned, one copy):  ids 4 n | status n
+//   the rest is the device's alone:    two (key, val) pairs, start, ok, the bins and their starts, the scans' block sums
+struct Block {
+  size_t np, leaf, limits, ext, ids, status, key[2], val[2], start, ok, bins, bin_start, sums, bytes;
+  size_t in_bytes() const { return ids; }
+  size_t out_bytes() const { return key[0] - ids; }
+  explicit Block(size_t n) {
+    np = (n + 3) / 4 * 4;
+    const quota::DrawPlan P = quota::plan_for(n, 1);
+    size_t at = 0;
+    auto take = [&](size_t b) {
+      const size_t here = at;
+      at += (b + 15) / 16 * 16;
+      return here;
+    };
+    leaf = take(4 * np);
+    limits = take(4 * np);
+    ext = take(32 * np);
+    ids = take(4 * np);
+    status = take(np);
+    for (int s = 0; s < 2; s++) key[s] = take(4 * np), val[s] = take(4 * np);
+    start = take(4 * np);
+    ok = take(4 * np);
+    bins = take(4 * P.bins);
+    bin_start = take(4 * P.bins);
+    sums = take(4 * std::max(ScanPlan(P.bins).words, ScanPlan(n).words));
+    bytes = at;
+  }
+};
+
+}  // namespace
+
+struct QuotaLedgerDev::Impl {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  uint32_t depth = 0, max_epochs = 0;
+  quota::Window window;           // (a member: the copy to the device reads it)
+  DevBuf<uint32_t> counters;      // max_epochs << depth
+  DevBuf<Row32> window_dev;       // EPOCHS_MAX rows
+  uint64_t draws = 0, issued = 0, over = 0, no_epoch = 0;
+  // the block of one call of up to stage_n requests, all zero between calls, on the device and in the pinned copies
+  size_t stage_n = 0, stage_bytes = 0, in_cap = 0, out_cap = 0;
+  DevBuf<uint8_t> block;
+  uint8_t* in_host = nullptr;
+  uint8_t* out_host = nullptr;
+  size_t held_n = 0;   // draw_hold's requests while their block is kept (quota_ledger.h); 0: none
+
+  void run(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, uint32_t* ids_out, uint8_t* status,
+           bool hold);
+  void reserve(size_t n) {
+    if (n <= stage_n) return;
+    release_staging();
+    const size_t m = n < 1024 ? 1024 : n;
+    const Block B(m);
+    RLN_HIP(hipHostMalloc((void**)&in_host, B.in_bytes(), hipHostMallocDefault));
+    in_cap = B.in_bytes();
+    memset(in_host, 0, in_cap);
+    RLN_HIP(hipHostMalloc((void**)&out_host, B.out_bytes(), hipHostMallocDefault));
+    out_cap = B.out_bytes();
+    memset(out_host, 0, out_cap);
+    block.alloc(B.bytes);
+    RLN_HIP(hipMemsetAsync(block.p, 0, B.bytes, stream));
+    stage_n = m;
+    stage_bytes = B.bytes;
+  }
+  // (what a call left is zero already -- draw() wipes before it returns -- and is wiped once more before it is freed)
+  void release_staging() {
+    if (block.p) {
+      (void)hipMemsetAsync(block.p, 0, stage_bytes, stream);
+      (void)hipStreamSynchronize(stream);
+    }
+    if (in_host) {
+      wipe_host(in_host, in_cap);
+      (void)hipHostFree(in_host);
+    }
+    if (out_host) {
+      wipe_host(out_host, out_cap);
+      (void)hipHostFree(out_host);
+    }
+    block.release();
+    in_host = out_host = nullptr;
+    stage_n = stage_bytes = in_cap = out_cap = 0;
+  }
+  ~Impl() {
+    held_n = 0;
+    if (stream) {
+      if (counters.p) (void)hipMemsetAsync(counters.p, 0, counters.bytes(), stream);   // who signed how often
+      (void)hipStreamSynchronize(stream);
+    }
+    release_staging();
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+QuotaLedgerDev::QuotaLedgerDev(size_t depth, size_t max_epochs) {
+  const std::string refused = quota::new_refusal(depth, max_epochs);
+  if (!refused.empty()) throw Error(refused);
+  require_gpu();
+  Impl* m = new Impl;
+  try {
+    RLN_HIP(hipGetDevice(&m->device));
+    RLN_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+    m->depth = (uint32_t)depth;
+    m->max_epochs = (uint32_t)max_epochs;
+    m->counters.alloc(max_epochs << depth);
+    m->window_dev.alloc(quota::EPOCHS_MAX);
+    RLN_HIP(hipMemsetAsync(m->counters.p, 0, m->counters.bytes(), m->stream));
+    RLN_HIP(hipMemsetAsync(m->window_dev.p, 0, m->window_dev.bytes(), m->stream));
+    RLN_HIP(hipStreamSynchronize(m->stream));
+  } catch (...) {
+    delete m;
+    throw;
+  }
+  d = m;
+}
+
+QuotaLedgerDev::~QuotaLedgerDev() {
+  if (!d) return;
+  int prev = 0;
+  const bool move = hipGetDevice(&prev) == hipSuccess && prev != d->device && hipSetDevice(d->device) == hipSuccess;
+  delete d;
+  if (move) (void)hipSetDevice(prev);
+}
+
+int QuotaLedgerDev::device() const { return d->device; }
+int QuotaLedgerDev::depth() const { return (int)d->depth; }
+
+void QuotaLedgerDev::fill_rows(const uint32_t* ids, const uint8_t* status, size_t count, uint32_t* rows, size_t row_words,
+                               uint32_t slot, void* on) {
+  if (count == 0) return;
+  if (count > 0xFFFFFFFFull || (size_t)slot * 8 + 8 > row_words) throw Error("quota ledger: fill_rows: the slot is outside the row");
+  hipLaunchKernelGGL(k_quota_fill, dim3(div_up(count, LOG_LANES)), dim3(LOG_LANES), 0, (hipStream_t)on, ids, status, (uint32_t)count,
+                     rows, row_words, slot);
+  RLN_HIP(hipGetLastError());
+}
+
+void QuotaLedgerDev::set_epochs(size_t k, const uint8_t* external_nullifiers_le) {
+  Impl& m = *d;
+  // the host check: nothing is enqueued and nothing of the ledger changes before it has passed
+  const std::string refused = quota::epochs_refusal(external_nullifiers_le, k, m.max_epochs);
+  if (!refused.empty()) throw Error(refused);
+  uint64_t leaving = 0;
+  const quota::Window next = quota::next_window(m.window, external_nullifiers_le, k, m.max_epochs, &leaving);
+  // From here on only a HIP error can stop the call, and such an error is not a refusal: the ledger is not left as it
+  // was.  It is left SAFE: the external nullifiers that leave are taken out of the host's window first (a draw looks
+  // slots up with the host's `live` mask), so no id is drawn under an epoch whose counters may be zeroed in part; the new
+  // ones are not in yet.  A slot whose zeroing did not finish may keep counters above zero for its next holder, which
+  // skips ids and never repeats one.
+  if (leaving) {
+    quota::Window mid = m.window;
+    mid.live &= ~leaving;
+    mid.k = 0;
+    for (uint32_t j = 0; j < m.window.k; j++)
+      if ((mid.live >> m.window.order[j]) & 1) mid.order[mid.k++] = m.window.order[j];
+    m.window = mid;
+  }
+  OnDevice on(m.device);
+  for (uint32_t s = 0; s < m.max_epochs; s++)
+    if ((leaving >> s) & 1) RLN_HIP(hipMemsetAsync(m.counters.p + ((size_t)s << m.depth), 0, (size_t)4 << m.depth, m.stream));
+  RLN_HIP(hipMemcpyAsync(m.window_dev.p, next.e, sizeof next.e, hipMemcpyHostToDevice, m.stream));
+  RLN_HIP(hipStreamSynchronize(m.stream));
+  m.window = next;
+}
+
+size_t QuotaLedgerDev::epochs(uint8_t out_le[32 * quota::EPOCHS_MAX]) const {
+  const quota::Window& W = d->window;
+  for (uint32_t j = 0; j < W.k; j++) memcpy(out_le + 32 * j, W.e[W.order[j]].w, 32);
+  return W.k;
+}
+
+void QuotaLedgerDev::draw(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, uint32_t* ids_out,
+                          uint8_t* status) {
+  d->run(n, leaf_indices, ext_le, limits, ids_out, status, false);
+}
+
+QuotaLedgerDev::Held QuotaLedgerDev::draw_hold(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
+                                               uint8_t* status) {
+  d->run(n, leaf_indices, ext_le, limits, nullptr, status, true);
+  if (!d->held_n) return Held{nullptr, nullptr, (void*)d->stream, d->device};
+  const Block B(d->held_n);
+  return Held{(const uint32_t*)(d->block.p + B.ids), d->block.p + B.status, (void*)d->stream, d->device};
+}
+
+void QuotaLedgerDev::held_ids(size_t first, size_t count, uint32_t* out) {
+  Impl& m = *d;
+  if (count == 0) return;
+  if (first > m.held_n || count > m.held_n - first) throw Error("quota ledger: internal error, ids asked for beyond the draw that is held");
+  OnDevice on(m.device);
+  RLN_HIP(hipMemcpyAsync(out, m.block.p + Block(m.held_n).ids + 4 * first, 4 * count, hipMemcpyDeviceToHost, m.stream));
+  RLN_HIP(hipStreamSynchronize(m.stream));
+}
+
+void QuotaLedgerDev::release() {
+  Impl& m = *d;
+  if (!m.held_n) return;
+  const Block B(m.held_n);
+  m.held_n = 0;
+  wipe_host(m.out_host, B.out_bytes());
+  int prev = 0;
+  const bool move = hipGetDevice(&prev) == hipSuccess && prev != m.device && hipSetDevice(m.device) == hipSuccess;
+  const hipError_t e1 = hipMemsetAsync(m.block.p, 0, B.bytes, m.stream), e2 = hipStreamSynchronize(m.stream);
+  if (move) (void)hipSetDevice(prev);
+  RLN_HIP(e1);
+  RLN_HIP(e2);
+}
+
+void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, uint32_t* ids_out,
+                               uint8_t* status, bool hold) {
+  Impl& m = *this;
+  if (m.held_n) throw Error("quota ledger: internal error, a draw while another draw's ids are held");
+  // the host check: nothing is enqueued and nothing of the ledger changes before it has passed
+  const std::string refused = quota::draw_refusal(n, leaf_indices, ext_le, limits, ids_out, status, m.depth, !hold);
+  if (!refused.empty()) throw Error(refused);
+  if (n == 0) return;
+  OnDevice on(m.device);
+  m.reserve(n);
+  const Block B(n);
+  const quota::DrawPlan P = quota::plan_for(n, m.depth);
+  struct Wipe {   // success or error: the call's block is zero again when draw() returns (a held draw: at release())
+    Impl& m;
+    const Block& B;
+    bool device_done = false, held = false;
+    ~Wipe() {
+      wipe_host(m.in_host, B.in_bytes());
+      if (held) return;
+      if (!device_done) {
+        (void)hipMemsetAsync(m.block.p, 0, B.bytes, m.stream);
+        (void)hipStreamSynchronize(m.stream);
+      }
+      wipe_host(m.out_host, B.out_bytes());
+    }
+  } wipe{m, B};
+
+  uint32_t* h_leaf = (uint32_t*)(m.in_host + B.leaf);
+  for (size_t i = 0; i < n; i++) h_leaf[i] = (uint32_t)leaf_indices[i];
+  memcpy(m.in_host + B.limits, limits, 4 * n);
+  memcpy(m.in_host + B.ext, ext_le, 32 * n);
+  uint8_t* base = m.block.p;
+  auto words = [&](size_t off) { return (uint32_t*)(base + off); };
+  const uint32_t n32 = (uint32_t)n, blocks = (uint32_t)P.blocks, slots = m.max_epochs;
+  const dim3 grid(blocks), lanes(LOG_LANES);
+  RLN_HIP(hipMemcpyAsync(base, m.in_host, B.in_bytes(), hipMemcpyHostToDevice, m.stream));
+  hipLaunchKernelGGL(k_quota_key, grid, lanes, 0, m.stream, (const Row32*)m.window_dev.p, m.window.live, slots,
+                     (const uint32_t*)words(B.leaf), (const Row32*)(base + B.ext), n32, words(B.key[0]), words(B.val[0]));
+  int cur = 0;
+  for (uint32_t p = 0; p < P.passes; p++, cur ^= 1) {
+    hipLaunchKernelGGL(k_quota_count, grid, lanes, 0, m.stream, (const uint32_t*)words(B.key[cur]), n32, P.shift[p], words(B.bins));
+    scan_positions((const uint32_t*)words(B.bins), P.bins, words(B.bin_start), words(B.sums), m.stream);
+    hipLaunchKernelGGL(k_quota_scatter, grid, lanes, 0, m.stream, (const uint32_t*)words(B.key[cur]),
+                       (const uint32_t*)words(B.val[cur]), n32, P.shift[p], (const uint32_t*)words(B.bin_start),
+                       words(B.key[cur ^ 1]), words(B.val[cur ^ 1]));
+  }
+  const uint32_t* key = words(B.key[cur]);
+  const uint32_t* val = words(B.val[cur]);
+  hipLaunchKernelGGL(k_quota_heads, grid, lanes, 0, m.stream, key, n32, words(B.start));
+  scan_running_max(words(B.start), n, words(B.start), words(B.sums), m.stream);
+  hipLaunchKernelGGL(k_quota_issue, grid, lanes, 0, m.stream, key, val, (const uint32_t*)words(B.start),
+                     (const uint32_t*)words(B.limits), (const uint32_t*)m.counters.p, m.depth, slots, n32, words(B.ids),
+                     base + B.status, words(B.ok));
+  scan_running_max(words(B.ok), n, words(B.ok), words(B.sums), m.stream);
+  hipLaunchKernelGGL(k_quota_advance, grid, lanes, 0, m.stream, key, (const uint32_t*)words(B.start), (const uint32_t*)words(B.ok),
+                     m.counters.p, m.depth, slots, n32);
+  RLN_HIP(hipGetLastError());
+  if (hold) {   // the statuses alone; the ids stay where they are
+    RLN_HIP(hipMemcpyAsync(m.out_host + (B.status - B.ids), base + B.status, B.out_bytes() - (B.status - B.ids), hipMemcpyDeviceToHost,
+                           m.stream));
+  } else {
+    RLN_HIP(hipMemcpyAsync(m.out_host, base + B.ids, B.out_bytes(), hipMemcpyDeviceToHost, m.stream));
+    RLN_HIP(hipMemsetAsync(base, 0, B.bytes, m.stream));   // behind the copy, in stream order
+  }
+  RLN_HIP(hipStreamSynchronize(m.stream));
+  wipe.device_done = !hold;
+
+  const uint8_t* h_status = m.out_host + (B.status - B.ids);
+  for (size_t i = 0; i < n; i++)
+    if (h_status[i] > quota::NO_EPOCH) throw Error("quota ledger: internal error, a request came back without a status");
+  if (!hold) memcpy(ids_out, m.out_host, 4 * n);
+  memcpy(status, h_status, n);
+  for (size_t i = 0; i < n; i++) {
+    m.issued += h_status[i] == quota::OK;
+    m.over += h_status[i] == quota::OVER;
+    m.no_epoch += h_status[i] == quota::NO_EPOCH;
+  }
+  m.draws++;
+  if (hold) {
+    wipe.held = true;
+    m.held_n = n;
+  }
+}
+
+void QuotaLedgerDev::used(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, uint32_t* used_out, uint8_t* in_window) {
+  Impl& m = *d;
+  if (n == 0) return;
+  if (!leaf_indices || !ext_le || !used_out || !in_window) throw Error("quota ledger: used was given a null pointer for n > 0 pairs");
+  for (size_t i = 0; i < n; i++)
+    if (leaf_indices[i] >> m.depth)
+      throw Error("quota ledger: leaf index " + std::to_string(leaf_indices[i]) + " of pair " + std::to_string(i) +
+                  " is outside a ledger of depth " + std::to_string(m.depth));
+  OnDevice on(m.device);
+  for (size_t i = 0; i < n; i++) {
+    Row32 ext;
+    memcpy(ext.w, ext_le + 32 * i, 32);
+    const uint32_t s = quota::slot_of(m.window.e, m.window.live, m.max_epochs, ext);
+    used_out[i] = 0;
+    in_window[i] = s != quota::NO_SLOT;
+    if (s == quota::NO_SLOT) continue;
+    RLN_HIP(hipMemcpyAsync(&used_out[i], m.counters.p + quota::counter_of(quota::pack_key(s, (uint32_t)leaf_indices[i]), m.depth), 4,
+                           hipMemcpyDeviceToHost, m.stream));
+  }
+  RLN_HIP(hipStreamSynchronize(m.stream));
+}
+
+void QuotaLedgerDev::info(uint64_t out[8]) {
+  Impl& m = *d;
+  out[0] = m.window.k;
+  out[1] = m.draws;
+  out[2] = m.issued;
+  out[3] = m.over;
+  out[4] = m.no_epoch;
+  out[5] = 0;
+  out[6] = m.depth;
+  out[7] = m.max_epochs;
+  if (m.stage_n) {
+    OnDevice on(m.device);
+    std::vector<uint8_t> dev(m.stage_bytes);
+    RLN_HIP(hipMemcpyAsync(dev.data(), m.block.p, m.stage_bytes, hipMemcpyDeviceToHost, m.stream));
+    RLN_HIP(hipStreamSynchronize(m.stream));
+    out[5] = nonzero_words16(dev.data(), m.stage_bytes) + nonzero_words16(m.in_host, m.in_cap) + nonzero_words16(m.out_host, m.out_cap);
+  }
+}
+
+}  // namespace rlnamd

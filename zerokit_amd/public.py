@@ -497,6 +497,28 @@ class RLN:
         _ok_bool(lib().ffi_generate_rln_proofs_for_members(C.byref(self._h), idx, n, *[v[0].ptr for v in vecs], rsp, outs))
         return [RLNProof(C.c_void_p(outs[i])) for i in range(n)]
 
+    def generate_rln_proofs_for_members_drawn(self, quota, leaf_indices, identity_secrets, user_message_limits, xs,
+                                              external_nullifiers, rs=None):
+        """EXT: generate_rln_proofs_for_members with the message ids drawn on the device from `quota`, a
+        zerokit_amd.batch.QuotaLedger (ffi_generate_rln_proofs_for_members_drawn) -> (proofs, statuses): proofs[i] is
+        None where statuses[i] is not QuotaLedger.OK -- a member past its limit, an external nullifier the ledger does
+        not sign under."""
+        n = len(leaf_indices)
+        cols = (identity_secrets, user_message_limits, xs, external_nullifiers)
+        if any(len(c) != n for c in cols) or (rs is not None and len(rs) != n):
+            raise RLNError("generate_rln_proofs_for_members_drawn: every argument holds one entry per leaf index")
+        idx = (C.c_size_t * max(n, 1))(*[int(i) for i in leaf_indices])
+        vecs = [_vec_cfr(list(c)) for c in cols]          # (kept alive until the call has returned)
+        outs = (C.c_void_p * max(n, 1))()
+        status = C.create_string_buffer(max(n, 1))
+        rsp, flat = None, None
+        if rs is not None:
+            flat = _vec_cfr([v for pair in rs for v in pair])
+            rsp = flat[0].ptr
+        _ok_bool(lib().ffi_generate_rln_proofs_for_members_drawn(C.byref(self._h), quota._h if quota is not None else None, idx, n,
+                                                                 *[v[0].ptr for v in vecs], rsp, status, outs))
+        return [RLNProof(C.c_void_p(outs[i])) if outs[i] else None for i in range(n)], list(status.raw[:n])
+
     def finish_rln_proofs_batch(self, partials, witnesses, rs=None):
         """EXT: n finishes in one call; partials[i] (the same object may repeat) is what witnesses[i] is finished from"""
         n = len(witnesses)
