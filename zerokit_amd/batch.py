@@ -1163,6 +1163,12 @@ class MsmG1:
         pb = b"".join(self._pt_bytes(p) for p in points)
         check(lib().rlnamd_msm_set(self._h, pb, b"".join(_b(s) for s in scalars), len(points)))
 
+    def set_raw(self, points_bytes, scalars_bytes, n):
+        """the same from bytes: n canonical little-endian points (pt_bytes each, all zero = infinity) and n 32-byte scalars"""
+        if len(points_bytes) != self.pt_bytes * n or len(scalars_bytes) != 32 * n:
+            raise ValueError("set_raw: %d points need %d + %d bytes" % (n, self.pt_bytes * n, 32 * n))
+        check(lib().rlnamd_msm_set(self._h, points_bytes, scalars_bytes, n))
+
     EQUAL_SCALARS, FOUR_POINTS = 1, 2
 
     def generate(self, seed, first_index, n, mode=0):

@@ -607,7 +607,7 @@ void MsmImpl<O>::generate(uint64_t seed, uint64_t first_index, size_t n_, uint32
 template <class O>
 void MsmImpl<O>::fetch(size_t first, size_t count_, uint8_t* points_le, uint8_t* scalars_le) {
   MsmImpl& D = *this;
-  if (first + count_ > D.n) throw Error("MSM fetch: range outside the loaded points");
+  if (first > D.n || count_ > D.n - first) throw Error("MSM fetch: range outside the loaded points");  // (first + count may wrap)
   constexpr int AW = O::AFF_WORDS;
   std::vector<Aff> p(count_);
   RLN_HIP(hipMemcpy(p.data(), D.pts.p + first, count_ * sizeof(Aff), hipMemcpyDeviceToHost));
