@@ -211,6 +211,21 @@ CBoolResult_t ffi_generate_rln_proofs_for_members_drawn(FFI_RLN_t* const* rln, s
                                                         const CFr_t* user_message_limits, const CFr_t* xs,
                                                         const CFr_t* external_nullifiers, const CFr_t* rs, uint8_t* status,
                                                         FFI_RLNProof_t** out);
+/* EXT: the same for a multi-message-id object, one proof of which uses up to max_out message slots.  counts[i] (n bytes,
+ * 1 .. max_out) is the number of slots proof i uses; request i is (leaf_indices[i], external_nullifiers[i],
+ * user_message_limits[i], counts[i]), ONE rlnamd_quota_draw_counts covers the call and grants each request a block of
+ * counts[i] consecutive ids whole or not at all (rln_amd.h states the rule, and that a call is NOT what every split of
+ * it gives: a refused request counts, with its whole block, in front of the later requests of its member in the same
+ * call).  out[i] is a V1 proof with MultiV1 values -- message ids first .. first + counts[i] - 1 in its first counts[i]
+ * slots, their selectors set, the others unused -- where status[i] is RLNAMD_QUOTA_OK, and NULL where no proof was made.
+ * The witness constructor's checks apply to what the caller supplies (a zero limit).  Errors before anything is drawn:
+ * a single message-id object, a null ledger, a count of 0 or above max_out, a ledger whose depth is not the tree's or
+ * that lives on another device, a leaf index >= 2^depth, a limit of 2^32 or more.  n = 0 succeeds. */
+CBoolResult_t ffi_generate_rln_proofs_for_members_drawn_multi(FFI_RLN_t* const* rln, struct rlnamd_quota* quota,
+                                                              const size_t* leaf_indices, size_t n, const CFr_t* identity_secrets,
+                                                              const CFr_t* user_message_limits, const uint8_t* counts,
+                                                              const CFr_t* xs, const CFr_t* external_nullifiers, const CFr_t* rs,
+                                                              uint8_t* status, FFI_RLNProof_t** out);
 
 FFI_RLNProofValues_t* ffi_rln_proof_get_values(FFI_RLNProof_t* const* proof);                 /* ffi_rln.rs:158 */
 uint8_t ffi_rln_proof_get_version_byte(FFI_RLNProof_t* const* proof);                         /* ffi_rln.rs:165 */

@@ -298,6 +298,13 @@ int rlnamd_prover_submit_members(rlnamd_prover* p, rlnamd_tree* t, size_t n, con
 int rlnamd_prover_prove_stream_members(rlnamd_prover* p, rlnamd_tree* t, size_t n, const uint64_t* leaf_indices,
                                        const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* proofs,
                                        uint8_t* values, uint32_t* errors);
+/* rlnamd_prover_prove_stream_members_public: the same call with EVERY public signal of a proof in values_public, n *
+ * num_public * 32 bytes (rlnamd_prover_collect_public's rows), read before each chunk is collected.  The 160 bytes a proof
+ * of the form above are the five values of the single message-id circuit and stay zero on any other: a multi-message-id
+ * prover's caller uses this one (15 values a proof: ys | root | nullifiers | x | external nullifier | selectors). */
+int rlnamd_prover_prove_stream_members_public(rlnamd_prover* p, rlnamd_tree* t, size_t n, const uint64_t* leaf_indices,
+                                              const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* proofs,
+                                              uint8_t* values_public /* n*num_public*32 */, uint32_t* errors);
 int rlnamd_prover_stage_ms(rlnamd_prover* p, float ms[RLNAMD_PROVER_STAGES]);
 const char* rlnamd_prover_stage_name(int i);
 /* mean shader clock (MHz) under the G1 / G2 table walks since the previous call (the walks are VALU-issue bound: their
@@ -635,13 +642,37 @@ int rlnamd_relay_info(rlnamd_relay* r, uint64_t out[8]);
  * Who signs how often is as secret as who proves: the staged leaf indices, the sort's keys and every other per-call word,
  * in device and in pinned memory, are overwritten before draw returns, on error paths too, and rlnamd_quota_free zeroes
  * the counters.
+ * rlnamd_quota_draw_counts: blocks of ids, for the multi-message-id circuit, one proof of which uses up to max_out
+ * message slots.  n requests (leaf_indices[i], ext_le[i], limits[i], counts[i]), counts[i] = 1 .. RLNAMD_QUOTA_COUNT_MAX
+ * the number of ids the request asks for -> firsts_out[i], status[i].
+ *   RLNAMD_QUOTA_NO_EPOCH  ext[i] is not in the window; the request touches nothing
+ *   otherwise              rank_i = the sum of counts[j] over the requests j < i of this call with the same (external
+ *                          nullifier, leaf), whatever their outcome; first_i = used + rank_i with `used` as it was
+ *                          before the call; RLNAMD_QUOTA_OK iff first_i + counts[i] <= limits[i] (in 64 bits), and the
+ *                          request then owns the ids first_i .. first_i + counts[i] - 1; else RLNAMD_QUOTA_OVER: a
+ *                          request is granted whole or not at all
+ *   afterwards             the counter is first + count of its last OK request of this call, and unchanged if none was
+ * firsts_out[i] is first_i for OK and limits[i] otherwise.  With every count 1 this is rlnamd_quota_draw.  With one
+ * limit per member the OK requests of a (external nullifier, leaf) are a prefix of its requests, and the blocks granted
+ * for it, over any sequence of calls, are pairwise disjoint and each lies below its limit.
+ *   A CALL IS NOT WHAT EVERY SPLIT OF IT GIVES: a refused request still counts, with its whole block, in the ranks
+ *   behind it, so a smaller request of the same member later in the same call is refused although it would have
+ *   fitted; the next call grants it.  Only the all-ones case keeps rlnamd_quota_draw's split property.
+ * Refused before anything is enqueued, each with a text of its own, the ledger unchanged: what rlnamd_quota_draw
+ * refuses, a null `counts`, a count of 0, a count above RLNAMD_QUOTA_COUNT_MAX (which a byte cannot hold: the text is
+ * for callers that pack wider counts), n >= 2^24 (n x 255 then stays below 2^32; judged before any array is read).  The
+ * passes are rlnamd_quota_draw's plus one gather of the counts into sorted order and one sum over them; one member n
+ * times and n members cost the same here too.  The wipe is rlnamd_quota_draw's.
  * rlnamd_quota_used: the counters of n (leaf, external nullifier) pairs, for diagnostics and tests; in_window[i] = 0 and
  * used_out[i] = 0 for an external nullifier outside the window.
- * info: [0] external nullifiers in the window, [1] draws, [2] ids issued, [3] requests refused OVER, [4] requests
+ * info: [0] external nullifiers in the window, [1] draws, [2] ids issued (a granted request of rlnamd_quota_draw_counts
+ * counts with its count), [3] requests refused OVER, [4] requests
  * refused NO_EPOCH, [5] non-zero 16-byte words left in the ledger's per-call buffers, device and pinned (0 expected),
  * [6] depth, [7] max_epochs.
  * rlnamd_quota_plan (host only): the passes of a draw of n requests on a ledger of `depth` -- [0] sort passes, [1]
- * workgroups a pass, [2] scan levels over a pass's bins, [3] scan levels over the requests. */
+ * workgroups a pass, [2] scan levels over a pass's bins, [3] scan levels over the requests.  It holds for
+ * rlnamd_quota_draw_counts as it stands: the sum over the counts is one more scan over the n requests, with the levels
+ * of [3], and the gather has the workgroups of [1]; nothing it reports changes. */
 typedef struct rlnamd_quota rlnamd_quota;
 #define RLNAMD_QUOTA_OK 0
 #define RLNAMD_QUOTA_OVER 1
@@ -652,6 +683,10 @@ int rlnamd_quota_set_epochs(rlnamd_quota* q, const uint8_t* external_nullifiers_
 int rlnamd_quota_epochs(rlnamd_quota* q, uint8_t* out_le /* RLNAMD_RELAY_EPOCHS_MAX*32 */, size_t* k);
 int rlnamd_quota_draw(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le /* n*32 */,
                       const uint32_t* limits /* n */, uint32_t* ids_out /* n */, uint8_t* status /* n */);
+#define RLNAMD_QUOTA_COUNT_MAX 255 /* the most message slots a relay takes a proof (a share count is a byte) */
+int rlnamd_quota_draw_counts(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le /* n*32 */,
+                             const uint32_t* limits /* n */, const uint8_t* counts /* n bytes */, uint32_t* firsts_out /* n */,
+                             uint8_t* status /* n */);
 int rlnamd_quota_used(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le /* n*32 */,
                       uint32_t* used_out /* n */, uint8_t* in_window /* n */);
 int rlnamd_quota_info(rlnamd_quota* q, uint64_t out[8]);
@@ -680,6 +715,33 @@ int rlnamd_prover_prove_stream_members_drawn(rlnamd_prover* p, rlnamd_tree* t, r
                                              const uint64_t* leaf_indices, const uint8_t* inputs_le, const uint8_t* rs_le,
                                              uint8_t* status /* n */, uint8_t* proofs /* n*128 */, uint8_t* values /* n*160 */,
                                              uint32_t* errors /* n */);
+
+/* ---- proving with drawn blocks of message ids: the multi-message-id circuit, one proof of which uses up to max_out
+ * message slots.  rlnamd_prover_submit_members_drawn_counts is rlnamd_prover_submit_members_drawn with counts[i] = 1 ..
+ * max_out, the number of slots proof i uses: ONE rlnamd_quota_draw_counts covers the call (its closed form and its
+ * caveat -- a call is NOT what every split of it gives -- hold as stated there), and status[i] is its answer.  The
+ * messageId and selectorUsed slots of inputs_le are ignored.  A granted row gets messageId[k] = first_i + k and
+ * selectorUsed[k] = 1 for k < counts[i], and 0 in both above; a request that is not RLNAMD_QUOTA_OK gets 0xFF bytes in
+ * EVERY message slot and zero selectors, the witness interpreter refuses the row, and collect and collect_public give
+ * errors[i] != 0, 128 zero proof bytes and num_public * 32 zero value bytes for it.  Routes, events and locks are those
+ * of rlnamd_prover_submit_members_drawn; one kernel behind the staging writes ids and selectors on the device route, and
+ * the host route copies the batch's firsts back once and writes the same bytes.  rlnamd_quota_info[5] is 0 afterwards.
+ * Refused before anything is drawn or enqueued, each with a text of its own: what submit_members refuses; a graph that
+ * does not name userMessageLimit, externalNullifier, messageId[max_out] and selectorUsed[max_out] (a single message-id
+ * graph names no selectors, needs none, and takes counts of 1: the call then gives what
+ * rlnamd_prover_submit_members_drawn gives); a count of 0; a count above max_out; a ledger whose depth is not the
+ * tree's; objects on different devices; a limit >= 2^32.
+ * rlnamd_prover_prove_stream_members_drawn_counts: the chunked form, all n blocks drawn first, every chunk reading its
+ * slice.  values_public is n * num_public * 32 bytes, every public signal of a proof: ys | root | nullifiers | x |
+ * external nullifier | selectors on the multi-message-id circuit. */
+int rlnamd_prover_submit_members_drawn_counts(rlnamd_prover* p, rlnamd_tree* t, rlnamd_quota* q, size_t n,
+                                              const uint64_t* leaf_indices, const uint8_t* inputs_le, const uint8_t* rs_le,
+                                              const uint8_t* counts /* n bytes */, uint8_t* status /* n */, uint64_t* ticket);
+int rlnamd_prover_prove_stream_members_drawn_counts(rlnamd_prover* p, rlnamd_tree* t, rlnamd_quota* q, size_t n,
+                                                    const uint64_t* leaf_indices, const uint8_t* inputs_le, const uint8_t* rs_le,
+                                                    const uint8_t* counts /* n bytes */, uint8_t* status /* n */,
+                                                    uint8_t* proofs /* n*128 */, uint8_t* values_public /* n*num_public*32 */,
+                                                    uint32_t* errors /* n */);
 
 /* ---- variable-base MSM on G1 / G2 (BASELINE config 5; north_star: "windowed Pippenger MSM on G1/G2") ---------
  * Replaces VariableBaseMSM::msm_bigint (ark-ec 0.5.0; call sites rln/src/partial_proof.rs:98-104,255-256: generic

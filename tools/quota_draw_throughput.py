@@ -2,7 +2,7 @@
 """Quota-ledger throughput: rlnamd_quota_draw by itself, and proving with drawn ids against proving with ids the host
 supplies.
 
-    python tools/quota_draw_throughput.py [--calls 9] [--out FILE]
+    python tools/quota_draw_throughput.py [--calls 9] [--out FILE] [--counts]
 
 prints ONE JSON line.  Torch-free (ctypes).  Each of the two steps runs in a child process of its own under a time
 limit; a step that fails or runs out of time ends the run there.
@@ -17,6 +17,15 @@ limit; a step that fails or runs out of time ends the run there.
           inputs, 1 024 and 8 192 proofs for distinct members through a prover of capacity 1 024; the two take turns in
           one process, median of `calls` calls after 1 warm-up call each.  "draw_share_1024" is the median of a
           1 024-request draw (step draw, distinct) over the median of the drawn 1 024-proof call.
+
+--counts measures the draw by count (rlnamd_quota_draw_counts) instead, by the same method:
+  draw_counts   the plain draw and the draw by count, counts 1 .. 4 in turn, each in both shapes: four series that take
+                turns in one process on one ledger.  "counts_over_draw" is the ratio of the medians per shape -- the
+                extra is one gather and one scan over n words -- and "one_member_over_distinct" is given for both.
+  prove_counts  on a multi-message-id prover of capacity 1 024, 1 024 proofs for distinct members:
+                rlnamd_prover_prove_stream_members with ids and selectors in the inputs (its 160-byte values stay zero
+                on this circuit), rlnamd_prover_prove_stream_members_public with the same inputs (every public value
+                read back, as the drawn call reads them) and rlnamd_prover_prove_stream_members_drawn_counts.
 """
 import argparse
 import ctypes as C
@@ -36,7 +45,7 @@ PROVE_SIZES = (1024, 8192)
 DEPTH = 20
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 EA, EB = 1001, 1002
-STEP_LIMIT_S = {"draw": 120, "prove": 420}
+STEP_LIMIT_S = {"draw": 120, "prove": 420, "draw_counts": 180, "prove_counts": 420}
 
 
 def row(n, ts):
@@ -129,7 +138,102 @@ def step_prove(calls):
     return out
 
 
-STEPS = {"draw": step_draw, "prove": step_prove}
+def step_draw_counts(calls):
+    from zerokit_amd import lib
+    from zerokit_amd._native import check
+    from zerokit_amd.batch import QuotaLedger
+    need_device()
+    q = QuotaLedger(DEPTH, 4)
+    q.set_epochs([EA, EB])
+    rnd = random.Random(20261021)
+    rows = []
+    for n in DRAW_SIZES:
+        ext = b"".join((EA if i & 1 else EB).to_bytes(32, "little") for i in range(n))
+        limits = (C.c_uint32 * n)(*([0xFFFFFFFF] * n))
+        counts = bytes(1 + (i & 3) for i in range(n))
+        ids, status = (C.c_uint32 * n)(), C.create_string_buffer(n)
+        leaves = {"distinct": (C.c_uint64 * n)(*rnd.sample(range(1 << DEPTH), n)), "one_member": (C.c_uint64 * n)(*([12345] * n))}
+
+        def draw(leaf):
+            check(lib().rlnamd_quota_draw(q._h, n, leaf, ext, limits, ids, status))
+
+        def draw_counts(leaf):
+            check(lib().rlnamd_quota_draw_counts(q._h, n, leaf, ext, limits, counts, ids, status))
+        series = [(kind + "_" + shape, fn, leaf) for shape, leaf in leaves.items() for kind, fn in (("draw", draw), ("counts", draw_counts))]
+        ts = {name: [] for name, _, _ in series}
+        for c in range(2 + calls):
+            for name, fn, leaf in series:
+                t0 = time.perf_counter()
+                fn(leaf)
+                t1 = time.perf_counter()
+                assert status.raw == b"\0" * n          # 65 536 x 4 ids a call: far below the limit
+                if c >= 2:
+                    ts[name].append(t1 - t0)
+        r = {name: row(n, t) for name, t in ts.items()}
+        for shape in leaves:
+            r["counts_over_draw_" + shape] = round(r["counts_" + shape]["median_ms"] / r["draw_" + shape]["median_ms"], 3)
+        for kind in ("draw", "counts"):
+            r[kind + "_one_member_over_distinct"] = round(r[kind + "_one_member"]["median_ms"] / r[kind + "_distinct"]["median_ms"], 3)
+        r["plan"] = list(QuotaLedger.plan(n, DEPTH))
+        rows.append(r)
+    info = q.info()
+    q.close()
+    return {"depth": DEPTH, "rows": rows, "residue": info["residue"]}
+
+
+def step_prove_counts(calls):
+    from zerokit_amd import lib
+    from zerokit_amd._native import check
+    from zerokit_amd.batch import BatchProver, PoseidonTree, QuotaLedger
+    need_device()
+    p = BatchProver(max_batch=1024, multi=True)
+    k, n = int(p.info.max_out), 1024
+    tree = PoseidonTree(DEPTH)
+    tree.fill_sequential(0, n, 1)
+    q = QuotaLedger(DEPTH, 4)
+    q.set_epochs([EA, EB])
+    rnd = random.Random(7)
+    cnt = [1 + (i % k) for i in range(n)]
+    ws = [dict(identity_secret=rnd.randrange(1, R), user_message_limit=1 << 20, x=rnd.randrange(R),
+               external_nullifier=EA if i & 1 else EB, message_id=[(7 * i + t) % 1000 if t < cnt[i] else 0 for t in range(k)],
+               selector_used=[int(t < cnt[i]) for t in range(k)]) for i in range(n)]
+    inputs = p.pack_member_inputs(ws)
+    rsb = p.pack_rs([(rnd.randrange(1, R), rnd.randrange(1, R)) for _ in range(n)])
+    idx, counts = (C.c_uint64 * n)(*range(n)), bytes(cnt)
+    proofs, values, public = C.create_string_buffer(128 * n), C.create_string_buffer(160 * n), C.create_string_buffer(32 * p.num_public * n)
+    errs, status = (C.c_uint32 * n)(), C.create_string_buffer(n)
+
+    def host_ids():
+        check(lib().rlnamd_prover_prove_stream_members(p._h, tree._h, n, idx, inputs, rsb, proofs, values, errs))
+
+    def host_ids_public():
+        check(lib().rlnamd_prover_prove_stream_members_public(p._h, tree._h, n, idx, inputs, rsb, proofs, public, errs))
+
+    def drawn_counts():
+        check(lib().rlnamd_prover_prove_stream_members_drawn_counts(p._h, tree._h, q._h, n, idx, inputs, rsb, counts, status, proofs,
+                                                                    public, errs))
+    fns = (("host_ids", host_ids), ("host_ids_public", host_ids_public), ("drawn_counts", drawn_counts))
+    ts = {name: [] for name, _ in fns}
+    for c in range(1 + calls):
+        for name, fn in fns:
+            t0 = time.perf_counter()
+            fn()
+            t1 = time.perf_counter()
+            assert not any(errs)
+            if c >= 1:
+                ts[name].append(t1 - t0)
+    assert status.raw == b"\0" * n
+    r = {name: row(n, t) for name, t in ts.items()}
+    r["drawn_counts_over_host_ids"] = round(r["drawn_counts"]["median_ms"] / r["host_ids"]["median_ms"], 4)
+    r["drawn_counts_over_host_ids_public"] = round(r["drawn_counts"]["median_ms"] / r["host_ids_public"]["median_ms"], 4)
+    out = {"capacity": 1024, "max_out": k, "rows": [r], "ledger_residue": q.info()["residue"]}
+    q.close()
+    tree.close()
+    p.close()
+    return out
+
+
+STEPS = {"draw": step_draw, "prove": step_prove, "draw_counts": step_draw_counts, "prove_counts": step_prove_counts}
 
 
 def main():
@@ -137,6 +241,7 @@ def main():
     ap.add_argument("--calls", type=int, default=9)
     ap.add_argument("--out")
     ap.add_argument("--step", choices=sorted(STEPS))
+    ap.add_argument("--counts", action="store_true", help="measure the draw by count (draw_counts, prove_counts)")
     a = ap.parse_args()
     if a.calls < 5:
         ap.error("--calls: at least 5")
@@ -144,7 +249,8 @@ def main():
         print(json.dumps(STEPS[a.step](a.calls)))
         return 0
     out = {"tool": "quota_draw_throughput", "calls": a.calls}
-    for name in ("draw", "prove"):
+    steps = ("draw_counts", "prove_counts") if a.counts else ("draw", "prove")
+    for name in steps:
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--calls", str(a.calls)],
                                stdout=subprocess.PIPE, timeout=STEP_LIMIT_S[name])
@@ -155,8 +261,8 @@ def main():
             out[name] = {"error": "exit status %d" % r.returncode}
             break   # nothing more is started on the device after a failed step
         out[name] = json.loads(r.stdout.decode().strip().splitlines()[-1])
-    good = all("error" not in out.get(k, {"error": 1}) for k in STEPS)
-    if good:
+    good = all("error" not in out.get(k, {"error": 1}) for k in steps)
+    if good and not a.counts:
         draw_1024 = next(r["distinct"]["median_ms"] for r in out["draw"]["rows"] if r["distinct"]["n"] == 1024)
         batch_1024 = next(r["drawn"]["median_ms"] for r in out["prove"]["rows"] if r["drawn"]["n"] == 1024)
         out["draw_share_1024"] = round(draw_1024 / batch_1024, 4)

@@ -137,6 +137,15 @@ SIGNATURES = {
     "rlnamd_quota_epochs": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_size_t)]),
     "rlnamd_quota_draw": (C.c_int, [P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.POINTER(C.c_uint32),
                                     C.POINTER(C.c_uint32), C.c_char_p]),
+    "rlnamd_quota_draw_counts": (C.c_int, [P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p,
+                                           C.POINTER(C.c_uint32), C.c_char_p]),
+    "rlnamd_prover_submit_members_drawn_counts": (C.c_int, [P, P, P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
+                                                            C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "rlnamd_prover_prove_stream_members_drawn_counts": (C.c_int, [P, P, P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
+                                                                  C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                                                  C.POINTER(C.c_uint32)]),
+    "rlnamd_prover_prove_stream_members_public": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p,
+                                                            C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
     "rlnamd_quota_used": (C.c_int, [P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p]),
     "rlnamd_quota_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_quota_plan": (C.c_int, [C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]),
@@ -284,6 +293,8 @@ SIGNATURES = {
                                                           CFRP, CFRP, PP]),
     "ffi_generate_rln_proofs_for_members_drawn": (CBoolResult, [PP, P, C.POINTER(C.c_size_t), C.c_size_t, CFRP, CFRP, CFRP, CFRP,
                                                                 CFRP, C.c_char_p, PP]),
+    "ffi_generate_rln_proofs_for_members_drawn_multi": (CBoolResult, [PP, P, C.POINTER(C.c_size_t), C.c_size_t, CFRP, CFRP, C.c_char_p,
+                                                                      CFRP, CFRP, CFRP, C.c_char_p, PP]),
     "ffi_verify_rln_proof": (CBoolResult, [PP, PP, CFRP]),
     "ffi_verify_rln_proofs_batch": (CBoolResult, [PP, PP, C.c_size_t, CFRP, C.POINTER(VecCFr), C.POINTER(C.c_bool)]),
     "ffi_verify_rln_signals_batch": (CBoolResult, [PP, PP, C.c_size_t, C.POINTER(VecU8), C.POINTER(VecCFr),

@@ -257,6 +257,80 @@ class BatchProver:
         p, v, e, st = self.prove_members_drawn_raw(tree, quota, leaf_indices, self.pack_member_inputs(ws), self.pack_rs(rs))
         return _unpack_results(p, v, e), st
 
+    # ---- blocks of ids for the multi-message-id circuit (rlnamd_prover_*_members_drawn_counts)
+    def _drawn_counts_args(self, what, leaf_indices, inputs, rsb, counts):
+        n = len(inputs) // (self.inputs_size * 32)
+        if len(inputs) != n * self.inputs_size * 32 or len(rsb) != 64 * n or len(leaf_indices) != n or len(counts) != n:
+            raise RLNError("%s: leaf indices / inputs / rs / counts sizes do not match" % what)
+        for i, c in enumerate(counts):      # what a byte cannot carry to the library's own check, in the library's words
+            if not 0 <= int(c) <= 255:
+                raise RLNError("quota ledger: request %d of draw_counts asks for %d ids, more than 255" % (i, int(c)))
+        return n, (C.c_uint64 * max(n, 1))(*[int(i) for i in leaf_indices]), bytes(int(c) for c in counts) or b"\0"
+
+    def submit_members_drawn_counts(self, tree: "PoseidonTree", quota: "QuotaLedger", leaf_indices, inputs: bytes, rsb: bytes,
+                                    counts):
+        """submit_members_drawn for a proof that uses counts[i] = 1 .. max_out message slots: one QuotaLedger.draw_counts
+        covers the call, a granted row gets the ids first .. first + counts[i] - 1 in its first counts[i] message slots
+        with their selectors set, the messageId and selectorUsed slots of `inputs` are ignored
+        (rlnamd_prover_submit_members_drawn_counts).  Returns (ticket, n, statuses); read the public values with
+        collect_public before collect_raw."""
+        n, idx, cb = self._drawn_counts_args("submit_members_drawn_counts", leaf_indices, inputs, rsb, counts)
+        t = C.c_uint64()
+        status = C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_prover_submit_members_drawn_counts(self._h, tree._h, quota._h, n, idx, inputs, rsb, cb, status, C.byref(t)))
+        return int(t.value), n, list(status.raw[:n])
+
+    def prove_members_drawn_counts_raw(self, tree: "PoseidonTree", quota: "QuotaLedger", leaf_indices, inputs: bytes, rsb: bytes,
+                                       counts):
+        """any n members through rlnamd_prover_prove_stream_members_drawn_counts: one draw for all n, chunks of `capacity`
+        -> (proofs, public values n * num_public * 32 bytes, errors, statuses)"""
+        n, idx, cb = self._drawn_counts_args("prove_members_drawn_counts", leaf_indices, inputs, rsb, counts)
+        proofs = C.create_string_buffer(128 * n)
+        values = C.create_string_buffer(max(32 * self.num_public * n, 1))
+        errs = (C.c_uint32 * max(n, 1))()
+        status = C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_prover_prove_stream_members_drawn_counts(self._h, tree._h, quota._h, n, idx, inputs, rsb, cb, status,
+                                                                    proofs, values, errs))
+        return proofs.raw, values.raw[:32 * self.num_public * n], list(errs)[:n], list(status.raw[:n])
+
+    def pack_member_inputs_multi(self, witnesses):
+        """pack_member_inputs for witnesses without message ids and selectors either (the drawn calls fill them in)"""
+        k = self.slots["messageId"][1]
+        extra = dict(message_id=[0] * k)
+        if "selectorUsed" in self.slots:
+            extra["selector_used"] = [0] * k
+        return self.pack_member_inputs([dict(w, **extra) for w in witnesses])
+
+    def prove_members_drawn_counts(self, tree: "PoseidonTree", quota: "QuotaLedger", leaf_indices, witnesses, rs, counts):
+        """witnesses: dicts with identity_secret, user_message_limit, x and external_nullifier, one per leaf index; message
+        ids and selectors, if given, are ignored -> ([dict(proof, public_inputs: num_public ints, error)], statuses)"""
+        p, v, e, st = self.prove_members_drawn_counts_raw(tree, quota, leaf_indices, self.pack_member_inputs_multi(witnesses),
+                                                          self.pack_rs(rs), counts)
+        row = 32 * self.num_public
+        return [dict(proof=p[128 * i:128 * i + 128], error=e[i],
+                     public_inputs=[int.from_bytes(v[row * i + 32 * j:row * i + 32 * j + 32], "little") for j in range(self.num_public)])
+                for i in range(len(e))], st
+
+    def prove_members_public_raw(self, tree: "PoseidonTree", leaf_indices, inputs: bytes, rsb: bytes):
+        """prove_members_raw with every public signal of a proof (num_public * 32 bytes a row) in the place of the 160
+        bytes of the single message-id circuit (rlnamd_prover_prove_stream_members_public)"""
+        n = len(inputs) // (self.inputs_size * 32)
+        if len(inputs) != n * self.inputs_size * 32 or len(rsb) != 64 * n or len(leaf_indices) != n:
+            raise RLNError("prove_members: leaf indices / inputs / rs sizes do not match")
+        idx = (C.c_uint64 * max(n, 1))(*[int(i) for i in leaf_indices])
+        proofs = C.create_string_buffer(128 * n)
+        values = C.create_string_buffer(max(32 * self.num_public * n, 1))
+        errs = (C.c_uint32 * max(n, 1))()
+        check(lib().rlnamd_prover_prove_stream_members_public(self._h, tree._h, n, idx, inputs, rsb, proofs, values, errs))
+        return proofs.raw, values.raw[:32 * self.num_public * n], list(errs)[:n]
+
+    def collect_public(self, ticket, n):
+        """every public signal of a finished batch, n * num_public * 32 bytes; call it BEFORE collect_raw, which ends the
+        batch (rlnamd_prover_collect_public)"""
+        buf = C.create_string_buffer(max(32 * self.num_public * n, 1))
+        check(lib().rlnamd_prover_collect_public(self._h, ticket, n, buf))
+        return buf.raw[:32 * self.num_public * n]
+
     def hints_for(self, inputs: bytes):
         """the hints of the proofs packed in `inputs`, one proof at a time on this thread (rlnamd_prover_hints_for): a list
         of ctypes arrays, or None when the circuit has no segments form"""
@@ -952,6 +1026,27 @@ class QuotaLedger:
                                       b"".join(_b(e) for e in external_nullifiers) or b"\0",
                                       (C.c_uint32 * max(n, 1))(*[int(v) for v in limits]), ids, status))
         return list(ids[:n]), list(status.raw[:n])
+
+    COUNT_MAX = 255
+
+    def draw_counts(self, leaf_indices, external_nullifiers, limits, counts):
+        """n requests of counts[i] ids each (1 .. COUNT_MAX: the message slots a multi-message-id proof uses) ->
+        (firsts, statuses); an OK request owns the ids firsts[i] .. firsts[i] + counts[i] - 1, and firsts[i] is
+        limits[i] where statuses[i] is not OK.  A request is granted whole or not at all, and one that is refused still
+        counts in the ranks behind it: a call is NOT what every split of it gives (rlnamd_quota_draw_counts)."""
+        n = len(leaf_indices)
+        if len(external_nullifiers) != n or len(limits) != n or len(counts) != n:
+            raise RLNError("QuotaLedger.draw_counts: %d leaf indices, %d external nullifiers, %d limits, %d counts" %
+                           (n, len(external_nullifiers), len(limits), len(counts)))
+        for i, c in enumerate(counts):      # what a byte cannot carry to the library's own check, in the library's words
+            if not 0 <= int(c) <= self.COUNT_MAX:
+                raise RLNError("quota ledger: request %d of draw_counts asks for %d ids, more than %d" % (i, int(c), self.COUNT_MAX))
+        firsts, status = (C.c_uint32 * max(n, 1))(), C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_quota_draw_counts(self._h, n, (C.c_uint64 * max(n, 1))(*[int(v) for v in leaf_indices]),
+                                             b"".join(_b(e) for e in external_nullifiers) or b"\0",
+                                             (C.c_uint32 * max(n, 1))(*[int(v) for v in limits]),
+                                             bytes(int(c) for c in counts) or b"\0", firsts, status))
+        return list(firsts[:n]), list(status.raw[:n])
 
     def used(self, leaf_indices, external_nullifiers):
         """the counters of n (leaf, external nullifier) pairs -> [next id, or None outside the window]"""

@@ -418,7 +418,7 @@ int rlnamd_relay_info(rlnamd_relay* r, uint64_t out[8]) {
 
 // ------------------------------------------------------------------------------------- quota ledger
 static_assert(RLNAMD_QUOTA_OK == quota::OK && RLNAMD_QUOTA_OVER == quota::OVER && RLNAMD_QUOTA_NO_EPOCH == quota::NO_EPOCH &&
-                  RLNAMD_RELAY_EPOCHS_MAX == quota::EPOCHS_MAX,
+                  RLNAMD_RELAY_EPOCHS_MAX == quota::EPOCHS_MAX && RLNAMD_QUOTA_COUNT_MAX == quota::COUNT_MAX,
               "the ledger's statuses and window");
 int rlnamd_quota_new(size_t depth, size_t max_epochs, rlnamd_quota** out) {
   RLN_TRY
@@ -458,6 +458,18 @@ int rlnamd_quota_draw(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, c
   }
   std::lock_guard<std::mutex> lk(q->mu);
   q->ledger.draw(n, leaf_indices, ext_le, limits, ids_out, status);
+  RLN_CATCH
+}
+int rlnamd_quota_draw_counts(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
+                             const uint8_t* counts, uint32_t* firsts_out, uint8_t* status) {
+  RLN_TRY
+  // what needs no object is judged without one (the ledger judges the same with its own depth, before it enqueues)
+  if (!q) {
+    const std::string refused = quota::draw_counts_refusal(n, leaf_indices, ext_le, limits, counts, firsts_out, status, quota::DEPTH_MAX);
+    throw Error(refused.empty() ? "rlnamd_quota_draw_counts: null ledger" : refused);
+  }
+  std::lock_guard<std::mutex> lk(q->mu);
+  q->ledger.draw_counts(n, leaf_indices, ext_le, limits, counts, firsts_out, status);
   RLN_CATCH
 }
 int rlnamd_quota_used(rlnamd_quota* q, size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, uint32_t* used_out,
@@ -672,6 +684,37 @@ int rlnamd_prover_prove_stream_members_drawn(rlnamd_prover* p, rlnamd_tree* t, r
   std::lock_guard<std::mutex> tree_lk(t->mu);
   std::lock_guard<std::mutex> quota_lk(q->mu);
   p->p->prove_stream_members_drawn(member_tree(t), q->ledger, n, leaf_indices, inputs_le, rs_le, status, proofs, values, errors);
+  RLN_CATCH
+}
+int rlnamd_prover_submit_members_drawn_counts(rlnamd_prover* p, rlnamd_tree* t, rlnamd_quota* q, size_t n, const uint64_t* leaf_indices,
+                                              const uint8_t* inputs_le, const uint8_t* rs_le, const uint8_t* counts, uint8_t* status,
+                                              uint64_t* ticket) {
+  RLN_TRY
+  if (!p || !t || !q || !ticket) throw Error("rlnamd_prover_submit_members_drawn_counts: null pointer");
+  std::lock_guard<std::mutex> tree_lk(t->mu);
+  std::lock_guard<std::mutex> quota_lk(q->mu);
+  *ticket = p->p->submit_members_drawn_counts(member_tree(t), q->ledger, n, leaf_indices, inputs_le, rs_le, counts, status);
+  RLN_CATCH
+}
+int rlnamd_prover_prove_stream_members_drawn_counts(rlnamd_prover* p, rlnamd_tree* t, rlnamd_quota* q, size_t n,
+                                                    const uint64_t* leaf_indices, const uint8_t* inputs_le, const uint8_t* rs_le,
+                                                    const uint8_t* counts, uint8_t* status, uint8_t* proofs, uint8_t* values_public,
+                                                    uint32_t* errors) {
+  RLN_TRY
+  if (!p || !t || !q) throw Error("rlnamd_prover_prove_stream_members_drawn_counts: null pointer");
+  std::lock_guard<std::mutex> tree_lk(t->mu);
+  std::lock_guard<std::mutex> quota_lk(q->mu);
+  p->p->prove_stream_members_drawn_counts(member_tree(t), q->ledger, n, leaf_indices, inputs_le, rs_le, counts, status, proofs,
+                                          values_public, errors);
+  RLN_CATCH
+}
+int rlnamd_prover_prove_stream_members_public(rlnamd_prover* p, rlnamd_tree* t, size_t n, const uint64_t* leaf_indices,
+                                              const uint8_t* inputs_le, const uint8_t* rs_le, uint8_t* proofs, uint8_t* values_public,
+                                              uint32_t* errors) {
+  RLN_TRY
+  if (!p || !t) throw Error("rlnamd_prover_prove_stream_members_public: null pointer");
+  std::lock_guard<std::mutex> tree_lk(t->mu);
+  p->p->prove_stream_members_public(member_tree(t), n, leaf_indices, inputs_le, rs_le, proofs, values_public, errors);
   RLN_CATCH
 }
 int rlnamd_prover_run_mode(rlnamd_prover* p, size_t n, int mode) {

@@ -1843,6 +1843,84 @@ CBoolResult_t ffi_generate_rln_proofs_for_members_drawn(FFI_RLN_t* const* rln, s
                               user_message_limits, nullptr, xs, external_nullifiers, rs, status, out);
   });
 }
+// EXT: the multi-message-id form -- counts[i] = 1 .. max_out message slots a proof, a block of ids drawn for each from the
+// ledger (Prover::submit_members_drawn_counts).  out[i]: a proof with MultiV1 values, or null where no proof was made.
+CBoolResult_t ffi_generate_rln_proofs_for_members_drawn_multi(FFI_RLN_t* const* rln, struct rlnamd_quota* quota,
+                                                              const size_t* leaf_indices, size_t n, const CFr_t* identity_secrets,
+                                                              const CFr_t* user_message_limits, const uint8_t* counts, const CFr_t* xs,
+                                                              const CFr_t* external_nullifiers, const CFr_t* rs, uint8_t* status,
+                                                              FFI_RLNProof_t** out) {
+  return guard_bool([&]() {
+    if (n == 0) return true;
+    const std::string name("ffi_generate_rln_proofs_for_members_drawn_multi");
+    if (!quota) throw Error(name + ": null ledger");
+    if (!rln || !*rln) throw Error(name + ": null RLN object");
+    if (!leaf_indices || !identity_secrets || !user_message_limits || !counts || !xs || !external_nullifiers || !status || !out)
+      throw Error(name + ": null argument");
+    FFI_RLN& r = *(FFI_RLN*)*rln;
+    if (r.stateless) throw Error(name + ": the object has no tree");
+    std::lock_guard<std::mutex> guard(*r.prove_mu);
+    Prover& P = *r.prover;
+    if (!P.graph().input_mapping.count("selectorUsed")) throw Error(name + ": multi message-id circuits only");
+    if (r.auto_partial) r.memo_adopt_pending();
+    const size_t ni = P.inputs_per_proof(), d = P.graph().tree_depth, mo = P.graph().max_out, npub = P.num_public();
+    std::vector<uint8_t> inputs(n * ni * 32), rsb(n * 64), idx8(n * 8);
+    ZeroOnExit z1{inputs}, z2{rsb}, z3{idx8};   // (who proves is a secret as well)
+    uint64_t* idx = reinterpret_cast<uint64_t*>(idx8.data());
+    {
+      // the witness constructor's checks and texts (validate_witness) on what the caller does supply; ids and selectors are
+      // the draw's, so the witness judged carries one used slot with the id 0, which every limit above zero admits
+      FFI_RLNWitnessInput w;
+      w.multi = true;
+      w.path_elements.assign(d, cfr_from_u64(0));
+      w.identity_path_index.assign(d, 0);
+      w.message_ids.assign(mo, cfr_from_u64(0));
+      w.selector_used.assign(mo, 0);
+      w.selector_used[0] = 1;
+      for (size_t i = 0; i < n; i++) {
+        w.identity_secret = R(&identity_secrets[i]);
+        w.user_message_limit = R(&user_message_limits[i]);
+        w.x = R(&xs[i]);
+        w.external_nullifier = R(&external_nullifiers[i]);
+        validate_witness(w);
+        fill_inputs(P, w, inputs.data() + i * ni * 32);   // (the message slots and selectors are overwritten with the draw's)
+        const CFr rr = rs ? R(&rs[2 * i]) : random_fr(), ss = rs ? R(&rs[2 * i + 1]) : random_fr();
+        memcpy(rsb.data() + i * 64, rr.le, 32);
+        memcpy(rsb.data() + i * 64 + 32, ss.le, 32);
+        idx[i] = leaf_indices[i];
+      }
+    }
+    std::vector<uint8_t> proofs(n * 128), values(n * npub * 32);
+    std::vector<uint32_t> errs(n);
+    {
+      std::lock_guard<std::mutex> tree_lk(r.tree.pend->mu);   // the order of the locks: prover, tree, ledger
+      r.tree.flush_pending_locked();
+      MemberTree mt;
+      mt.dense = r.tree.sparse ? nullptr : &r.tree.dense;
+      mt.depth = r.tree.depth;
+      mt.proofs_at = [&](const uint64_t* ix, size_t k, uint8_t* e, uint8_t* b) { r.tree.proofs_at_locked(ix, k, e, b); };
+      std::lock_guard<std::mutex> quota_lk(quota->mu);
+      P.prove_stream_members_drawn_counts(mt, quota->ledger, n, idx, inputs.data(), rsb.data(), counts, status, proofs.data(),
+                                          values.data(), errs.data());
+    }
+    for (size_t i = 0; i < n; i++)
+      if (errs[i] && status[i] == quota::OK)
+        throw Error("Error calculating witness: graph evaluation failed (code " + std::to_string(errs[i]) + ")");
+    std::vector<std::unique_ptr<FFI_RLNProof>> made;
+    for (size_t i = 0; i < n; i++) {
+      if (status[i] != quota::OK) {
+        made.push_back(nullptr);
+        continue;
+      }
+      std::unique_ptr<FFI_RLNProof> pr(new FFI_RLNProof);
+      memcpy(pr->proof, proofs.data() + 128 * i, 128);
+      values_from_public(values.data() + i * npub * 32, mo, &pr->values);
+      made.push_back(std::move(pr));
+    }
+    for (size_t i = 0; i < n; i++) out[i] = (FFI_RLNProof_t*)made[i].release();
+    return true;
+  });
+}
 CBoolResult_t ffi_verify_rln_proof(FFI_RLN_t* const* rln, FFI_RLNProof_t* const* proof, const CFr_t* x) {
   return guard_bool([&]() {  // public.rs:725-745: proof -> root -> signal, first failure is an error
     FFI_RLN& r = *(FFI_RLN*)*rln;

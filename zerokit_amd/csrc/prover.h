@@ -114,6 +114,7 @@ struct MemberGather {   // enqueue's view of a device-route members batch
   const uint32_t* ids = nullptr;
   const uint8_t* ids_status = nullptr;   // ... and the draw's statuses beside them: a refused request gets no field element
   void* ids_stream = nullptr;
+  const uint8_t* ids_counts = nullptr;   // submit_members_drawn_counts: ids are each block's first id, these the block sizes
 };
 struct QuotaLedgerDev;
 struct DrawnIds;   // prover.hip: a held draw and where a chunk's ids start in it
@@ -195,6 +196,26 @@ class Prover {
   void prove_stream_members_drawn(const MemberTree& tree, QuotaLedgerDev& quota, size_t n, const uint64_t* leaf_indices,
                                   const uint8_t* inputs, const uint8_t* rs, uint8_t* status, uint8_t* proofs, uint8_t* values,
                                   uint32_t* errors);
+  // The same for the multi-message-id circuit, whose proof uses up to max_out message slots: counts[i] = 1 .. max_out is
+  // the number of slots proof i uses, ONE QuotaLedgerDev::draw_counts covers the call and grants each request a block of
+  // ids whole or not at all.  The messageId and selectorUsed slots of `inputs` are ignored: a granted row gets messageId[k]
+  // = first + k and selectorUsed[k] = 1 for k < counts[i], both 0 above; a refused row gets no field element in any
+  // message slot and zero selectors, so the interpreter refuses it.  The routes, the events, the locks and what collect
+  // and collect_public hand out for a refused row (nothing) are submit_members_drawn's.  Refused before anything is drawn,
+  // each with its own text: what submit_members refuses; a graph that does not name the four inputs (messageId and
+  // selectorUsed max_out wide; a single message-id graph needs no selectors and takes counts of 1); a count of 0 or above
+  // max_out; a ledger of another depth or on another device; a limit >= 2^32.  The stream form hands out EVERY public
+  // signal of a proof, num_public() x 32 bytes a row (the multi circuit: ys | root | nullifiers | x | external nullifier |
+  // selectors), read with collect_public before each chunk is collected.
+  uint64_t submit_members_drawn_counts(const MemberTree& tree, QuotaLedgerDev& quota, size_t n, const uint64_t* leaf_indices,
+                                       const uint8_t* inputs, const uint8_t* rs, const uint8_t* counts, uint8_t* status);
+  void prove_stream_members_drawn_counts(const MemberTree& tree, QuotaLedgerDev& quota, size_t n, const uint64_t* leaf_indices,
+                                         const uint8_t* inputs, const uint8_t* rs, const uint8_t* counts, uint8_t* status,
+                                         uint8_t* proofs, uint8_t* values_public, uint32_t* errors);
+  // prove_stream_members with every public signal a row (num_public() x 32 bytes) in the place of the five values of the
+  // single message-id circuit, which is all the 160-byte form can carry: what a multi-message-id prover's caller needs
+  void prove_stream_members_public(const MemberTree& tree, size_t n, const uint64_t* leaf_indices, const uint8_t* inputs,
+                                   const uint8_t* rs, uint8_t* proofs, uint8_t* values_public, uint32_t* errors);
   // The hints of a lone small batch (the values between the circuit's chained hashes: prover_plan.h, HintChains) may be
   // computed ahead of the call, by any thread, one proof at a time: hint_words() 32-bit words per proof (0: this circuit
   // has no such form), hints_for() fills them from one proof's packed inputs.  submit_hinted() is submit() for a full
@@ -221,7 +242,7 @@ class Prover {
   typedef std::function<bool(size_t* off, size_t* cnt)> ChunkSource;
   void prove_stream_from(const ChunkSource& next, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs, uint8_t* values,
                          uint32_t* errors, int max_in_flight = 0, const MemberTree* tree = nullptr,
-                         const uint64_t* leaf_indices = nullptr, const DrawnIds* drawn = nullptr);
+                         const uint64_t* leaf_indices = nullptr, const DrawnIds* drawn = nullptr, bool public_values = false);
   void prove_stream(size_t n, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs, uint8_t* values,
                     uint32_t* errors);
   // Partial proofs.  PROVE_PARTIAL: inputs carry only the partial witness (unknown slots zero); the result is
@@ -300,6 +321,8 @@ class Prover {
   // the checks of a drawn batch behind check_members; fills the draw's limits and external nullifiers from the rows
   void check_drawn(const MemberTree& tree, const QuotaLedgerDev& quota, size_t n, const uint8_t* inputs,
                    std::vector<uint32_t>* limits, std::vector<uint8_t>* ext_le) const;
+  void check_drawn_counts(const MemberTree& tree, const QuotaLedgerDev& quota, size_t n, const uint8_t* inputs, const uint8_t* counts,
+                          std::vector<uint32_t>* limits, std::vector<uint8_t>* ext_le) const;
   void fetch_public_slot(void* slot, size_t n, std::vector<uint8_t>* out_le);
   void residue_of(void* slot, uint64_t out[RESIDUE_SLOT_FIELDS]);
   struct Impl;

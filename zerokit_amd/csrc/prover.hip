@@ -322,6 +322,9 @@ struct Prover::Impl {
   uint32_t path_off = 0, path_idx_off = 0;
   bool have_drawn_slots = false;          // ... and userMessageLimit, externalNullifier and ONE messageId (submit_members_drawn)
   uint32_t drawn_msg_off = 0;
+  // ... or messageId[max_out] and selectorUsed[max_out] (submit_members_drawn_counts; no selectors on a single message-id graph)
+  bool have_drawn_multi_slots = false, drawn_sel = false;
+  uint32_t drawn_multi_msg_off = 0, drawn_multi_sel_off = 0, drawn_multi_slots = 1;
   bool have_values_kernel = false;
   // resident inputs (shared by both slots; upload() drains the pipeline first)
   DevBuf<uint32_t> inputs, rs;
@@ -666,6 +669,11 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
   D.path_idx_off = named.path_idx_off;
   D.have_drawn_slots = named.have_drawn_slots;
   D.drawn_msg_off = named.drawn_msg_off;
+  D.have_drawn_multi_slots = named.have_drawn_multi_slots;
+  D.drawn_sel = named.drawn_sel;
+  D.drawn_multi_msg_off = named.drawn_multi_msg_off;
+  D.drawn_multi_sel_off = named.drawn_multi_sel_off;
+  D.drawn_multi_slots = named.drawn_multi_slots;
   D.hints.configure(named, D.tune.hint_chains);
   // ---- where the graph can be cut (segments behind hints; find_hint_cuts): a circuit on which a hint matches no node
   //      keeps the whole-graph interpreter
@@ -1116,6 +1124,7 @@ struct DrawnIds {
   QuotaLedgerDev::Held held;
   const uint8_t* status;   // the draw's statuses on the host (the caller's array), from request 0
   size_t first;
+  const uint8_t* counts = nullptr;   // a draw by count: the requests' counts on the host, from request 0; the ids are firsts
 };
 
 uint64_t Prover::submit_members(const MemberTree& t, size_t n, const uint64_t* leaf, const uint8_t* inputs, const uint8_t* rs,
@@ -1196,6 +1205,87 @@ void Prover::prove_stream_members_drawn(const MemberTree& t, QuotaLedgerDev& q, 
   }, inputs, rs, proofs, values, errors, 0, &t, leaf, &drawn);
 }
 
+// Blocks of ids for the multi-message-id circuit: the same call with a count a proof, the number of message slots it uses.
+void Prover::check_drawn_counts(const MemberTree& t, const QuotaLedgerDev& q, size_t n, const uint8_t* inputs, const uint8_t* counts,
+                                std::vector<uint32_t>* limits, std::vector<uint8_t>* ext_le) const {
+  const Impl& D = *d_;
+  if (!D.have_drawn_multi_slots)
+    throw Error("submit_members_drawn_counts: the witness graph does not name userMessageLimit, externalNullifier, messageId and "
+                "selectorUsed with one message id and one selector per message slot");
+  if (q.depth() != t.depth)
+    throw Error("submit_members_drawn_counts: the ledger's depth (" + std::to_string(q.depth()) + ") is not the tree's (" +
+                std::to_string(t.depth) + ")");
+  if (q.device() != D.device.dev) throw Error("submit_members_drawn_counts: the ledger and the prover are on different devices");
+  const size_t NIB = (size_t)D.NI * 32;
+  limits->resize(n);
+  ext_le->resize(32 * n);
+  for (size_t i = 0; i < n; i++) {
+    const std::string bad = quota::count_refusal(i, counts[i]);   // (a count of 0: the ledger's own text, before the draw)
+    if (!bad.empty()) throw Error(bad);
+    if (counts[i] > D.drawn_multi_slots)
+      throw Error("submit_members_drawn_counts: proof " + std::to_string(i) + " asks for " + std::to_string(counts[i]) +
+                  " message ids, the circuit has " + std::to_string(D.drawn_multi_slots) + " message slots (max_out)");
+    const uint8_t* limit = inputs + i * NIB + (size_t)D.slots.limit * 32;
+    uint8_t high = 0;
+    for (int b = 4; b < 32; b++) high |= limit[b];
+    if (high) throw Error("submit_members_drawn_counts: the message limit of proof " + std::to_string(i) + " is 2^32 or more");
+    memcpy(&(*limits)[i], limit, 4);
+    memcpy(ext_le->data() + 32 * i, inputs + i * NIB + (size_t)D.slots.ext * 32, 32);
+  }
+}
+
+uint64_t Prover::submit_members_drawn_counts(const MemberTree& t, QuotaLedgerDev& q, size_t n, const uint64_t* leaf, const uint8_t* inputs,
+                                             const uint8_t* rs, const uint8_t* counts, uint8_t* status) {
+  if (n == 0) throw Error("empty batch");
+  if (!leaf || !inputs || !rs || !counts || !status)
+    throw Error("submit_members_drawn_counts: leaf indices, inputs, rs, counts and status are required");
+  if (n > B_) throw Error("batch larger than the prover workspace (max_batch)");
+  check_members(t, n, leaf);
+  std::vector<uint32_t> limits;
+  std::vector<uint8_t> ext;
+  check_drawn_counts(t, q, n, inputs, counts, &limits, &ext);
+  ReleaseDraw release{q};
+  const DrawnIds drawn{&q, q.draw_hold_counts(n, leaf, ext.data(), limits.data(), counts, status), status, 0, counts};
+  return submit_members_by(t, n, leaf, inputs, rs, PROVE_FULL, &drawn);
+}
+
+void Prover::prove_stream_members_drawn_counts(const MemberTree& t, QuotaLedgerDev& q, size_t n, const uint64_t* leaf,
+                                               const uint8_t* inputs, const uint8_t* rs, const uint8_t* counts, uint8_t* status,
+                                               uint8_t* proofs, uint8_t* values_public, uint32_t* errors) {
+  if (n && (!leaf || !inputs || !rs || !counts || !status))
+    throw Error("prove_stream_members_drawn_counts: leaf indices, inputs, rs, counts and status are required");
+  check_members(t, n, leaf);   // all of it before anything is drawn or enqueued
+  std::vector<uint32_t> limits;
+  std::vector<uint8_t> ext;
+  check_drawn_counts(t, q, n, inputs, counts, &limits, &ext);
+  if (n == 0) return;
+  ReleaseDraw release{q};
+  // ONE draw: the chunks read their slices
+  const DrawnIds drawn{&q, q.draw_hold_counts(n, leaf, ext.data(), limits.data(), counts, status), status, 0, counts};
+  size_t at = 0;
+  prove_stream_from([&](size_t* off, size_t* cnt) {
+    if (at >= n) return false;
+    *off = at;
+    *cnt = std::min(B_, n - at);
+    at += *cnt;
+    return true;
+  }, inputs, rs, proofs, values_public, errors, 0, &t, leaf, &drawn, true);
+}
+
+void Prover::prove_stream_members_public(const MemberTree& tree, size_t n, const uint64_t* leaf, const uint8_t* inputs,
+                                         const uint8_t* rs, uint8_t* proofs, uint8_t* values_public, uint32_t* errors) {
+  if (n && (!leaf || !inputs || !rs)) throw Error("prove_stream_members: leaf indices, inputs and rs are required");
+  check_members(tree, n, leaf);   // all of it before the first chunk is enqueued
+  size_t at = 0;
+  prove_stream_from([&](size_t* off, size_t* cnt) {
+    if (at >= n) return false;
+    *off = at;
+    *cnt = std::min(B_, n - at);
+    at += *cnt;
+    return true;
+  }, inputs, rs, proofs, values_public, errors, 0, &tree, leaf, nullptr, true);
+}
+
 uint64_t Prover::submit_members_by(const MemberTree& t, size_t n, const uint64_t* leaf, const uint8_t* inputs, const uint8_t* rs,
                                    int mode, const DrawnIds* drawn) {
   if (n == 0) throw Error("empty batch");
@@ -1213,6 +1303,7 @@ uint64_t Prover::submit_members_by(const MemberTree& t, size_t n, const uint64_t
       g.ids = drawn->held.ids + drawn->first;
       g.ids_status = drawn->held.status + drawn->first;
       g.ids_stream = drawn->held.stream;
+      if (drawn->counts) g.ids_counts = drawn->held.counts + drawn->first;
     }
     const uint64_t ticket = enqueue(n, mode, inputs, rs, nullptr, nullptr, nullptr, &g);
     if (drawn) D.mark_drawn(ticket);
@@ -1235,7 +1326,17 @@ uint64_t Prover::submit_members_by(const MemberTree& t, size_t n, const uint64_t
       memcpy(row + (size_t)D.path_off * 32, elems.data() + i * d * 32, d * 32);
       memset(row + (size_t)D.path_idx_off * 32, 0, d * 32);
       for (size_t l = 0; l < d; l++) row[((size_t)D.path_idx_off + l) * 32] = bits[i * d + l];
-      if (drawn) {   // the bytes k_quota_fill writes on the device route
+      if (drawn && drawn->counts) {   // the bytes k_quota_fill_counts writes on the device route
+        uint32_t first = 0;
+        memcpy(&first, ids.data() + 4 * i, 4);
+        std::vector<uint32_t> words(NIB / 4);   // (a row of bytes is not aligned for words)
+        memcpy(words.data(), row, NIB);
+        QuotaLedgerDev::fill_row_counts(words.data(), drawn->status[drawn->first + i] == quota::OK, first, drawn->counts[drawn->first + i],
+                                        D.drawn_multi_msg_off, D.drawn_multi_sel_off, D.drawn_sel, D.drawn_multi_slots);
+        memcpy(row, words.data(), NIB);
+        memset(words.data(), 0, NIB);
+        __asm__ __volatile__("" : : "r"(words.data()) : "memory");
+      } else if (drawn) {   // the bytes k_quota_fill writes on the device route
         const bool granted = drawn->status[drawn->first + i] == quota::OK;
         memset(row + (size_t)D.drawn_msg_off * 32, granted ? 0 : 0xFF, 32);
         if (granted) memcpy(row + (size_t)D.drawn_msg_off * 32, ids.data() + 4 * i, 4);
@@ -1534,7 +1635,7 @@ void Prover::prove_stream_members(const MemberTree& tree, size_t n, const uint64
 
 void Prover::prove_stream_from(const ChunkSource& next, const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs,
                                uint8_t* values, uint32_t* errors, int max_in_flight, const MemberTree* tree,
-                               const uint64_t* leaf, const DrawnIds* drawn) {
+                               const uint64_t* leaf, const DrawnIds* drawn, bool public_values) {
   Impl& D = *d_;
   struct Pending { uint64_t ticket; size_t off, cnt; };
   std::deque<Pending> q;
@@ -1543,6 +1644,16 @@ void Prover::prove_stream_from(const ChunkSource& next, const uint8_t* inputs, c
   auto take = [&]() {
     Pending f = q.front();
     q.pop_front();
+    if (public_values) {   // every public signal, read before the collect that ends the batch; a refused row of a drawn batch: zero
+      const size_t row = num_public() * 32;
+      if (values) {
+        std::vector<uint8_t> pub;
+        collect_public(f.ticket, f.cnt, &pub);
+        memcpy(values + f.off * row, pub.data(), f.cnt * row);
+      }
+      collect(f.ticket, f.cnt, proofs ? proofs + f.off * 128 : nullptr, nullptr, errors ? errors + f.off : nullptr);
+      return;
+    }
     collect(f.ticket, f.cnt, proofs ? proofs + f.off * 128 : nullptr, values ? values + f.off * 160 : nullptr,
             errors ? errors + f.off : nullptr);
   };
@@ -1554,7 +1665,7 @@ void Prover::prove_stream_from(const ChunkSource& next, const uint8_t* inputs, c
       if (cnt == 0) continue;
       if (cnt > B_) throw Error("prove_stream: a chunk larger than the prover workspace (max_batch)");
       DrawnIds slice{};
-      if (drawn) slice = DrawnIds{drawn->quota, drawn->held, drawn->status, drawn->first + off};
+      if (drawn) slice = DrawnIds{drawn->quota, drawn->held, drawn->status, drawn->first + off, drawn->counts};
       q.push_back({tree ? submit_members_by(*tree, cnt, leaf + off, inputs + off * NIB, rs + off * 64, PROVE_FULL, drawn ? &slice : nullptr)
                         : submit(cnt, inputs + off * NIB, rs + off * 64),
                    off, cnt});
@@ -1759,7 +1870,11 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
         hipStream_t sQ = (hipStream_t)members->ids_stream;
         RLN_HIP(hipEventRecord(S.evQ, sQ));
         RLN_HIP(hipStreamWaitEvent(sA, S.evQ, 0));
-        QuotaLedgerDev::fill_rows(members->ids, members->ids_status, n, S.inputs.p, (size_t)D.NI * 8, D.drawn_msg_off, (void*)sA);
+        if (members->ids_counts)
+          QuotaLedgerDev::fill_rows_counts(members->ids, members->ids_status, members->ids_counts, n, S.inputs.p, (size_t)D.NI * 8,
+                                           D.drawn_multi_msg_off, D.drawn_multi_sel_off, D.drawn_sel, D.drawn_multi_slots, (void*)sA);
+        else
+          QuotaLedgerDev::fill_rows(members->ids, members->ids_status, n, S.inputs.p, (size_t)D.NI * 8, D.drawn_msg_off, (void*)sA);
       }
       RLN_HIP(hipEventRecord(S.evG, sA));
       RLN_HIP(hipStreamWaitEvent(tree.stream, S.evG, 0));

@@ -58,6 +58,10 @@ NamedInputs find_named_inputs(const Graph& graph, uint32_t ni) {
   if (R.have_values_kernel) sl.msg_id = R.hint_msg_off;
   R.have_drawn_slots = find("userMessageLimit", 1, &sl.limit) && find("externalNullifier", 1, &sl.ext) &&
                        find("messageId", 1, &R.drawn_msg_off);
+  R.drawn_multi_slots = graph.max_out;
+  R.drawn_sel = find("selectorUsed", graph.max_out, &R.drawn_multi_sel_off);
+  R.have_drawn_multi_slots = graph.max_out >= 1 && find("userMessageLimit", 1, &sl.limit) && find("externalNullifier", 1, &sl.ext) &&
+                             find("messageId", graph.max_out, &R.drawn_multi_msg_off) && (R.drawn_sel || graph.max_out == 1);
   return R;
 }
 

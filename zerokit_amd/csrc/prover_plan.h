@@ -34,6 +34,11 @@ struct NamedInputs {
   // each input row, and ONE messageId slot -- the multi-message-id circuit, which has max_out of them, is refused
   bool have_drawn_slots = false;
   uint32_t drawn_msg_off = 0;
+  // ... and a batch with drawn BLOCKS of ids (Prover::submit_members_drawn_counts): slots.limit, slots.ext, messageId[max_out]
+  // and selectorUsed[max_out], max_out >= 1.  A single message-id graph names no selectors and needs none (drawn_sel false):
+  // its one slot is always used.
+  bool have_drawn_multi_slots = false, drawn_sel = false;
+  uint32_t drawn_multi_msg_off = 0, drawn_multi_sel_off = 0, drawn_multi_slots = 1;
 };
 NamedInputs find_named_inputs(const Graph& graph, uint32_t ni);
 

@@ -35,6 +35,30 @@
 // a radix sort of 8-bit digits over the leaf's bits and the slot's (DrawPlan), every pass three kernels and a scan, so
 // that a call of n requests of ONE member and a call of n distinct members run the same passes over the same amount of
 // data.
+//
+// draw_counts: blocks of ids, for the multi-message-id circuit, one proof of which uses up to max_out message slots.
+// Request i is (leaf_i, ext_i, limit_i, count_i), count_i = 1 .. COUNT_MAX the number of ids it asks for:
+//   ext_i not in the window                     NO_EPOCH; touches nothing
+//   otherwise, with key (slot, leaf)            rank_i = the sum of count_j over the requests j < i of this call with the
+//                                               same key, whatever their outcome; first_i = used + rank_i, `used` as it
+//                                               was before the call; OK iff first_i + count_i <= limit_i (in 64 bits),
+//                                               and the request then owns the ids first_i .. first_i + count_i - 1; else
+//                                               OVER: a request is granted whole or not at all
+//   afterwards                                  used = first + count of the key's last OK request of this call; unchanged
+//                                               if there was none
+// firsts_out[i] = first_i for OK and limit_i otherwise.  With every count 1 this is draw, word for word.  With one limit
+// per member the OK requests of a key are a prefix of its requests: a later first is at least an earlier first + count,
+// so once one request is over, all behind it are.  The blocks granted for a key, over any sequence of calls, are
+// pairwise disjoint and each lies below its limit: within a call they are used + [rank_i, rank_i + count_i) with the
+// ranks running sums of the counts, and the next call starts at or above the end of the last one granted.
+// What does NOT carry over from draw: a refused request still counts in the ranks behind it, and here it counts with
+// its whole block.  A request of 4 that is over pushes a request of 1 of the same member, later IN THE SAME CALL, over
+// too, although one id was left -- the next call grants it.  So a call is not what every split of it into consecutive
+// calls gives, one limit per member or not; only the all-ones case has that property.  Nothing is issued twice either
+// way, and nothing above a limit.
+// The plan is the one above with two more passes: the counts gathered into sorted order, and an exclusive sum over them
+// (log_scan.h, as the bins are summed), so that rank = S[position] - S[position of the group's first].  n < 2^24
+// requests of at most 255 ids keep every such sum below 2^32.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -45,6 +69,7 @@
 #include <vector>
 
 #include "nullifier_log.h"
+#include "relay.h"
 
 namespace rlnamd {
 namespace quota {
@@ -58,6 +83,9 @@ constexpr uint32_t LEAF_BITS = 24;                  // a key is slot << 24 | lea
 constexpr uint32_t NO_SLOT = EPOCHS_MAX;            // the slot of a request outside the window: above every real one
 constexpr uint32_t BLOCK = 256;                     // requests a workgroup (log_scan.h: LOG_LANES)
 constexpr uint32_t DIGIT_BITS = 8, DIGITS = 1u << DIGIT_BITS;
+constexpr uint32_t COUNT_MAX = relay::SLOTS_MAX;    // ids a request of draw_counts asks for: a count is a byte, as a share count is
+constexpr uint64_t COUNTS_N_MAX = (uint64_t)1 << 24;   // requests a draw_counts call stays below: n x COUNT_MAX < 2^32
+static_assert(COUNTS_N_MAX * COUNT_MAX < ((uint64_t)1 << 32), "the sums of a call's counts fit 32 bits");
 
 // ---- the window
 struct Window {
@@ -98,6 +126,22 @@ RLN_HD Issue issue(uint32_t used, uint32_t rank, uint32_t limit) {
 // `used` when the group issued nothing.
 RLN_HD uint32_t advance(uint32_t used, uint32_t start, uint32_t last_ok) {
   return last_ok > start ? used + (last_ok - 1 - start) + 1 : used;
+}
+
+// ---- the rule of draw_counts: rank (a sum of counts) -> first id -> status
+RLN_HD Issue issue_counts(uint32_t used, uint32_t rank, uint32_t count, uint32_t limit) {
+  const uint64_t first = (uint64_t)used + rank;
+  const bool ok = first + count <= limit;   // 64 bits: used and limit may both be at 2^32 - 1
+  Issue r;
+  r.status = ok ? OK : OVER;
+  r.id = ok ? (uint32_t)first : limit;
+  return r;
+}
+// At the last request of a group, as advance(): `last_ok` is 1 + the highest sorted position of the group whose request
+// was OK (at or below `start`: none), `rank_last` and `count_last` are that request's.  Firsts rise with the rank, so
+// the group's last OK request owns its highest ids.  (No overflow: it was granted, so the sum is at most its limit.)
+RLN_HD uint32_t advance_counts(uint32_t used, uint32_t start, uint32_t last_ok, uint32_t rank_last, uint32_t count_last) {
+  return last_ok > start ? used + rank_last + count_last : used;
 }
 
 // ---- the plan of a draw
@@ -158,6 +202,32 @@ inline std::string draw_refusal(size_t n, const uint64_t* leaf_indices, const ui
     if (leaf_indices[i] >> depth)
       return "quota ledger: leaf index " + std::to_string(leaf_indices[i]) + " of request " + std::to_string(i) +
              " is outside a ledger of depth " + std::to_string(depth);
+  return std::string();
+}
+// one count, of request i: the text, or the empty string for 1 .. COUNT_MAX
+inline std::string count_refusal(size_t i, uint64_t count) {
+  if (count == 0) return "quota ledger: request " + std::to_string(i) + " of draw_counts asks for no id (a count is 1 .. " +
+                         std::to_string(COUNT_MAX) + ")";
+  if (count > COUNT_MAX)
+    return "quota ledger: request " + std::to_string(i) + " of draw_counts asks for " + std::to_string(count) + " ids, more than " +
+           std::to_string(COUNT_MAX);
+  return std::string();
+}
+// draw_counts: the pointers first, then n -- before any array is read -- then what the arrays hold
+inline std::string draw_counts_refusal(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
+                                       const uint8_t* counts, const uint32_t* firsts_out, const uint8_t* status, uint32_t depth,
+                                       bool firsts_wanted = true) {
+  if (n == 0) return std::string();
+  if (!leaf_indices || !ext_le || !limits || (firsts_wanted && !firsts_out) || !status)
+    return draw_refusal(n, leaf_indices, ext_le, limits, firsts_out, status, depth, firsts_wanted);
+  if (!counts) return "quota ledger: draw_counts was given a null pointer for the counts of n > 0 requests";
+  if ((uint64_t)n >= COUNTS_N_MAX) return "quota ledger: a draw by count takes fewer than 2^24 requests, not " + std::to_string(n);
+  const std::string refused = draw_refusal(n, leaf_indices, ext_le, limits, firsts_out, status, depth, firsts_wanted);
+  if (!refused.empty()) return refused;
+  for (size_t i = 0; i < n; i++) {
+    const std::string bad = count_refusal(i, counts[i]);
+    if (!bad.empty()) return bad;
+  }
   return std::string();
 }
 
@@ -250,6 +320,41 @@ struct SeqLedger {
     draws++;
     return std::string();
   }
+  // draw with blocks of ids: the same sort, S the running sum of the sorted counts.  `issued` counts ids.
+  std::string draw_counts(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, const uint8_t* counts,
+                          uint32_t* firsts_out, uint8_t* status) {
+    const std::string refused = draw_counts_refusal(n, leaf_indices, ext_le, limits, counts, firsts_out, status, depth);
+    if (!refused.empty()) return refused;
+    if (n == 0) return std::string();
+    std::vector<uint32_t> key(n), at(n);
+    for (size_t i = 0; i < n; i++) {
+      Row32 ext;
+      memcpy(ext.w, ext_le + 32 * i, 32);
+      key[i] = pack_key(slot_of(window.e, window.live, max_epochs, ext), (uint32_t)leaf_indices[i]);
+      at[i] = (uint32_t)i;
+    }
+    std::stable_sort(at.begin(), at.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+    uint32_t start = 0, last_ok = 0, S = 0, S_start = 0, rank_last = 0, count_last = 0;
+    for (size_t j = 0; j < n; S += counts[at[j]], j++) {
+      const uint32_t i = at[j], k = key[i];
+      if (j == 0 || key[at[j - 1]] != k) start = (uint32_t)j, S_start = S;
+      if (key_slot(k) == NO_SLOT) {
+        status[i] = NO_EPOCH;
+        firsts_out[i] = limits[i];
+        no_epoch++;
+        continue;
+      }
+      uint32_t& counter = used[counter_of(k, depth)];
+      const Issue r = issue_counts(counter, S - S_start, counts[i], limits[i]);
+      status[i] = r.status;
+      firsts_out[i] = r.id;
+      if (r.status == OK) last_ok = (uint32_t)j + 1, rank_last = S - S_start, count_last = counts[i], issued += counts[i];
+      else over++;
+      if (j + 1 == n || key[at[j + 1]] != k) counter = advance_counts(counter, start, last_ok, rank_last, count_last);
+    }
+    draws++;
+    return std::string();
+  }
 };
 
 }  // namespace quota
@@ -272,6 +377,11 @@ struct QuotaLedgerDev {
   // secret as who proves: the staged requests, the sort's keys and every other per-call word, device and pinned, are
   // overwritten before draw returns, on error paths too.
   void draw(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, uint32_t* ids_out, uint8_t* status);
+  // draw with a block of counts[i] ids a request (the text at the top).  Refused (quota::draw_counts_refusal) before
+  // anything is enqueued; the same passes plus a gather and a sum over the counts; wiped as draw wipes.  info()'s
+  // `issued` counts ids: the counts of the granted requests.
+  void draw_counts(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, const uint8_t* counts,
+                   uint32_t* firsts_out, uint8_t* status);
   // the counters of n (member, external nullifier) pairs: used_out[i], and in_window[i] = 0 with used_out[i] = 0 for an
   // external nullifier outside the window (diagnostics and tests: one small copy per pair)
   void used(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, uint32_t* used_out, uint8_t* in_window);
@@ -289,8 +399,12 @@ struct QuotaLedgerDev {
     const uint8_t* status; // on the device, beside them
     void* stream;          // a hipStream_t
     int device;
+    const uint8_t* counts = nullptr;   // draw_hold_counts: the requests' counts on the device (ids: each block's first id)
   };
   Held draw_hold(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, uint8_t* status);
+  // draw_counts held the same way (Prover::submit_members_drawn_counts): held_ids gives the firsts, release() wipes
+  Held draw_hold_counts(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, const uint8_t* counts,
+                        uint8_t* status);
   void held_ids(size_t first, size_t count, uint32_t* out);
   void release();
   // ids[0 .. count) into field element `slot` of `count` rows of `row_words` 32-bit words each, on stream `on` (a
@@ -302,6 +416,25 @@ struct QuotaLedgerDev {
   static constexpr uint32_t REFUSED_WORD = 0xFFFFFFFFu;
   static void fill_rows(const uint32_t* ids, const uint8_t* status, size_t count, uint32_t* rows, size_t row_words, uint32_t slot,
                         void* on);
+  // The multi-message-id form: row i has max_out message slots from field element `msg_slot` on and, where has_sel, as
+  // many selectors from `sel_slot` on.  A granted request of counts[i] ids: messageId[k] = firsts[i] + k and selector 1
+  // for k < counts[i], both 0 above.  A refused one: REFUSED_WORD in all eight words of EVERY message slot, selectors 0.
+  // fill_row_counts is the rule for one row, shared by the kernel and the host route of the prover.
+  RLN_HD static void fill_row_counts(uint32_t* row, bool granted, uint32_t first, uint32_t count, uint32_t msg_slot, uint32_t sel_slot,
+                                     bool has_sel, uint32_t max_out) {
+    for (uint32_t k = 0; k < max_out; k++) {
+      uint32_t* id = row + (size_t)(msg_slot + k) * 8;
+      const bool used = granted && k < count;
+      id[0] = granted ? (used ? first + k : 0) : REFUSED_WORD;
+      for (int w = 1; w < 8; w++) id[w] = granted ? 0 : REFUSED_WORD;
+      if (!has_sel) continue;
+      uint32_t* sel = row + (size_t)(sel_slot + k) * 8;
+      sel[0] = used ? 1 : 0;
+      for (int w = 1; w < 8; w++) sel[w] = 0;
+    }
+  }
+  static void fill_rows_counts(const uint32_t* firsts, const uint8_t* status, const uint8_t* counts, size_t count, uint32_t* rows,
+                               size_t row_words, uint32_t msg_slot, uint32_t sel_slot, bool has_sel, uint32_t max_out, void* on);
   int depth() const;
 };
 

@@ -15,6 +15,11 @@
 //   k_max_up / k_max_down       last[j] = the running maximum of ok: the last granted position at or below j
 //   k_quota_advance             the last lane of each group stores the group's counter (quota::advance)
 // then one copy back of ids and statuses, one memset over the whole block and one stream wait.
+// draw_counts() is the same call with blocks of ids: behind the sort
+//   k_quota_weights             w[j] = the count of the request at sorted position j
+//   k_scan_up / k_scan_down     S[j] = the counts before j (log_scan.h, as the bins are summed: no look-back)
+// and k_quota_issue_counts / k_quota_advance_counts in the place of the two kernels above, with rank = S[j] - S[start[j]]
+// and quota::issue_counts / advance_counts as the rule.  Sort, heads and both running maxima are the same kernels.
 // The rule of nullifier_log.hip holds: passes are ordered by kernel boundaries only, and no lane waits for, or reads,
 // what another lane of the same kernel writes.  The issue pass reads the counters, the advance pass behind it writes
 // them, one lane per key.  Nothing walks a chain per duplicate: n requests of one member and n requests of n members run
@@ -143,6 +148,55 @@ __global__ void __launch_bounds__(LOG_LANES) k_quota_advance(const uint32_t* __r
   if (next != used) __hip_atomic_store(counter, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- blocks of ids (draw_counts)
+__global__ void __launch_bounds__(LOG_LANES) k_quota_weights(const uint32_t* __restrict__ val, const uint8_t* __restrict__ counts,
+                                                             uint32_t n, uint32_t* __restrict__ w) {
+  const uint32_t j = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t i = val[j];
+  w[j] = i < n ? counts[i] : 0;   // (i >= n: not reached)
+}
+
+// S: the exclusive sums of w.  start[j] <= j, so every index read is below n.
+__global__ void __launch_bounds__(LOG_LANES) k_quota_issue_counts(const uint32_t* __restrict__ key, const uint32_t* __restrict__ val,
+                                                                  const uint32_t* __restrict__ start, const uint32_t* __restrict__ limits,
+                                                                  const uint32_t* __restrict__ w, const uint32_t* __restrict__ S,
+                                                                  const uint32_t* __restrict__ counters, uint32_t depth, uint32_t slots,
+                                                                  uint32_t n, uint32_t* __restrict__ firsts, uint8_t* __restrict__ status,
+                                                                  uint32_t* __restrict__ ok) {
+  const uint32_t j = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t k = key[j], i = val[j], st = start[j];
+  ok[j] = 0;
+  if (i >= n || st > j) return;   // (not reached)
+  const uint32_t limit = limits[i];
+  if (!counted(k, slots, depth)) {
+    firsts[i] = limit;
+    status[i] = quota::NO_EPOCH;
+    return;
+  }
+  const quota::Issue r = quota::issue_counts(counters[quota::counter_of(k, depth)], S[j] - S[st], w[j], limit);
+  firsts[i] = r.id;
+  status[i] = r.status;
+  if (r.status == quota::OK) ok[j] = j + 1;
+}
+
+__global__ void __launch_bounds__(LOG_LANES) k_quota_advance_counts(const uint32_t* __restrict__ key, const uint32_t* __restrict__ start,
+                                                                    const uint32_t* __restrict__ last, const uint32_t* __restrict__ w,
+                                                                    const uint32_t* __restrict__ S, uint32_t* __restrict__ counters,
+                                                                    uint32_t depth, uint32_t slots, uint32_t n) {
+  const uint32_t j = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t k = key[j];
+  if (j + 1 < n && key[j + 1] == k) return;   // the group's last lane alone
+  if (!counted(k, slots, depth)) return;
+  const uint32_t st = start[j], l = last[j];
+  if (l <= st || l > j + 1) return;           // nothing granted in this group (l > j + 1: not reached)
+  uint32_t* counter = counters + quota::counter_of(k, depth);
+  const uint32_t used = *counter, next = quota::advance_counts(used, st, l, S[l - 1] - S[st], w[l - 1]);
+  if (next != used) __hip_atomic_store(counter, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Proving with drawn ids (Prover::enqueue): a lane per staged input row, behind the row's staging on the same stream
 __global__ void __launch_bounds__(LOG_LANES) k_quota_fill(const uint32_t* __restrict__ ids, const uint8_t* __restrict__ status,
                                                           uint32_t n, uint32_t* __restrict__ rows, size_t row_words, uint32_t slot) {
@@ -153,6 +207,19 @@ __global__ void __launch_bounds__(LOG_LANES) k_quota_fill(const uint32_t* __rest
   to[0] = granted ? ids[i] : QuotaLedgerDev::REFUSED_WORD;
 #pragma unroll
   for (int w = 1; w < 8; w++) to[w] = granted ? 0 : QuotaLedgerDev::REFUSED_WORD;
+}
+
+// the same with blocks of ids (Prover::submit_members_drawn_counts): max_out message slots and selectors a row
+__global__ void __launch_bounds__(LOG_LANES) k_quota_fill_counts(const uint32_t* __restrict__ firsts, const uint8_t* __restrict__ status,
+                                                                 const uint8_t* __restrict__ counts, uint32_t n, uint32_t* __restrict__ rows,
+                                                                 size_t row_words, uint32_t msg_slot, uint32_t sel_slot, bool has_sel,
+                                                                 uint32_t max_out) {
+  const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t count = counts[i];
+  // (a count above max_out is refused on the host before the draw; a row is never written past its slots)
+  QuotaLedgerDev::fill_row_counts(rows + (size_t)i * row_words, status[i] == quota::OK && count <= max_out, firsts[i], count, msg_slot,
+                                  sel_slot, has_sel, max_out);
 }
 
 void wipe_host(void* p, size_t n) {   // through a volatile pointer: not elided as dead (ffi_wire.h: secure_zero)
@@ -182,14 +249,16 @@ struct OnDevice {   // the ledger's device for the length of a call, the caller'
 };
 
 // The block of one call of n requests, in bytes from its start; every array starts 16-byte aligned.
-//   in  (pinned -> device, one copy):  leaf 4 n | limits 4 n | ext 32 n
+//   in  (pinned -> device, one copy):  leaf 4 n | limits 4 n | ext 32 n | counts n
 //   out (device -> pinned, one copy):  ids 4 n | status n
-//   the rest is the device's alone:    two (key, val) pairs, start, ok, the bins and their starts, the scans' block sums
+//   the rest is the device's alone:    two (key, val) pairs, start, ok, the sorted counts w and their sums S, the bins and
+//                                      their starts, the scans' block sums
+// counts, w and S are there for a draw_counts call alone: the block of a plain draw is what it was without them.
 struct Block {
-  size_t np, leaf, limits, ext, ids, status, key[2], val[2], start, ok, bins, bin_start, sums, bytes;
+  size_t np, leaf, limits, ext, counts, ids, status, key[2], val[2], start, ok, w, wsum, bins, bin_start, sums, bytes;
   size_t in_bytes() const { return ids; }
   size_t out_bytes() const { return key[0] - ids; }
-  explicit Block(size_t n) {
+  Block(size_t n, bool by_count) {
     np = (n + 3) / 4 * 4;
     const quota::DrawPlan P = quota::plan_for(n, 1);
     size_t at = 0;
@@ -201,11 +270,14 @@ struct Block {
     leaf = take(4 * np);
     limits = take(4 * np);
     ext = take(32 * np);
+    counts = take(by_count ? np : 0);
     ids = take(4 * np);
     status = take(np);
     for (int s = 0; s < 2; s++) key[s] = take(4 * np), val[s] = take(4 * np);
     start = take(4 * np);
     ok = take(4 * np);
+    w = take(by_count ? 4 * np : 0);
+    wsum = take(by_count ? 4 * np : 0);
     bins = take(4 * P.bins);
     bin_start = take(4 * P.bins);
     sums = take(4 * std::max(ScanPlan(P.bins).words, ScanPlan(n).words));
@@ -229,14 +301,16 @@ struct QuotaLedgerDev::Impl {
   uint8_t* in_host = nullptr;
   uint8_t* out_host = nullptr;
   size_t held_n = 0;   // draw_hold's requests while their block is kept (quota_ledger.h); 0: none
+  bool held_by_count = false;   // ... and whether that draw was one by count: the block's layout
 
-  void run(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, uint32_t* ids_out, uint8_t* status,
-           bool hold);
+  // counts null: a plain draw
+  void run(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, const uint8_t* counts,
+           uint32_t* ids_out, uint8_t* status, bool hold);
   void reserve(size_t n) {
     if (n <= stage_n) return;
     release_staging();
     const size_t m = n < 1024 ? 1024 : n;
-    const Block B(m);
+    const Block B(m, true);   // the larger of the two layouts
     RLN_HIP(hipHostMalloc((void**)&in_host, B.in_bytes(), hipHostMallocDefault));
     in_cap = B.in_bytes();
     memset(in_host, 0, in_cap);
@@ -319,6 +393,17 @@ void QuotaLedgerDev::fill_rows(const uint32_t* ids, const uint8_t* status, size_
   RLN_HIP(hipGetLastError());
 }
 
+void QuotaLedgerDev::fill_rows_counts(const uint32_t* firsts, const uint8_t* status, const uint8_t* counts, size_t count, uint32_t* rows,
+                                      size_t row_words, uint32_t msg_slot, uint32_t sel_slot, bool has_sel, uint32_t max_out, void* on) {
+  if (count == 0) return;
+  if (count > 0xFFFFFFFFull || max_out == 0 || ((size_t)msg_slot + max_out) * 8 > row_words ||
+      (has_sel && ((size_t)sel_slot + max_out) * 8 > row_words))
+    throw Error("quota ledger: fill_rows_counts: the slots are outside the row");
+  hipLaunchKernelGGL(k_quota_fill_counts, dim3(div_up(count, LOG_LANES)), dim3(LOG_LANES), 0, (hipStream_t)on, firsts, status, counts,
+                     (uint32_t)count, rows, row_words, msg_slot, sel_slot, has_sel, max_out);
+  RLN_HIP(hipGetLastError());
+}
+
 void QuotaLedgerDev::set_epochs(size_t k, const uint8_t* external_nullifiers_le) {
   Impl& m = *d;
   // the host check: nothing is enqueued and nothing of the ledger changes before it has passed
@@ -355,15 +440,34 @@ size_t QuotaLedgerDev::epochs(uint8_t out_le[32 * quota::EPOCHS_MAX]) const {
 
 void QuotaLedgerDev::draw(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, uint32_t* ids_out,
                           uint8_t* status) {
-  d->run(n, leaf_indices, ext_le, limits, ids_out, status, false);
+  d->run(n, leaf_indices, ext_le, limits, nullptr, ids_out, status, false);
+}
+
+void QuotaLedgerDev::draw_counts(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
+                                 const uint8_t* counts, uint32_t* firsts_out, uint8_t* status) {
+  // the host check: nothing is enqueued and nothing of the ledger changes before it has passed
+  const std::string refused = quota::draw_counts_refusal(n, leaf_indices, ext_le, limits, counts, firsts_out, status, d->depth);
+  if (!refused.empty()) throw Error(refused);
+  if (n == 0) return;
+  d->run(n, leaf_indices, ext_le, limits, counts, firsts_out, status, false);
 }
 
 QuotaLedgerDev::Held QuotaLedgerDev::draw_hold(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
                                                uint8_t* status) {
-  d->run(n, leaf_indices, ext_le, limits, nullptr, status, true);
+  d->run(n, leaf_indices, ext_le, limits, nullptr, nullptr, status, true);
   if (!d->held_n) return Held{nullptr, nullptr, (void*)d->stream, d->device};
-  const Block B(d->held_n);
+  const Block B(d->held_n, d->held_by_count);
   return Held{(const uint32_t*)(d->block.p + B.ids), d->block.p + B.status, (void*)d->stream, d->device};
+}
+
+QuotaLedgerDev::Held QuotaLedgerDev::draw_hold_counts(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le,
+                                                      const uint32_t* limits, const uint8_t* counts, uint8_t* status) {
+  const std::string refused = quota::draw_counts_refusal(n, leaf_indices, ext_le, limits, counts, nullptr, status, d->depth, false);
+  if (!refused.empty()) throw Error(refused);
+  if (n) d->run(n, leaf_indices, ext_le, limits, counts, nullptr, status, true);
+  if (!d->held_n) return Held{nullptr, nullptr, (void*)d->stream, d->device, nullptr};
+  const Block B(d->held_n, true);
+  return Held{(const uint32_t*)(d->block.p + B.ids), d->block.p + B.status, (void*)d->stream, d->device, d->block.p + B.counts};
 }
 
 void QuotaLedgerDev::held_ids(size_t first, size_t count, uint32_t* out) {
@@ -371,14 +475,14 @@ void QuotaLedgerDev::held_ids(size_t first, size_t count, uint32_t* out) {
   if (count == 0) return;
   if (first > m.held_n || count > m.held_n - first) throw Error("quota ledger: internal error, ids asked for beyond the draw that is held");
   OnDevice on(m.device);
-  RLN_HIP(hipMemcpyAsync(out, m.block.p + Block(m.held_n).ids + 4 * first, 4 * count, hipMemcpyDeviceToHost, m.stream));
+  RLN_HIP(hipMemcpyAsync(out, m.block.p + Block(m.held_n, m.held_by_count).ids + 4 * first, 4 * count, hipMemcpyDeviceToHost, m.stream));
   RLN_HIP(hipStreamSynchronize(m.stream));
 }
 
 void QuotaLedgerDev::release() {
   Impl& m = *d;
   if (!m.held_n) return;
-  const Block B(m.held_n);
+  const Block B(m.held_n, m.held_by_count);
   m.held_n = 0;
   wipe_host(m.out_host, B.out_bytes());
   int prev = 0;
@@ -389,8 +493,8 @@ void QuotaLedgerDev::release() {
   RLN_HIP(e2);
 }
 
-void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, uint32_t* ids_out,
-                               uint8_t* status, bool hold) {
+void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
+                               const uint8_t* counts, uint32_t* ids_out, uint8_t* status, bool hold) {
   Impl& m = *this;
   if (m.held_n) throw Error("quota ledger: internal error, a draw while another draw's ids are held");
   // the host check: nothing is enqueued and nothing of the ledger changes before it has passed
@@ -399,7 +503,7 @@ void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uin
   if (n == 0) return;
   OnDevice on(m.device);
   m.reserve(n);
-  const Block B(n);
+  const Block B(n, counts != nullptr);
   const quota::DrawPlan P = quota::plan_for(n, m.depth);
   struct Wipe {   // success or error: the call's block is zero again when draw() returns (a held draw: at release())
     Impl& m;
@@ -420,6 +524,7 @@ void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uin
   for (size_t i = 0; i < n; i++) h_leaf[i] = (uint32_t)leaf_indices[i];
   memcpy(m.in_host + B.limits, limits, 4 * n);
   memcpy(m.in_host + B.ext, ext_le, 32 * n);
+  if (counts) memcpy(m.in_host + B.counts, counts, n);
   uint8_t* base = m.block.p;
   auto words = [&](size_t off) { return (uint32_t*)(base + off); };
   const uint32_t n32 = (uint32_t)n, blocks = (uint32_t)P.blocks, slots = m.max_epochs;
@@ -439,12 +544,24 @@ void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uin
   const uint32_t* val = words(B.val[cur]);
   hipLaunchKernelGGL(k_quota_heads, grid, lanes, 0, m.stream, key, n32, words(B.start));
   scan_running_max(words(B.start), n, words(B.start), words(B.sums), m.stream);
-  hipLaunchKernelGGL(k_quota_issue, grid, lanes, 0, m.stream, key, val, (const uint32_t*)words(B.start),
-                     (const uint32_t*)words(B.limits), (const uint32_t*)m.counters.p, m.depth, slots, n32, words(B.ids),
-                     base + B.status, words(B.ok));
-  scan_running_max(words(B.ok), n, words(B.ok), words(B.sums), m.stream);
-  hipLaunchKernelGGL(k_quota_advance, grid, lanes, 0, m.stream, key, (const uint32_t*)words(B.start), (const uint32_t*)words(B.ok),
-                     m.counters.p, m.depth, slots, n32);
+  if (counts) {
+    hipLaunchKernelGGL(k_quota_weights, grid, lanes, 0, m.stream, val, (const uint8_t*)(base + B.counts), n32, words(B.w));
+    scan_positions((const uint32_t*)words(B.w), n, words(B.wsum), words(B.sums), m.stream);
+    hipLaunchKernelGGL(k_quota_issue_counts, grid, lanes, 0, m.stream, key, val, (const uint32_t*)words(B.start),
+                       (const uint32_t*)words(B.limits), (const uint32_t*)words(B.w), (const uint32_t*)words(B.wsum),
+                       (const uint32_t*)m.counters.p, m.depth, slots, n32, words(B.ids), base + B.status, words(B.ok));
+    scan_running_max(words(B.ok), n, words(B.ok), words(B.sums), m.stream);
+    hipLaunchKernelGGL(k_quota_advance_counts, grid, lanes, 0, m.stream, key, (const uint32_t*)words(B.start),
+                       (const uint32_t*)words(B.ok), (const uint32_t*)words(B.w), (const uint32_t*)words(B.wsum), m.counters.p, m.depth,
+                       slots, n32);
+  } else {
+    hipLaunchKernelGGL(k_quota_issue, grid, lanes, 0, m.stream, key, val, (const uint32_t*)words(B.start),
+                       (const uint32_t*)words(B.limits), (const uint32_t*)m.counters.p, m.depth, slots, n32, words(B.ids),
+                       base + B.status, words(B.ok));
+    scan_running_max(words(B.ok), n, words(B.ok), words(B.sums), m.stream);
+    hipLaunchKernelGGL(k_quota_advance, grid, lanes, 0, m.stream, key, (const uint32_t*)words(B.start), (const uint32_t*)words(B.ok),
+                       m.counters.p, m.depth, slots, n32);
+  }
   RLN_HIP(hipGetLastError());
   if (hold) {   // the statuses alone; the ids stay where they are
     RLN_HIP(hipMemcpyAsync(m.out_host + (B.status - B.ids), base + B.status, B.out_bytes() - (B.status - B.ids), hipMemcpyDeviceToHost,
@@ -462,7 +579,7 @@ void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uin
   if (!hold) memcpy(ids_out, m.out_host, 4 * n);
   memcpy(status, h_status, n);
   for (size_t i = 0; i < n; i++) {
-    m.issued += h_status[i] == quota::OK;
+    m.issued += h_status[i] == quota::OK ? (counts ? counts[i] : 1) : 0;   // ids
     m.over += h_status[i] == quota::OVER;
     m.no_epoch += h_status[i] == quota::NO_EPOCH;
   }
@@ -470,6 +587,7 @@ void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uin
   if (hold) {
     wipe.held = true;
     m.held_n = n;
+    m.held_by_count = counts != nullptr;
   }
 }
 

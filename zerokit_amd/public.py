@@ -519,6 +519,31 @@ class RLN:
                                                                  *[v[0].ptr for v in vecs], rsp, status, outs))
         return [RLNProof(C.c_void_p(outs[i])) if outs[i] else None for i in range(n)], list(status.raw[:n])
 
+    def generate_rln_proofs_for_members_drawn_multi(self, quota, leaf_indices, identity_secrets, user_message_limits, counts, xs,
+                                                    external_nullifiers, rs=None):
+        """EXT: generate_rln_proofs_for_members_drawn on a multi-message-id object: counts[i] = 1 .. max_out message
+        slots a proof, a block of that many consecutive ids drawn for each, whole or not at all
+        (ffi_generate_rln_proofs_for_members_drawn_multi) -> (proofs, statuses): proofs[i] has MultiV1 values, or is None
+        where statuses[i] is not QuotaLedger.OK."""
+        n = len(leaf_indices)
+        cols = (identity_secrets, user_message_limits, xs, external_nullifiers)
+        if any(len(c) != n for c in cols) or len(counts) != n or (rs is not None and len(rs) != n):
+            raise RLNError("generate_rln_proofs_for_members_drawn_multi: every argument holds one entry per leaf index")
+        if any(not 0 <= int(c) <= 255 for c in counts):
+            raise RLNError("generate_rln_proofs_for_members_drawn_multi: a count is a byte")
+        idx = (C.c_size_t * max(n, 1))(*[int(i) for i in leaf_indices])
+        vecs = [_vec_cfr(list(c)) for c in cols]          # (kept alive until the call has returned)
+        outs = (C.c_void_p * max(n, 1))()
+        status = C.create_string_buffer(max(n, 1))
+        rsp, flat = None, None
+        if rs is not None:
+            flat = _vec_cfr([v for pair in rs for v in pair])
+            rsp = flat[0].ptr
+        _ok_bool(lib().ffi_generate_rln_proofs_for_members_drawn_multi(
+            C.byref(self._h), quota._h if quota is not None else None, idx, n, vecs[0][0].ptr, vecs[1][0].ptr,
+            bytes(int(c) for c in counts) or b"\0", vecs[2][0].ptr, vecs[3][0].ptr, rsp, status, outs))
+        return [RLNProof(C.c_void_p(outs[i])) if outs[i] else None for i in range(n)], list(status.raw[:n])
+
     def finish_rln_proofs_batch(self, partials, witnesses, rs=None):
         """EXT: n finishes in one call; partials[i] (the same object may repeat) is what witnesses[i] is finished from"""
         n = len(witnesses)
