@@ -624,8 +624,46 @@ int rlnamd_relay_info(rlnamd_relay* r, uint64_t out[8]);
  * RLNAMD_RELAY_EPOCHS_MAX.
  *   AN EXTERNAL NULLIFIER THAT HAS LEFT THE WINDOW MUST NOT COME BACK: its counters are gone, and the ids drawn after
  *   its return repeat the ids drawn before it left.
- *   THE LEDGER IS NOT PERSISTED: a process that is restarted must not sign under an external nullifier that was open
- *   before the restart.
+ *   A LEDGER MADE BY rlnamd_quota_new IS NOT PERSISTED: a process that is restarted must not sign under an external
+ *   nullifier that was open before the restart -- unless the ledger was opened on a directory, rlnamd_quota_open below.
+ * rlnamd_quota_open: the same ledger on a directory that holds a checksummed snapshot (rlnamd_quota.bin) and a
+ * write-ahead journal (rlnamd_quota.wal); the formats are in zerokit_amd/csrc/quota_store.h.  The store is created if
+ * the directory is empty or absent and reopened otherwise.  journal_max_bytes: the journal's size behind which the call
+ * that crossed it compacts (a new snapshot, an empty journal); 0 means max(1 MiB, the snapshot's bytes).  Every other
+ * call keeps its meaning; what the store adds is an ORDER OF EVENTS:
+ *   draw, draw_counts   1. the kernels run; 2. the draw's delta -- the counters it moved, as (key, absolute value) pairs
+ *                       compacted on the device -- is copied back; 3. the record is appended and fdatasynced; 4. ONLY
+ *                       THEN are ids and statuses copied into the caller's arrays.  A draw that granted nothing appends
+ *                       nothing and syncs nothing.  If the append or the sync fails the call fails: ids_out and status
+ *                       are untouched, the per-call buffers are wiped, the device counters stay advanced (those ids are
+ *                       burnt, which is the safe side) and the ledger stays usable: the next record carries absolute
+ *                       values.
+ *   the *_members_drawn and *_members_drawn_counts proving calls
+ *                       the same, the sync complete before anything is staged or enqueued for proving.  The streamed
+ *                       forms draw all n ids first: one sync a call.
+ *   set_epochs          1. the window record is appended and synced; 2. the window is applied.  A crash between the two
+ *                       reopens into the new window, under which nothing was signed yet; a crash before the sync reopens
+ *                       into the old one.  (A device error behind the record leaves the store refusing writes, and the
+ *                       ledger so refusing draws, until it is reopened.)
+ *   rlnamd_quota_free   compacts if the journal holds records, then closes.
+ * AFTER REOPENING, HOWEVER THE PROCESS ENDED: the window is that of the last set_epochs that returned, or of one that was
+ * in progress; every counter is >= one past the highest id of every call that returned; it may be higher by the ids of a
+ * call that never returned; after a clean close it is exactly the counters.
+ *   A LEDGER NEVER GOES BACKWARDS.  A record at the journal's end that is short, fails its CRC or is ill-formed is a torn
+ *   tail -- it was never synced, so none of its ids left a call -- and is cut off.  A bad record with records behind it, a
+ *   snapshot that fails its CRC, a damaged journal header, and a depth or max_epochs other than the caller's make
+ *   rlnamd_quota_open FAIL, each with a text of its own (a bad record's names its offset).  No flag opens such a store
+ *   anyway: removing the directory, and with it the duty not to sign under the epochs that were open, is the
+ *   operator's decision.  A directory that another ledger holds (in this process or another: flock on the journal) is
+ *   refused too, and so is a directory that is not empty and holds neither file.  An open that fails -- refused, or
+ *   for want of device memory behind the store's own checks -- writes nothing: the directory is left as it was found.
+ *   THE DIRECTORY IS AS SECRET AS THE LEDGER: the journal shows who signs how often.  Its files are created with mode
+ *   0600 and are NOT encrypted.
+ *   "An external nullifier that has left must not come back" stays the caller's duty, with a store as without.
+ * rlnamd_quota_compact: the snapshot of the next generation and an empty journal, now.  Fails on a ledger without a store.
+ * rlnamd_quota_store_info: [0] generation, [1] journal bytes, [2] records appended by this object, [3] syncs, [4]
+ * compactions, [5] records replayed at open, [6] torn bytes cut at open, [7] (key, counter) pairs restored to the device
+ * at open.  All zero for a ledger without a store.
  * rlnamd_quota_draw: n requests (leaf_indices[i], ext_le[i], limits[i]) -> ids_out[i], status[i].
  *   RLNAMD_QUOTA_NO_EPOCH  ext[i] is not in the window; the request touches nothing
  *   otherwise              rank_i = the number of requests j < i of this call with the same (external nullifier, leaf),
@@ -678,6 +716,10 @@ typedef struct rlnamd_quota rlnamd_quota;
 #define RLNAMD_QUOTA_OVER 1
 #define RLNAMD_QUOTA_NO_EPOCH 2
 int rlnamd_quota_new(size_t depth, size_t max_epochs, rlnamd_quota** out);
+int rlnamd_quota_open(const char* dir, size_t depth, size_t max_epochs, uint64_t journal_max_bytes /* 0: max(1 MiB, snapshot bytes) */,
+                      rlnamd_quota** out);
+int rlnamd_quota_compact(rlnamd_quota* q);
+int rlnamd_quota_store_info(rlnamd_quota* q, uint64_t out[8]);
 void rlnamd_quota_free(rlnamd_quota* q);
 int rlnamd_quota_set_epochs(rlnamd_quota* q, const uint8_t* external_nullifiers_le /* k*32 */, size_t k /* 0: empty */);
 int rlnamd_quota_epochs(rlnamd_quota* q, uint8_t* out_le /* RLNAMD_RELAY_EPOCHS_MAX*32 */, size_t* k);

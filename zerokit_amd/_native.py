@@ -132,6 +132,9 @@ SIGNATURES = {
     "rlnamd_relay_epochs": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_size_t)]),
     "rlnamd_relay_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_quota_new": (C.c_int, [C.c_size_t, C.c_size_t, PP]),
+    "rlnamd_quota_open": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_uint64, PP]),
+    "rlnamd_quota_compact": (C.c_int, [P]),
+    "rlnamd_quota_store_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_quota_free": (None, [P]),
     "rlnamd_quota_set_epochs": (C.c_int, [P, C.c_char_p, C.c_size_t]),
     "rlnamd_quota_epochs": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_size_t)]),

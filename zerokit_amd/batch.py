@@ -983,17 +983,42 @@ class QuotaLedger:
     next ids of a batch of requests.  A request past its member's limit gets no id, so no proof, and no two proofs under
     one (external nullifier, member) ever carry the same id -- the NullifierLog of a relay never says SPAM.
 
-    An external nullifier that has left the window must not come back (its counters are gone), and the ledger is not
-    persisted: a restarted process must not sign under an external nullifier that was open before the restart."""
+    An external nullifier that has left the window must not come back (its counters are gone).  QuotaLedger(depth,
+    max_epochs) is not persisted: a restarted process must not sign under an external nullifier that was open before
+    the restart.  QuotaLedger.open(path, ...) is: every draw is journalled and synced before an id of it is returned,
+    and a reopen, however the process ended, restores the window and every counter at or above everything ever issued
+    (rlnamd_quota_open).  The directory is as secret as the ledger: its files are 0600 and not encrypted."""
     OK, OVER, NO_EPOCH = range(3)
     EPOCHS_MAX = 64
     INFO = ("window", "draws", "issued", "over", "no_epoch", "residue", "depth", "max_epochs")
+    STORE_INFO = ("generation", "journal_bytes", "records", "syncs", "compactions", "replayed", "torn_bytes", "restored_pairs")
 
     def __init__(self, depth, max_epochs):
         self._h = C.c_void_p()
         check(lib().rlnamd_quota_new(depth, max_epochs, C.byref(self._h)))
 
+    @classmethod
+    def open(cls, path, depth, max_epochs, journal_max_bytes=0):
+        """the ledger on the directory `path`: created if it is empty or absent, otherwise reopened; refused (RLNError)
+        for damage that would lower a counter, another depth or max_epochs, or a directory another ledger holds.
+        journal_max_bytes: the journal's size behind which a call compacts; 0: max(1 MiB, the snapshot's bytes)"""
+        q = cls.__new__(cls)
+        q._h = C.c_void_p()
+        check(lib().rlnamd_quota_open(os.fsencode(path), depth, max_epochs, journal_max_bytes, C.byref(q._h)))
+        return q
+
+    def compact(self):
+        """the snapshot of the next generation and an empty journal, now (a ledger opened on a directory only)"""
+        check(lib().rlnamd_quota_compact(self._h))
+
+    def store_info(self):
+        """the store's counts as a dict of STORE_INFO; all zero for a ledger without a store"""
+        out = (C.c_uint64 * 8)()
+        check(lib().rlnamd_quota_store_info(self._h, out))
+        return dict(zip(self.STORE_INFO, (int(v) for v in out)))
+
     def close(self):
+        """frees the ledger; one opened on a directory compacts first if its journal holds records"""
         if self._h:
             lib().rlnamd_quota_free(self._h)
             self._h = C.c_void_p()

@@ -429,7 +429,30 @@ int rlnamd_quota_new(size_t depth, size_t max_epochs, rlnamd_quota** out) {
   *out = new rlnamd_quota(depth, max_epochs);
   RLN_CATCH
 }
-void rlnamd_quota_free(rlnamd_quota* q) { delete q; }
+int rlnamd_quota_open(const char* dir, size_t depth, size_t max_epochs, uint64_t journal_max_bytes, rlnamd_quota** out) {
+  RLN_TRY
+  // what needs no device is checked before one is asked for: the shape, and then the whole store (quota_store.h)
+  const std::string refused = quota::new_refusal(depth, max_epochs);
+  if (!refused.empty()) throw Error(refused);
+  if (!out || !dir) throw Error("rlnamd_quota_open: null pointer");
+  *out = new rlnamd_quota(dir, depth, max_epochs, journal_max_bytes);
+  RLN_CATCH
+}
+int rlnamd_quota_compact(rlnamd_quota* q) {
+  RLN_TRY
+  if (!q) throw Error("rlnamd_quota_compact: null ledger");
+  std::lock_guard<std::mutex> lk(q->mu);
+  q->ledger.compact();
+  RLN_CATCH
+}
+int rlnamd_quota_store_info(rlnamd_quota* q, uint64_t out[8]) {
+  RLN_TRY
+  if (!q || !out) throw Error("rlnamd_quota_store_info: null pointer");
+  std::lock_guard<std::mutex> lk(q->mu);
+  q->ledger.store_info(out);
+  RLN_CATCH
+}
+void rlnamd_quota_free(rlnamd_quota* q) { delete q; }   // (a ledger with a store compacts, then closes: quota_ledger.hip)
 int rlnamd_quota_set_epochs(rlnamd_quota* q, const uint8_t* external_nullifiers_le, size_t k) {
   RLN_TRY
   // what needs no object is judged without one (the ledger judges the same with its own max_epochs, before it enqueues)

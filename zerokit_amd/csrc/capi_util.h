@@ -60,6 +60,8 @@ struct rlnamd_quota {
   std::mutex mu;
   rlnamd::QuotaLedgerDev ledger;
   rlnamd_quota(size_t depth, size_t max_epochs) : ledger(depth, max_epochs) {}
+  rlnamd_quota(const char* dir, size_t depth, size_t max_epochs, uint64_t journal_max_bytes)
+      : ledger(dir, depth, max_epochs, journal_max_bytes) {}
 };
 struct rlnamd_msm {   // one of the two (rlnamd_msm_new / rlnamd_msm_new_g2)
   std::unique_ptr<rlnamd::MsmG1> m;

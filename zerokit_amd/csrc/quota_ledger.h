@@ -232,6 +232,10 @@ inline std::string draw_counts_refusal(size_t n, const uint64_t* leaf_indices, c
 }
 
 // The window after set_epochs(E), E checked (epochs_refusal).  *leaving: the slots whose counters are to be zeroed.
+// SLOT ASSIGNMENT MUST STAY A PURE FUNCTION OF THE WINDOW HISTORY -- of `now`, E and max_epochs, and of nothing else (no
+// clock, no address, no counter of calls).  The durable store (quota_store.h) journals E as set_epochs was given it and
+// replays it through this function; the keys of the advance records behind it name slots, and they mean the same
+// counters after a reopen only if replay hands every external nullifier the slot the live ledger gave it.
 inline Window next_window(const Window& now, const uint8_t* external_nullifiers_le, size_t k, uint32_t max_epochs, uint64_t* leaving) {
   Window next;
   for (uint32_t s = 0; s < EPOCHS_MAX; s++) next.e[s] = now.e[s];
@@ -366,6 +370,20 @@ struct QuotaLedgerDev {
   struct Impl;
   Impl* d = nullptr;
   QuotaLedgerDev(size_t depth, size_t max_epochs);   // quota::new_refusal
+  // The ledger on a directory (quota_store.h): created when the directory is empty or absent, otherwise reopened -- the
+  // window and every counter at or above everything ever issued -- or refused with the store's text: damage that
+  // would lower a counter, another depth or max_epochs, a directory another object holds.  From then on
+  //   draw, draw_counts         the kernels, then the draw's delta (the counters it moved, absolute values) copied back,
+  //                             appended and fdatasynced, and ONLY THEN ids and statuses into the caller's arrays.  A
+  //                             draw that granted nothing appends and syncs nothing.  A failed append fails the call:
+  //                             the caller's arrays untouched, the block wiped, the counters advanced (ids burnt)
+  //   draw_hold(_counts)        the same, durable before it returns
+  //   set_epochs                the window record appended and synced, then the window applied
+  //   the destructor            compacts if the journal holds records, then closes
+  // journal_max_bytes: the journal's size behind which the call that crossed it compacts; 0: max(1 MiB, snapshot bytes).
+  QuotaLedgerDev(const char* dir, size_t depth, size_t max_epochs, uint64_t journal_max_bytes);
+  void compact();                             // the next generation's snapshot and an empty journal; throws without a store
+  void store_info(uint64_t out[8]) const;     // include/rln_amd.h: rlnamd_quota_store_info; all zero without a store
   ~QuotaLedgerDev();                                 // zeroes the counters before they are freed
   QuotaLedgerDev(const QuotaLedgerDev&) = delete;
   QuotaLedgerDev& operator=(const QuotaLedgerDev&) = delete;

@@ -25,18 +25,34 @@
 // them, one lane per key.  Nothing walks a chain per duplicate: n requests of one member and n requests of n members run
 // the same kernels over the same n words (profiles/quota_ledger.md).
 //
+// A ledger opened on a directory (quota_store.h) journals every draw before an id of it leaves the call.  Which counters a
+// draw moved is known only here, so behind the advance pass
+//   k_quota_delta_mark          flag[j] = 1 iff sorted position j is the last of its group, its key is counted and the
+//                               group was granted something
+//   k_scan_up / k_scan_down     pos[j] = the flags before j
+//   k_quota_delta_pack          rec[pos[j]] = (key[j], the counter as the advance pass left it); the total m to one word
+// then one copy brings back m and one the m pairs, the record is appended and synced, and only then do ids and statuses
+// reach the caller's arrays.  A ledger without a store launches none of this and its block has none of these arrays.
+// A snapshot compacts the counters where they live, one live slot at a time: k_quota_snap_mark (a byte per counter,
+// != 0), the same scan, k_quota_snap_pack ((leaf, used) in leaf order), one copy of the count and one of the pairs, in
+// temporary memory that is zeroed before it is freed.  A reopen uploads the replayed image in pieces and k_quota_restore
+// stores one pair per lane into the zeroed counters: the image has one entry per key, so plain stores do.
+//
 // Proving with drawn ids (Prover::submit_members_drawn): draw_hold() is the same call that copies back the statuses alone
 // and leaves the block where it is until release(); in between, k_quota_fill -- launched by the prover on its own stream,
 // ordered against the ledger's by events -- copies each batch's ids into the messageId slot of its staged input rows.
 #include "quota_ledger.h"
 
+#include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "log_scan.h"
+#include "quota_store.h"
 
 namespace rlnamd {
 
@@ -197,6 +213,61 @@ __global__ void __launch_bounds__(LOG_LANES) k_quota_advance_counts(const uint32
   if (next != used) __hip_atomic_store(counter, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- the delta of a draw, for the journal of a ledger with a store.  `last` is the running maximum the advance pass
+// read: a group was granted something iff it is above the group's start.
+__global__ void __launch_bounds__(LOG_LANES) k_quota_delta_mark(const uint32_t* __restrict__ key, const uint32_t* __restrict__ start,
+                                                                const uint32_t* __restrict__ last, uint32_t depth, uint32_t slots,
+                                                                uint32_t n, uint8_t* __restrict__ flag) {
+  const uint32_t j = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t k = key[j];
+  const bool tail = !(j + 1 < n && key[j + 1] == k);
+  flag[j] = tail && counted(k, slots, depth) && last[j] > start[j] && last[j] <= j + 1;
+}
+
+// the counters are read behind the advance pass that wrote them: their absolute values
+__global__ void __launch_bounds__(LOG_LANES) k_quota_delta_pack(const uint32_t* __restrict__ key, const uint8_t* __restrict__ flag,
+                                                                const uint32_t* __restrict__ pos, const uint32_t* __restrict__ counters,
+                                                                uint32_t depth, uint32_t n, uint2* __restrict__ rec,
+                                                                uint32_t* __restrict__ total) {
+  const uint32_t j = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (j >= n) return;
+  const bool moved = flag[j] != 0;
+  const uint32_t to = pos[j];
+  if (j == n - 1) *total = to + moved;
+  if (!moved || to >= n) return;   // (to >= n: not reached)
+  const uint32_t k = key[j];       // counted: the mark pass saw to it
+  rec[to] = make_uint2(k, counters[quota::counter_of(k, depth)]);
+}
+
+// ---- a snapshot: the non-zero counters of one slot, compacted in leaf order (n = 2^depth <= 2^24 counters)
+__global__ void __launch_bounds__(LOG_LANES) k_quota_snap_mark(const uint32_t* __restrict__ counters, uint32_t n,
+                                                               uint8_t* __restrict__ mark) {
+  const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (i < n) mark[i] = counters[i] != 0;
+}
+__global__ void __launch_bounds__(LOG_LANES) k_quota_snap_pack(const uint32_t* __restrict__ counters, const uint8_t* __restrict__ mark,
+                                                               const uint32_t* __restrict__ pos, uint32_t n, uint2* __restrict__ pairs,
+                                                               uint32_t* __restrict__ total) {
+  const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (i >= n) return;
+  const bool kept = mark[i] != 0;
+  const uint32_t to = pos[i];
+  if (i == n - 1) *total = to + kept;
+  if (!kept || to >= n) return;   // (to >= n: not reached)
+  pairs[to] = make_uint2(i, counters[i]);
+}
+
+// ---- a reopen: one (key, used) pair a lane into the zeroed counters; the keys are distinct, a plain store does
+__global__ void __launch_bounds__(LOG_LANES) k_quota_restore(const uint2* __restrict__ pairs, uint32_t m, uint32_t depth, uint32_t slots,
+                                                             uint32_t* __restrict__ counters) {
+  const uint32_t i = blockIdx.x * LOG_LANES + threadIdx.x;
+  if (i >= m) return;
+  const uint2 p = pairs[i];
+  if (!counted(p.x, slots, depth)) return;   // (not reached: the store refuses such a pair)
+  counters[quota::counter_of(p.x, depth)] = p.y;
+}
+
 // Proving with drawn ids (Prover::enqueue): a lane per staged input row, behind the row's staging on the same stream
 __global__ void __launch_bounds__(LOG_LANES) k_quota_fill(const uint32_t* __restrict__ ids, const uint8_t* __restrict__ status,
                                                           uint32_t n, uint32_t* __restrict__ rows, size_t row_words, uint32_t slot) {
@@ -254,11 +325,15 @@ struct OnDevice {   // the ledger's device for the length of a call, the caller'
 //   the rest is the device's alone:    two (key, val) pairs, start, ok, the sorted counts w and their sums S, the bins and
 //                                      their starts, the scans' block sums
 // counts, w and S are there for a draw_counts call alone: the block of a plain draw is what it was without them.
+// The delta's arrays -- flags n | positions 4 n | (key, used) pairs 8 n | their number, one word -- come last, and only
+// in the block of a ledger with a store: without one the block is what it was.
 struct Block {
-  size_t np, leaf, limits, ext, counts, ids, status, key[2], val[2], start, ok, w, wsum, bins, bin_start, sums, bytes;
+  size_t np, leaf, limits, ext, counts, ids, status, key[2], val[2], start, ok, w, wsum, bins, bin_start, sums, dflag, dpos, drec,
+      dtotal, bytes;
+  size_t delta_host_bytes() const { return 8 * np + 16; }   // the pinned copy: the pairs, then their number
   size_t in_bytes() const { return ids; }
   size_t out_bytes() const { return key[0] - ids; }
-  Block(size_t n, bool by_count) {
+  Block(size_t n, bool by_count, bool delta) {
     np = (n + 3) / 4 * 4;
     const quota::DrawPlan P = quota::plan_for(n, 1);
     size_t at = 0;
@@ -281,6 +356,10 @@ struct Block {
     bins = take(4 * P.bins);
     bin_start = take(4 * P.bins);
     sums = take(4 * std::max(ScanPlan(P.bins).words, ScanPlan(n).words));
+    dflag = take(delta ? np : 0);
+    dpos = take(delta ? 4 * np : 0);
+    drec = take(delta ? 8 * np : 0);
+    dtotal = take(delta ? 16 : 0);
     bytes = at;
   }
 };
@@ -302,6 +381,27 @@ struct QuotaLedgerDev::Impl {
   uint8_t* out_host = nullptr;
   size_t held_n = 0;   // draw_hold's requests while their block is kept (quota_ledger.h); 0: none
   bool held_by_count = false;   // ... and whether that draw was one by count: the block's layout
+  // a ledger opened on a directory: the store, and the pinned copy of a draw's delta (null without a store)
+  std::unique_ptr<qstore::QuotaStore> store;
+  // Set as the last step of the durable constructor, once window and counters are on the device as the store has them.
+  // Until then nothing may be written from the device's state: the counters are zero, or restored in part, and a
+  // snapshot of them would put the ledger below ids it has issued.
+  bool restored = false;
+  uint8_t* delta_host = nullptr;
+  size_t delta_cap = 0;
+  Block block_of(size_t n, bool by_count) const { return Block(n, by_count, store != nullptr); }
+  void init(size_t depth, size_t max_epochs);
+  void restore(const qstore::Image& im, bool fail_midway);
+  void compact_now();
+  // behind the call that let the journal outgrow its threshold.  The call itself is done and durable; a compaction that
+  // fails leaves the journal as it is (or the store refusing writes, which the next call reports).
+  void compact_if_due() {
+    if (!store || !store->wants_compaction()) return;
+    try {
+      compact_now();
+    } catch (const std::exception&) {
+    }
+  }
 
   // counts null: a plain draw
   void run(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, const uint8_t* counts,
@@ -310,13 +410,18 @@ struct QuotaLedgerDev::Impl {
     if (n <= stage_n) return;
     release_staging();
     const size_t m = n < 1024 ? 1024 : n;
-    const Block B(m, true);   // the larger of the two layouts
+    const Block B = block_of(m, true);   // the larger of the two layouts
     RLN_HIP(hipHostMalloc((void**)&in_host, B.in_bytes(), hipHostMallocDefault));
     in_cap = B.in_bytes();
     memset(in_host, 0, in_cap);
     RLN_HIP(hipHostMalloc((void**)&out_host, B.out_bytes(), hipHostMallocDefault));
     out_cap = B.out_bytes();
     memset(out_host, 0, out_cap);
+    if (store) {
+      RLN_HIP(hipHostMalloc((void**)&delta_host, B.delta_host_bytes(), hipHostMallocDefault));
+      delta_cap = B.delta_host_bytes();
+      memset(delta_host, 0, delta_cap);
+    }
     block.alloc(B.bytes);
     RLN_HIP(hipMemsetAsync(block.p, 0, B.bytes, stream));
     stage_n = m;
@@ -336,12 +441,25 @@ struct QuotaLedgerDev::Impl {
       wipe_host(out_host, out_cap);
       (void)hipHostFree(out_host);
     }
+    if (delta_host) {
+      wipe_host(delta_host, delta_cap);
+      (void)hipHostFree(delta_host);
+    }
     block.release();
-    in_host = out_host = nullptr;
-    stage_n = stage_bytes = in_cap = out_cap = 0;
+    in_host = out_host = delta_host = nullptr;
+    stage_n = stage_bytes = in_cap = out_cap = delta_cap = 0;
   }
   ~Impl() {
     held_n = 0;
+    // rlnamd_quota_free compacts, then closes.  A FAILED OPEN NEVER WRITES A SNAPSHOT: a ledger whose construction
+    // threw (no memory for the counters, an error while the image was uploaded) is destroyed here too, and its store is
+    // closed as it was found -- the journal still holds the truth for the next open.
+    if (stream && store && restored && store->has_records()) {
+      try {
+        compact_now();
+      } catch (const std::exception&) {
+      }
+    }
     if (stream) {
       if (counters.p) (void)hipMemsetAsync(counters.p, 0, counters.bytes(), stream);   // who signed how often
       (void)hipStreamSynchronize(stream);
@@ -351,26 +469,154 @@ struct QuotaLedgerDev::Impl {
   }
 };
 
+void QuotaLedgerDev::Impl::init(size_t depth_, size_t max_epochs_) {
+  RLN_HIP(hipGetDevice(&device));
+  RLN_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  depth = (uint32_t)depth_;
+  max_epochs = (uint32_t)max_epochs_;
+  counters.alloc(max_epochs_ << depth_);
+  window_dev.alloc(quota::EPOCHS_MAX);
+  RLN_HIP(hipMemsetAsync(counters.p, 0, counters.bytes(), stream));
+  RLN_HIP(hipMemsetAsync(window_dev.p, 0, window_dev.bytes(), stream));
+  RLN_HIP(hipStreamSynchronize(stream));
+}
+
 QuotaLedgerDev::QuotaLedgerDev(size_t depth, size_t max_epochs) {
   const std::string refused = quota::new_refusal(depth, max_epochs);
   if (!refused.empty()) throw Error(refused);
   require_gpu();
   Impl* m = new Impl;
   try {
-    RLN_HIP(hipGetDevice(&m->device));
-    RLN_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-    m->depth = (uint32_t)depth;
-    m->max_epochs = (uint32_t)max_epochs;
-    m->counters.alloc(max_epochs << depth);
-    m->window_dev.alloc(quota::EPOCHS_MAX);
-    RLN_HIP(hipMemsetAsync(m->counters.p, 0, m->counters.bytes(), m->stream));
-    RLN_HIP(hipMemsetAsync(m->window_dev.p, 0, m->window_dev.bytes(), m->stream));
-    RLN_HIP(hipStreamSynchronize(m->stream));
+    m->init(depth, max_epochs);
   } catch (...) {
     delete m;
     throw;
   }
   d = m;
+}
+
+// The store is opened, and refused, on the host before a device is asked for; then the image goes to the device.
+QuotaLedgerDev::QuotaLedgerDev(const char* dir, size_t depth, size_t max_epochs, uint64_t journal_max_bytes) {
+  const std::string refused = quota::new_refusal(depth, max_epochs);
+  if (!refused.empty()) throw Error(refused);
+  if (!dir || !dir[0]) throw Error("quota ledger: open was given no directory");
+  Impl* m = new Impl;
+  try {
+    qstore::Image im;
+    m->store.reset(new qstore::QuotaStore);
+    try {
+      m->store->open(dir, depth, max_epochs, journal_max_bytes, im);
+    } catch (const qstore::StoreError& e) {
+      throw Error(e.what());
+    }
+    require_gpu();
+    m->init(depth, max_epochs);
+    // (test hook: the open fails here, "init", or behind the first piece of the image, "restore" -- as it would for want
+    // of device memory -- so that a test can hold the directory against what it was)
+    const char* fail = getenv("RLNAMD_QUOTA_OPEN_FAULT");
+    if (fail && !strcmp(fail, "init")) throw Error("quota ledger: RLNAMD_QUOTA_OPEN_FAULT=init");
+    m->restore(im, fail && !strcmp(fail, "restore"));
+    m->restored = true;
+  } catch (...) {
+    delete m;
+    throw;
+  }
+  d = m;
+}
+
+// the replayed image into the zeroed counters, PIECE pairs a copy; the window as set_epochs puts it there
+void QuotaLedgerDev::Impl::restore(const qstore::Image& im, bool fail_midway) {
+  constexpr size_t PIECE = (size_t)1 << 18;
+  window = im.window;
+  RLN_HIP(hipMemcpyAsync(window_dev.p, window.e, sizeof window.e, hipMemcpyHostToDevice, stream));
+  RLN_HIP(hipStreamSynchronize(stream));
+  if (im.used.empty()) return;
+  DevBuf<uint2> piece(std::min(PIECE, im.used.size()));
+  std::vector<uint2> host;
+  host.reserve(piece.n);
+  struct Zeroed {   // success or error: the piece is zero before it is freed
+    Impl& m;
+    DevBuf<uint2>& piece;
+    std::vector<uint2>& host;
+    ~Zeroed() {
+      (void)hipMemsetAsync(piece.p, 0, piece.bytes(), m.stream);
+      (void)hipStreamSynchronize(m.stream);
+      wipe_host(host.data(), host.size() * sizeof(uint2));
+    }
+  } zeroed{*this, piece, host};
+  auto flush = [&]() {
+    if (host.empty()) return;
+    RLN_HIP(hipMemcpyAsync(piece.p, host.data(), host.size() * sizeof(uint2), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_quota_restore, dim3(div_up(host.size(), LOG_LANES)), dim3(LOG_LANES), 0, stream, (const uint2*)piece.p,
+                       (uint32_t)host.size(), depth, max_epochs, counters.p);
+    RLN_HIP(hipGetLastError());
+    RLN_HIP(hipStreamSynchronize(stream));   // the host vector is filled again behind this
+    wipe_host(host.data(), host.size() * sizeof(uint2));
+    host.clear();
+  };
+  for (const auto& kv : im.used) {
+    host.push_back(make_uint2(kv.first, kv.second));
+    if (host.size() == piece.n || (fail_midway && host.size() == 1)) {
+      flush();
+      if (fail_midway) throw Error("quota ledger: RLNAMD_QUOTA_OPEN_FAULT=restore");
+    }
+  }
+  flush();
+  store->set_restored(im.used.size());
+}
+
+// The counters as the snapshot of the next generation: each live slot compacted on the device, in the window's order.
+void QuotaLedgerDev::Impl::compact_now() {
+  if (!store) throw Error("quota ledger: this ledger has no store (it was made by rlnamd_quota_new)");
+  if (!restored) throw Error("quota ledger: internal error, a compaction before the store's image is on the device");
+  if (held_n) throw Error("quota ledger: internal error, a compaction while a draw's ids are held");
+  OnDevice on(device);
+  const size_t N = (size_t)1 << depth;
+  const ScanPlan SP(N);
+  // pairs 8 N | positions 4 N | the scan's block sums | the number of pairs (16 bytes) | marks N
+  const size_t pairs_at = 0, pos_at = 8 * N, sums_at = pos_at + 4 * N, total_at = sums_at + 4 * ((SP.words + 3) / 4 * 4),
+               mark_at = total_at + 16, bytes = mark_at + N;
+  DevBuf<uint8_t> tmp(bytes);
+  struct Zeroed {   // success or error: zeroed before it is freed
+    Impl& m;
+    DevBuf<uint8_t>& tmp;
+    ~Zeroed() {
+      (void)hipMemsetAsync(tmp.p, 0, tmp.bytes(), m.stream);
+      (void)hipStreamSynchronize(m.stream);
+    }
+  } zeroed{*this, tmp};
+  RLN_HIP(hipMemsetAsync(tmp.p, 0, bytes, stream));
+  try {
+    store->compact(window, [&](uint32_t slot, std::vector<uint32_t>& leaf_used) {
+      const uint32_t* slot_counters = counters.p + ((size_t)slot << depth);
+      uint8_t* mark = tmp.p + mark_at;
+      uint32_t* pos = (uint32_t*)(tmp.p + pos_at);
+      uint32_t* total = (uint32_t*)(tmp.p + total_at);
+      const dim3 grid(div_up(N, LOG_LANES)), lanes(LOG_LANES);
+      hipLaunchKernelGGL(k_quota_snap_mark, grid, lanes, 0, stream, slot_counters, (uint32_t)N, mark);
+      scan_positions((const uint8_t*)mark, N, pos, (uint32_t*)(tmp.p + sums_at), stream);
+      hipLaunchKernelGGL(k_quota_snap_pack, grid, lanes, 0, stream, slot_counters, (const uint8_t*)mark, (const uint32_t*)pos, (uint32_t)N,
+                         (uint2*)(tmp.p + pairs_at), total);
+      RLN_HIP(hipGetLastError());
+      uint32_t pairs = 0;
+      RLN_HIP(hipMemcpyAsync(&pairs, total, 4, hipMemcpyDeviceToHost, stream));
+      RLN_HIP(hipStreamSynchronize(stream));
+      if (pairs > N) throw Error("quota ledger: internal error, a slot came back with more pairs than counters");
+      leaf_used.resize(2 * (size_t)pairs);
+      if (!pairs) return;
+      RLN_HIP(hipMemcpyAsync(leaf_used.data(), tmp.p + pairs_at, 8 * (size_t)pairs, hipMemcpyDeviceToHost, stream));
+      RLN_HIP(hipStreamSynchronize(stream));
+    });
+  } catch (const qstore::StoreError& e) {
+    throw Error(e.what());
+  }
+}
+
+void QuotaLedgerDev::compact() { d->compact_now(); }
+
+void QuotaLedgerDev::store_info(uint64_t out[8]) const {
+  for (int i = 0; i < 8; i++) out[i] = 0;
+  if (d->store) d->store->info(out);
 }
 
 QuotaLedgerDev::~QuotaLedgerDev() {
@@ -411,6 +657,25 @@ void QuotaLedgerDev::set_epochs(size_t k, const uint8_t* external_nullifiers_le)
   if (!refused.empty()) throw Error(refused);
   uint64_t leaving = 0;
   const quota::Window next = quota::next_window(m.window, external_nullifiers_le, k, m.max_epochs, &leaving);
+  // A ledger with a store: the window record is appended and synced first, then the window is applied.  A failure to
+  // append is a refusal like the ones above.  A crash between the two reopens into the new window, under which nothing
+  // was signed yet.  A HIP error behind the record leaves the journal a window ahead of this object: the store takes no
+  // more writes then -- and the ledger so draws nothing more -- until it is reopened.
+  struct Ahead {
+    Impl& m;
+    bool applied = false;
+    ~Ahead() {
+      if (!applied && m.store) m.store->poison("a set_epochs that failed on the device behind its record");
+    }
+  };
+  if (m.store) {
+    try {
+      m.store->append_window(k, external_nullifiers_le);
+    } catch (const qstore::StoreError& e) {
+      throw Error(e.what());
+    }
+  }
+  Ahead ahead{m};
   // From here on only a HIP error can stop the call, and such an error is not a refusal: the ledger is not left as it
   // was.  It is left SAFE: the external nullifiers that leave are taken out of the host's window first (a draw looks
   // slots up with the host's `live` mask), so no id is drawn under an epoch whose counters may be zeroed in part; the new
@@ -430,6 +695,8 @@ void QuotaLedgerDev::set_epochs(size_t k, const uint8_t* external_nullifiers_le)
   RLN_HIP(hipMemcpyAsync(m.window_dev.p, next.e, sizeof next.e, hipMemcpyHostToDevice, m.stream));
   RLN_HIP(hipStreamSynchronize(m.stream));
   m.window = next;
+  ahead.applied = true;
+  m.compact_if_due();
 }
 
 size_t QuotaLedgerDev::epochs(uint8_t out_le[32 * quota::EPOCHS_MAX]) const {
@@ -441,6 +708,7 @@ size_t QuotaLedgerDev::epochs(uint8_t out_le[32 * quota::EPOCHS_MAX]) const {
 void QuotaLedgerDev::draw(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits, uint32_t* ids_out,
                           uint8_t* status) {
   d->run(n, leaf_indices, ext_le, limits, nullptr, ids_out, status, false);
+  d->compact_if_due();
 }
 
 void QuotaLedgerDev::draw_counts(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
@@ -450,13 +718,14 @@ void QuotaLedgerDev::draw_counts(size_t n, const uint64_t* leaf_indices, const u
   if (!refused.empty()) throw Error(refused);
   if (n == 0) return;
   d->run(n, leaf_indices, ext_le, limits, counts, firsts_out, status, false);
+  d->compact_if_due();
 }
 
 QuotaLedgerDev::Held QuotaLedgerDev::draw_hold(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
                                                uint8_t* status) {
   d->run(n, leaf_indices, ext_le, limits, nullptr, nullptr, status, true);
   if (!d->held_n) return Held{nullptr, nullptr, (void*)d->stream, d->device};
-  const Block B(d->held_n, d->held_by_count);
+  const Block B = d->block_of(d->held_n, d->held_by_count);
   return Held{(const uint32_t*)(d->block.p + B.ids), d->block.p + B.status, (void*)d->stream, d->device};
 }
 
@@ -466,7 +735,7 @@ QuotaLedgerDev::Held QuotaLedgerDev::draw_hold_counts(size_t n, const uint64_t* 
   if (!refused.empty()) throw Error(refused);
   if (n) d->run(n, leaf_indices, ext_le, limits, counts, nullptr, status, true);
   if (!d->held_n) return Held{nullptr, nullptr, (void*)d->stream, d->device, nullptr};
-  const Block B(d->held_n, true);
+  const Block B = d->block_of(d->held_n, true);
   return Held{(const uint32_t*)(d->block.p + B.ids), d->block.p + B.status, (void*)d->stream, d->device, d->block.p + B.counts};
 }
 
@@ -475,22 +744,24 @@ void QuotaLedgerDev::held_ids(size_t first, size_t count, uint32_t* out) {
   if (count == 0) return;
   if (first > m.held_n || count > m.held_n - first) throw Error("quota ledger: internal error, ids asked for beyond the draw that is held");
   OnDevice on(m.device);
-  RLN_HIP(hipMemcpyAsync(out, m.block.p + Block(m.held_n, m.held_by_count).ids + 4 * first, 4 * count, hipMemcpyDeviceToHost, m.stream));
+  RLN_HIP(hipMemcpyAsync(out, m.block.p + m.block_of(m.held_n, m.held_by_count).ids + 4 * first, 4 * count, hipMemcpyDeviceToHost, m.stream));
   RLN_HIP(hipStreamSynchronize(m.stream));
 }
 
 void QuotaLedgerDev::release() {
   Impl& m = *d;
   if (!m.held_n) return;
-  const Block B(m.held_n, m.held_by_count);
+  const Block B = m.block_of(m.held_n, m.held_by_count);
   m.held_n = 0;
   wipe_host(m.out_host, B.out_bytes());
+  if (m.delta_host) wipe_host(m.delta_host, B.delta_host_bytes());
   int prev = 0;
   const bool move = hipGetDevice(&prev) == hipSuccess && prev != m.device && hipSetDevice(m.device) == hipSuccess;
   const hipError_t e1 = hipMemsetAsync(m.block.p, 0, B.bytes, m.stream), e2 = hipStreamSynchronize(m.stream);
   if (move) (void)hipSetDevice(prev);
   RLN_HIP(e1);
   RLN_HIP(e2);
+  m.compact_if_due();
 }
 
 void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uint8_t* ext_le, const uint32_t* limits,
@@ -501,9 +772,16 @@ void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uin
   const std::string refused = quota::draw_refusal(n, leaf_indices, ext_le, limits, ids_out, status, m.depth, !hold);
   if (!refused.empty()) throw Error(refused);
   if (n == 0) return;
+  if (m.store) {   // a store that takes no more writes draws nothing: its ids could not be made durable
+    try {
+      m.store->check_writable();
+    } catch (const qstore::StoreError& e) {
+      throw Error(e.what());
+    }
+  }
   OnDevice on(m.device);
   m.reserve(n);
-  const Block B(n, counts != nullptr);
+  const Block B = m.block_of(n, counts != nullptr);
   const quota::DrawPlan P = quota::plan_for(n, m.depth);
   struct Wipe {   // success or error: the call's block is zero again when draw() returns (a held draw: at release())
     Impl& m;
@@ -511,6 +789,7 @@ void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uin
     bool device_done = false, held = false;
     ~Wipe() {
       wipe_host(m.in_host, B.in_bytes());
+      if (m.delta_host) wipe_host(m.delta_host, B.delta_host_bytes());   // journalled, or the call failed
       if (held) return;
       if (!device_done) {
         (void)hipMemsetAsync(m.block.p, 0, B.bytes, m.stream);
@@ -563,19 +842,51 @@ void QuotaLedgerDev::Impl::run(size_t n, const uint64_t* leaf_indices, const uin
                        m.counters.p, m.depth, slots, n32);
   }
   RLN_HIP(hipGetLastError());
+  uint32_t* h_moved = nullptr;   // a ledger with a store: where the number of counters this draw moved arrives
+  if (m.store) {
+    hipLaunchKernelGGL(k_quota_delta_mark, grid, lanes, 0, m.stream, key, (const uint32_t*)words(B.start), (const uint32_t*)words(B.ok),
+                       m.depth, slots, n32, base + B.dflag);
+    scan_positions((const uint8_t*)(base + B.dflag), n, words(B.dpos), words(B.sums), m.stream);
+    hipLaunchKernelGGL(k_quota_delta_pack, grid, lanes, 0, m.stream, key, (const uint8_t*)(base + B.dflag),
+                       (const uint32_t*)words(B.dpos), (const uint32_t*)m.counters.p, m.depth, n32, (uint2*)(base + B.drec),
+                       words(B.dtotal));
+    RLN_HIP(hipGetLastError());
+    h_moved = (uint32_t*)(m.delta_host + 8 * B.np);
+    RLN_HIP(hipMemcpyAsync(h_moved, base + B.dtotal, 4, hipMemcpyDeviceToHost, m.stream));
+  }
   if (hold) {   // the statuses alone; the ids stay where they are
     RLN_HIP(hipMemcpyAsync(m.out_host + (B.status - B.ids), base + B.status, B.out_bytes() - (B.status - B.ids), hipMemcpyDeviceToHost,
                            m.stream));
   } else {
     RLN_HIP(hipMemcpyAsync(m.out_host, base + B.ids, B.out_bytes(), hipMemcpyDeviceToHost, m.stream));
-    RLN_HIP(hipMemsetAsync(base, 0, B.bytes, m.stream));   // behind the copy, in stream order
+    if (!m.store) RLN_HIP(hipMemsetAsync(base, 0, B.bytes, m.stream));   // behind the copy, in stream order
   }
   RLN_HIP(hipStreamSynchronize(m.stream));
+  size_t moved = 0;
+  if (m.store) {   // the second copy: the pairs, now that their number is known; then the block's wipe
+    moved = *h_moved;
+    if (moved > n) throw Error("quota ledger: internal error, a draw moved more counters than it has requests");
+    if (moved) RLN_HIP(hipMemcpyAsync(m.delta_host, base + B.drec, 8 * moved, hipMemcpyDeviceToHost, m.stream));
+    if (!hold) RLN_HIP(hipMemsetAsync(base, 0, B.bytes, m.stream));
+    if (moved || !hold) RLN_HIP(hipStreamSynchronize(m.stream));
+  }
   wipe.device_done = !hold;
 
   const uint8_t* h_status = m.out_host + (B.status - B.ids);
   for (size_t i = 0; i < n; i++)
     if (h_status[i] > quota::NO_EPOCH) throw Error("quota ledger: internal error, a request came back without a status");
+  // Durable before any id leaves the call: the record is appended and synced, and only then are ids and statuses copied
+  // into the caller's arrays (a held draw: before draw_hold returns, so before anything is staged for proving).  A draw
+  // that granted nothing appends nothing.  If this fails the call fails: the caller's arrays are untouched, the block is
+  // wiped (a held draw's too: it is not held), the counters stay advanced -- those ids are burnt, the safe side -- and
+  // the ledger stays usable, since the next record carries absolute values.
+  if (moved) {
+    try {
+      m.store->append_advance(moved, (const uint32_t*)m.delta_host);
+    } catch (const qstore::StoreError& e) {
+      throw Error(e.what());
+    }
+  }
   if (!hold) memcpy(ids_out, m.out_host, 4 * n);
   memcpy(status, h_status, n);
   for (size_t i = 0; i < n; i++) {
@@ -628,7 +939,8 @@ void QuotaLedgerDev::info(uint64_t out[8]) {
     std::vector<uint8_t> dev(m.stage_bytes);
     RLN_HIP(hipMemcpyAsync(dev.data(), m.block.p, m.stage_bytes, hipMemcpyDeviceToHost, m.stream));
     RLN_HIP(hipStreamSynchronize(m.stream));
-    out[5] = nonzero_words16(dev.data(), m.stage_bytes) + nonzero_words16(m.in_host, m.in_cap) + nonzero_words16(m.out_host, m.out_cap);
+    out[5] = nonzero_words16(dev.data(), m.stage_bytes) + nonzero_words16(m.in_host, m.in_cap) + nonzero_words16(m.out_host, m.out_cap) +
+             (m.delta_host ? nonzero_words16(m.delta_host, m.delta_cap) : 0);
   }
 }
 
