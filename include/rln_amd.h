@@ -191,7 +191,9 @@ typedef struct {
   int32_t window_bits_g2, windows_g2; /* the same for the G2 comb */
   int32_t glv;                        /* always 1: scalars are split k1 + lambda k2 and the combs cover 127 bits */
   int32_t reserved;
-  uint64_t g1_rows, g2_rows;          /* finite points of the G1 / G2 walk (table rows) */
+  uint64_t g1_rows, g2_rows;          /* rows a big batch walks per full proof: G2 the table rows (finite points); G1 the table
+                                         rows minus the B1 rows that share their point with the A row of the same wire and are
+                                         not walked (RLNAMD_SHARED_ROWS=0: every table row) */
 } rlnamd_prover_info;
 int rlnamd_prover_get_info(rlnamd_prover* p, rlnamd_prover_info* info);
 /* the same for the prover behind an object of include/rln.h (FFI_RLN_t* / FFI_RLNV3_t*, passed as void*): shows how

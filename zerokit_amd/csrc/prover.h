@@ -42,6 +42,7 @@ struct ProverConfig {
   size_t max_batch = 1024;  // workspace capacity in proofs (rounded up to a multiple of 64)
   long partial_cache = -1;  // entries of the partial-proof cache (collect_partial_cached); -1 = RLNAMD_PARTIAL_CACHE or 64
   int stream_shape = -1;    // streams of a big batch: -1 = RLNAMD_STREAM_SHAPE or auto; 0 auto, 1 wide, 2 compact (ProverTuning::stream_shape)
+  int shared_rows = -1;     // -1 = RLNAMD_SHARED_ROWS or 1; 0 / 1 (ProverTuning::shared_rows)
 };
 
 // Every switch of the prover, read from the environment ONCE when a Prover is built (ProverTuning::from_env; printed by
@@ -81,6 +82,9 @@ struct ProverTuning {
                                        // keeps busy (prover_plan.h: stream_plan).  wide: eight streams, for a process with 8 hardware queues or
                                        // more; compact: four, with the public values read off the witness.  auto: compact at 4 .. 7 hw_queues, else wide.  Small batches
                                        // take the same streams either way.  A Prover holds the resolved shape (never auto)
+  int shared_rows = 1;                 // RLNAMD_SHARED_ROWS (config key "shared_rows"): 1: the G1 walk of a BIG batch walks a proving-key row that the A
+                                       // and B1 queries share (A_i = +- B1_i) once and uses its sum twice (prover_plan.h: G1Rows::shared);
+                                       // 0: the three-segment plan that walks every table row.  Same bytes either way
   int hw_queues = 4;                   // GPU_MAX_HW_QUEUES as the process got it (read, never set); 4, HIP's default, when absent or unparsable
   int hint_fault = 0;                  // RLNAMD_HINT_FAULT (test hook): j > 0 corrupts hint j - 1 of the first proof of every hinted batch
   static ProverTuning from_env();
@@ -139,7 +143,9 @@ class Prover {
   int windows() const { return W_; }          // table additions per G1 point and proof (windows x GLV halves)
   int window_bits_g2() const { return c2_; }
   int windows_g2() const { return W2_; }
-  size_t g1_rows() const;                     // table rows (finite points) of the G1 / G2 walk
+  // rows the throughput plans walk for a full proof.  G2: the table rows (finite points).  G1: the table rows minus the B1
+  // rows whose sum the walk takes from the A row of the same wire (ProverTuning::shared_rows; all of them when that is 0)
+  size_t g1_rows() const;
   size_t g2_rows() const;
   size_t inputs_per_proof() const { return graph_.inputs_size; }
   size_t table_bytes() const;

@@ -278,6 +278,7 @@ struct Prover::Impl {
   uint32_t max_chunks1s = 0, max_chunks2s = 0, small_stride = 64;   // partial sums of a small batch: [chunk][64]
   uint32_t max_chunks1 = 0, max_chunks2 = 0, max_groups1 = 0, max_groups2 = 0;
   uint32_t npts1 = 0, npts2 = 0, npaired1 = 0;   // npaired1: G1 points [0, npaired1) are pair members
+  uint32_t nseg1_big = G1_SEGS, nwalked1 = 0;    // PLAN_BIG of the G1 walk: output segments; table rows a full proof walks (tune.shared_rows)
   std::vector<uint8_t> known;  // per witness signal: computable from the partial witness (evaluate_partial)
   // ---- the graph as independent segments behind hints (witness_sched.h: wl_segments; Prover::enqueue): the values between
   //      the circuit's chained hashes are computed on a host core (HintChains: depth + 2 Poseidon hashes, ~0.3 ms), every
@@ -511,6 +512,7 @@ ProverTuning ProverTuning::from_env() {
     t.stream_shape = shape >= 0 ? shape : SHAPE_AUTO;
     t.hw_queues = hw_queues_from_env(getenv("GPU_MAX_HW_QUEUES"));   // read, never set: the host program's to choose
   }
+  t.shared_rows = env_int("RLNAMD_SHARED_ROWS", t.shared_rows) != 0;
   t.verify_lanes = env_int("RLNAMD_VERIFY_LANES", 0);
   if (t.verify_lanes != 1 && t.verify_lanes != 8) t.verify_lanes = 0;
   {   // (at most half of the host's hardware threads unless the switch says otherwise)
@@ -526,9 +528,11 @@ std::string ProverTuning::describe() const {
   char b[768];
   snprintf(b, sizeof b,
            "window_bits=%d slots=%d lanechunk=%u lanechunk_walk=%u witlanes_max=%u tiny=%u ntt_lg_max=%u partial_cache=%u lone=%d "
-           "lone_small=%u hints=%u hints_warm=%u hint_threads=%u hint_chains=%u verify_lanes=%d stream_shape=%s hw_queues=%d",
+           "lone_small=%u hints=%u hints_warm=%u hint_threads=%u hint_chains=%u verify_lanes=%d stream_shape=%s hw_queues=%d "
+           "shared_rows=%d",
            window_bits, slots, lanechunk_max, lanechunk_walk_max, witlanes_max, tiny_max, ntt_lg_max, partial_cache, lone,
-           lone_small_max, hint_max, hint_max_warm, hint_threads, hint_chains, verify_lanes, stream_shape_name(stream_shape), hw_queues);
+           lone_small_max, hint_max, hint_max_warm, hint_threads, hint_chains, verify_lanes, stream_shape_name(stream_shape), hw_queues,
+           shared_rows);
   return b;
 }
 const ProverTuning& Prover::tuning() const { return d_->tune; }
@@ -589,6 +593,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
   // additions per G2 point.
   D.tune = ProverTuning::from_env();
   if (cfg.stream_shape >= SHAPE_AUTO && cfg.stream_shape <= SHAPE_COMPACT) D.tune.stream_shape = cfg.stream_shape;
+  if (cfg.shared_rows >= 0) D.tune.shared_rows = cfg.shared_rows != 0;
   const int wb = cfg.window_bits > 0 ? cfg.window_bits : D.tune.window_bits;
   D.tune.window_bits = wb;
   const int spec1 = wb % 10000, spec2 = wb / 10000 ? wb / 10000 : spec1;
@@ -838,8 +843,12 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     D.npaired1 = R.npaired;
     D.npts1 = (uint32_t)R.pts.size();
     D.sid1.assign(R.sids, s);
+    // the throughput plan: five segments, the rows A and B1 share walked once (prover_plan.h: G1Rows::shared)
+    const std::vector<VRow>& big = D.tune.shared_rows ? R.shared : R.rows;
+    D.nseg1_big = D.tune.shared_rows ? G1_SHARED_SEGS : G1_SEGS;
+    D.nwalked1 = (uint32_t)big.size();
     for (int m : modes) {
-      plan(D.plan1[PLAN_BIG][m], R.rows, 3, 16u, m, &D.max_chunks1, R.npaired, true);   // rows (x halves) per single-wave workgroup
+      plan(D.plan1[PLAN_BIG][m], big, D.nseg1_big, 16u, m, &D.max_chunks1, R.npaired, true);   // rows (x halves) per single-wave workgroup
       D.max_groups1 = std::max(D.max_groups1, D.plan1[PLAN_BIG][m].ngroups);
     }
     for (int m : modes) plan(D.plan1[PLAN_SMALL][m], R.rows, 3, 4u, m, &D.max_chunks1s, R.npaired);
@@ -893,7 +902,7 @@ Prover::Prover(const uint8_t* zkey, size_t zkey_len, const uint8_t* graph, size_
     S.part1.alloc(std::max({(size_t)D.max_chunks1 * B, (size_t)D.max_chunks1s * D.small_stride,
                             (size_t)D.max_chunks1t * TINY_STRIDE}));
     S.grp1.alloc(std::max((size_t)D.max_groups1 * B, (size_t)D.max_blocks1t * TINY_STRIDE));
-    S.sums1.alloc(3 * D.nh * B);
+    S.sums1.alloc(D.nseg1_big * D.nh * B);   // (no plan has more segments than the throughput plan)
     S.part2.alloc(std::max({(size_t)D.max_chunks2 * B, (size_t)D.max_chunks2s * D.small_stride,
                             (size_t)D.max_chunks2t * TINY_STRIDE}));
     S.grp2.alloc(std::max((size_t)D.max_groups2 * B, (size_t)D.max_blocks2t * TINY_STRIDE));
@@ -1002,7 +1011,7 @@ Prover::~Prover() {
 }
 
 size_t Prover::table_bytes() const { return d_->t1_29.bytes() + d_->t2_29.bytes(); }
-size_t Prover::g1_rows() const { return d_->npts1; }
+size_t Prover::g1_rows() const { return d_->nwalked1; }
 size_t Prover::g2_rows() const { return d_->npts2; }
 
 void Prover::upload(size_t n, const uint8_t* inputs, const uint8_t* rs) {
@@ -2234,8 +2243,15 @@ uint64_t Prover::enqueue(size_t n, int mode, const uint8_t* h_inputs, const uint
     hipLaunchKernelGGL(k_sum_ranges<Fq>, dim3(pg, P1.nseg), dim3(64), 0, sC, S.grp1.p, P1.segs.p, P1.nseg, S.sums1.p, B, nbp);
     hipLaunchKernelGGL(k_sum_ranges<Fq2>, dim3(pg, P2.nseg), dim3(64), 0, sC, S.grp2.p, P2.segs.p, P2.nseg, S.sums2.p, B, nbp);
   }
-  if (!early)   // sums of the second halves through phi, onto the first: afterwards sums1[0..3) / sums2[0]
-    hipLaunchKernelGGL(k_glv_fold, dim3(pg, 4), dim3(64), 0, sC, S.sums1.p, S.sums2.p, 3u, B, nbp, all4);
+  if (!early) {   // sums of the second halves through phi, onto the first: afterwards sums1[0..3) / sums2[0]
+    if (P1.nseg / D.nh == G1_SHARED_SEGS) {   // (a big batch that walked the shared rows once: their two sums join A and B1)
+      hipLaunchKernelGGL(k_glv_fold, dim3(pg, 6), dim3(64), 0, sC, S.sums1.p, S.sums2.p, G1_SHARED_SEGS, B, nbp,
+                         task_sel({0, 1, 2, SEG_SHARED_EQ, SEG_SHARED_OPP, G1_SHARED_SEGS}));   // (the last: the G2 sum)
+      hipLaunchKernelGGL(k_shared_join, dim3(pg, 2), dim3(64), 0, sC, S.sums1.p, B, nbp);
+    } else {
+      hipLaunchKernelGGL(k_glv_fold, dim3(pg, 4), dim3(64), 0, sC, S.sums1.p, S.sums2.p, 3u, B, nbp, all4);
+    }
+  }
   if (mode == PROVE_PARTIAL) {
     hipLaunchKernelGGL(k_partial_out, dim3(pg, 4), dim3(64), 0, sC, S.sums1.p, S.sums2.p, S.pp_out.p, B, nbp);
     RLN_HIP(hipGetLastError());

@@ -52,4 +52,9 @@ struct ChunkDesc {
 //               pair chunks of the throughput plan read both with a lane pair and halve the HBM requests of those rows.
 constexpr uint32_t ROW_HALF2 = 1u << 31, ROW_PAIRED = 1u << 30, ROW_INDEX = ROW_PAIRED - 1;
 
+// Output segments of the G1 walk.  Every family of rows has A, B1 and Cpart; the shared family of the throughput plan
+// (prover_plan.h: G1Rows::shared) has two more: the A rows of the wires whose B1 row is the same point (SEG_SHARED_EQ) or
+// its negative (SEG_SHARED_OPP).  k_shared_join, behind the fold, adds their sums to A and B1.
+constexpr uint32_t G1_SEGS = 3, G1_SHARED_SEGS = 5, SEG_SHARED_EQ = 3, SEG_SHARED_OPP = 4;
+
 }  // namespace rlnamd

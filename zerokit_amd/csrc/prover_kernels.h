@@ -108,6 +108,7 @@ __global__ void __launch_bounds__(SUM_TREE_LANES) k_sum_blocks(const XYZZ<F>* __
                                                     TaskSel sel);
 __global__ void __launch_bounds__(64) k_glv_fold(G1XYZZ* __restrict__ sums1, G2XYZZ* __restrict__ sums2, uint32_t nseg1,
                                                  uint32_t B, uint32_t nb, TaskSel sel);
+__global__ void __launch_bounds__(64) k_shared_join(G1XYZZ* __restrict__ sums1, uint32_t B, uint32_t nb);
 template <class F>
 __global__ void __launch_bounds__(64) k_table_build(const Affine<F>* __restrict__ pts, uint32_t npts, WinSched ws,
                                                     Affine<F>* __restrict__ table, F* __restrict__ scratch);

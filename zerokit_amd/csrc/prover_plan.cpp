@@ -412,6 +412,25 @@ G1Rows g1_walk_rows(const Zkey& zk, uint32_t NS, uint32_t n, uint32_t ni) {
   }
   for (uint32_t k = 0; k < sids.size(); k++)
     R.rows.push_back({k, sids[k], sids[k], row_seg[k], sids[k] >= NS && sids[k] < NS + n});
+  // Throughput plan, shared rows: the wires whose A and B1 rows are one point up to sign (affine coordinates: x equal, y
+  // equal or opposite).  Scalar id 0 never: its rows carry alpha and beta beside query[0].
+  {
+    std::vector<uint8_t> kind(NS, 0);   // 1: A_i == B1_i, 2: A_i == -B1_i
+    for (uint32_t i = 1; i < NS; i++) {
+      const G1Affine &a = zk.a_query[i], &b = zk.b_g1_query[i];
+      if (a.is_inf() || b.is_inf() || a.x != b.x) continue;
+      if (a.y == b.y) kind[i] = 1;
+      else if (a.y == b.y.neg()) kind[i] = 2;
+      if (kind[i]) (kind[i] == 1 ? R.shared_eq : R.shared_opp).push_back(i);
+    }
+    for (const VRow& v : R.rows) {
+      const uint32_t kd = v.sid < NS ? kind[v.sid] : 0;
+      if (kd && v.seg == 1) continue;   // the B1 row: the sum of the A row serves for it
+      VRow w = v;
+      if (kd && v.seg == 0) w.seg = kd == 1 ? SEG_SHARED_EQ : SEG_SHARED_OPP;
+      R.shared.push_back(w);
+    }
+  }
   // Small full proofs, fused plan: s A + r B1 - r s delta = s alpha + r beta + r s delta + sum (s w_i) A_i + sum (r w_i) B1_i,
   // so the two variable-base products of the back end (k_fin_smul: a lone lane's ladder of 127 doublings, the longest
   // kernel behind the interpreter) become extra rows of the C segment -- the A and B1 rows walked a second time under
@@ -482,8 +501,9 @@ WalkPlan make_walk_plan(const std::vector<VRow>& vrows, uint32_t nseg, uint32_t 
   // pair chunks first: entries grouped by (half, segment of member 0, segment of member 1)
   struct PairChunk { uint32_t h, sg0, sg1, begin, end; };
   std::vector<PairChunk> pcs;
+  std::vector<const VRow*> byk;   // pair members the family holds, by table row
   if (pairs_here) {
-    std::vector<const VRow*> byk(npaired, nullptr);
+    byk.assign(npaired, nullptr);
     for (const VRow& v : vrows)
       if (v.k < npaired) byk[v.k] = &v;
     for (uint32_t h = 0; h < GLV_HALVES; h++)
@@ -514,7 +534,8 @@ WalkPlan make_walk_plan(const std::vector<VRow>& vrows, uint32_t nseg, uint32_t 
         uint32_t first = (uint32_t)P.rows.size();
         for (const VRow& v : vrows) {
           if (v.seg != sg || (int)v.is_h != late) continue;
-          if (pairs_here && v.k < npaired) continue;   // walked by a pair chunk
+          // walked by a pair chunk -- unless the family leaves its partner out: then it is a single row here
+          if (pairs_here && v.k < npaired && byk[v.k ^ 1u]) continue;
           if (walked(v)) {
             P.rows.push_back(roww(v.k, h));
             P.rsid.push_back(v.dig_sid);

@@ -107,6 +107,15 @@ struct G1Rows {
   std::vector<uint32_t> sids;        // scalar id of every point
   uint32_t npaired = 0;              // points [0, npaired) are pair members (ROW_PAIRED)
   std::vector<VRow> rows, fused;     // the plain rows; the rows of the fused small-batch plan
+  // The throughput plan's rows.  For a wire i >= 1 with a_query[i] and b_g1_query[i] finite and a_query[i] = +- b_g1_query[i]
+  // (a constraint that squares a linear combination has the same combination on both sides: a third of the A rows of the
+  // shipped keys) the walk of the B1 row would repeat, under the same scalar, the partial sum the A row makes.  `shared` is
+  // `rows` without those B1 rows and with their A rows moved to SEG_SHARED_EQ / SEG_SHARED_OPP; with S+ and S- the sums of
+  // those two segments, A = seg 0 + S+ + S- and B1 = seg 1 + S+ - S- (k_shared_join).  Rows of scalar id 0 and the blinding
+  // rows are never shared.  The points, their order and the tables do not depend on any of this: the dropped B1 rows stay
+  // resident for the other plans.
+  std::vector<VRow> shared;
+  std::vector<uint32_t> shared_eq, shared_opp;   // the wires, ascending
 };
 struct G2Rows {
   std::vector<G2Affine> pts;
@@ -138,7 +147,8 @@ struct WalkPlan {
 constexpr uint32_t GLV_HALVES = 2;   // halves per scalar: the GLV split k1 + lambda k2 (glv.h)
 // npaired: points [0, npaired) are pair members (their row words carry ROW_PAIRED in every plan).  pair_chunks: walk them
 // as pair chunks (lane pairs, one 128-byte line per two additions) instead of as single rows; every pair chunk owns a chunk
-// slot in each of its two members' segments.
+// slot in each of its two members' segments.  A pair member whose partner the family does not hold (G1Rows::shared) is
+// walked as a single row of its interleaved table.
 WalkPlan make_walk_plan(const std::vector<VRow>& vrows, uint32_t nseg, uint32_t chunk_pts, int mode,
                         const std::vector<uint8_t>& known, uint32_t npaired = 0, bool pair_chunks = false,
                         uint32_t block_pts = SUM_TREE_LANES);

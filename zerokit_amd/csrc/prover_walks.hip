@@ -105,6 +105,7 @@ __global__ void __launch_bounds__(SUM_TREE_LANES) k_sum_blocks(const XYZZ<F>* __
 
 // GLV: segment t holds sum k1_i P_i, segment nseg + t holds sum k2_i P_i; the result is the first plus phi of the
 // second, phi(X, Y, ZZ, ZZZ) = (beta X, Y, ZZ, ZZZ) (x = X / ZZ).  One Fq product per output point and proof.
+// Tasks below nseg1 (the G1 plan's segments per half): that G1 segment; any other task: the G2 sum.
 __global__ void __launch_bounds__(64) k_glv_fold(G1XYZZ* __restrict__ sums1, G2XYZZ* __restrict__ sums2, uint32_t nseg1,
                                                  uint32_t B, uint32_t nb, TaskSel sel) {
   __builtin_amdgcn_s_setprio(3);
@@ -122,6 +123,21 @@ __global__ void __launch_bounds__(64) k_glv_fold(G1XYZZ* __restrict__ sums1, G2X
     a.add(b);
     sums2[p] = a;
   }
+}
+
+// Behind the fold of a five-segment plan (prover_plan.h: G1Rows::shared): the walk took the rows that A and B1 share once,
+// S+ = sums1[SEG_SHARED_EQ] and S- = sums1[SEG_SHARED_OPP] are their folded sums.  blockIdx.y = 0: A += S+ + S-; 1:
+// B1 += S+ - S- (an XYZZ point is negated in Y).  General additions: either sum may be the point at infinity, equal the
+// output's own sum or cancel it.  Four per proof, against 21 738 x 18 of the walk.
+__global__ void __launch_bounds__(64) k_shared_join(G1XYZZ* __restrict__ sums1, uint32_t B, uint32_t nb) {
+  __builtin_amdgcn_s_setprio(3);
+  const uint32_t p = blockIdx.x * 64 + threadIdx.x, t = blockIdx.y;
+  if (p >= nb || t >= 2) return;
+  G1XYZZ a = sums1[(size_t)t * B + p];
+  const G1XYZZ opp = sums1[(size_t)SEG_SHARED_OPP * B + p];
+  a.add(sums1[(size_t)SEG_SHARED_EQ * B + p]);
+  a.add(t == 0 ? opp : opp.neg());
+  sums1[(size_t)t * B + p] = a;
 }
 
 // one-time comb table: row (k, j) = { d * 2^(c j) * P_k : d = 1..2^(c-1) } in affine form.

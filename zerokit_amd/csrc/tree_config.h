@@ -103,6 +103,9 @@ struct TreeConfig {
   // "stream_shape": "auto" | "wide" | "compact" -- the streams a big batch keeps busy (prover.h: ProverTuning::stream_shape).
   // -1: RLNAMD_STREAM_SHAPE or auto (by the process's GPU_MAX_HW_QUEUES)
   int stream_shape = -1;
+  // "shared_rows": 1 | 0 (or true | false) -- a big batch's G1 walk takes a proving-key row that the A and B1 queries share
+  // once (prover.h: ProverTuning::shared_rows).  -1: RLNAMD_SHARED_ROWS or 1
+  int shared_rows = -1;
   bool persistent() const { return !temporary && has_path; }
   ProverConfig prover_config() const {
     ProverConfig cfg;
@@ -113,6 +116,7 @@ struct TreeConfig {
     cfg.max_batch = max_batch > 0 ? (size_t)max_batch : pb > 0 ? (size_t)pb : (mb && *mb ? (size_t)atoll(mb) : 256);
     cfg.window_bits = window_bits > 0 ? (int)window_bits : (int)pw;   // 0: Prover takes RLNAMD_WINDOW_BITS or its default schedule
     cfg.stream_shape = stream_shape;
+    cfg.shared_rows = shared_rows;
     cfg.partial_cache = partial_cache >= 0 ? partial_cache : (auto_partial > 0 ? std::max(64l, auto_partial + 8) : -1);
     return cfg;
   }
@@ -171,6 +175,7 @@ inline TreeConfig parse_tree_config(const std::string& js) {
       i += v ? 4 : 5;
       if (key == "temporary") c.temporary = v;
       if (key == "dynamic_shards") c.dynamic_shards = v;
+      if (key == "shared_rows") c.shared_rows = v ? 1 : 0;
       if (key == "verify_optimistic") c.verify_optimistic = v;
       if (key == "verify_optimistic_teams") c.verify_optimistic_teams = v;
     } else if (!js.compare(i, 4, "null")) {
@@ -228,6 +233,10 @@ inline TreeConfig parse_tree_config(const std::string& js) {
       if (key == "tree_depth") c.tree_depth = num;
       if (key == "window_bits") c.window_bits = num;
       if (key == "max_batch") c.max_batch = num;
+      if (key == "shared_rows") {
+        if (num != 0 && num != 1) throw Error("Configuration error: shared_rows: expected 0 or 1");
+        c.shared_rows = (int)num;
+      }
       if (key == "flush_every_ms") {
         if (num < 0 || num > 3600000) throw Error("Configuration error: flush_every_ms: expected 0 .. 3600000 milliseconds");
         c.flush_every_ms = num;
