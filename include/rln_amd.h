@@ -787,6 +787,81 @@ int rlnamd_prover_prove_stream_members_drawn_counts(rlnamd_prover* p, rlnamd_tre
                                                     uint8_t* proofs /* n*128 */, uint8_t* values_public /* n*num_public*32 */,
                                                     uint32_t* errors /* n */);
 
+/* ---- member directory on the device: register, resolve secrets, slash ----------------------------------------------
+ * The object that closes the loop tree -> prove by member -> quota ledger / hasher -> verifier -> nullifier log -> relay:
+ * for every RLNAMD_SHARE_SPAM a relay step returns the member's identity secret, and the directory answers whose secret
+ * that is, which leaf it holds and what its limit is, and removes it.  The tree in HBM holds only rate commitments,
+ * Poseidon(id_commitment, limit); the directory keeps, beside it, (id_commitment, limit) per leaf index and a keyed hash
+ * table from id_commitment to leaf index.  The reference has no such state.  The meaning below is the sequential text of
+ * zerokit_amd/csrc/member_directory.h.
+ * rlnamd_directory_new: a directory D over the dense tree `tree`, which it BORROWS (the tree must outlive it), covering the
+ * leaf indices [0, capacity), 1 <= capacity <= min(2^depth, 2^31); seed keys the table's hash, 0 = drawn from getrandom
+ * (registrations arrive from outside: a sender who does not know the seed cannot aim commitments at one slot).  Per index D
+ * holds a state, FREE or LIVE, and for a LIVE index the member's identity commitment (canonical Fr) and its limit (uint32 >=
+ * 1, the type the quota ledger uses).  At most one LIVE index carries a given commitment.  D starts empty.  37 bytes per
+ * index plus 4 bytes per table slot, 2 * capacity slots rounded up to a power of two (45 MiB at 2^20).
+ *   D WRITES ONLY THE LEAVES OF INDICES IT REGISTERS OR REMOVES.  A leaf written behind its back through rlnamd_tree_set_*
+ *   is not noticed: D still answers from its own rows.
+ *   D IS NOT PERSISTED.  A directory made over a tree that already holds leaves is empty.  Registering the same events
+ *   again rebuilds it: they write the same leaves, so the root does not move.  That is the way back after a restart.
+ * Every call runs on the tree's stream and takes the directory's mutex and then the tree handle's, both for the call:
+ * that orders it against rlnamd_tree_* and against the path gathers of rlnamd_prover_submit_members with no extra event.
+ * rlnamd_directory_register: n requests (indices[i], idcs_le[i], limits[i]) -> status[i].  Refused as a whole before
+ * anything is enqueued, each with a text of its own, D and the tree untouched: a null pointer with n > 0, an index >=
+ * capacity, an index that occurs twice in the call, a commitment >= r, a limit of 0, n >= 2^32.  Otherwise the call is a
+ * SET of requests, and its outcome does not depend on their order:
+ *   RLNAMD_DIR_OCCUPIED  the index was LIVE before the call.  This is checked first.
+ *   RLNAMD_DIR_KNOWN     not OCCUPIED, and either the commitment was LIVE somewhere before the call, or another request of
+ *                        the call that is not OCCUPIED carries the same commitment at a lower index.
+ *   RLNAMD_DIR_OK        otherwise: the index becomes LIVE with (commitment, limit), and its leaf becomes
+ *                        Poseidon(commitment, Fr(limit)) (t = 3, rln/src/hashers.rs), computed and written on the device.
+ * An OCCUPIED request never blocks another request that carries the same commitment at a free index.  After the call the
+ * tree's root reflects the new leaves: one bottom-up pass runs over the union of the paths.
+ *   A CALL WITH DUPLICATE COMMITMENTS IS NOT WHAT EVERY SPLIT OF IT GIVES: inside a call the lowest index wins, across
+ *   calls the first call wins.
+ * rlnamd_directory_find: n commitments -> RLNAMD_DIR_FOUND with the live index and its limit, else RLNAMD_DIR_UNKNOWN with
+ * index UINT64_MAX and limit 0 (a commitment >= r is never LIVE, so it is UNKNOWN).
+ * rlnamd_directory_resolve: n identity secrets -> the same outputs for Poseidon(secret) (t = 2), hashed on the device.
+ * take may be NULL, which means all; take[i] == 0 gives RLNAMD_DIR_SKIPPED, the secret is not read, index and limit are
+ * as for UNKNOWN.  A taken secret >= r refuses the call.  `take` exists so that status == RLNAMD_SHARE_SPAM of a relay step
+ * goes in as it is, beside the step's secrets.
+ * rlnamd_directory_slash: resolve's outputs, and every FOUND member is removed: state FREE, leaf = the tree's default
+ * leaf, one pass over the union of the paths.  Two secrets of one member in a call are both FOUND with the same index;
+ * *removed counts distinct members.  The call is exactly resolve followed by remove of the distinct found indices.
+ * rlnamd_directory_remove: a withdrawal by index -> RLNAMD_DIR_REMOVED, or RLNAMD_DIR_VACANT: the index was not LIVE, and
+ * nothing is written.  The refusals follow register's index rules.  A removed commitment may be registered again, at the
+ * same index or another.
+ * rlnamd_directory_get: n indices, repeats allowed -> live[i] (0 / 1), the commitment and the limit; FREE rows read as zero.
+ *   RECOVERED SECRETS ARE AS SENSITIVE AS ANYWHERE ELSE HERE: resolve and slash overwrite their device and pinned staging
+ *   before they return, on every error path too, as the relay does; info[7] proves it.
+ * info: [0] capacity, [1] live members, [2] table slots, [3] slots taken, those of removed members included, [4] table
+ * rebuilds (a removed member's slot is not handed out again, so before a call that could leave more than half of the slots
+ * taken the table is rebuilt from the live rows), [5] longest walk of any call, [6] calls, [7] non-zero 16-byte words left in
+ * the staging that held secrets, device and pinned (0 expected). */
+typedef struct rlnamd_directory rlnamd_directory;
+#define RLNAMD_DIR_OK 0
+#define RLNAMD_DIR_OCCUPIED 1
+#define RLNAMD_DIR_KNOWN 2
+#define RLNAMD_DIR_FOUND 0
+#define RLNAMD_DIR_UNKNOWN 1
+#define RLNAMD_DIR_SKIPPED 2
+#define RLNAMD_DIR_REMOVED 0
+#define RLNAMD_DIR_VACANT 1
+int rlnamd_directory_new(rlnamd_tree* tree, size_t capacity, uint64_t seed /* 0 = random */, rlnamd_directory** out);
+void rlnamd_directory_free(rlnamd_directory* d);
+int rlnamd_directory_register(rlnamd_directory* d, size_t n, const uint64_t* indices, const uint8_t* idcs_le /* n*32 */,
+                              const uint32_t* limits /* n */, uint8_t* status /* n */);
+int rlnamd_directory_find(rlnamd_directory* d, size_t n, const uint8_t* idcs_le /* n*32 */, uint8_t* status /* n */,
+                          uint64_t* index /* n */, uint32_t* limit /* n */);
+int rlnamd_directory_resolve(rlnamd_directory* d, size_t n, const uint8_t* secrets_le /* n*32 */, const uint8_t* take /* n or NULL */,
+                             uint8_t* status /* n */, uint64_t* index /* n */, uint32_t* limit /* n */);
+int rlnamd_directory_slash(rlnamd_directory* d, size_t n, const uint8_t* secrets_le /* n*32 */, const uint8_t* take /* n or NULL */,
+                           uint8_t* status /* n */, uint64_t* index /* n */, uint32_t* limit /* n */, uint64_t* removed /* or NULL */);
+int rlnamd_directory_remove(rlnamd_directory* d, size_t n, const uint64_t* indices, uint8_t* status /* n */);
+int rlnamd_directory_get(rlnamd_directory* d, size_t n, const uint64_t* indices, uint8_t* live /* n */, uint8_t* idcs_le /* n*32 */,
+                         uint32_t* limits /* n */);
+int rlnamd_directory_info(rlnamd_directory* d, uint64_t out[8]);
+
 /* ---- variable-base MSM on G1 / G2 (BASELINE config 5; north_star: "windowed Pippenger MSM on G1/G2") ---------
  * Replaces VariableBaseMSM::msm_bigint (ark-ec 0.5.0; call sites rln/src/partial_proof.rs:98-104,255-256: generic
  * over the group) for large n with bases that are not fixed.  Multi-GPU: every rank runs rlnamd_msm_run on its slice of

@@ -118,6 +118,17 @@ SIGNATURES = {
     "rlnamd_nullifier_log_get": (C.c_int, [P, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_home_slot": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_uint64)]),
     "rlnamd_nullifier_log_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "rlnamd_directory_new": (C.c_int, [P, C.c_size_t, C.c_uint64, PP]),
+    "rlnamd_directory_free": (None, [P]),
+    "rlnamd_directory_register": (C.c_int, [P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p]),
+    "rlnamd_directory_find": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "rlnamd_directory_resolve": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint32)]),
+    "rlnamd_directory_slash": (C.c_int, [P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "rlnamd_directory_remove": (C.c_int, [P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p]),
+    "rlnamd_directory_get": (C.c_int, [P, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
+    "rlnamd_directory_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "rlnamd_hasher_new": (C.c_int, [C.c_size_t, C.c_size_t, PP]),
     "rlnamd_hasher_free": (None, [P]),
     "rlnamd_hasher_hash_to_field": (C.c_int, [P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_char_p]),

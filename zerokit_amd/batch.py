@@ -977,6 +977,118 @@ class NullifierLog:
         return [int(v) for v in out]
 
 
+class MemberDirectory:
+    """Device-resident member directory beside a PoseidonTree (rlnamd_directory_*): who sits at which leaf.  register()
+    takes (index, identity commitment, limit) events and writes the rate commitments Poseidon(idc, limit) into the tree
+    on the device; resolve() turns recovered identity secrets into leaf indices and limits; slash() removes them.  The
+    contract is the header comment of include/rln_amd.h (zerokit_amd/csrc/member_directory.h is its sequential text).
+
+    The directory borrows `tree`, which must outlive it, and writes only the leaves of indices it registers or removes.
+    It is not persisted: after a restart, registering the same events again rebuilds it and leaves the root where it
+    was.  In one register call with duplicate commitments the lowest index wins; across calls the first call wins."""
+    OK, OCCUPIED, KNOWN = range(3)
+    FOUND, UNKNOWN, SKIPPED = range(3)
+    REMOVED, VACANT = range(2)
+    NO_INDEX = (1 << 64) - 1
+
+    def __init__(self, tree: "PoseidonTree", capacity=None, seed=0):
+        self._h = C.c_void_p()
+        self.tree = tree               # (kept alive: the directory borrows it)
+        if capacity is None:
+            capacity = min(1 << tree.depth, 1 << 31)
+        check(lib().rlnamd_directory_new(tree._h, capacity, seed, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rlnamd_directory_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _w(x):
+        """32 bytes LE of any 256-bit value: whether it is a field element is the library's check, with its own text"""
+        return int(x).to_bytes(32, "little")
+
+    def register(self, members):
+        """[(index, identity commitment, limit)] -> [status]"""
+        n = len(members)
+        idx = (C.c_uint64 * max(n, 1))(*[int(m[0]) for m in members])
+        lim = (C.c_uint32 * max(n, 1))(*[int(m[2]) for m in members])
+        status = C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_directory_register(self._h, n, idx, b"".join(self._w(m[1]) for m in members) or b"\0", lim, status))
+        return list(status.raw[:n])
+
+    def _lookup(self, fn, n, front, tail=()):
+        status = C.create_string_buffer(max(n, 1))
+        index = (C.c_uint64 * max(n, 1))()
+        limit = (C.c_uint32 * max(n, 1))()
+        check(fn(self._h, n, *front, status, index, limit, *tail))
+        return list(status.raw[:n]), [int(v) for v in index[:n]], [int(v) for v in limit[:n]]
+
+    def find(self, idcs):
+        """[identity commitment] -> (status, index, limit), three lists; UNKNOWN: index NO_INDEX, limit 0"""
+        return self._lookup(lib().rlnamd_directory_find, len(idcs), (b"".join(self._w(v) for v in idcs) or b"\0",))
+
+    @staticmethod
+    def _take(take, n):
+        if take is None:
+            return None
+        take = bytes(1 if t else 0 for t in take)
+        if len(take) != n:
+            raise RLNError("MemberDirectory: %d secrets and %d take marks" % (n, len(take)))
+        return take or b"\0"
+
+    def resolve_raw(self, secrets: bytes, take=None):
+        """n packed secrets (32 bytes each, canonical LE) and n take marks (bytes or bools; None: all) ->
+        (status, index, limit).  A relay step's `secrets` and (status == SPAM) go in unchanged."""
+        n = len(secrets) // 32
+        if len(secrets) != 32 * n:
+            raise RLNError("MemberDirectory.resolve: %d bytes of secrets" % len(secrets))
+        return self._lookup(lib().rlnamd_directory_resolve, n, (secrets or b"\0", self._take(take, n)))
+
+    def resolve(self, secrets, take=None):
+        return self.resolve_raw(b"".join(self._w(s) for s in secrets), take)
+
+    def slash_raw(self, secrets: bytes, take=None):
+        """resolve_raw, and every FOUND member is removed -> (status, index, limit, distinct members removed)"""
+        n = len(secrets) // 32
+        if len(secrets) != 32 * n:
+            raise RLNError("MemberDirectory.slash: %d bytes of secrets" % len(secrets))
+        removed = C.c_uint64()
+        out = self._lookup(lib().rlnamd_directory_slash, n, (secrets or b"\0", self._take(take, n)), (C.byref(removed),))
+        return out + (int(removed.value),)
+
+    def slash(self, secrets, take=None):
+        return self.slash_raw(b"".join(self._w(s) for s in secrets), take)
+
+    def remove(self, indices):
+        """a withdrawal by index: [index] -> [REMOVED | VACANT]"""
+        n = len(indices)
+        status = C.create_string_buffer(max(n, 1))
+        check(lib().rlnamd_directory_remove(self._h, n, (C.c_uint64 * max(n, 1))(*[int(i) for i in indices]), status))
+        return list(status.raw[:n])
+
+    def get(self, indices):
+        """[index], repeats allowed -> [(live, identity commitment, limit)]; FREE rows read as (False, 0, 0)"""
+        n = len(indices)
+        live, idcs = C.create_string_buffer(max(n, 1)), C.create_string_buffer(max(32 * n, 1))
+        limits = (C.c_uint32 * max(n, 1))()
+        check(lib().rlnamd_directory_get(self._h, n, (C.c_uint64 * max(n, 1))(*[int(i) for i in indices]), live, idcs, limits))
+        return [(bool(live.raw[i]), int.from_bytes(idcs.raw[32 * i:32 * i + 32], "little"), int(limits[i])) for i in range(n)]
+
+    def info(self):
+        """[capacity, live members, table slots, slots taken (those of removed members included), table rebuilds, longest
+        walk of any call, calls, non-zero 16-byte words left in the staging that held secrets (0 expected)]"""
+        out = (C.c_uint64 * 8)()
+        check(lib().rlnamd_directory_info(self._h, out))
+        return [int(v) for v in out]
+
+
 class QuotaLedger:
     """Device-resident ledger of the message ids a signer has handed out (rlnamd_quota_*): max_epochs x 2^depth counters,
     the next message id of each member under each external nullifier of the window, and draw(), which hands out the

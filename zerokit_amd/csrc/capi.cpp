@@ -16,6 +16,7 @@
 #include "common.h"
 #include "keccak.h"
 #include "keccak_batch.h"
+#include "member_directory.h"
 #include "merkle.h"
 #include "msm.h"
 #include "nullifier_log.h"
@@ -44,6 +45,15 @@ struct rlnamd_tree {
   MerkleTreeDev t;
   size_t host_max = 0;   // rlnamd_tree_set_leaves: up to this many distinct leaves take MerkleTreeDev::set_few
   DevBuf<uint8_t> bench_elems, bench_bits;
+};
+
+struct rlnamd_directory {
+  // every rlnamd_directory_* call takes this and then the tree handle's mutex, and holds both for the call: the
+  // directory's passes run on the tree's stream and write the tree's leaves
+  std::mutex mu;
+  rlnamd_tree* tree;   // borrowed: it outlives the directory
+  std::unique_ptr<MemberDirectoryDev> dir;
+  rlnamd_directory(rlnamd_tree* t, uint64_t capacity, uint64_t seed) : tree(t), dir(new MemberDirectoryDev(t->t, capacity, seed)) {}
 };
 
 struct rlnamd_relay {
@@ -317,6 +327,93 @@ int rlnamd_nullifier_log_info(rlnamd_nullifier_log* l, uint64_t out[8]) {
   if (!l || !out) throw Error("rlnamd_nullifier_log_info: null pointer");
   std::lock_guard<std::mutex> lk(l->mu);
   l->log.info(out);
+  RLN_CATCH
+}
+
+// --------------------------------------------------------------------------------- member directory
+// What needs no object is checked before the handle is followed (without one the bound of an index is the largest a
+// directory can have).  Lock order: the directory's mutex, then the tree handle's; nothing takes them the other way round
+// (the relay's order -- relay, hasher, verifier, log -- and the proving calls' -- tree, then ledger -- do not meet these two).
+#define RLN_DIR_REFUSE(text)                     \
+  {                                              \
+    const std::string refused_ = (text);         \
+    if (!refused_.empty()) throw Error(refused_); \
+  }
+#define RLN_DIR_LOCK(d)                              \
+  std::lock_guard<std::mutex> dir_lk((d)->mu);       \
+  std::lock_guard<std::mutex> tree_lk((d)->tree->mu)
+int rlnamd_directory_new(rlnamd_tree* tree, size_t capacity, uint64_t seed, rlnamd_directory** out) {
+  RLN_TRY
+  RLN_DIR_REFUSE(mdir::new_refusal(capacity, tree ? (uint64_t)tree->t.depth : 63));
+  if (!tree || !out) throw Error("rlnamd_directory_new: null pointer");
+  std::lock_guard<std::mutex> tree_lk(tree->mu);
+  *out = new rlnamd_directory(tree, capacity, seed);
+  RLN_CATCH
+}
+void rlnamd_directory_free(rlnamd_directory* d) {
+  if (!d) return;
+  {
+    RLN_DIR_LOCK(d);   // (the staging is released on the tree's stream)
+    d->dir.reset();
+  }
+  delete d;
+}
+int rlnamd_directory_register(rlnamd_directory* d, size_t n, const uint64_t* indices, const uint8_t* idcs_le, const uint32_t* limits,
+                              uint8_t* status) {
+  RLN_TRY
+  RLN_DIR_REFUSE(mdir::register_refusal(n, indices, idcs_le, limits, status, d ? d->dir->capacity() : mdir::MAX_CAPACITY));
+  if (!d) throw Error("rlnamd_directory_register: null directory");
+  RLN_DIR_LOCK(d);
+  d->dir->do_register(n, indices, idcs_le, limits, status);
+  RLN_CATCH
+}
+int rlnamd_directory_find(rlnamd_directory* d, size_t n, const uint8_t* idcs_le, uint8_t* status, uint64_t* index, uint32_t* limit) {
+  RLN_TRY
+  RLN_DIR_REFUSE(mdir::find_refusal(n, idcs_le, status, index, limit));
+  if (!d) throw Error("rlnamd_directory_find: null directory");
+  RLN_DIR_LOCK(d);
+  d->dir->find(n, idcs_le, status, index, limit);
+  RLN_CATCH
+}
+int rlnamd_directory_resolve(rlnamd_directory* d, size_t n, const uint8_t* secrets_le, const uint8_t* take, uint8_t* status,
+                             uint64_t* index, uint32_t* limit) {
+  RLN_TRY
+  RLN_DIR_REFUSE(mdir::resolve_refusal("resolve", n, secrets_le, take, status, index, limit));
+  if (!d) throw Error("rlnamd_directory_resolve: null directory");
+  RLN_DIR_LOCK(d);
+  d->dir->resolve(n, secrets_le, take, status, index, limit);
+  RLN_CATCH
+}
+int rlnamd_directory_slash(rlnamd_directory* d, size_t n, const uint8_t* secrets_le, const uint8_t* take, uint8_t* status,
+                           uint64_t* index, uint32_t* limit, uint64_t* removed) {
+  RLN_TRY
+  RLN_DIR_REFUSE(mdir::resolve_refusal("slash", n, secrets_le, take, status, index, limit));
+  if (!d) throw Error("rlnamd_directory_slash: null directory");
+  RLN_DIR_LOCK(d);
+  d->dir->slash(n, secrets_le, take, status, index, limit, removed);
+  RLN_CATCH
+}
+int rlnamd_directory_remove(rlnamd_directory* d, size_t n, const uint64_t* indices, uint8_t* status) {
+  RLN_TRY
+  RLN_DIR_REFUSE(mdir::remove_refusal(n, indices, status, d ? d->dir->capacity() : mdir::MAX_CAPACITY));
+  if (!d) throw Error("rlnamd_directory_remove: null directory");
+  RLN_DIR_LOCK(d);
+  d->dir->remove(n, indices, status);
+  RLN_CATCH
+}
+int rlnamd_directory_get(rlnamd_directory* d, size_t n, const uint64_t* indices, uint8_t* live, uint8_t* idcs_le, uint32_t* limits) {
+  RLN_TRY
+  RLN_DIR_REFUSE(mdir::get_refusal(n, indices, live, idcs_le, limits, d ? d->dir->capacity() : mdir::MAX_CAPACITY));
+  if (!d) throw Error("rlnamd_directory_get: null directory");
+  RLN_DIR_LOCK(d);
+  d->dir->get(n, indices, live, idcs_le, limits);
+  RLN_CATCH
+}
+int rlnamd_directory_info(rlnamd_directory* d, uint64_t out[8]) {
+  RLN_TRY
+  if (!d || !out) throw Error("rlnamd_directory_info: null pointer");
+  RLN_DIR_LOCK(d);
+  d->dir->info(out);
   RLN_CATCH
 }
 

@@ -28,6 +28,7 @@ struct MerkleTreeDev {
   DevBuf<uint8_t> proof_dev;    // proof_host's device scratch (depth * 33 bytes), allocated once
   int device = 0;               // the HIP device init() ran on: where `nodes` lives
   void reserve_staging(size_t words);
+  void scattered_pass(const uint64_t* idx, const uint8_t* leaves_le, size_t k);   // set_scattered / rehash_scattered
 
   MerkleTreeDev() = default;
   ~MerkleTreeDev();
@@ -46,6 +47,10 @@ struct MerkleTreeDev {
   // k leaves at strictly increasing indices `idx`, then ONE bottom-up pass over the union of their paths (the parents of
   // what changed, level by level; the top levels in a single launch).  Stream-ordered: returns without a host wait.
   void set_scattered(const uint64_t* idx, const uint8_t* leaves_le, size_t k);
+  // The dirty-list pass of set_scattered for leaves that kernels already enqueued on the tree's stream have written
+  // (member_directory.hip): the same checks on idx, no leaf is staged or written.  Rehashing the path of a leaf that
+  // did not change is harmless.  Stream-ordered.
+  void rehash_scattered(const uint64_t* idx, size_t k);
   // The same update for a HANDFUL of leaves, the dependent chain on a host core: one gather of the <= depth * k clean
   // siblings of the dirty paths (a kernel writing pinned host memory), the hashes of the paths with the library's own
   // host Poseidon (poseidon_hash_host: ~20 us each, against 146 us per link of the same chain on a lone wave), one

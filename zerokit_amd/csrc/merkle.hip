@@ -360,6 +360,20 @@ void MerkleTreeDev::set_scattered(const uint64_t* idx, const uint8_t* leaves_le,
   if (k > 0xFFFFFFFFull) throw Error("TooManySet");
   for (size_t i = 0; i < k; i++)
     if (idx[i] >= capacity() || (i && idx[i] <= idx[i - 1])) throw Error("set_scattered: indices must be increasing and inside the tree");
+  scattered_pass(idx, leaves_le, k);
+}
+
+// The dirty-list pass alone: the leaves at idx were written by kernels already enqueued on the tree's stream.
+void MerkleTreeDev::rehash_scattered(const uint64_t* idx, size_t k) {
+  if (k == 0) return;
+  if (k > 0xFFFFFFFFull) throw Error("TooManySet");
+  for (size_t i = 0; i < k; i++)
+    if (idx[i] >= capacity() || (i && idx[i] <= idx[i - 1])) throw Error("rehash_scattered: indices must be increasing and inside the tree");
+  scattered_pass(idx, nullptr, k);
+}
+
+// leaves_le null: no leaves are staged or written, the parents of idx are rehashed
+void MerkleTreeDev::scattered_pass(const uint64_t* idx, const uint8_t* leaves_le, size_t k) {
   root_known = false;
   // host side: the dirty node lists, bottom-up.  Heap indices fit 32 bits (depth <= 30).
   LevelOffsets lo{};
@@ -380,17 +394,19 @@ void MerkleTreeDev::set_scattered(const uint64_t* idx, const uint8_t* leaves_le,
     lo.off[depth] = (uint32_t)lists.size();
   }
   // staging: [k leaf indices][lists][k x 32 B leaves], pinned; the previous pass may still be reading it
-  const size_t words = k + lists.size() + 8 * k;
+  const size_t words = k + lists.size() + (leaves_le ? 8 * k : 0);
+  if (words == k) return;   // (depth 0 and nothing to write: the leaf is the root)
   reserve_staging(words);
   for (size_t i = 0; i < k; i++) scat_host[i] = (uint32_t)idx[i];
   if (!lists.empty()) memcpy(scat_host + k, lists.data(), lists.size() * 4);
-  memcpy(scat_host + k + lists.size(), leaves_le, 32 * k);
+  if (leaves_le) memcpy(scat_host + k + lists.size(), leaves_le, 32 * k);
   RLN_HIP(hipMemcpyAsync(scat_dev.p, scat_host, words * 4, hipMemcpyHostToDevice, stream));
   const uint32_t* d_idx = scat_dev.p;
   const uint32_t* d_list = scat_dev.p + k;
   const uint32_t* d_leaves = scat_dev.p + k + lists.size();
-  hipLaunchKernelGGL(k_scatter_leaves, dim3(div_up(k, 256)), dim3(256), 0, stream, nodes.p, capacity() - 1, d_idx, d_leaves,
-                     (uint32_t)k);
+  if (leaves_le)
+    hipLaunchKernelGGL(k_scatter_leaves, dim3(div_up(k, 256)), dim3(256), 0, stream, nodes.p, capacity() - 1, d_idx, d_leaves,
+                       (uint32_t)k);
   PoseidonView pv = poseidon_view(3);
   int l = 0;
   for (; l < depth; l++) {
